@@ -7,6 +7,7 @@
     python bench.py --gpus N ...                                    # starts N ranks of itself (torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W [--config I]         # the same, launched from outside
+    python bench.py ... --dump-outputs DIR                          # also: rank 0's records of the last timed step
 
 One process per GPU.
   * demuxlet (configs 1, 2): a "step" is one full pass of the hot path (entry likelihoods + sample-pair sweep +
@@ -59,6 +60,7 @@ FMX_METRIC = "freemuxlet EM cell-cluster-pair LLs/sec"
 HBM_PEAK_GBS = 8000.0      # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP64_PEAK_TFLOPS = 78.6    # vector FP64 = half the 157.3 TF FP32 vector rate (same guide); FP64 MFMA runs at the same rate
 SIMDS, PEAK_CLOCK_HZ, VALU_CYCLES = 1024, 2.4e9, 4.0  # 256 CUs x 4 SIMDs; one wave64 VALU instruction = 4 issue cycles
+DUMP_MAX_BYTES = 64 * 10**6  # --dump-outputs: all files together
 
 
 # ---- per-entry work, SURVEY.md 8d -------------------------------------------------------------------------------------
@@ -498,11 +500,12 @@ def free_torch_cache(ctx):
 
 
 # ---- demuxlet leg (configs 1, 2): weak scaling -----------------------------------------------------------------------
-def demux_leg(args, ctx, config, steps=None, warmup=None, ramp_seconds=None, cpu_budget_s=9.0, strong=False):
+def demux_leg(args, ctx, config, steps=None, warmup=None, ramp_seconds=None, cpu_budget_s=9.0, strong=False,
+              dump_dir=None):
     """strong = False: weak scaling, every rank sweeps a config-sized shard of its own (the driver's contract for the
     headline).  strong = True: ONE config-sized job, the same on every rank count, its cells cut into contiguous ranges
     balanced by entries (shard.cell_shards, what popscle_amd/demuxlet.py does): the N-GPU number then says how much
-    faster the same job got."""
+    faster the same job got.  dump_dir: rank 0 writes the records of the last timed pass there (dump_outputs)."""
     steps = args.steps if steps is None else steps
     warmup = args.warmup if warmup is None else warmup
     ramp_seconds = args.ramp_seconds if ramp_seconds is None else ramp_seconds
@@ -558,6 +561,8 @@ def demux_leg(args, ctx, config, steps=None, warmup=None, ramp_seconds=None, cpu
     # per pass cost 7.6 us of the 350 us step
     kern_ms, n_timed = eng.timing_sum()
     assert n_timed == steps
+    if dump_dir and ctx.rank == 0:
+        dump_outputs(dump_dir, eng.demux_results_view())
     total_cells, total_entries = ctx.sum_over_ranks([p.C, p.nnz])
     rank_sweep_ms = ctx.gather_floats(kern_ms[muxgl.T_DEMUX_SWEEP] / steps)
     rank_entries = ctx.gather_floats(p.nnz)
@@ -634,7 +639,7 @@ def demux_leg(args, ctx, config, steps=None, warmup=None, ramp_seconds=None, cpu
 
 
 # ---- freemuxlet leg (configs 3, 4): strong scaling -------------------------------------------------------------------
-def fmx_leg(args, ctx, config, steps, warmup, cpu_baseline=True, cpu_budget_s=10.0):
+def fmx_leg(args, ctx, config, steps, warmup, cpu_baseline=True, cpu_budget_s=10.0, dump_dir=None):
     torch, dist = ctx.torch, ctx.dist
     cfg = synth.CONFIGS[config]
     C = args.cells or max(1, int(round(cfg["C"] * args.scale)))
@@ -778,6 +783,8 @@ def fmx_leg(args, ctx, config, steps, warmup, cpu_baseline=True, cpu_budget_s=10
             out["cpu_baseline"] = None
         if args.dump:
             np.savez(args.dump, cells=cells, hist=np.array(hist, dtype=np.int64))
+        if dump_dir:
+            dump_outputs(dump_dir, cells, {"em_counters": np.array(hist[-1], dtype=np.float64)})
     eng.close()
     return out
 
@@ -825,6 +832,24 @@ def guarded_leg(args, ctx, headline, config):
             time.sleep(1.0)
 
 
+def dump_outputs(dirname, records, extra=None):
+    """--dump-outputs: the per-cell records the timed path returned in its last step, one float64 DIR/<field>.npy per
+    record field (the int32 fields are exact in float64), plus `extra` arrays.  When that would exceed DUMP_MAX_BYTES,
+    a fixed seeded sample of the cells is written instead and their indices go to DIR/cell_index.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = dict(extra or {})
+    names = records.dtype.names
+    budget = DUMP_MAX_BYTES - sum(a.nbytes for a in arrays.values()) - 256 * (len(names) + len(arrays) + 1)  # .npy headers
+    rows = np.arange(records.shape[0])
+    if rows.size * len(names) * 8 > budget:
+        rows = np.sort(np.random.default_rng(0).choice(rows.size, budget // (8 * (len(names) + 1)), replace=False))
+        arrays["cell_index"] = rows.astype(np.float64)
+    for name in names:
+        arrays[name] = records[name][rows].astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def flush_c_stdio():
     try:
         import ctypes
@@ -867,6 +892,9 @@ def main():
     ap.add_argument("--clusters", type=int, default=0, help="freemuxlet: override K (tests)")
     ap.add_argument("--mean-entries", type=float, default=800.0)
     ap.add_argument("--dump", default="", help="freemuxlet: write rank 0's final records (tests)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path returned in its last step (rank 0, the --config leg only) as "
+                         "DIR/<name>.npy, float64, at most 64 MB in all (a fixed seeded sample of the cells beyond that)")
     ap.add_argument("--dense", action="store_true",
                     help="demuxlet sensitivity run: the same shape with 1 + Poisson(2.0) reads per entry (one entry in seven "
                          "linear instead of three quarters); adds a 'sensitivity' key to the line")
@@ -885,7 +913,7 @@ def main():
         self_launch(args)
     ctx = Ctx(args)
     if args.config in (1, 2):
-        out = demux_leg(args, ctx, args.config)
+        out = demux_leg(args, ctx, args.config, dump_dir=args.dump_outputs)
         legs = args.legs if args.legs is not None else ("3,2,2s,4" if ctx.world > 1 else "3,2,4")
         if args.config == 1 and not args.no_legs and (args.scale == 1.0 or args.legs is not None):
             for cfg in [x.strip() for x in legs.split(",") if x.strip()]:
@@ -898,7 +926,7 @@ def main():
                 if ctx.rank == 0:
                     out[LEGS[cfg][0]] = leg
     else:
-        out = fmx_leg(args, ctx, args.config, args.steps, args.warmup)
+        out = fmx_leg(args, ctx, args.config, args.steps, args.warmup, dump_dir=args.dump_outputs)
     if ctx.dist_on:  # RCCL writes a version banner through C stdio: get it out of the way, the JSON line comes last
         ctx.barrier()
         flush_c_stdio()

@@ -7,6 +7,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -130,32 +131,33 @@ def test_two_rank_launch_line():
     assert "exchange_ms_rank0" in fx
 
 
-def test_eight_ranks_line_explains_itself():
-    """what the driver's first 8-GPU run will print, as far as a 1-GPU box can show it: eight real processes (gloo staging,
+def test_four_ranks_line_explains_itself():
+    """what the driver's N-GPU runs will print, as far as a 1-GPU box can show it: four real processes (gloo staging,
     every rank on device 0), a hundredth of the cells, the legs that have an exchange step (configs[3], [4]) and the
     strong-scaling demuxlet leg.  Every N > 1 line names the ranks that answered an all-reduce, the per-rank rates, the
-    exchange times and the scaling model next to the measurement."""
+    exchange times and the scaling model next to the measurement.  Four ranks, not eight: with this test's own process
+    and the launcher, no more than six processes hold the GPU at once."""
     with socket.socket() as so:
         so.bind(("127.0.0.1", 0))
         port = so.getsockname()[1]
-    d = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8", "--master-addr",
-             "127.0.0.1", "--master-port", str(port), BENCH, "--gpus", "8", "--steps", "5", "--warmup", "1",
+    d = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=4", "--master-addr",
+             "127.0.0.1", "--master-port", str(port), BENCH, "--gpus", "4", "--steps", "5", "--warmup", "1",
              "--ramp-seconds", "0", "--dist-backend", "gloo", "--single-device", "--scale", "0.01", "--fmx-leg-steps", "2",
              "--legs", "3,2s,4", "--no-cpu-baseline"], timeout=900)
-    assert d["n_gpus"] == 8 and d["ranks_seen"] == 8 and d["dist"]["world_size"] == 8
-    assert len(d["per_rank"]["sweep_kernel_ms"]) == 8 and min(d["per_rank"]["sweep_kernel_ms"]) > 0
+    assert d["n_gpus"] == 4 and d["ranks_seen"] == 4 and d["dist"]["world_size"] == 4
+    assert len(d["per_rank"]["sweep_kernel_ms"]) == 4 and min(d["per_rank"]["sweep_kernel_ms"]) > 0
     for key in ("freemuxlet_em", "freemuxlet_config4"):
         fx = d[key]
         assert "error" not in fx, fx
-        assert fx["n_gpus"] == 8 and fx["scaling"] == "strong" and fx["ranks_seen"] == 8
+        assert fx["n_gpus"] == 4 and fx["scaling"] == "strong" and fx["ranks_seen"] == 4
         assert "exchange_ms_rank0" in fx and "scaling_model" in fx
-        assert len(fx["per_rank"]["ms_per_iteration"]) == 8 and min(fx["per_rank"]["ms_per_iteration"]) > 0
+        assert len(fx["per_rank"]["ms_per_iteration"]) == 4 and min(fx["per_rank"]["ms_per_iteration"]) > 0
         assert fx["scaling_model"]["measured_ms_per_iteration"] == fx["ms_per_step"]
     st = d["demuxlet_config2_strong"]
     assert "error" not in st, st
-    assert st["scaling"] == "strong" and st["n_gpus"] == 8 and "ONE job" in st["scaling_note"]
+    assert st["scaling"] == "strong" and st["n_gpus"] == 4 and "ONE job" in st["scaling_note"]
     ents = st["per_rank"]["entries"]
-    assert len(ents) == 8 and max(ents) < 1.2 * min(ents)       # ranges balanced by entries
+    assert len(ents) == 4 and max(ents) < 1.2 * min(ents)       # ranges balanced by entries
     # the job's LLs, not N x a shard's: 1000 cells x (64 + 64 x 63 x 5) hypotheses per pass
     assert abs(st["value"] - 1000 * 20224 / (st["ms_per_step"] * 1e-3)) / st["value"] < 1e-9
 
@@ -179,3 +181,27 @@ def test_plain_shell_gpus_n_launches_itself():
              "--dist-backend", "gloo", "--single-device", "--fmx-leg-steps", "2", "--legs", "3", "--no-cpu-baseline"])
     assert d["n_gpus"] == 2 and d["steps"] == 10 and d["freemuxlet_em"]["n_gpus"] == 2
     assert "error" not in d["freemuxlet_em"], d["freemuxlet_em"]
+
+
+def test_dump_outputs_are_the_timed_pass_records(tmp_path):
+    """`--dump-outputs DIR`: the records of the last timed pass, one float64 .npy per field, equal to what the library
+    returns for the same seeded input; `--steps` is the number of timed passes"""
+    from popscle_amd import muxgl, synth
+
+    d = run([sys.executable, BENCH, "--steps", "7", "--warmup", "1", "--ramp-seconds", "0", "--no-legs", "--no-cpu-baseline",
+             "--dump-outputs", str(tmp_path)])
+    assert d["steps"] == 7
+    files = sorted(os.listdir(tmp_path))
+    assert files == sorted(n + ".npy" for n in muxgl.DEMUX_CELL.names)
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64 * 10**6
+    cfg = synth.CONFIGS[1]
+    p = synth.make_pileup(cfg["C"], cfg["S"], cfg["V"], seed=synth.BASE_SEED + 1, donor_seed=synth.BASE_SEED + 1)
+    with muxgl.Engine(0) as eng:
+        eng.set_pileup(p.S, p.cell_ptr, p.entry_snp, p.entry_rptr, p.reads)
+        eng.demux_set_gp(p.gp, p.has_gp)
+        want = eng.demux_run(tuple(cfg["alphas"]), 0.5)
+    assert want["valid"].sum() > 0.9 * p.C
+    for name in muxgl.DEMUX_CELL.names:
+        got = np.load(tmp_path / (name + ".npy"))
+        assert got.dtype == np.float64 and got.shape == (p.C,), name
+        assert np.array_equal(got, want[name].astype(np.float64)), name
