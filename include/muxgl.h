@@ -39,6 +39,9 @@ extern "C" {
 #define MUXGL_READ_OTHER 0xFF
 #define MUXGL_MAX_ALPHA 16
 #define MUXGL_MAX_DEVICES 16
+/* demuxlet: largest V of muxgl_demux_set_gp.  The scans name a doublet by its int32 position (j V + k) n_alpha + n, so
+ * V * V * n_alpha < 2^31: 11585 samples (2^31 / 16 alphas, square root); muxgl_demux_run checks the product for its grid */
+#define MUXGL_MAX_SAMPLES 11585
 
 enum { MUXGL_SNG = 0, MUXGL_DBL = 1, MUXGL_AMB = 2 };
 
@@ -67,6 +70,9 @@ enum { MUXGL_SNG = 0, MUXGL_DBL = 1, MUXGL_AMB = 2 };
 #define MUXGL_FLAG_GROUP_PROBE_SELF 1024 /* device group: muxgl_create also walks the pairs of members that share a device when
                                            it enables peer access (tests: the refusal path on a one-GPU box) */
 /* (128 was MUXGL_FLAG_MSTEP_LDS_STATES until round 6: the M-step variant with the cluster states in LDS is retired) */
+#define MUXGL_FLAG_FORCE_STREAMED_CALL 2048 /* demuxlet beyond 32 samples: take the streamed call (demux_stream.hip), which
+                                            jobs with more than 255 samples take anyway (lets tests compare it with the
+                                            other paths) */
 #define MUXGL_FLAG_SPLIT_GENERAL_SWEEP 512 /* demuxlet beyond 32 samples: sweep the entries with more than one usable read in
                                              launches of their own on top of the linear entries' slab (round 3's scheme)
                                              instead of in the same launch with the same accumulators (lets tests
@@ -177,11 +183,17 @@ int muxgl_set_pileup(muxgl_handle* h, int64_t C, int64_t S, int64_t nnz, int64_t
 
 /* ---- demuxlet ------------------------------------------------------------------------------------------------ */
 /* genotype-probability tensor gp[S][V][3] (sc_snp_t::gps, sc_drop_seq.h:29-37, built at sc_drop_seq.cpp:287-315) and
- * has_gp[S] (0 <=> gps == NULL, sc_drop_seq.cpp:258-282) */
+ * has_gp[S] (0 <=> gps == NULL, sc_drop_seq.cpp:258-282).  1 <= V <= MUXGL_MAX_SAMPLES (and V * V * n_alpha < 2^31 for
+ * the grid of muxgl_demux_run).  Beyond 255 samples muxgl_demux_run takes the streamed call, which does not produce
+ * full_ll. */
 int muxgl_demux_set_gp(muxgl_handle* h, int32_t V, const double* gp, const uint8_t* has_gp);
 
 /* replaces the per-cell loop cmd_cram_demuxlet.cpp:636-991.  out: NULL or [C].  full_ll: NULL or [C][V][V][n_alpha]
- * receiving llksAB for the entries the reference ever reads: (j,0,0) and (j,k!=j,n>=1); other slots are 0. */
+ * receiving llksAB for the entries the reference ever reads: (j,0,0) and (j,k!=j,n>=1); other slots are 0.
+ * The streamed call (V > 255, MUXGL_FLAG_FORCE_STREAMED_CALL at V > 32, or a job whose [C][V][V][n_alpha] tensor does not
+ * fit the device) folds the hypotheses into the scans as it goes and never holds the tensor: there full_ll must be NULL
+ * (the call fails, naming the reason, otherwise).  Its device memory beyond the pileup and the per-entry likelihoods is a
+ * slab budget, 4 GiB or a third of the device's memory if less; MUXGL_DEMUX_SLAB_MB=<n> in the environment sets it. */
 int muxgl_demux_run(muxgl_handle* h, const muxgl_demux_params* p, muxgl_demux_cell* out, double* full_ll);
 
 /* The calls rounding noise could decide, settled in the reference's own arithmetic -- HOST pass, no device work, no

@@ -524,6 +524,8 @@ struct ring_sel {          // one launch of demux_ring.hip
 
 // kernel launchers implemented in the kernel TUs
 int demux_launch(muxgl_handle* h, const muxgl_demux_params* p);
+bool demux_stream_wanted(muxgl_handle* h, const muxgl_demux_params* p);  // demux_stream.hip: V > 255, the flag, or no room
+int demux_stream_launch(muxgl_handle* h, const muxgl_demux_params* p);   // streamed sweep + fold + call
 int demux_entry_pg_launch(muxgl_handle* h, const muxgl_demux_params* p, double* d_pg, bool gen_stream = false,
                           bool by_record = false);
 int demux_ring_lin_launch(muxgl_handle* h, const muxgl_demux_params* p, const wave_item* items, int64_t n_items,

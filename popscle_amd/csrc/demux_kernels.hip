@@ -389,6 +389,9 @@ int demux_launch(muxgl_handle* h, const muxgl_demux_params* p) {
   }
   h->records_on_host = false;
   h->ll_wave = false;
+  // more than 255 samples, MUXGL_FLAG_FORCE_STREAMED_CALL, or a job the paths below cannot fit: the streamed call
+  // (demux_stream.hip), which never holds more than a budget's worth of hypotheses
+  if (demux_stream_wanted(h, p)) return demux_stream_launch(h, p);
   int rc = -1;
   if (h->V <= 16) {
     if (demux_ensure_ll(h, p)) return 1;

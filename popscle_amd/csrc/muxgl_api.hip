@@ -455,7 +455,7 @@ int muxgl_demux_set_gp(muxgl_handle* h, int32_t V, const double* gp, const uint8
   if (!h) return 1;
   if (h->group) return group_demux_set_gp(h, V, gp, has_gp);
   HIPCHK(h, hipSetDevice(h->device));
-  if (V < 1 || V > 255) MUXGL_FAIL(h, "muxgl_demux_set_gp: V=%d outside [1,255]", V);
+  if (V < 1 || V > MUXGL_MAX_SAMPLES) MUXGL_FAIL(h, "muxgl_demux_set_gp: V=%d outside [1,%d]", V, MUXGL_MAX_SAMPLES);
   if (!gp || !has_gp) MUXGL_FAIL(h, "muxgl_demux_set_gp: NULL array");
   if (h->S <= 0 && h->nnz > 0) MUXGL_FAIL(h, "muxgl_demux_set_gp: call muxgl_set_pileup first");
   const size_t n = (size_t)h->S * V * 3;

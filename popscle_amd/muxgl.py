@@ -31,6 +31,7 @@ FLAG_NO_LINEAR_ENTRIES = 64
 FLAG_NO_PIVOT_SUMS = 256
 FLAG_SPLIT_GENERAL_SWEEP = 512
 FLAG_GROUP_PROBE_SELF = 1024
+FLAG_FORCE_STREAMED_CALL = 2048
 MAX_DEVICES = 16
 XCHG_PAD = 64
 T_FMX_ENTRY, T_FMX_GP, T_FMX_ESTEP, T_FMX_CALL, T_FMX_MSTEP = 4, 5, 6, 7, 8
