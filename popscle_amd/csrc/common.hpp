@@ -17,6 +17,7 @@
 #include <unordered_set>
 
 #include "../../include/muxgl.h"
+#include "path_choice.hpp"
 
 constexpr int MUXGL_ROW_CH = 128;   // entries per chunk of the row kernels (16-lane slots)
 constexpr int MUXGL_QUAD_CH = 192;  // entries per chunk of the freemuxlet oct E-step (configs[3], E-step in ms: 128: 1.63,
@@ -63,7 +64,7 @@ struct muxgl_row_state {
   uint2* d_orec = nullptr;              // ... and the linear ones as {row offset, table offset} records, step-major per
   int64_t* d_unit_ptr = nullptr;        //     unit of eight chunks: unit u starts at d_orec[d_unit_ptr[u]] (demux_oct.hip)
   int32_t* d_quad_order = nullptr;      // ... and the launch order of the chunks (sorted by trip count within buckets)
-  // freemuxlet quad E-step (fmx_quad.hip, built on first use after muxgl_fmx_prepare): per chunk, its linear entries
+  // freemuxlet oct E-step (fmx_oct.hip, built on first use after muxgl_fmx_prepare): per chunk, its linear entries
   // as {c0, c1, snp} records in front, then the SNP ids and six likelihoods of the others
   int32_t* d_fq_nlin = nullptr;
   int32_t *d_fo_lsteps = nullptr, *d_fo_gsteps = nullptr;  // steps of every unit's two loops (fmx_oct.hip)
@@ -218,14 +219,13 @@ struct muxgl_handle {
   double* d_segls6 = nullptr;     // [nnz][6] their six distinct values {00,11,22,01,02,12}: the ordered M-step streams them
   uint16_t* d_scode = nullptr;    // [nnz] SNP-major: read byte of an entry with at most one usable read, 0x100 otherwise (fmx_scode_kernel)
   double* d_mtab = nullptr;       // [256][6] the six values of a one-read entry by its read byte (fmx_mstep.hip)
-  double* d_egls6 = nullptr;      // (unused since round 4: the oct E-step's streams are repacked from d_egls)
   int32_t* d_secnt = nullptr;     // [nnz][3] entry counts in SNP-major order
   bool fmx_prepared = false;
   int64_t fc0 = 0, fc1 = 0, fs0 = 0, fs1 = 0;  // active cell / SNP shard of the EM phases (default: everything)
   muxgl_row_state* frow = nullptr;             // chunk tables restricted to the cell shard
   muxgl_row_state* fqrow = nullptr;            // same for the quad E-step
-  double* d_cgpq = nullptr;                    // [S][6][4][2] cluster-GP rows re-laid per quad (fmx_quad.hip)
-  double* d_ceq = nullptr;                     // [S + 1][2][4][2] their moments E = g1 + 2 g2 (fmx_quad.hip)
+  double* d_cgpq = nullptr;                    // [S][6][4][2] cluster-GP rows re-laid per quad (fmx_oct.hip)
+  double* d_ceq = nullptr;                     // [S + 1][2][4][2] their moments E = g1 + 2 g2 (fmx_oct.hip)
   size_t ceq_cap = 0;
   size_t cgpq_cap = 0;
 
@@ -515,6 +515,17 @@ struct wave_item {
 struct wave_cut {
   int64_t cell, first, count;  // overflow slabs [first, first + count)
 };
+// the wave plan of a handle (demux_wave_plan, at muxgl_set_pileup time) and the wave path's tables (demux_wave.hip)
+struct muxgl_wave_state {
+  int32_t* d_order = nullptr;  // cells, longest first
+  wave_item* d_items = nullptr;  // work units of the demuxlet wave kernels, longest first
+  wave_cut* d_cuts = nullptr;    // cells cut into several units
+  int64_t n_items = 0, n_cuts = 0, n_over = 0;
+  double* d_pg = nullptr;      // [nnz][A][9]
+  double* d_gm = nullptr;      // [S][V][2], see wave_gm_kernel
+  size_t gm_cap = 0;
+  size_t pg_cap = 0;
+};
 struct ring_sel {          // one launch of demux_ring.hip
   int32_t n[4];            // alpha indices of the non-symmetric slots
   int32_t nsym;            // ... of the symmetric slot (0: none)
@@ -522,9 +533,9 @@ struct ring_sel {          // one launch of demux_ring.hip
   int32_t jbase, blk, nblk2;  // first sample of the diagonal block, its slab, slabs per cell
 };
 
-// kernel launchers implemented in the kernel TUs
+// kernel launchers implemented in the kernel TUs.  Which one runs is decided by demux_launch, fmx_phase_estep, ... from
+// the choosers of path_choice.hpp; a launcher is only called for a job its path takes (0 ok, 1 error)
 int demux_launch(muxgl_handle* h, const muxgl_demux_params* p);
-bool demux_stream_wanted(muxgl_handle* h, const muxgl_demux_params* p);  // demux_stream.hip: V > 255, the flag, or no room
 int demux_stream_launch(muxgl_handle* h, const muxgl_demux_params* p);   // streamed sweep + fold + call
 int demux_entry_pg_launch(muxgl_handle* h, const muxgl_demux_params* p, double* d_pg, bool gen_stream = false,
                           bool by_record = false);
@@ -533,20 +544,21 @@ int demux_ring_lin_launch(muxgl_handle* h, const muxgl_demux_params* p, const wa
                           bool pg_by_record = false);
 void demux_ring_release(muxgl_handle* h);
 int demux_row_plan(muxgl_handle* h);
-int demux_row_launch(muxgl_handle* h, const muxgl_demux_params* p);  // -1: not applicable
+int demux_row_launch(muxgl_handle* h, const muxgl_demux_params* p);
 void demux_row_free(muxgl_handle* h);
 int demux_row_build(muxgl_handle* h, muxgl_row_state** st, int64_t c0, int64_t c1, int ch);
-int demux_oct_launch(muxgl_handle* h, const muxgl_demux_params* p);  // -1: not applicable
-int demux_row2_launch(muxgl_handle* h, const muxgl_demux_params* p);  // -1: not applicable (demux_row2.hip)
+int demux_oct_launch(muxgl_handle* h, const muxgl_demux_params* p);
+int demux_row2_launch(muxgl_handle* h, const muxgl_demux_params* p);  // (demux_row2.hip)
+double row2_part_bytes(const muxgl_row_state* st);  // chunk partials of the two-per-lane row kernels (demux_row2.hip)
 int demux_call16_launch(muxgl_handle* h, const muxgl_demux_params* p);
-int fmx_oct_estep_launch(muxgl_handle* h, muxgl_row_state* st, int64_t c0, int64_t nc);  // -1: not applicable
-int fmx_row2_estep_launch(muxgl_handle* h, muxgl_row_state* st, int64_t c0, int64_t nc);  // -1: not applicable
+int fmx_oct_estep_launch(muxgl_handle* h, muxgl_row_state* st, int64_t c0, int64_t nc);
+int fmx_row2_estep_launch(muxgl_handle* h, muxgl_row_state* st, int64_t c0, int64_t nc);
 int demux_wave_plan(muxgl_handle* h, const int64_t* cell_ptr);
-int demux_wave_launch(muxgl_handle* h, const muxgl_demux_params* p);  // -1: not applicable
+int demux_wave_launch(muxgl_handle* h, const muxgl_demux_params* p);
 const int32_t* demux_wave_order(const muxgl_handle* h);  // cells, longest first (device)
 int demux_wave_items(const muxgl_handle* h, const wave_item** items, int64_t* n_items, const wave_cut** cuts,
                      int64_t* n_cuts, int64_t* n_over);  // work units of the wave kernels (device)
-int fmx_wave_estep_launch(muxgl_handle* h, int64_t c0, int64_t nc);  // 16 < K <= 255; -1: not applicable
+int fmx_wave_estep_launch(muxgl_handle* h, int64_t c0, int64_t nc);  // 32 < K <= 255
 int64_t fmx_wave_fll_rows(const muxgl_handle* h);  // rows of d_fll: C + extra parts of long cells
 void fmx_wave_streams_release(muxgl_handle* h);  // the linear/general entry streams and their rank table
 int demux_ensure_ll(muxgl_handle* h, const muxgl_demux_params* p);  // standard LL tensor allocated and zeroed
@@ -577,7 +589,7 @@ int fmx_snp_major_full(muxgl_handle* h);  // d_segls / d_secnt on first use (fre
 int fmx_phase_gp(muxgl_handle* h, const muxgl_fmx_params* p);
 int fmx_phase_estep(muxgl_handle* h, const muxgl_fmx_params* p);
 int fmx_phase_mstep(muxgl_handle* h);
-int fmx_mstep_stream_launch(muxgl_handle* h);  // K <= 64 (fmx_mstep.hip); -1: not applicable
+int fmx_mstep_stream_launch(muxgl_handle* h);  // K <= 64 (fmx_mstep.hip)
 // fmx_exact.hip: near-tie calls settled in the reference's arithmetic (steps A, B, C; all three on one handle)
 int fmx_exact_snps(muxgl_handle* h, std::vector<int32_t>* snps);
 int fmx_exact_rows(muxgl_handle* h, const muxgl_fmx_params* p, const int32_t* snps, int64_t n, double* rows, uint8_t* owned);

@@ -389,38 +389,51 @@ int demux_launch(muxgl_handle* h, const muxgl_demux_params* p) {
   }
   h->records_on_host = false;
   h->ll_wave = false;
-  // more than 255 samples, MUXGL_FLAG_FORCE_STREAMED_CALL, or a job the paths below cannot fit: the streamed call
-  // (demux_stream.hip), which never holds more than a budget's worth of hypotheses
-  if (demux_stream_wanted(h, p)) return demux_stream_launch(h, p);
-  int rc = -1;
-  if (h->V <= 16) {
-    if (demux_ensure_ll(h, p)) return 1;
-    rc = demux_oct_launch(h, p);               // the reference's default grid {0, 0.5}: oct kernel
-    if (rc == 0 && h->records_on_host) return 0;  // reduce and call were fused into the oct path's finish kernel
-    if (rc < 0) rc = demux_row_launch(h, p);    // other grids: row kernel
+  const int V = h->V;
+  const int64_t n_over = h->wave ? h->wave->n_over : 0;
+  size_t fr = 0, tot = 0;  // (the fit rule reads the device's size beyond 32 samples only)
+  if (V > 32 && hipMemGetInfo(&fr, &tot) != hipSuccess) {
+    tot = 0;                  // unknown: the rule does not apply
+    (void)hipGetLastError();  // (and the next launch check does not report this failure)
   }
-  if (h->V > 16 && h->V <= 32 && !(h->flags & (MUXGL_FLAG_FORCE_TILE_SWEEP | MUXGL_FLAG_FORCE_WAVE_KERNEL))) {
-    if (h->want_full_ll && demux_ensure_ll(h, p)) return 1;  // (without the tensor the call is made in LDS)
-    rc = demux_oct_launch(h, p);     // the default grid {0, 0.5}: the oct tiling with sixteen lanes per entry
-    if (rc == 0 && h->records_on_host) return 0;
-    if (rc < 0) rc = demux_row2_launch(h, p);  // {a0, 0.5} (or MUXGL_FLAG_FORCE_ROW_KERNEL): row kernel, two samples per lane
-    if (rc == 0 && h->records_on_host) return 0;  // reduce and call were fused into its finish kernel
-  }
-  if (rc < 0) rc = demux_wave_launch(h, p);  // one wave per cell and 64 x 64 block of the pair matrix, lane = sample
-  if (rc > 0) return rc;
-  if (rc < 0) {                     // general tile sweep
-    if (demux_ensure_ll(h, p)) return 1;
-    if (!h->pairs_valid) {
-      if (build_pairs(h, p, &symmask)) return 1;
-      h->pairs_valid = true;
-    }
-    tic(h, MUXGL_T_DEMUX_SWEEP);
+  const path_choice::demux_facts f = {V, A, p->alpha, h->flags, h->C, h->S, h->row != nullptr, h->qrow != nullptr,
+                                      h->d_gpq != nullptr, h->d_qent != nullptr, h->wave != nullptr, h->want_full_ll,
+                                      h->row ? row2_part_bytes(h->row) : 0.0,
+                                      path_choice::demux_wave_sizes(h->nnz, h->C, n_over, V, A).bytes(), (double)tot};
+  const path_choice::demux_path path = path_choice::choose_demux_path(f);
+  if (path_choice::demux_ll_first(f, path) && demux_ensure_ll(h, p)) return 1;
+  int rc = 0;
+  switch (path) {
+    case path_choice::demux_path::stream:  // never holds more than a budget's worth of hypotheses (demux_stream.hip)
+      return demux_stream_launch(h, p);
+    case path_choice::demux_path::oct8:
+    case path_choice::demux_path::oct16:
+      rc = demux_oct_launch(h, p);
+      break;
+    case path_choice::demux_path::row:
+      rc = demux_row_launch(h, p);
+      break;
+    case path_choice::demux_path::row2:  // row kernel, two samples per lane
+      rc = demux_row2_launch(h, p);
+      break;
+    case path_choice::demux_path::wave:  // one wave per cell and 64 x 64 block of the pair matrix, lane = sample
+      rc = demux_wave_launch(h, p);
+      break;
+    case path_choice::demux_path::tile:  // general tile sweep
+      if (!h->pairs_valid) {
+        if (build_pairs(h, p, &symmask)) return 1;
+        h->pairs_valid = true;
+      }
+      tic(h, MUXGL_T_DEMUX_SWEEP);
 #define CALL_SWEEP(N) launch_sweep<N>(h, p, symmask, al)
-    rc = [&]() -> int { DISPATCH_NA(A, CALL_SWEEP); }();
+      rc = [&]() -> int { DISPATCH_NA(A, CALL_SWEEP); }();
 #undef CALL_SWEEP
-    if (rc) return rc;
-    toc(h, MUXGL_T_DEMUX_SWEEP);
+      if (rc) return rc;
+      toc(h, MUXGL_T_DEMUX_SWEEP);
+      break;
   }
+  if (rc) return rc;
+  if (h->records_on_host) return 0;  // reduce and call were fused into the oct / row2 path's finish kernel
 
   tic(h, MUXGL_T_DEMUX_CALL);
   if (h->ll_wave) {

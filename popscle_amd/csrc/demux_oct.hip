@@ -902,7 +902,7 @@ __global__ void __launch_bounds__(256)
 
 }  // namespace
 
-// the launch order of the chunks of the oct / quad kernels (quad_order_key_kernel), shared with fmx_quad.hip
+// the launch order of the chunks of the oct / quad kernels (quad_order_key_kernel), shared with fmx_oct.hip
 int quad_launch_order(muxgl_handle* h, const row_chunk* d_chunks, const int32_t* d_nlin, int64_t n, int32_t** order) {
   int32_t* d_iota = nullptr;
   uint64_t *d_key = nullptr, *d_key2 = nullptr;
@@ -1037,13 +1037,7 @@ int oct_launch_t(muxgl_handle* h, const muxgl_demux_params* p) {
 }
 }  // namespace
 
-// returns -1 when the path does not apply, 0 ok, 1 error
+// the default grid {0, 0.5} at V <= 32 (path_choice.hpp): eight lanes per entry up to 16 samples, sixteen beyond
 int demux_oct_launch(muxgl_handle* h, const muxgl_demux_params* p) {
-  if (h->V > 32 || !h->qrow || !h->d_gpq || !h->d_qent || h->C == 0) return -1;
-  const int P = h->V <= 16 ? 8 : 16;
-  // (row offsets of the linear entries' records are 32-bit byte offsets)
-  if ((uint64_t)(h->S + 1) * (32u * (unsigned)P) >= ((uint64_t)1 << 32)) return -1;
-  if (h->flags & (MUXGL_FLAG_FORCE_TILE_SWEEP | MUXGL_FLAG_FORCE_ROW_KERNEL | MUXGL_FLAG_FORCE_WAVE_KERNEL)) return -1;
-  if (p->n_alpha != 2 || p->alpha[0] != 0.0 || p->alpha[1] != 0.5) return -1;
-  return P == 8 ? oct_launch_t<8>(h, p) : oct_launch_t<16>(h, p);
+  return h->V <= 16 ? oct_launch_t<8>(h, p) : oct_launch_t<16>(h, p);
 }

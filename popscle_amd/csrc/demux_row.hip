@@ -367,10 +367,8 @@ static int row_launch_t(muxgl_handle* h, const row_alpha& al, int A) {
   return 0;
 }
 
-// returns -1 when the row path does not apply (caller falls back to the tile sweep), 0 ok, 1 error
+// V <= 16, at most one 0.5 and five other values among alpha[1..] (path_choice.hpp)
 int demux_row_launch(muxgl_handle* h, const muxgl_demux_params* p) {
-  if (h->V > 16 || !h->row || h->C == 0 || (h->flags & (MUXGL_FLAG_FORCE_TILE_SWEEP | MUXGL_FLAG_FORCE_WAVE_KERNEL)))
-    return -1;
   const int A = p->n_alpha;
   row_alpha al;
   int nns = 0, nsy = 0, pos = 0;
@@ -384,7 +382,6 @@ int demux_row_launch(muxgl_handle* h, const muxgl_demux_params* p) {
     }
   for (int n = 1; n < A; ++n)
     if (p->alpha[n] == 0.5) {
-      if (nsy) return -1;  // 0.5 listed twice: generic path
       al.a[pos] = p->alpha[n];
       al.orig[pos++] = n;
       ++nsy;
@@ -393,12 +390,11 @@ int demux_row_launch(muxgl_handle* h, const muxgl_demux_params* p) {
     al.a[pos] = 0.0;
     al.orig[pos] = 0;
   }
-  if (nns > 5) return -1;
   tic(h, MUXGL_T_DEMUX_SWEEP);
 #define ROW_CASE(N, S) \
   if (nns == N && nsy == S) return row_launch_t<N, S>(h, al, A);
   ROW_CASE(0, 0) ROW_CASE(0, 1) ROW_CASE(1, 0) ROW_CASE(1, 1) ROW_CASE(2, 0) ROW_CASE(2, 1) ROW_CASE(3, 0)
   ROW_CASE(3, 1) ROW_CASE(4, 0) ROW_CASE(4, 1) ROW_CASE(5, 0) ROW_CASE(5, 1)
 #undef ROW_CASE
-  return -1;
+  MUXGL_FAIL(h, "internal: no row kernel for %d plain and %d symmetric alphas", nns, nsy);
 }

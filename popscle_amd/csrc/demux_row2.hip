@@ -267,14 +267,13 @@ __global__ void __launch_bounds__(256)
 
 }  // namespace
 
-// returns -1 when the two-samples-per-lane row path does not apply, 0 ok, 1 error
+// bytes of the chunk partials of the two-per-lane row kernels (here and fmx_row2.hip) over the chunk tables st
+double row2_part_bytes(const muxgl_row_state* st) { return (double)((size_t)st->n_chunks * ROW2_NACC * 16) * 8.0; }
+
+// 17..32 samples, grid {a0, 0.5} with a0 != 0.5, partials within ROW2_PART_LIMIT (path_choice.hpp)
 int demux_row2_launch(muxgl_handle* h, const muxgl_demux_params* p) {
-  if (h->V <= 16 || h->V > 32 || !h->row || h->C == 0) return -1;
-  if (h->flags & (MUXGL_FLAG_FORCE_TILE_SWEEP | MUXGL_FLAG_FORCE_WAVE_KERNEL)) return -1;
-  if (p->n_alpha != 2 || p->alpha[1] != 0.5 || p->alpha[0] == 0.5) return -1;
   muxgl_row_state* st = h->row;
   const size_t need = (size_t)st->n_chunks * R2_NACC * 16;
-  if ((double)need * 8.0 > ROW2_PART_LIMIT) return -1;
   if (need > st->part_cap) {
     if (dev_alloc(h, &st->d_part, need)) return 1;
     st->part_cap = need;

@@ -276,30 +276,6 @@ static size_t stream_budget() {
   return b;
 }
 
-bool demux_stream_wanted(muxgl_handle* h, const muxgl_demux_params* p) {
-  const int V = h->V, A = p->n_alpha;
-  if (V > 255) return true;
-  if (V <= 32) return false;
-  if (h->flags & MUXGL_FLAG_FORCE_STREAMED_CALL) return true;
-  if (A < 2) return false;
-  // jobs the other paths cannot fit: the wave path declines beyond 230 GB (demux_wave_launch), and then the tile sweep's
-  // [C][V][V][A] tensor has to fit the device
-  const int nblk = (V + 63) / 64;
-  int64_t n_over = 0;
-  {
-    const wave_item* it;
-    const wave_cut* cu;
-    int64_t ni, nc;
-    if (demux_wave_items(h, &it, &ni, &cu, &nc, &n_over)) n_over = 0;
-  }
-  const double wave = ((double)h->nnz * A * 9 + (double)(h->C + n_over) * nblk * nblk * A * 4096 +
-                       (nblk > 1 ? (double)h->C * V * V * A : 0.0)) * 8.0;
-  if (wave <= 230e9) return false;
-  size_t fr = 0, tot = 0;
-  if (hipMemGetInfo(&fr, &tot) != hipSuccess || tot == 0) return false;
-  return (double)h->C * V * V * A * 8.0 > 0.9 * (double)tot;
-}
-
 int demux_stream_launch(muxgl_handle* h, const muxgl_demux_params* p) {
   const int V = h->V, A = p->n_alpha;
   if (A < 2) MUXGL_FAIL(h, "streamed demuxlet call: the alpha grid needs a doublet alpha (n_alpha >= 2)");

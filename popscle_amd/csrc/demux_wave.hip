@@ -620,17 +620,6 @@ __global__ void __launch_bounds__(64)
 
 }  // namespace
 
-struct muxgl_wave_state {
-  int32_t* d_order = nullptr;  // cells, longest first
-  wave_item* d_items = nullptr;  // work units of the demuxlet wave kernels, longest first
-  wave_cut* d_cuts = nullptr;    // cells cut into several units
-  int64_t n_items = 0, n_cuts = 0, n_over = 0;
-  double* d_pg = nullptr;      // [nnz][A][9]
-  double* d_gm = nullptr;      // [S][V][2], see wave_gm_kernel
-  size_t gm_cap = 0;
-  size_t pg_cap = 0;
-};
-
 namespace {
 __global__ void __launch_bounds__(256)
     gp_neutral_rows_kernel(int64_t S, int V, const uint8_t* __restrict__ has_gp, double* __restrict__ gp) {
@@ -716,21 +705,14 @@ int demux_wave_plan(muxgl_handle* h, const int64_t* cell_ptr) {
   return 0;
 }
 
-// returns -1 when the wave path does not apply, 0 ok, 1 error
+// a doublet alpha, the wave plan, and its tables within WAVE_BYTE_LIMIT (path_choice.hpp)
 int demux_wave_launch(muxgl_handle* h, const muxgl_demux_params* p) {
-  if (!h->wave || h->C == 0 || (h->flags & MUXGL_FLAG_FORCE_TILE_SWEEP)) return -1;
-  if (p->n_alpha < 2) return -1;  // singlets only: left to the general path
-  // a handful of samples beyond a block boundary fill the extra blocks so thinly that the tile sweep is faster
-  // (measured: V = 65 tile 195 ms vs 249 ms, V = 96 tile 497 ms vs 253 ms, per 2000 cells)
-  if (h->V > 64 && h->V % 64 != 0 && h->V % 64 <= 8 && h->V < 128) return -1;
-  if (h->V <= 16 && !(h->flags & MUXGL_FLAG_FORCE_WAVE_KERNEL)) return -1;  // the row/quad kernels are better there
   muxgl_wave_state* st = h->wave;
   const int A = p->n_alpha, V = h->V;
   const int nblk = (V + 63) / 64, nblk2 = nblk * nblk;  // 64 x 64 blocks of the pair matrix
-  size_t need = (size_t)h->nnz * A * 9;
-  const size_t llw_need = (size_t)(h->C + st->n_over) * nblk2 * A * 4096;
-  // pG table, result slabs and (V > 64) the tensor the call kernel reads must fit comfortably: else the tile sweep
-  if (((double)need + (double)llw_need + (nblk > 1 ? (double)h->C * V * V * A : 0.0)) * 8.0 > 230e9) return -1;
+  const path_choice::wave_sizes sz = path_choice::demux_wave_sizes(h->nnz, h->C, st->n_over, V, A);
+  size_t need = sz.pg;
+  const size_t llw_need = sz.llw;
   if (llw_need > h->llw_cap) {
     if (dev_alloc(h, &h->d_llw, llw_need)) return 1;
     h->llw_cap = llw_need;

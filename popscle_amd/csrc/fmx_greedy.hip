@@ -1362,7 +1362,7 @@ extern "C" int muxgl_fmx_greedy_init(muxgl_handle* h, int32_t K, const double* s
   // batched path (K <= 64): chunk tables and chunk partials of the distance kernel, chain tables of the fixpoint.
   // It takes the chain of memory round trips of a step off the critical path for every K it covers (1.x us per cell
   // against 22 us at K = 16 and 58 us at K = 64 for the serial kernel), so it is the default; the serial kernel remains
-  // for K > 64, for jobs with 2^31 or more entries to cluster, and behind MUXGL_FLAG_FORCE_TILE_SWEEP.
+  // for K > 64, for jobs with 2^31 or more entries to cluster, and under the test flag (path_choice.hpp).
   int64_t P = 0;
   std::vector<int64_t> pos_ptr(npad + 1, 0);
   for (size_t i = 0; i < npad; ++i) pos_ptr[i + 1] = pos_ptr[i] + (i < n ? hlen[i] : 0);
@@ -1371,8 +1371,7 @@ extern "C" int muxgl_fmx_greedy_init(muxgl_handle* h, int32_t K, const double* s
   //  takes the serial kernel)
   int cus = 0;
   HIPCHK(h, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
-  const bool batched =
-      K <= 64 && P > 0 && P < ((int64_t)1 << 31) && !(h->flags & MUXGL_FLAG_FORCE_TILE_SWEEP) && cus >= 2 * GB;
+  const bool batched = path_choice::choose_greedy({(int)K, h->flags, P, cus, GB}) == path_choice::greedy_path::batched;
   int64_t *d_chunk_first = nullptr, *d_chunk_p0 = nullptr, *d_pos_e = nullptr, *d_cinc_ptr = nullptr, *d_inc_e = nullptr;
   int32_t *d_chunk_n = nullptr, *d_pos_snp = nullptr, *d_inc_hp = nullptr;
   unsigned long long* d_passw = nullptr;

@@ -312,7 +312,7 @@ __device__ __forceinline__ double fmx_wave_sum(double v) {
 // WAVE: one wave per cell -- the K (K + 1) / 2 log-likelihoods of a cell are read once, coalesced, by 64 lanes (one lane
 // per cell reads them 16 KB apart from its neighbours' at K = 64: 0.7 TB/s); the evidence sums become max-shifted
 // log-sum-exps (independent exps, one log) instead of the reference's serial logAdd chain -- the same value to ~1e-16
-// relative.  !WAVE: one lane per cell, the reference's loop as written (kept behind MUXGL_FLAG_FORCE_TILE_SWEEP).
+// relative.  !WAVE: one lane per cell, the reference's loop as written (kept for the test flag: path_choice.hpp).
 template <bool WAVE>
 __global__ void __launch_bounds__(64)
     fmx_call_kernel(int64_t c0, int64_t c1, int K, double log_single_prior, double log_double_prior, const double* __restrict__ fll,
@@ -680,11 +680,10 @@ __global__ void __launch_bounds__(256)
 static int fmx_mstep_launch(muxgl_handle* h) {
   const int64_t n = (h->fs1 - h->fs0) * h->K;
   if (n <= 0) return 0;
-  if (!(h->flags & MUXGL_FLAG_FORCE_TILE_SWEEP)) {  // K <= 64: lane = chain, the SNP's list as a stream (fmx_mstep.hip)
-    const int rc = fmx_mstep_stream_launch(h);
-    if (rc >= 0) return rc;
-  }
-  // beyond 64 clusters (no BASELINE shape), or under MUXGL_FLAG_FORCE_TILE_SWEEP: lane = (SNP, cluster), every chain on its own
+  const path_choice::fmx_mstep_facts f = {h->K, h->flags, h->fs1 - h->fs0, h->nnz, h->C};
+  if (path_choice::choose_fmx_mstep(f) == path_choice::fmx_mstep_path::stream)
+    return fmx_mstep_stream_launch(h);  // lane = chain, the SNP's list as a stream (fmx_mstep.hip)
+  // lane = (SNP, cluster), every chain on its own
   hipLaunchKernelGGL(fmx_mstep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->S, h->fs0, h->fs1,
                      h->K, h->d_snp_ptr, h->d_snp_entry, h->d_entry_cell, h->d_clust, h->d_egls, h->d_segls6, h->d_ecnt,
                      h->d_cgls, h->d_ccnt);
@@ -1057,23 +1056,33 @@ int fmx_phase_estep(muxgl_handle* h, const muxgl_fmx_params* p) {
   const int K = h->K;
   const int npairs = K * (K + 1) / 2;
   tic(h, MUXGL_T_FMX_ESTEP);
-  muxgl_row_state* st = h->frow ? h->frow : h->row;
-  int qrc = -1;
-  // (the chunk tables of the quad E-step are its own: demuxlet's oct kernel cuts cells into longer chunks, and a sharded
-  //  run must cut a cell exactly as the whole-pileup run does)
-  if (nc > 0 && K <= 16 && !h->fqrow && h->qrow && !(h->flags & (MUXGL_FLAG_FORCE_TILE_SWEEP | MUXGL_FLAG_FORCE_ROW_KERNEL)) &&
-      demux_row_build(h, &h->fqrow, 0, h->C, fmx_oct_chunk()))
-    return 1;
-  if (nc > 0) qrc = fmx_oct_estep_launch(h, h->fqrow, c0, nc);  // K <= 16: eight lanes per entry
-  if (nc > 0 && qrc < 0) qrc = fmx_row2_estep_launch(h, st, c0, nc);  // 16 < K <= 32: two clusters per lane
-  if (nc > 0 && qrc < 0) qrc = fmx_wave_estep_launch(h, c0, nc);  // 32 < K: one wave per cell (part) and block
-  if (qrc > 0) return 1;
-  if (nc > 0 && qrc < 0) {  // the plain kernel: workgroup <-> (cell, tile of pairs).  K > 255 never happens (muxgl_fmx_set_clusters):
-                            // reached under MUXGL_FLAG_FORCE_TILE_SWEEP / _FORCE_ROW_KERNEL, which tests use to cover it
-    const int T = 256, PPT = 4;
-    const unsigned tiles = (unsigned)((npairs + T * PPT - 1) / (T * PPT));
-    hipLaunchKernelGGL(fmx_estep_pair_kernel<PPT>, dim3((unsigned)nc, tiles), dim3(T), 0, h->stream, h->d_cell_ptr,
-                       h->d_entry_snp, h->d_egls, h->d_cgp, K, c0, h->d_fll);
+  if (nc > 0) {
+    muxgl_row_state* st = h->frow ? h->frow : h->row;
+    const path_choice::fmx_estep_facts f = {K, h->flags, h->S, h->fqrow != nullptr, h->qrow != nullptr, st != nullptr,
+                                            st ? row2_part_bytes(st) : 0.0, h->wave ? h->wave->n_items : 0};
+    int rc = 0;
+    switch (path_choice::choose_fmx_estep(f)) {
+      case path_choice::fmx_estep_path::oct:  // eight lanes per entry
+        // (the chunk tables of the oct E-step are its own: demuxlet's oct kernel cuts cells into longer chunks, and a
+        //  sharded run must cut a cell exactly as the whole-pileup run does)
+        if (!h->fqrow && demux_row_build(h, &h->fqrow, 0, h->C, fmx_oct_chunk())) return 1;
+        rc = fmx_oct_estep_launch(h, h->fqrow, c0, nc);
+        break;
+      case path_choice::fmx_estep_path::row2:  // two clusters per lane
+        rc = fmx_row2_estep_launch(h, st, c0, nc);
+        break;
+      case path_choice::fmx_estep_path::wave:  // one wave per cell (part) and block
+        rc = fmx_wave_estep_launch(h, c0, nc);
+        break;
+      case path_choice::fmx_estep_path::pair: {  // the plain kernel: workgroup <-> (cell, tile of pairs)
+        const int T = 256, PPT = 4;
+        const unsigned tiles = (unsigned)((npairs + T * PPT - 1) / (T * PPT));
+        hipLaunchKernelGGL(fmx_estep_pair_kernel<PPT>, dim3((unsigned)nc, tiles), dim3(T), 0, h->stream, h->d_cell_ptr,
+                           h->d_entry_snp, h->d_egls, h->d_cgp, K, c0, h->d_fll);
+        break;
+      }
+    }
+    if (rc) return 1;
   }
   toc(h, MUXGL_T_FMX_ESTEP);
   tic(h, MUXGL_T_FMX_CALL);
@@ -1095,8 +1104,7 @@ int fmx_phase_estep(muxgl_handle* h, const muxgl_fmx_params* p) {
   const double ldp = log(p->doublet_prior / K / (K - 1) * 2.0);  // :380
   if (nc > 0)
   {
-    if ((h->flags & MUXGL_FLAG_FORCE_TILE_SWEEP) || K <= 24)  // (few hypotheses per cell: a wave per cell is mostly overhead,
-                                                             //  0.54 against 0.13 ms at configs[3])
+    if (path_choice::choose_fmx_call(K, h->flags) == path_choice::fmx_call_path::lane_per_cell)
       hipLaunchKernelGGL(fmx_call_kernel<false>, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, h->stream, c0, c1, K,
                          lsp, ldp, h->d_fll, h->d_fcells, h->d_clust, h->d_fstat, h->d_prev_state, h->d_flagged,
                          h->d_xc_epoch, h->d_xc, h->xs_epoch);

@@ -212,11 +212,10 @@ int mstep_go(muxgl_handle* h, int64_t ns) {
 
 }  // namespace
 
-// -1: not applicable (K > 64 or an empty pileup: fmx_mstep_snp_kernel)
+// K <= 64 and a pileup that is not empty (path_choice.hpp)
 int fmx_mstep_stream_launch(muxgl_handle* h) {
   const int64_t ns = h->fs1 - h->fs0;
   const int K = h->K;
-  if (K > 64 || ns <= 0 || h->nnz <= 0 || h->C <= 0) return -1;
   const int64_t C = h->C;  // cells d_clust spans (a column slab: the cells of the whole job)
   if (h->clust8_n != C || !h->d_clust8) {
     if (dev_alloc(h, &h->d_clust8, (size_t)((C + 15) / 16 * 16))) return 1;

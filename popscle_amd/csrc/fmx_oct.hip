@@ -378,10 +378,8 @@ int fo_unit_ptr(muxgl_handle* h, const int32_t* d_steps, int n_units, int64_t** 
 
 }  // namespace
 
-// oct E-step for the cell shard [c0, c0+nc) described by the chunk tables st; -1 if not applicable
+// oct E-step (K <= 16, S + 1 < 2^23: path_choice.hpp) for the cell shard [c0, c0+nc) described by the chunk tables st
 int fmx_oct_estep_launch(muxgl_handle* h, muxgl_row_state* st, int64_t c0, int64_t nc) {
-  if (h->K > 16 || !st || (h->flags & (MUXGL_FLAG_FORCE_TILE_SWEEP | MUXGL_FLAG_FORCE_ROW_KERNEL))) return -1;
-  if (h->S + 1 >= ((int64_t)1 << 23)) return -1;  // (32-bit byte offsets of the rows)
   if (!st->d_tmap) {
     if (dev_alloc(h, &st->d_tmap, 32)) return 1;
     hipLaunchKernelGGL(pmap_kernel, dim3(1), dim3(64), 0, h->stream, st->d_tmap);

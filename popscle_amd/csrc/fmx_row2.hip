@@ -136,17 +136,15 @@ __global__ void __launch_bounds__(192)
 
 }  // namespace
 
-// E-step with two clusters per lane for the cell shard [c0, c0+nc) described by the chunk tables st; -1 if not applicable
+// E-step with two clusters per lane (17..32 clusters, partials within ROW2_PART_LIMIT: path_choice.hpp) for the cell
+// shard [c0, c0+nc) described by the chunk tables st
 int fmx_row2_estep_launch(muxgl_handle* h, muxgl_row_state* st, int64_t c0, int64_t nc) {
-  if (h->K <= 16 || h->K > 32 || !st) return -1;
-  if (h->flags & (MUXGL_FLAG_FORCE_TILE_SWEEP | MUXGL_FLAG_FORCE_WAVE_KERNEL)) return -1;
   if (!st->d_tmap) {  // (the quad tile-map slot of this table set is unused beyond 16 clusters) lane map of the rotations
     if (dev_alloc(h, &st->d_tmap, 9 * 16)) return 1;
     hipLaunchKernelGGL(row2_kmap_kernel, dim3(1), dim3(64), 0, h->stream, st->d_tmap);
     HIPCHK(h, hipGetLastError());
   }
   const size_t need = (size_t)st->n_chunks * F2_NACC * 16;
-  if ((double)need * 8.0 > ROW2_PART_LIMIT) return -1;
   if (need > st->part_cap) {
     if (dev_alloc(h, &st->d_part, need)) return 1;
     st->part_cap = need;

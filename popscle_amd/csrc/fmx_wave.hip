@@ -538,13 +538,12 @@ static int fmx_wave_streams_build(muxgl_handle* h) {
   return 0;
 }
 
-// returns -1 when this path does not apply, 0 ok, 1 error
+// 32 < K and a wave plan with work units (path_choice.hpp)
 int fmx_wave_estep_launch(muxgl_handle* h, int64_t c0, int64_t nc) {
-  if (h->K <= 32 || (h->flags & MUXGL_FLAG_FORCE_TILE_SWEEP)) return -1;  // (up to 32 clusters: fmx_row2.hip, fmx_oct.hip)
   const wave_item* items;
   const wave_cut* cuts;
   int64_t n_items, n_cuts, n_over;
-  if (demux_wave_items(h, &items, &n_items, &cuts, &n_cuts, &n_over) || n_items == 0) return -1;
+  if (demux_wave_items(h, &items, &n_items, &cuts, &n_cuts, &n_over)) MUXGL_FAIL(h, "internal: wave E-step without a wave plan");
   const int nblk = (h->K + 63) / 64;
   const bool use_lin = h->d_flin && !(h->flags & MUXGL_FLAG_NO_LINEAR_ENTRIES);  // linear-entry stream
   if (use_lin) {

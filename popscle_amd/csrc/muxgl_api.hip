@@ -426,7 +426,6 @@ void muxgl_destroy(muxgl_handle* h) {
   dev_free(&h->d_segls6);
   dev_free(&h->d_scode);
   dev_free(&h->d_mtab);
-  dev_free(&h->d_egls6);
   dev_free(&h->d_cgpq);
   dev_free(&h->d_ceq);
   dev_free(&h->d_secnt);

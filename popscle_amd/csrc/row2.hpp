@@ -47,7 +47,4 @@ __device__ __forceinline__ bool row2_pair_of(int a, int j, const int32_t* __rest
   return true;
 }
 
-// per-chunk partials beyond this many bytes: the caller falls back to the wave kernels
-constexpr double ROW2_PART_LIMIT = 64e9;
-
 }  // namespace

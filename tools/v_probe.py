@@ -1,6 +1,7 @@
 #!/usr/bin/env python
-"""demuxlet pass time for a given number of samples (which sweep kernel a shape gets: quad/row <= 16, wave <= 64, tile
-sweep above):  python tools/v_probe.py V cells [snps]"""
+"""demuxlet pass time for a given number of samples (which sweep kernel a shape gets: popscle_amd/csrc/path_choice.hpp,
+choose_demux_path -- oct/row up to 16, oct/row2/wave up to 32, wave up to 255 but tile at 65..72, streamed call beyond):
+python tools/v_probe.py V cells [snps]"""
 import json
 import os
 import sys
