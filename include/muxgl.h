@@ -42,6 +42,10 @@ extern "C" {
 /* demuxlet: largest V of muxgl_demux_set_gp.  The scans name a doublet by its int32 position (j V + k) n_alpha + n, so
  * V * V * n_alpha < 2^31: 11585 samples (2^31 / 16 alphas, square root); muxgl_demux_run checks the product for its grid */
 #define MUXGL_MAX_SAMPLES 11585
+/* freemuxlet: largest K of muxgl_fmx_greedy_init and muxgl_fmx_set_clusters.  The serial greedy start
+ * (fmx_greedy_kernel, one workgroup of 1024 threads) holds one stripe of Kp clusters, K rounded up to a power of two, in
+ * its threads: Kp <= 1024.  Beyond 255 clusters the EM takes the streamed E-step (see muxgl_fmx_iterate). */
+#define MUXGL_MAX_CLUSTERS 1024
 
 enum { MUXGL_SNG = 0, MUXGL_DBL = 1, MUXGL_AMB = 2 };
 
@@ -73,6 +77,9 @@ enum { MUXGL_SNG = 0, MUXGL_DBL = 1, MUXGL_AMB = 2 };
 #define MUXGL_FLAG_FORCE_STREAMED_CALL 2048 /* demuxlet beyond 32 samples: take the streamed call (demux_stream.hip), which
                                             jobs with more than 255 samples take anyway (lets tests compare it with the
                                             other paths) */
+#define MUXGL_FLAG_FORCE_STREAMED_ESTEP 4096 /* freemuxlet beyond 32 clusters: take the streamed E-step (fmx_stream.hip),
+                                             which jobs with more than 255 clusters take anyway (lets tests compare it with
+                                             the other paths) */
 #define MUXGL_FLAG_SPLIT_GENERAL_SWEEP 512 /* demuxlet beyond 32 samples: sweep the entries with more than one usable read in
                                              launches of their own on top of the linear entries' slab (round 3's scheme)
                                              instead of in the same launch with the same accumulators (lets tests
@@ -275,7 +282,12 @@ int muxgl_fmx_greedy_stats(const muxgl_handle* h, int64_t* near_ties, int64_t* o
 int muxgl_fmx_set_clusters(muxgl_handle* h, int32_t K, const int32_t* clust);
 
 /* one EM iteration, cmd_cram_freemux2.cpp:375-597: E-step, scans, re-assignment, ordered M-step.
- * out: NULL or [C].  full_ll: NULL or [C][K(K+1)/2]. */
+ * out: NULL or [C].  full_ll: NULL or [C][K(K+1)/2].
+ * The streamed E-step (K > 255, MUXGL_FLAG_FORCE_STREAMED_ESTEP at K > 32, or a K <= 255 job whose [C][K(K+1)/2] table
+ * does not fit 0.9 x the device's memory) sweeps the pair matrix in 64 x 64 blocks of clusters, a group of
+ * (cells x blocks) at a time, and keeps only what the call reads per cell: its device memory does not depend on C x K^2
+ * (a slab budget of 4 GiB or a third of device memory; MUXGL_FMX_SLAB_MB in the environment overrides it).  It keeps no
+ * [C][K(K+1)/2] table, so full_ll must be NULL there: otherwise the call fails with an error. */
 int muxgl_fmx_iterate(muxgl_handle* h, const muxgl_fmx_params* p, muxgl_fmx_cell* out, int32_t* nsingle, int32_t* namb,
                       int32_t* nchanged, double* full_ll);
 

@@ -62,7 +62,7 @@ def source_hash(config: int | None = None) -> str | None:
     """config given: fingerprint of the machine code of that config's kernel family (FAMILY_UNITS), cached in
     popscle_amd/lib/code_hashes.json next to the objects it was taken from (the cache travels with the built library;
     it is recomputed when an object file is newer).  None when it cannot be determined (no objects, no LLVM tools).
-    No config: fingerprint of all kernel SOURCES (csrc/*.hip, *.hpp, include/muxgl.h)."""
+    No config: fingerprint of all kernel SOURCES (csrc/*.hip, *.hpp, *.inc, include/muxgl.h)."""
     import glob
     import hashlib
     import json
@@ -82,7 +82,8 @@ def source_hash(config: int | None = None) -> str | None:
             return None
         return hashlib.sha256("".join(u + cache[u] for u in units).encode()).hexdigest()[:16]
     h = hashlib.sha256()
-    files = sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")))
+    files = sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")) +
+                   glob.glob(os.path.join(CSRC, "*.inc")))
     files.append(os.path.join(os.path.dirname(HERE), "include", "muxgl.h"))
     for f in files:
         h.update(os.path.basename(f).encode())

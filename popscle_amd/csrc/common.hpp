@@ -194,12 +194,20 @@ struct muxgl_handle {
   int64_t clust8_n = -1;
   muxgl_fmx_cell* d_fcells = nullptr;
   muxgl_fmx_cell* h_fcells = nullptr;  // pinned
-  double* d_fll = nullptr;        // [C][K(K+1)/2]
+  double* d_fll = nullptr;        // [C][K(K+1)/2]; not allocated when the E-step is streamed (fmx_stream.hip)
+  bool fmx_streamed = false;      // muxgl_fmx_set_clusters chose the streamed E-step (path_choice.hpp)
+  // the streamed E-step's buffers (fmx_stream.hip), kept between iterations: block list, slab, per-cell states
+  int32_t* d_fblocks = nullptr;
+  int fblocks_k = -1;
+  double* d_fslab = nullptr;
+  size_t fslab_cap = 0;
+  double* d_fss = nullptr;
+  size_t fss_cap = 0;
   int32_t* d_fstat = nullptr;     // nsingle, namb, nchanged, cells listed for the exact-call path
   // near-tie calls (fmx_exact.hip): what fmx_call_kernel keeps aside for the exact path
   int32_t* d_prev_clust = nullptr;  // the assignments the cluster pileups of the running iteration were built from: a copy
                                     // of d_clust taken before the call kernel runs, on the handle that runs the M-step
-  int32_t* d_prev_state = nullptr;  // [C] (type, jBest, kBest) before the running iteration, a byte each
+  int32_t* d_prev_state = nullptr;  // [C] (type, jBest, kBest) before the running iteration (fmx_pack_prev)
   int32_t* d_flagged = nullptr;     // [C] cells whose call is within rounding reach, d_fstat[3] of them
   int32_t* d_xc_epoch = nullptr;    // [C] epoch a cell's entry of d_xc was written in (0: none)
   fmx_xc* d_xc = nullptr;           // [C] exact scan results of settled cells
@@ -560,6 +568,9 @@ int demux_wave_items(const muxgl_handle* h, const wave_item** items, int64_t* n_
                      int64_t* n_cuts, int64_t* n_over);  // work units of the wave kernels (device)
 int fmx_wave_estep_launch(muxgl_handle* h, int64_t c0, int64_t nc);  // 32 < K <= 255
 int64_t fmx_wave_fll_rows(const muxgl_handle* h);  // rows of d_fll: C + extra parts of long cells
+int fmx_stream_estep_launch(muxgl_handle* h, const muxgl_fmx_params* p, int64_t c0, int64_t nc);  // fmx_stream.hip
+int fmx_stream_call_launch(muxgl_handle* h, int64_t c0, int64_t c1, double lsp, double ldp);
+int fmx_stream_rows(muxgl_handle* h, const std::vector<int32_t>& cells, double* rows);  // deep-tie rows, host
 void fmx_wave_streams_release(muxgl_handle* h);  // the linear/general entry streams and their rank table
 int demux_ensure_ll(muxgl_handle* h, const muxgl_demux_params* p);  // standard LL tensor allocated and zeroed
 int demux_call_wave_launch(muxgl_handle* h, const muxgl_demux_params* p);

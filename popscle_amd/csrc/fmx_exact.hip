@@ -39,6 +39,7 @@
 
 #include "common.hpp"
 #include "exact_arith.hpp"
+#include "fmx_call_body.hpp"
 
 namespace {
 
@@ -396,7 +397,14 @@ int fmx_exact_finish(muxgl_handle* h, const muxgl_fmx_params* p, const int32_t* 
       }
     }
     deep_rows.resize((size_t)dof.back());
-    if (gather_spans<double>(h, so, dof, h->d_fll, deep_rows.data())) return 1;
+    if (h->fmx_streamed) {  // no table: the listed cells' rows swept again (fmx_stream.hip)
+      std::vector<int32_t> dc;
+      for (size_t f = 0; f < nf; ++f)
+        if (deep_at[f] >= 0) dc.push_back(xs.cells[f]);
+      if (fmx_stream_rows(h, dc, deep_rows.data())) return 1;
+    } else if (gather_spans<double>(h, so, dof, h->d_fll, deep_rows.data())) {
+      return 1;
+    }
   }
   for (size_t f = 0; f < nf; ++f) {
     const muxgl_fmx_cell& x = xs.info[f].rec;
@@ -497,8 +505,8 @@ int fmx_exact_finish(muxgl_handle* h, const muxgl_fmx_params* p, const int32_t* 
     c.dblBestLLK = td.bv, c.dblNextLLK = td.nv;
     // state before this iteration (what the nchanged rules compare with, :523,543-544,566)
     const int32_t ps = xs.info[f].prev;
-    auto byte = [](int32_t v) { return v == 0xff ? -1 : v; };
-    const int32_t ptype = (int8_t)(ps & 0xff), pj = byte((ps >> 8) & 0xff), pk = byte((ps >> 16) & 0xff);
+    int32_t ptype, pj, pk;
+    fmx_unpack_prev(ps, K > 255, &ptype, &pj, &pk);
     int chg;
     c.clust = -1;  // :520
     if (c.dblBestLLK > c.sngBestLLK + 2) {  // :521

@@ -65,6 +65,7 @@ __device__ __forceinline__ double greedy_score(double m2, int32_t e2, double m0,
 
 constexpr double kMinNormGL = 1e-6;  // sc_drop_seq.h:14
 constexpr int GT = 1024;             // threads of the persistent workgroup
+static_assert(MUXGL_MAX_CLUSTERS <= GT, "the serial kernel holds one stripe of Kp clusters in its threads");
 constexpr int GU = 6;                // gathers a thread has in flight in the distance phase
 constexpr int ST = GT;               // entries staged in LDS per pass (one per thread)
 
@@ -1287,7 +1288,8 @@ extern "C" int muxgl_fmx_greedy_init(muxgl_handle* h, int32_t K, const double* s
   if (h->col) MUXGL_FAIL(h, "muxgl_fmx_greedy_init: needs the whole pileup on one handle (this one holds slabs)");
   HIPCHK(h, hipSetDevice(h->device));
   if (!h->fmx_prepared) MUXGL_FAIL(h, "muxgl_fmx_greedy_init: call muxgl_fmx_prepare first");
-  if (K < 1 || K > 255) MUXGL_FAIL(h, "muxgl_fmx_greedy_init: K=%d outside [1,255]", K);
+  if (K < 1 || K > MUXGL_MAX_CLUSTERS)  // (the serial kernel's stripe of Kp <= GT clusters: muxgl.h)
+    MUXGL_FAIL(h, "muxgl_fmx_greedy_init: K=%d outside [1,%d] (MUXGL_MAX_CLUSTERS)", K, MUXGL_MAX_CLUSTERS);
   if ((!scores || !clust_out) && h->C) MUXGL_FAIL(h, "muxgl_fmx_greedy_init: NULL array");
   const int64_t C = h->C, S = h->S;
   host_timer tm;

@@ -21,6 +21,7 @@
 
 #include "common.hpp"
 #include "demux_call_body.hpp"
+#include "fmx_call_body.hpp"
 #include "score_exact.hpp"
 
 namespace {
@@ -261,30 +262,7 @@ __global__ void __launch_bounds__(256)
 
 // ------------------------------------------------------------------------------------------------ scans + re-assignment
 
-// cmd_cram_freemux2.cpp:458-584 for one cell per lane; stat[0..2] = nsingle, namb, nchanged
-// top two of a scan under the reference's update rule (strict >, first come first kept): the two largest under the
-// total order (value descending, scan position ascending), which is associative -- lanes scan strided positions and
-// merge their lists
-struct fmx_top2 {
-  double v1, v2;
-  int32_t p1, p2;
-  double v3;  // third-largest value (no position), for the exact-call pass: see muxgl_fmx_cell
-};
-__device__ __forceinline__ bool fmx_better(double va, int32_t pa, double vb, int32_t pb) {
-  return va > vb || (va == vb && pa < pb);
-}
-__device__ __forceinline__ void fmx_top2_push(fmx_top2& t, double v, int32_t p) {
-  if (fmx_better(v, p, t.v1, t.p1)) {
-    t.v3 = t.v2;
-    t.v2 = t.v1, t.p2 = t.p1;
-    t.v1 = v, t.p1 = p;
-  } else if (fmx_better(v, p, t.v2, t.p2)) {
-    t.v3 = t.v2;
-    t.v2 = v, t.p2 = p;
-  } else {
-    t.v3 = fmax(t.v3, v);
-  }
-}
+// cmd_cram_freemux2.cpp:458-584; stat[0..2] = nsingle, namb, nchanged.  Top two of a scan: fmx_call_body.hpp
 __device__ __forceinline__ fmx_top2 fmx_top2_wave(fmx_top2 t) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
@@ -441,111 +419,8 @@ __global__ void __launch_bounds__(64)
   if (sall > 0.0) sumLLK = mall + log(sall);
   if (ssng > 0.0) sngLLK = msng + log(ssng);
   }
-  // (round 6) A decision whose margin is within rounding reach of the kernels' numbers -- best / next of a scan, next /
-  // third, one of the four +2 thresholds -- is not this kernel's to make: the cell goes on the list fmx_exact.hip settles
-  // in the reference's own arithmetic.  What that needs of the state BEFORE this iteration is kept aside (the previous
-  // (type, jBest, kBest) of the nchanged rules below; the assignments the cluster pileups were built from: the launcher).
-  // A cell settled in an earlier iteration whose inputs have not changed since (no assignment changed anywhere: same
-  // `epoch`) takes the exact scan results from the table instead of being listed again: a converged job pays nothing.
-  bool listed = false;
-  double sngBestDev = -1e300;  // the kernels' own value where the table overrides it (sngOnlyPP stays what a listed cell keeps)
-  bool from_table = false;
-  if (prev_state) {
-    double mag = 1.0;
-    if (sngBestLLK > -1e299) mag = fmax(mag, fabs(sngBestLLK));
-    if (dblBestLLK > -1e299) mag = fmax(mag, fabs(dblBestLLK));
-    if (sngNextLLK > -1e299) mag = fmax(mag, fabs(sngNextLLK));
-    if (dblNextLLK > -1e299) mag = fmax(mag, fabs(dblNextLLK));
-    const double eps = 1e-9 * mag;
-    auto near = [eps](double a, double b) { return a > -1e299 && b > -1e299 && fabs(a - b) <= eps; };
-    if (near(sngBestLLK, sngNextLLK) || near(sngNextLLK, sngThird) || near(dblBestLLK, dblNextLLK) ||
-        near(dblNextLLK, dblThird) || near(dblBestLLK, sngBestLLK + 2) || near(dblNextLLK, sngBestLLK + 2) ||
-        near(sngBestLLK, sngNextLLK + 2) || near(dblBestLLK, sngNextLLK + 2)) {
-      if (xc_epoch && xc_epoch[i] == epoch) {
-        const fmx_xc e = xc[i];
-        sngBestDev = sngBestLLK;
-        from_table = true;
-        sBest = e.sBest, sNext = e.sNext, dBest1 = e.dBest1, dBest2 = e.dBest2, dNext1 = e.dNext1, dNext2 = e.dNext2;
-        sngBestLLK = e.sngBestLLK, sngNextLLK = e.sngNextLLK, dblBestLLK = e.dblBestLLK, dblNextLLK = e.dblNextLLK;
-      } else {
-        listed = true;
-      }
-    }
-  }
-  muxgl_fmx_cell c = cells[i];
-  const int32_t prev_type = c.type, prev_j = c.jBest, prev_k = c.kBest;
-  c.sBest = sBest;
-  c.sngBestLLK = sngBestLLK;
-  c.sNext = sNext;
-  c.sngNextLLK = sngNextLLK;
-  c.dBest1 = dBest1;
-  c.dBest2 = dBest2;
-  c.dblBestLLK = dblBestLLK;
-  c.dNext1 = dNext1;
-  c.dNext2 = dNext2;
-  c.dblNextLLK = dblNextLLK;
-  c.sngPP = exp(sngLLK - sumLLK);
-  c.sngOnlyPP = exp((from_table ? sngBestDev : sngBestLLK) + log_single_prior - sngLLK);
-  c.sumLLK = sumLLK;
-  c.sngThirdLLK = sngThird;
-  c.dblThirdLLK = dblThird;
-
-  int32_t dsingle = 0, damb = 0, dchanged = 0;
-  c.clust = -1;                           // :520
-  if (dblBestLLK > sngBestLLK + 2) {      // :521
-    if (c.type != 1) dchanged = 1;
-    c.type = 1;
-    c.bestPP = (dblBestLLK + log_double_prior - sumLLK);
-    c.jBest = dBest1;
-    c.kBest = dBest2;
-    c.bestLLK = dblBestLLK;
-    if (dblNextLLK > sngBestLLK + 2) {
-      c.jNext = dNext1;
-      c.kNext = dNext2;
-      c.nextLLK = dblNextLLK;
-    } else {
-      c.jNext = c.kNext = sBest;
-      c.nextLLK = sngBestLLK;
-    }
-  } else if (sngBestLLK > sngNextLLK + 2) {  // :542
-    if ((c.type != 0) || (c.jBest != sBest) || (c.kBest != sBest)) dchanged = 1;
-    c.type = 0;
-    dsingle = 1;
-    c.bestPP = (sngBestLLK + log_single_prior - sumLLK);
-    c.jBest = c.kBest = sBest;
-    c.bestLLK = sngBestLLK;
-    c.clust = sBest;
-    if (dblBestLLK > sngNextLLK + 2) {
-      c.jNext = dBest1;
-      c.kNext = dBest2;
-      c.nextLLK = dblBestLLK;
-    } else {
-      c.jNext = c.kNext = sNext;
-      c.nextLLK = sngNextLLK;
-    }
-  } else {  // :565
-    if (c.type != 2) dchanged = 1;
-    c.type = 2;
-    damb = 1;
-    c.bestPP = (sngBestLLK + log_single_prior - sumLLK);
-    c.jBest = c.kBest = sBest;
-    c.bestLLK = sngBestLLK;
-    if (dblBestLLK > sngNextLLK + 2) {
-      c.jNext = dBest1;
-      c.kNext = dBest2;
-      c.nextLLK = dblNextLLK;  // sic, :577
-    } else {
-      c.jNext = c.kNext = sNext;
-      c.nextLLK = sngNextLLK;
-    }
-  }
-  if (prev_state) prev_state[i] = (prev_type & 0xff) | ((prev_j & 0xff) << 8) | ((prev_k & 0xff) << 16);
-  if (listed) flagged[atomicAdd(&stat[3], 1)] = (int32_t)i;
-  cells[i] = c;
-  clust[i] = c.clust;
-  if (dsingle) atomicAdd(&stat[0], 1);
-  if (damb) atomicAdd(&stat[1], 1);
-  if (dchanged) atomicAdd(&stat[2], 1);
+  constexpr bool FMX_WIDE_PREV = false;
+#include "fmx_call_finish.inc"
 }
 
 // ------------------------------------------------------------------------------------------------ M-step
@@ -954,6 +829,13 @@ int fmx_cluster_counts_device(muxgl_handle* m) {
   return 0;
 }
 
+// the bytes of d_fll and of the device, the facts of the E-step's fit rule (path_choice.hpp)
+static void fmx_fll_facts(const muxgl_handle* h, int K, double* fll_bytes, double* device_bytes) {
+  size_t fr = 0, tot = 0;
+  *fll_bytes = path_choice::fmx_fll_bytes(fmx_wave_fll_rows(h), K);
+  *device_bytes = hipMemGetInfo(&fr, &tot) == hipSuccess ? (double)tot : 0.0;
+}
+
 extern "C" {
 
 int muxgl_fmx_set_clusters(muxgl_handle* h, int32_t K, const int32_t* clust) {
@@ -961,7 +843,8 @@ int muxgl_fmx_set_clusters(muxgl_handle* h, int32_t K, const int32_t* clust) {
   if (h->group) return group_fmx_set_clusters(h, K, clust);
   HIPCHK(h, hipSetDevice(h->device));
   if (!h->fmx_prepared) MUXGL_FAIL(h, "muxgl_fmx_set_clusters: call muxgl_fmx_prepare first");
-  if (K < 1 || K > 255) MUXGL_FAIL(h, "muxgl_fmx_set_clusters: K=%d outside [1,255]", K);
+  if (K < 1 || K > MUXGL_MAX_CLUSTERS)
+    MUXGL_FAIL(h, "muxgl_fmx_set_clusters: K=%d outside [1,%d] (MUXGL_MAX_CLUSTERS)", K, MUXGL_MAX_CLUSTERS);
   const int64_t C = h->C, S = h->S;
   const int64_t CT = h->col ? h->C_total : C, cb = h->col ? h->cell_base : 0;  // clust[] spans the whole job
   if (!clust && CT) MUXGL_FAIL(h, "muxgl_fmx_set_clusters: clust is NULL");
@@ -973,7 +856,15 @@ int muxgl_fmx_set_clusters(muxgl_handle* h, int32_t K, const int32_t* clust) {
   if (dev_alloc(h, &m->d_cgls, (size_t)K * S * 9)) return 1;
   if (dev_alloc(h, &m->d_ccnt, (size_t)K * S * 3)) return 1;
   if (dev_alloc(h, &h->d_cgp, (size_t)(S + MUXGL_XCHG_PAD) * K * 3)) return 1;
-  if (dev_alloc(h, &h->d_fll, (size_t)fmx_wave_fll_rows(h) * K * (K + 1) / 2)) return 1;
+  {  // the streamed E-step keeps no [C][K(K+1)/2] table (only the choice between it and the others is made here)
+    path_choice::fmx_estep_facts f = {};
+    f.K = K;
+    f.flags = h->flags;
+    fmx_fll_facts(h, K, &f.fll_bytes, &f.device_bytes);
+    h->fmx_streamed = path_choice::choose_fmx_estep(f) == path_choice::fmx_estep_path::stream;
+  }
+  if (h->fmx_streamed) dev_free(&h->d_fll);
+  else if (dev_alloc(h, &h->d_fll, (size_t)fmx_wave_fll_rows(h) * K * (K + 1) / 2)) return 1;
   if (h->col) {  // rows of SNPs outside the own range stay zero until a caller gathers them
     HIPCHK(h, hipMemsetAsync(m->d_cgls, 0, sizeof(double) * (size_t)K * S * 9, h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_cgp, 0, sizeof(double) * (size_t)(S + MUXGL_XCHG_PAD) * K * 3, h->stream));
@@ -1058,10 +949,15 @@ int fmx_phase_estep(muxgl_handle* h, const muxgl_fmx_params* p) {
   tic(h, MUXGL_T_FMX_ESTEP);
   if (nc > 0) {
     muxgl_row_state* st = h->frow ? h->frow : h->row;
+    // (the streamed E-step or not: decided by muxgl_fmx_set_clusters, which allocated d_fll or not; the facts of that
+    //  decision, fll_bytes and device_bytes, stay zero here)
     const path_choice::fmx_estep_facts f = {K, h->flags, h->S, h->fqrow != nullptr, h->qrow != nullptr, st != nullptr,
                                             st ? row2_part_bytes(st) : 0.0, h->wave ? h->wave->n_items : 0};
+    const path_choice::fmx_estep_path path = h->fmx_streamed ? path_choice::fmx_estep_path::stream : path_choice::choose_fmx_estep(f);
+    if (path == path_choice::fmx_estep_path::stream && !h->fmx_streamed)
+      MUXGL_FAIL(h, "internal: the streamed E-step was not chosen when the clusters were set");
     int rc = 0;
-    switch (path_choice::choose_fmx_estep(f)) {
+    switch (path) {
       case path_choice::fmx_estep_path::oct:  // eight lanes per entry
         // (the chunk tables of the oct E-step are its own: demuxlet's oct kernel cuts cells into longer chunks, and a
         //  sharded run must cut a cell exactly as the whole-pileup run does)
@@ -1073,6 +969,9 @@ int fmx_phase_estep(muxgl_handle* h, const muxgl_fmx_params* p) {
         break;
       case path_choice::fmx_estep_path::wave:  // one wave per cell (part) and block
         rc = fmx_wave_estep_launch(h, c0, nc);
+        break;
+      case path_choice::fmx_estep_path::stream:  // 64 x 64 blocks into per-cell states; the call follows below
+        rc = fmx_stream_estep_launch(h, p, c0, nc);
         break;
       case path_choice::fmx_estep_path::pair: {  // the plain kernel: workgroup <-> (cell, tile of pairs)
         const int T = 256, PPT = 4;
@@ -1102,7 +1001,9 @@ int fmx_phase_estep(muxgl_handle* h, const muxgl_fmx_params* p) {
   }
   const double lsp = log((1.0 - p->doublet_prior) / K);          // cmd_cram_freemux2.cpp:379
   const double ldp = log(p->doublet_prior / K / (K - 1) * 2.0);  // :380
-  if (nc > 0)
+  if (nc > 0 && h->fmx_streamed) {
+    if (fmx_stream_call_launch(h, c0, c1, lsp, ldp)) return 1;
+  } else if (nc > 0)
   {
     if (path_choice::choose_fmx_call(K, h->flags) == path_choice::fmx_call_path::lane_per_cell)
       hipLaunchKernelGGL(fmx_call_kernel<false>, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, h->stream, c0, c1, K,
@@ -1159,6 +1060,10 @@ static int fmx_phase_fetch(muxgl_handle* h, muxgl_fmx_cell* out, int32_t* nsingl
   h->fmx_listed = h->h_fstat[3];
   h->fmx_exact_unresolved += h->h_fstat[3];
   h->h_fstat[3] = 0;
+  if (full_ll && h->fmx_streamed)
+    MUXGL_FAIL(h, "muxgl_fmx_iterate: full_ll is not available on the streamed E-step (K=%d; more than 255 clusters, a "
+                  "job whose [C][K(K+1)/2] table does not fit the device, or MUXGL_FLAG_FORCE_STREAMED_ESTEP): pass "
+                  "full_ll = NULL", h->K);
   if (full_ll && C) HIPCHK(h, hipMemcpy(full_ll, h->d_fll, sizeof(double) * (size_t)C * npairs, hipMemcpyDeviceToHost));
   return 0;
 }
@@ -1172,6 +1077,9 @@ int muxgl_fmx_iterate(muxgl_handle* h, const muxgl_fmx_params* p, muxgl_fmx_cell
   if (h->col || h->fc0 != 0 || h->fc1 != h->C || h->fs0 != 0 || h->fs1 != h->S)
     MUXGL_FAIL(h, "muxgl_fmx_iterate: handle is sharded (muxgl_fmx_set_shard / muxgl_fmx_set_column_slab); use the "
                   "muxgl_fmx_iter_* phases");
+  if (full_ll && h->fmx_streamed) MUXGL_FAIL(h, "muxgl_fmx_iterate: full_ll is not available on the streamed E-step (K=%d; more than 255 clusters, a "
+                  "job whose [C][K(K+1)/2] table does not fit the device, or MUXGL_FLAG_FORCE_STREAMED_ESTEP): pass "
+                  "full_ll = NULL", h->K);
   clear_timing(h);
   if (fmx_phase_gp(h, p) || fmx_phase_estep(h, p) || fmx_phase_mstep(h)) return 1;
   HIPCHK(h, hipStreamSynchronize(h->stream));

@@ -1,0 +1,498 @@
+// fmx_stream.hip -- the streamed freemuxlet E-step and call: up to MUXGL_MAX_CLUSTERS clusters, device memory independent
+// of C x K^2.
+//
+// Every other E-step writes the whole [C][K(K+1)/2] table d_fll, which the call kernel then scans (263 KB a cell at
+// K = 256, 4.2 MB at K = 1024).  The call only needs a few numbers per cell: the best, next and third value of each scan
+// and the two evidence sums.  So here the pair matrix is walked in 64 x 64 blocks of clusters (X >= Y), a GROUP of
+// (cells x blocks) at a time whose slab fits a fixed budget; after each group a fold kernel merges the slab into a running
+// state per cell, and the slab is reused.  A last kernel makes the call from that state with the tail every freemuxlet call
+// kernel ends in (fmx_call_finish.inc).  The design of demux_stream.hip, with the entry's nine genotype-pair likelihoods in
+// the role of pG.
+//
+// Reference being replaced: cmd_cram_freemux2.cpp:383-456 (E-step), :458-513 (scans), :515-584 (re-assignment).
+//
+// Arithmetic.  Each hypothesis is the factor and the product order of the wave E-step (fmx_wave.hip), in a plainer
+// mapping, so that a job below 256 clusters gets the wave path's log-likelihoods bit for bit on this path:
+//   * diagonal block X = Y: lane j holds cluster 64X + j; wave w takes the rotations t = 8w + 1 .. 8w + 8 of the wave
+//     kernel (partner 64X + ((j - t) mod 64), rotation 32 written by the higher lane only), so every pair is formed by the
+//     lane and in the orientation the wave kernel forms it.  With linear entries (MUXGL_FLAG_NO_LINEAR_ENTRIES unset) those
+//     come first, in the one-moment form c0 + c1 (E_j + E_k), then the others; without MUXGL_FLAG_NO_PIVOT_SUMS the others'
+//     pair sums are taken around the lane's smallest u.  Slot t - 1 of the block's slab holds rotation t, slot 32 the
+//     singlet (the diagonal of glis);
+//   * off-diagonal block X > Y: lane j holds cluster 64X + j and wave w the partners 64Y + 16w .. 64Y + 16w + 15, every
+//     entry in entry order through the three-term sum; slot k holds partner 64Y + k;
+//   * a cell of more than 2048 entries is cut into the parts of the wave plan (demux_wave_plan): one product per part,
+//     their logs added in entry order, as fmx_wave_combine_kernel does.  The sweep walks a cell's parts itself, so nothing
+//     else is needed for long cells.
+// Products are mantissa x 2^exponent with one log per (cell, hypothesis); the renormalisation points do not change a bit
+// (scaling by powers of two is exact, and pos_log takes the exponent apart itself).
+//
+// State per cell (fmx_stream_state): fmx_top2 of the singlet and of the doublet scan (value, position p = j(j+1)/2 + k, and
+// the third value), the evidence sums as (largest term, sum of exp(term - largest)) of all hypotheses with their priors and
+// of the singlets without.  Order: value descending, then position ascending (fmx_better) -- the order fmx_top2_push and
+// the reference's strict `>` updates leave, a total order, so grouping cannot change the top two or the third value.
+// A block's partial is reduced in a fixed tree and merged into the state in block order: records are bit-identical
+// whatever the budget.
+#include <algorithm>
+#include <cstdlib>
+#include <vector>
+
+#include "fmx_call_body.hpp"
+
+namespace {
+
+constexpr int CB = 64;              // clusters per side of a block
+constexpr int SLAB = CB * CB;       // doubles per (cell, block) of the slab: [slot][lane]
+constexpr int64_t PART = 2048;      // entries per part of a long cell (demux_wave_plan's WAVE_ITEM)
+constexpr int32_t NO_POS = 0x7fffffff;
+
+struct fmx_stream_state {
+  fmx_top2 sng, dbl;
+  double M, S, Ms, Ss;  // evidence: largest term, sum of exp(term - M); the same for the singlets without their prior
+};
+constexpr int STATE_DOUBLES = (int)(sizeof(fmx_stream_state) / sizeof(double));
+static_assert(sizeof(fmx_stream_state) % sizeof(double) == 0, "the state is kept in a double buffer");
+
+__device__ __forceinline__ fmx_top2 top2_empty() { return fmx_top2{-1e300, -1e300, NO_POS, NO_POS, -1e300}; }
+
+__device__ __forceinline__ fmx_stream_state state_empty() {
+  fmx_stream_state s;
+  s.sng = s.dbl = top2_empty();
+  s.M = s.Ms = -__builtin_huge_val();
+  s.S = s.Ss = 0.0;
+  return s;
+}
+
+// a merged before b (the LSE merge is one fixed expression, so the order fixes the bits)
+__device__ __forceinline__ fmx_top2 top2_merge(fmx_top2 a, const fmx_top2& b) {
+  fmx_top2_push(a, b.v1, b.p1);
+  fmx_top2_push(a, b.v2, b.p2);
+  a.v3 = fmax(a.v3, b.v3);  // (b.v1 >= b.v2 >= b.v3 are all in the union: b.v3 can be its third at best)
+  return a;
+}
+
+__device__ __forceinline__ fmx_stream_state state_merge(const fmx_stream_state& a, const fmx_stream_state& b) {
+  using muxgl_call::exp_nonpos;
+  fmx_stream_state r;
+  r.sng = top2_merge(a.sng, b.sng);
+  r.dbl = top2_merge(a.dbl, b.dbl);
+  r.M = fmax(a.M, b.M);
+  r.S = (a.S > 0.0 ? a.S * exp_nonpos(a.M - r.M) : 0.0) + (b.S > 0.0 ? b.S * exp_nonpos(b.M - r.M) : 0.0);
+  r.Ms = fmax(a.Ms, b.Ms);
+  r.Ss = (a.Ss > 0.0 ? a.Ss * exp_nonpos(a.Ms - r.Ms) : 0.0) + (b.Ss > 0.0 ? b.Ss * exp_nonpos(b.Ms - r.Ms) : 0.0);
+  return r;
+}
+
+__device__ __forceinline__ void lse_push(double& M, double& S, double t) {
+  using muxgl_call::exp_nonpos;
+  if (!(t > -__builtin_huge_val())) return;
+  if (t > M) {
+    S = (S > 0.0 ? S * exp_nonpos(M - t) : 0.0) + 1.0;
+    M = t;
+  } else {
+    S += exp_nonpos(t - M);
+  }
+}
+
+__device__ __forceinline__ fmx_top2 top2_partner(const fmx_top2& t, int m) {
+  fmx_top2 o;
+  o.v1 = __shfl_xor(t.v1, m, 64), o.p1 = __shfl_xor(t.p1, m, 64);
+  o.v2 = __shfl_xor(t.v2, m, 64), o.p2 = __shfl_xor(t.p2, m, 64);
+  o.v3 = __shfl_xor(t.v3, m, 64);
+  return o;
+}
+
+__device__ __forceinline__ fmx_stream_state state_partner(const fmx_stream_state& s, int m) {
+  fmx_stream_state o;
+  o.sng = top2_partner(s.sng, m);
+  o.dbl = top2_partner(s.dbl, m);
+  o.M = __shfl_xor(s.M, m, 64), o.S = __shfl_xor(s.S, m, 64);
+  o.Ms = __shfl_xor(s.Ms, m, 64), o.Ss = __shfl_xor(s.Ss, m, 64);
+  return o;
+}
+
+__device__ __forceinline__ bool lin_bit(const uint32_t* __restrict__ lin, int64_t e) { return (lin[e >> 5] >> (e & 31)) & 1u; }
+
+// products of one part [e0, e1) for the lane's NS slots; DIAG: partner pk[i] per lane (rotations), else wave-uniform
+template <int NS, bool DIAG, bool LIN, bool PIV>
+__device__ __forceinline__ void sweep_part(int64_t e0, int64_t e1, const int32_t* __restrict__ entry_snp,
+                                           const double* __restrict__ egls, const uint32_t* __restrict__ lin,
+                                           const double* __restrict__ cgp, int K3, int jo, const int (&ko)[NS], bool live,
+                                           const bool (&live2)[NS], double (&acc)[NS], int32_t (&ex)[NS], double& accS,
+                                           int32_t& exS) {
+  int cnt = 0;
+  auto renorm = [&]() {
+    if (++cnt == 16) {  // a factor is >= ~1e-13 (clamped likelihoods, mixed posteriors): sixteen cannot underflow
+      cnt = 0;
+#pragma unroll
+      for (int i = 0; i < NS; ++i) prodacc_renorm(acc[i], ex[i]);
+      prodacc_renorm(accS, exS);
+    }
+  };
+  if (DIAG && LIN) {  // linear entries first (fw_walk_lin)
+    for (int64_t e = e0; e < e1; ++e) {
+      if (!lin_bit(lin, e)) continue;
+      const double* q = egls + (size_t)e * 9;
+      const double rc0 = q[0], u1 = q[1] - q[0];
+      const double* row = cgp + (size_t)entry_snp[e] * K3;
+      const double c0r = live ? fma(2.0, row[jo + 2], row[jo + 1]) : 0.0;  // E of the lane's cluster (fw_ce_kernel)
+      const double u0 = fma(u1, c0r, rc0);
+      accS *= fma(2.0 * u1, c0r, rc0);
+#pragma unroll
+      for (int i = 0; i < NS; ++i) {
+        const double r0 = live2[i] ? fma(2.0, row[ko[i] + 2], row[ko[i] + 1]) : 0.0;
+        acc[i] *= fma(u1, r0, u0);
+      }
+      renorm();
+    }
+  }
+  for (int64_t e = e0; e < e1; ++e) {  // the others (fw_walk_gen)
+    if (DIAG && LIN && lin_bit(lin, e)) continue;
+    const double* q = egls + (size_t)e * 9;
+    const double q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], q5 = q[5], q6 = q[6], q7 = q[7], q8 = q[8];
+    const double* row = cgp + (size_t)entry_snp[e] * K3;
+    const double g0 = live ? row[jo] : 1.0, g1 = live ? row[jo + 1] : 0.0, g2 = live ? row[jo + 2] : 0.0;
+    const double u0 = fma(g2, q6, fma(g1, q3, g0 * q0));
+    const double u1 = fma(g2, q7, fma(g1, q4, g0 * q1));
+    const double u2 = fma(g2, q8, fma(g1, q5, g0 * q2));
+    if (DIAG) accS *= fma(g2, q8, fma(g1, q4, g0 * q0));
+    if (DIAG && PIV) {
+      const bool p0 = u0 <= u1 && u0 <= u2, p1 = !p0 && u1 <= u2;
+      const double up = p0 ? u0 : (p1 ? u1 : u2);
+      const double da = (p0 ? u1 : u0) - up;
+      const double db = ((p0 || p1) ? u2 : u1) - up;
+      const int ca = p0 ? 1 : 0, cb = (p0 || p1) ? 2 : 1;
+#pragma unroll
+      for (int i = 0; i < NS; ++i) {
+        const double ra = live2[i] ? row[ko[i] + ca] : (ca == 0 ? 1.0 : 0.0);
+        const double rb = live2[i] ? row[ko[i] + cb] : 0.0;
+        acc[i] *= fma(rb, db, fma(ra, da, up));
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < NS; ++i) {
+        const double r0 = live2[i] ? row[ko[i]] : 1.0, r1 = live2[i] ? row[ko[i] + 1] : 0.0,
+                     r2 = live2[i] ? row[ko[i] + 2] : 0.0;
+        acc[i] *= fma(r2, u2, fma(r1, u1, r0 * u0));
+      }
+    }
+    renorm();
+  }
+}
+
+// the lane's NS slots of one (cell, block) over the cell's parts, written to the slab
+template <int NS, bool DIAG, bool LIN, bool PIV>
+__device__ __forceinline__ void sweep_block(int64_t b, int64_t n, int X, int Y, int w, int j,
+                                            const int32_t* __restrict__ entry_snp, const double* __restrict__ egls,
+                                            const uint32_t* __restrict__ lin, const double* __restrict__ cgp, int K,
+                                            double* __restrict__ out) {
+  const int sj = CB * X + j;
+  const bool live = sj < K;
+  const int jo = (live ? sj : K - 1) * 3;
+  int ko[NS];
+  bool live2[NS];
+#pragma unroll
+  for (int i = 0; i < NS; ++i) {
+    const int sk = DIAG ? CB * X + ((j - (NS * w + i + 1)) & 63) : CB * Y + NS * w + i;
+    live2[i] = sk < K;
+    ko[i] = (live2[i] ? sk : K - 1) * 3;
+  }
+  double sum[NS], sumS = 0.0;
+#pragma unroll
+  for (int i = 0; i < NS; ++i) sum[i] = 0.0;
+  const int64_t parts = n > PART ? (n + PART - 1) / PART : 1;
+  for (int64_t q = 0; q < parts; ++q) {
+    double acc[NS], accS = 1.0;
+    int32_t ex[NS], exS = 0;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) acc[i] = 1.0, ex[i] = 0;
+    sweep_part<NS, DIAG, LIN, PIV>(b + n * q / parts, b + n * (q + 1) / parts, entry_snp, egls, lin, cgp, K * 3, jo, ko,
+                                   live, live2, acc, ex, accS, exS);
+    if (q == 0) {
+#pragma unroll
+      for (int i = 0; i < NS; ++i) sum[i] = prodacc_log(acc[i], ex[i]);
+      sumS = prodacc_log(accS, exS);
+    } else {  // (fmx_wave_combine_kernel: the parts' rows added in entry order)
+#pragma unroll
+      for (int i = 0; i < NS; ++i) sum[i] += prodacc_log(acc[i], ex[i]);
+      sumS += prodacc_log(accS, exS);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NS; ++i) out[(NS * w + i) * CB + j] = sum[i];
+  if (DIAG && w == 0) out[32 * CB + j] = sumS;
+}
+
+// Sweep of one group: grid = (cells of the group, blocks of the group), 4 waves.  Cell = cells[c0 + x] when a cell list
+// is given (the rows of the exact pass), else c0 + x.  slab[x][z][slot][lane].
+template <bool LIN, bool PIV>
+__global__ void __launch_bounds__(256)
+    fmx_stream_sweep_kernel(int64_t c0, const int32_t* __restrict__ cells, int32_t b0, const int32_t* __restrict__ blocks,
+                            const int64_t* __restrict__ cell_ptr, const int32_t* __restrict__ entry_snp,
+                            const double* __restrict__ egls, const uint32_t* __restrict__ lin,
+                            const double* __restrict__ cgp, int K, double* __restrict__ slab) {
+  const int64_t c = cells ? (int64_t)cells[c0 + blockIdx.x] : c0 + blockIdx.x;
+  const int64_t e0 = cell_ptr[c], n = cell_ptr[c + 1] - e0;
+  const int bz = blocks[b0 + (int)blockIdx.y];
+  const int X = bz >> 16, Y = bz & 0xffff;
+  const int j = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  double* out = slab + ((size_t)blockIdx.x * gridDim.y + blockIdx.y) * SLAB;
+  if (X == Y)
+    sweep_block<8, true, LIN, PIV>(e0, n, X, Y, w, j, entry_snp, egls, lin, cgp, K, out);
+  else
+    sweep_block<16, false, false, false>(e0, n, X, Y, w, j, entry_snp, egls, lin, cgp, K, out);
+}
+
+// the valid hypotheses of thread (w, j) in block (X, Y): f(position, value, singlet)
+template <typename F>
+__device__ __forceinline__ void block_hyps(int X, int Y, int w, int j, int K, const double* __restrict__ in, F&& f) {
+  const int sj = CB * X + j;
+  if (sj >= K) return;
+  if (X == Y) {
+    for (int i = 0; i < 8; ++i) {
+      const int t = 8 * w + i + 1, kk = (j - t) & 63, sk = CB * X + kk;
+      if (sk >= K || (t == 32 && j < kk)) continue;  // rotation 32 meets every pair twice: the higher lane writes
+      const int hi = sj > sk ? sj : sk, lo = sj > sk ? sk : sj;
+      f(hi * (hi + 1) / 2 + lo, in[(t - 1) * CB + j], false);
+    }
+    if (w == 0) f(sj * (sj + 1) / 2 + sj, in[32 * CB + j], true);
+  } else {
+    for (int i = 0; i < 16; ++i) {
+      const int sk = CB * Y + 16 * w + i;
+      if (sk >= K) break;
+      f(sj * (sj + 1) / 2 + sk, in[(16 * w + i) * CB + j], false);
+    }
+  }
+}
+
+// Fold of one group: one workgroup per cell; the group's blocks in order, each reduced over the workgroup in a fixed tree
+// (thread -> wave butterfly -> the four waves in order) and merged into the cell's state
+__global__ void __launch_bounds__(256)
+    fmx_stream_fold_kernel(int64_t c0, int32_t b0, int32_t nb, const int32_t* __restrict__ blocks, int K,
+                           double log_single_prior, double log_double_prior, const double* __restrict__ slab,
+                           fmx_stream_state* __restrict__ state) {
+  __shared__ fmx_stream_state parts[4];
+  const int64_t c = c0 + blockIdx.x;
+  const int j = threadIdx.x & 63, w = threadIdx.x >> 6;
+  fmx_stream_state st = state[c];  // (read by every thread, written by thread 0 at the end)
+  for (int z = 0; z < nb; ++z) {
+    const int bz = blocks[b0 + z];
+    const int X = bz >> 16, Y = bz & 0xffff;
+    const double* in = slab + ((size_t)blockIdx.x * nb + z) * SLAB;
+    fmx_stream_state t = state_empty();
+    block_hyps(X, Y, w, j, K, in, [&](int p, double v, bool singlet) {
+      if (singlet) {
+        fmx_top2_push(t.sng, v, p);
+        lse_push(t.M, t.S, v + log_single_prior);
+        lse_push(t.Ms, t.Ss, v);
+      } else {
+        fmx_top2_push(t.dbl, v, p);
+        lse_push(t.M, t.S, v + log_double_prior);
+      }
+    });
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) t = state_merge(t, state_partner(t, m));
+    if (j == 0) parts[w] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) st = state_merge(st, state_merge(state_merge(parts[0], parts[1]), state_merge(parts[2], parts[3])));
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) state[c] = st;
+}
+
+__global__ void __launch_bounds__(256) fmx_stream_init_kernel(int64_t n, fmx_stream_state* __restrict__ st) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) st[i] = state_empty();
+}
+
+__device__ __forceinline__ int row_of(int p) {
+  int r = (int)((sqrt(8.0 * p + 1.0) - 1.0) * 0.5);
+  while ((r + 1) * (r + 2) / 2 <= p) ++r;
+  while (r * (r + 1) / 2 > p) --r;
+  return r;
+}
+
+// the call of cells [c0, c1) from their states (state[i - c0]): one lane per cell
+template <bool FMX_WIDE_PREV>
+__global__ void __launch_bounds__(64)
+    fmx_stream_call_kernel(int64_t c0, int64_t c1, double log_single_prior, double log_double_prior,
+                           const fmx_stream_state* __restrict__ state, muxgl_fmx_cell* __restrict__ cells,
+                           int32_t* __restrict__ clust, int32_t* __restrict__ stat, int32_t* __restrict__ prev_state,
+                           int32_t* __restrict__ flagged, const int32_t* __restrict__ xc_epoch,
+                           const fmx_xc* __restrict__ xc, int32_t epoch) {
+  const int64_t i = c0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= c1) return;
+  const fmx_stream_state s = state[i - c0];
+  int32_t sBest = -1, sNext = -1, dBest1 = -1, dBest2 = -1, dNext1 = -1, dNext2 = -1;
+  double sngBestLLK = -1e300, sngNextLLK = -1e300, dblBestLLK = -1e300, dblNextLLK = -1e300;
+  double sumLLK = -1e300, sngLLK = -1e300;
+  if (s.S > 0.0) sumLLK = s.M + log(s.S);
+  if (s.Ss > 0.0) sngLLK = s.Ms + log_single_prior + log(s.Ss);
+  if (s.sng.p1 != NO_POS) sBest = row_of(s.sng.p1), sngBestLLK = s.sng.v1;
+  if (s.sng.p2 != NO_POS) sNext = row_of(s.sng.p2), sngNextLLK = s.sng.v2;
+  if (s.dbl.p1 != NO_POS) dBest1 = row_of(s.dbl.p1), dBest2 = s.dbl.p1 - dBest1 * (dBest1 + 1) / 2, dblBestLLK = s.dbl.v1;
+  if (s.dbl.p2 != NO_POS) dNext1 = row_of(s.dbl.p2), dNext2 = s.dbl.p2 - dNext1 * (dNext1 + 1) / 2, dblNextLLK = s.dbl.v2;
+  double sngThird = s.sng.v3, dblThird = s.dbl.v3;
+#include "fmx_call_finish.inc"
+}
+
+// rows[x][p] = the E-step's value of hypothesis p of cell x of the batch, from a sweep over all blocks
+__global__ void __launch_bounds__(256)
+    fmx_stream_rows_kernel(int32_t nb, const int32_t* __restrict__ blocks, int K, const double* __restrict__ slab,
+                           double* __restrict__ rows) {
+  const int z = blockIdx.y;
+  const int bz = blocks[z];
+  const int X = bz >> 16, Y = bz & 0xffff;
+  const int j = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const double* in = slab + ((size_t)blockIdx.x * nb + z) * SLAB;
+  double* row = rows + (size_t)blockIdx.x * ((size_t)K * (K + 1) / 2);
+  block_hyps(X, Y, w, j, K, in, [&](int p, double v, bool) { row[p] = v; });
+}
+
+// the blocks (X, Y), X >= Y, in sweep order, as X << 16 | Y
+std::vector<int32_t> block_list(int K) {
+  const int nblk = (K + CB - 1) / CB;
+  std::vector<int32_t> b;
+  for (int X = 0; X < nblk; ++X)
+    for (int Y = 0; Y <= X; ++Y) b.push_back(X << 16 | Y);
+  return b;
+}
+
+// slab budget in bytes: MUXGL_FMX_SLAB_MB, else 4 GiB bounded by a third of the device's memory (read at each call, so
+// that a test can change the environment between handles)
+size_t slab_budget() {
+  if (const char* s = getenv("MUXGL_FMX_SLAB_MB")) {
+    const long long mb = atoll(s);
+    if (mb > 0) return (size_t)mb << 20;
+  }
+  size_t fr = 0, tot = 0;
+  size_t b = (size_t)4 << 30;
+  if (hipMemGetInfo(&fr, &tot) == hipSuccess && tot > 0) b = std::min(b, tot / 3);
+  return b;
+}
+
+int sweep_launch(muxgl_handle* h, int64_t c0, const int32_t* d_cells, int64_t nc, int32_t b0, int32_t nb,
+                 const int32_t* d_blocks, double* d_slab) {
+  const bool lin = h->d_flin && !(h->flags & MUXGL_FLAG_NO_LINEAR_ENTRIES);
+  const bool piv = !(h->flags & MUXGL_FLAG_NO_PIVOT_SUMS);
+#define SW(L, P)                                                                                                       \
+  hipLaunchKernelGGL((fmx_stream_sweep_kernel<L, P>), dim3((unsigned)nc, (unsigned)nb), dim3(256), 0, h->stream, c0,    \
+                     d_cells, b0, d_blocks, h->d_cell_ptr, h->d_entry_snp, h->d_egls, h->d_flin, h->d_cgp, h->K, d_slab)
+  if (lin && piv) SW(true, true);
+  else if (lin) SW(true, false);
+  else if (piv) SW(false, true);
+  else SW(false, false);
+#undef SW
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+
+// E-step of the cell shard [c0, c0 + nc) into the per-cell states (h->d_fss); the call follows in fmx_stream_call_launch
+int fmx_stream_estep_launch(muxgl_handle* h, const muxgl_fmx_params* p, int64_t c0, int64_t nc) {
+  const int K = h->K;
+  const std::vector<int32_t> blocks = block_list(K);
+  const int64_t nb_all = (int64_t)blocks.size();
+  const size_t per = (size_t)SLAB * sizeof(double);  // one (cell, block) of the slab
+  const size_t budget = std::max(slab_budget(), per);
+  // groups (sized here, before anything is enqueued): all cells x as many blocks as fit; if one block of every cell does
+  // not fit, one block x as many cells as fit
+  int64_t gb, gc;
+  if ((size_t)nc * per <= budget) {
+    gc = nc;
+    gb = std::min<int64_t>(nb_all, (int64_t)(budget / ((size_t)nc * per)));
+  } else {
+    gb = 1;
+    gc = (int64_t)(budget / per);
+  }
+  gb = std::min<int64_t>(gb, 65535);
+  gc = std::min<int64_t>(gc, (int64_t)1 << 30);
+  const size_t slab_n = (size_t)gc * gb * SLAB, st_n = (size_t)nc * STATE_DOUBLES;
+  if (h->fblocks_k != K) {
+    if (dev_alloc(h, &h->d_fblocks, blocks.size())) return 1;
+    HIPCHK(h, hipMemcpyAsync(h->d_fblocks, blocks.data(), sizeof(int32_t) * blocks.size(), hipMemcpyHostToDevice, h->stream));
+    h->fblocks_k = K;
+  }
+  if (h->fslab_cap < slab_n) {
+    if (dev_alloc(h, &h->d_fslab, slab_n)) return 1;
+    h->fslab_cap = slab_n;
+  }
+  if (h->fss_cap < st_n) {
+    if (dev_alloc(h, &h->d_fss, st_n)) return 1;
+    h->fss_cap = st_n;
+  }
+  fmx_stream_state* st = reinterpret_cast<fmx_stream_state*>(h->d_fss);
+  hipLaunchKernelGGL(fmx_stream_init_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, h->stream, nc, st);
+  HIPCHK(h, hipGetLastError());
+  const double lsp = log((1.0 - p->doublet_prior) / K);          // cmd_cram_freemux2.cpp:379
+  const double ldp = log(p->doublet_prior / K / (K - 1) * 2.0);  // :380
+  tic(h, MUXGL_T_FMX_ESTEP_SWEEP);
+  for (int64_t g0 = 0; g0 < nc; g0 += gc) {
+    const int64_t ng = std::min(gc, nc - g0);
+    for (int64_t b0 = 0; b0 < nb_all; b0 += gb) {  // blocks in order: see the header (determinism)
+      const int32_t nb = (int32_t)std::min(gb, nb_all - b0);
+      if (sweep_launch(h, c0 + g0, nullptr, ng, (int32_t)b0, nb, h->d_fblocks, h->d_fslab)) return 1;
+      hipLaunchKernelGGL(fmx_stream_fold_kernel, dim3((unsigned)ng), dim3(256), 0, h->stream, g0, (int32_t)b0, nb,
+                         h->d_fblocks, K, lsp, ldp, h->d_fslab, st);
+      HIPCHK(h, hipGetLastError());
+    }
+  }
+  toc(h, MUXGL_T_FMX_ESTEP_SWEEP);
+  return 0;
+}
+
+int fmx_stream_call_launch(muxgl_handle* h, int64_t c0, int64_t c1, double lsp, double ldp) {
+  const int64_t nc = c1 - c0;
+  const fmx_stream_state* st = reinterpret_cast<const fmx_stream_state*>(h->d_fss);
+#define CALL(WIDE)                                                                                                   \
+  hipLaunchKernelGGL(fmx_stream_call_kernel<WIDE>, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, h->stream, c0, c1, \
+                     lsp, ldp, st, h->d_fcells, h->d_clust, h->d_fstat, h->d_prev_state, h->d_flagged, h->d_xc_epoch,  \
+                     h->d_xc, h->xs_epoch)
+  if (h->K > 255) CALL(true);
+  else CALL(false);
+#undef CALL
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+// The E-step's rows [n][K(K+1)/2] of the cells cells[0..n) (host ids), into rows (host), for the exact pass's deep ties
+// (fmx_exact.hip): swept again over all blocks, in batches whose slab fits the budget.  Uses the cluster posteriors of the
+// running iteration (d_cgp), as the E-step did.
+int fmx_stream_rows(muxgl_handle* h, const std::vector<int32_t>& cells, double* rows) {
+  const int K = h->K;
+  const size_t npairs = (size_t)K * (K + 1) / 2;
+  const int64_t n = (int64_t)cells.size();
+  if (n == 0) return 0;
+  const std::vector<int32_t> blocks = block_list(K);
+  const int32_t nb = (int32_t)blocks.size();
+  const size_t per_cell = (size_t)nb * SLAB * sizeof(double) + npairs * sizeof(double);
+  const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)(slab_budget() / per_cell)));
+  int32_t *d_blocks = nullptr, *d_cells = nullptr;
+  double *d_slab = nullptr, *d_rows = nullptr;
+  auto run = [&]() -> int {
+    if (dev_alloc(h, &d_blocks, blocks.size()) || dev_alloc(h, &d_cells, (size_t)n) ||
+        dev_alloc(h, &d_slab, (size_t)batch * nb * SLAB) || dev_alloc(h, &d_rows, (size_t)batch * npairs))
+      return 1;
+    HIPCHK(h, hipMemcpyAsync(d_blocks, blocks.data(), sizeof(int32_t) * blocks.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_cells, cells.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    for (int64_t x0 = 0; x0 < n; x0 += batch) {
+      const int64_t m = std::min(batch, n - x0);
+      if (sweep_launch(h, x0, d_cells, m, 0, nb, d_blocks, d_slab)) return 1;
+      hipLaunchKernelGGL(fmx_stream_rows_kernel, dim3((unsigned)m, (unsigned)nb), dim3(256), 0, h->stream, nb, d_blocks, K,
+                         d_slab, d_rows);
+      HIPCHK(h, hipGetLastError());
+      HIPCHK(h, hipMemcpyAsync(rows + (size_t)x0 * npairs, d_rows, sizeof(double) * (size_t)m * npairs,
+                               hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return 0;
+  };
+  const int rc = run();
+  dev_free(&d_blocks);
+  dev_free(&d_cells);
+  dev_free(&d_slab);
+  dev_free(&d_rows);
+  return rc;
+}

@@ -412,6 +412,12 @@ void muxgl_destroy(muxgl_handle* h) {
   h->clust8_n = -1;
   dev_free(&h->d_fcells);
   dev_free(&h->d_fll);
+  dev_free(&h->d_fblocks);
+  h->fblocks_k = -1;
+  dev_free(&h->d_fslab);
+  h->fslab_cap = 0;
+  dev_free(&h->d_fss);
+  h->fss_cap = 0;
   dev_free(&h->d_fstat);
   dev_free(&h->d_prev_clust);
   dev_free(&h->d_prev_state);

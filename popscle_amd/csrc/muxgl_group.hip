@@ -385,6 +385,12 @@ int group_fmx_iterate(muxgl_handle* h, const muxgl_fmx_params* p, muxgl_fmx_cell
   if (!g->prepared || g->K < 1) MUXGL_FAIL(h, "muxgl_fmx_iterate: call muxgl_fmx_prepare and muxgl_fmx_set_clusters first");
   const int n = g->n, K = g->K;
   const size_t row = (size_t)K * 3;
+  if (full_ll)
+    for (int r = 0; r < n; ++r)
+      if (g->m[(size_t)r]->fmx_streamed)
+        MUXGL_FAIL(h, "muxgl_fmx_iterate: full_ll is not available on the streamed E-step (K=%d; more than 255 clusters, a "
+                      "job whose [C][K(K+1)/2] table does not fit the device, or MUXGL_FLAG_FORCE_STREAMED_ESTEP): pass "
+                      "full_ll = NULL", K);
 #define GCHK(m, call)                                                                                     \
   do {                                                                                                    \
     hipError_t _e = (call);                                                                               \

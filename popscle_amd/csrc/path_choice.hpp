@@ -16,7 +16,8 @@ constexpr double ROW2_PART_LIMIT = 64e9;
 constexpr double WAVE_BYTE_LIMIT = 230e9;
 
 constexpr int32_t FORCE_T = MUXGL_FLAG_FORCE_TILE_SWEEP, FORCE_R = MUXGL_FLAG_FORCE_ROW_KERNEL,
-                  FORCE_W = MUXGL_FLAG_FORCE_WAVE_KERNEL, FORCE_X = MUXGL_FLAG_FORCE_STREAMED_CALL;
+                  FORCE_W = MUXGL_FLAG_FORCE_WAVE_KERNEL, FORCE_X = MUXGL_FLAG_FORCE_STREAMED_CALL,
+                  FORCE_XE = MUXGL_FLAG_FORCE_STREAMED_ESTEP;
 
 // what the demuxlet wave path holds on the device, in doubles: the pG table (entry-indexed), the result slabs of the
 // cells and their parts (64 x 64 blocks of the pair matrix), and beyond 64 samples the [C][V][V][A] tensor the call reads
@@ -87,7 +88,7 @@ inline bool demux_ll_first(const demux_facts& f, demux_path p) {
 }
 
 // ---- freemuxlet E-step (fmx_phase_estep; runs only when the cell shard is not empty)
-enum class fmx_estep_path { oct, row2, wave, pair };
+enum class fmx_estep_path { oct, row2, wave, pair, stream };
 
 struct fmx_estep_facts {
   int K;
@@ -97,10 +98,19 @@ struct fmx_estep_facts {
   bool row;                // row chunk tables of the shard (frow) or the pileup (row)
   double row2_part_bytes;  // the row2 kernel's chunk partials (those tables)
   int64_t wave_items;      // work units of the wave plan (0: none)
+  double fll_bytes;        // the [C][K(K+1)/2] table the other paths write (fmx_fll_bytes); 0 when unknown
+  double device_bytes;     // total device memory; 0 when unknown
 };
 
+// what the E-step of every path but the streamed one writes and the call reads: a row of K(K+1)/2 doubles per cell and
+// per extra part of a long cell (fmx_wave_fll_rows)
+inline double fmx_fll_bytes(int64_t rows, int K) { return (double)rows * ((double)K * (K + 1) / 2) * 8.0; }
+
 inline fmx_estep_path choose_fmx_estep(const fmx_estep_facts& f) {
-  const bool T = f.flags & FORCE_T, R = f.flags & FORCE_R, W = f.flags & FORCE_W;
+  const bool T = f.flags & FORCE_T, R = f.flags & FORCE_R, W = f.flags & FORCE_W, XE = f.flags & FORCE_XE;
+  // more than 255 clusters, the flag, or a job whose table does not fit the device (fmx_stream.hip)
+  if (f.K > 255 || (f.K > 32 && XE)) return fmx_estep_path::stream;
+  if (f.fll_bytes > 0 && f.device_bytes > 0 && f.fll_bytes > 0.9 * f.device_bytes) return fmx_estep_path::stream;
   // (row offsets of the posterior rows are 32-bit byte offsets)
   if (f.K <= 16 && (f.fqrow || f.qrow) && !T && !R && f.S + 1 < ((int64_t)1 << 23)) return fmx_estep_path::oct;
   if (f.K > 16 && f.K <= 32 && f.row && !T && !W && f.row2_part_bytes <= ROW2_PART_LIMIT) return fmx_estep_path::row2;
@@ -108,7 +118,7 @@ inline fmx_estep_path choose_fmx_estep(const fmx_estep_facts& f) {
   return fmx_estep_path::pair;  // workgroup = (cell, tile of pairs)
 }
 
-// ---- freemuxlet call: few hypotheses per cell make a wave per cell mostly overhead (0.54 against 0.13 ms at configs[3])
+// ---- freemuxlet call (not consulted on the streamed E-step, which makes its own call): few hypotheses per cell make a wave per cell mostly overhead (0.54 against 0.13 ms at configs[3])
 enum class fmx_call_path { lane_per_cell, wave_per_cell };
 
 inline fmx_call_path choose_fmx_call(int K, int32_t flags) {

@@ -382,6 +382,9 @@ int cmd_freemuxlet(int argc, char** argv) {
   a.add_bool("no-early-stop", &noEarlyStop);       // extension for benchmarking fixed iteration counts
   a.parse(argc, argv);
   if (cf.plpPrefix.empty() || cf.outPrefix.empty() || nSamples == 0) fatal("Missing required option(s) : --plp, --out, --nsample");
+  if (nSamples < 0 || nSamples > MUXGL_MAX_CLUSTERS)
+    fatal("freemuxlet: --nsample %d outside [1, %d], the clusters the library supports (MUXGL_MAX_CLUSTERS)", nSamples,
+          MUXGL_MAX_CLUSTERS);
 
   Pileup p;
   StageTimer tmr;

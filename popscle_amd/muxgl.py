@@ -32,6 +32,8 @@ FLAG_NO_PIVOT_SUMS = 256
 FLAG_SPLIT_GENERAL_SWEEP = 512
 FLAG_GROUP_PROBE_SELF = 1024
 FLAG_FORCE_STREAMED_CALL = 2048
+FLAG_FORCE_STREAMED_ESTEP = 4096
+MAX_CLUSTERS = 1024  # freemuxlet: largest K (MUXGL_MAX_CLUSTERS)
 MAX_DEVICES = 16
 XCHG_PAD = 64
 T_FMX_ENTRY, T_FMX_GP, T_FMX_ESTEP, T_FMX_CALL, T_FMX_MSTEP = 4, 5, 6, 7, 8
