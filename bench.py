@@ -8,6 +8,12 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W [--config I]         # the same, launched from outside
     python bench.py ... --dump-outputs DIR                          # also: rank 0's records of the last timed step
+    python bench.py ... --full                                      # also: roofline, CPU baselines, parity, legs
+
+A plain run does what its headline needs and no more: it generates the input, hands it over, ramps up, warms up, times
+the steps, writes --dump-outputs and prints the line (the timed figures and what the library timed inside those steps).
+Everything else the benchmark measures or checks runs only under --full: the roofline and floor of the dominant kernel,
+the CPU baselines with their parity checks, the exact-call pass and, on configs[1], the secondary legs below.
 
 One process per GPU.
   * demuxlet (configs 1, 2): a "step" is one full pass of the hot path (entry likelihoods + sample-pair sweep +
@@ -17,7 +23,7 @@ One process per GPU.
   * freemuxlet (configs 3, 4): a "step" is one EM iteration (cluster posteriors, E-step, scans, re-assignment, ordered
     M-step and the two all-gathers + one all-reduce between them) of the fixed job (STRONG scaling): the E-step is
     sharded by cells, the ordered M-step by SNPs, each rank holding 2/N of the pileup (popscle_amd/freemuxlet.py).
-  * The default run (config 1) also times, on the same ranks and inside the same JSON line, the other BASELINE.json
+  * With --full, the configs[1] run also times, on the same ranks and inside the same JSON line, the other BASELINE.json
     configs: "freemuxlet_em" (configs[3], 20 EM iterations), "demuxlet_config2" (configs[2], the north_star's
     100 k x 64 x 200 k shape, 3 passes) and "freemuxlet_config4" (configs[4], 500 k x 500 k, K = 64: 2 EM iterations;
     sharded over the ranks for N > 1) -- each with its own roofline and CPU baseline, each behind a watchdog so that it
@@ -28,7 +34,7 @@ One process per GPU.
 Prints ONE JSON line (rank 0).  LL = one hypothesis log-likelihood feeding a call: demuxlet V singlets +
 V(V-1)(A-1) ordered doublets per cell, freemuxlet K(K+1)/2 per cell and iteration.
 
-Roofline ("the binding fraction is the max of the two"): two roofs are priced for the dominant kernel,
+Roofline (--full; SURVEY.md 8d: "the binding fraction is the max of the two"): two roofs are priced for the dominant kernel,
     hbm   bytes that actually crossed the L2<->fabric boundary (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE, own passes,
           profiles/traffic.json, quoted only when it was measured on these very sources) / time / 8.0 TB/s -- next to
           the ALGORITHMIC bytes of SURVEY 8d (a gather of cache-resident GP rows: an equivalent rate, not a bandwidth);
@@ -573,7 +579,8 @@ def demux_leg(args, ctx, config, steps=None, warmup=None, ramp_seconds=None, cpu
         kern_ms /= steps
         rpe = p.R / max(p.nnz, 1)
         sweep_s = kern_ms[muxgl.T_DEMUX_SWEEP] * 1e-3
-        frac_lin = linear_fraction(p.entry_rptr, p.reads)
+        sensitivity = reads_lambda is not None or args.no_linear
+        frac_lin = linear_fraction(p.entry_rptr, p.reads) if args.full or sensitivity else None
         out = {
             "metric": METRIC if config == 1 else f"cell-sample-pair LLs/sec (singlet+doublet), demuxlet BASELINE.json configs[{config}]",
             "value": total_cells * lls_per_cell / step_s, "unit": "LLs/s", "n_gpus": ctx.world, "steps": steps,
@@ -594,14 +601,19 @@ def demux_leg(args, ctx, config, steps=None, warmup=None, ramp_seconds=None, cpu
             # memory), "call" and "d2h" are then 0; other paths run them as separate launches
             "kernel_ms": {"sweep": float(kern_ms[muxgl.T_DEMUX_SWEEP]), "reduce": float(kern_ms[muxgl.T_DEMUX_REDUCE]),
                           "call": float(kern_ms[muxgl.T_DEMUX_CALL]), "d2h": float(kern_ms[muxgl.T_DEMUX_D2H])},
-            "roofline": roofline(demux_sweep_kernel(V, alphas), sweep_s, demux_bytes_per_entry(V, rpe) * p.nnz,
-                                 demux_flops_per_entry(V, A, rpe) * p.nnz,
-                                 demux_issued_flops_model(V, alphas, rpe, 0.0 if args.no_linear else frac_lin) * p.nnz, config,
-                                 scale=float(p.nnz)),
         }
-        out["roofline"]["floor"] = demux_floor(V, alphas, float(p.nnz), 0.0 if args.no_linear else frac_lin, rpe, cfg["S"],
-                                               C, sweep_s * 1e3)
-        if reads_lambda is not None or args.no_linear:
+        if args.full:
+            out["roofline"] = roofline(demux_sweep_kernel(V, alphas), sweep_s, demux_bytes_per_entry(V, rpe) * p.nnz,
+                                       demux_flops_per_entry(V, A, rpe) * p.nnz,
+                                       demux_issued_flops_model(V, alphas, rpe, 0.0 if args.no_linear else frac_lin) * p.nnz,
+                                       config, scale=float(p.nnz))
+            out["roofline"]["floor"] = demux_floor(V, alphas, float(p.nnz), 0.0 if args.no_linear else frac_lin, rpe,
+                                                   cfg["S"], C, sweep_s * 1e3)
+            out["roofline"]["note_8d"] = ("SURVEY 8d's per-entry bytes / flops (reference_equiv_*) exceed the roofs for V <= 16: "
+                                          "they count cache-resident GP-row gathers as HBM bytes and all V*V*A slots of the "
+                                          "reference's loop nest as work; `floor` is the recomputable bound of the algorithm as "
+                                          "built")
+        if sensitivity:
             out["sensitivity"] = {"reads_lambda": 0.3 if reads_lambda is None else reads_lambda, "reads_per_entry": rpe,
                                   "linear_entry_share": frac_lin, "linear_entry_form": not args.no_linear,
                                   "note": "not the BASELINE workload: the default line's entries carry 1 + Poisson(0.3) reads "
@@ -617,10 +629,7 @@ def demux_leg(args, ctx, config, steps=None, warmup=None, ramp_seconds=None, cpu
                                    % (ctx.world, C))
             out["per_rank_value"] = out["value"] / ctx.world
             out["per_rank"] = {"sweep_kernel_ms": rank_sweep_ms, "entries": rank_entries}
-        out["roofline"]["note_8d"] = ("SURVEY 8d's per-entry bytes / flops (reference_equiv_*) exceed the roofs for V <= 16: they count "
-                                      "cache-resident GP-row gathers as HBM bytes and all V*V*A slots of the reference's loop "
-                                      "nest as work; `floor` is the recomputable bound of the algorithm as built")
-        if not args.no_cpu_baseline and ctx.world == 1:
+        if args.full and not args.no_cpu_baseline and ctx.world == 1:
             raw = eng.demux_results_view().copy()
             out["cpu_baseline"] = cpu_baseline_demux(p, alphas, raw, budget_s=cpu_budget_s)
             # The product's exact-call pass over ALL cells of the step (host threads; what popscle-amd demuxlet runs after
@@ -632,7 +641,7 @@ def demux_leg(args, ctx, config, steps=None, warmup=None, ramp_seconds=None, cpu
             ms = (time.perf_counter() - t0) * 1e3
             out["exact_calls_pass"] = dict(st, ms_all_cells=ms, threads=usable_cores(), timed_in_value=False)
             out["pair_order_ms_all_cells"] = ms   # (the name round 5's review asked for; the pass now also settles near ties)
-        else:
+        elif args.full:
             out["cpu_baseline"] = None
     eng.close()
     return out
@@ -653,26 +662,29 @@ def fmx_leg(args, ctx, config, steps, warmup, cpu_baseline=True, cpu_budget_s=10
                min_entries=min(50, max(1, int(args.mean_entries // 4))))
     t_gen = time.perf_counter()
     on_device = use_device_synth(args, C * args.mean_entries * 1.2)
+    want_cpu = args.full and cpu_baseline and ctx.world == 1 and not args.no_cpu_baseline
     p = rows = cols = None
     if on_device:
         d = synth.make_pileup_device(C, S, K, device=f"cuda:{ctx.dev}", **gen)
         nnz_total, my_entries = d.nnz, float(d.cell_ptr[c_ranges[0][1]] - d.cell_ptr[c_ranges[0][0]])
-        usable = torch.cumsum((d.reads != 0xFF).to(torch.int64), 0)
-        usable = torch.cat([usable.new_zeros(1), usable])
-        frac_lin = float(((usable[d.entry_rptr[1:]] - usable[d.entry_rptr[:-1]]) <= 1).double().mean())
-        del usable
+        if args.full:
+            usable = torch.cumsum((d.reads != 0xFF).to(torch.int64), 0)
+            usable = torch.cat([usable.new_zeros(1), usable])
+            frac_lin = float(((usable[d.entry_rptr[1:]] - usable[d.entry_rptr[:-1]]) <= 1).double().mean())
+            del usable
         af, truth_s1 = d.af.cpu().numpy(), d.truth["s1"].cpu().numpy()
         if ctx.dist_on:
             rows = d.take_cells(*c_ranges[ctx.rank])
             cols = d.take_snps(*s_ranges[ctx.rank])
-        if not ctx.dist_on or (ctx.rank == 0 and cpu_baseline and ctx.world == 1 and not args.no_cpu_baseline):
+        if not ctx.dist_on or (ctx.rank == 0 and want_cpu):
             p = d.host()
         del d
         free_torch_cache(ctx)
     else:
         p = synth.make_pileup(C, S, K, **gen)
         nnz_total, my_entries = p.nnz, float(p.cell_ptr[c_ranges[0][1]] - p.cell_ptr[c_ranges[0][0]])
-        frac_lin = linear_fraction(p.entry_rptr, p.reads)
+        if args.full:
+            frac_lin = linear_fraction(p.entry_rptr, p.reads)
         af, truth_s1 = p.af, p.truth["s1"]
         if ctx.dist_on:
             rows = shard.take_cells(p, *c_ranges[ctx.rank])
@@ -715,9 +727,6 @@ def fmx_leg(args, ctx, config, steps, warmup, cpu_baseline=True, cpu_budget_s=10
     out = None
     if ctx.rank == 0:
         npairs = K * (K + 1) // 2
-        # the roofline prices the pair-sweep kernel(s) alone -- the kernels the PMC traffic belongs to -- not the whole
-        # E-step bracket (which also holds the relayout of the posteriors and the reduction of the chunk partials)
-        est_s = float(kern[muxgl.T_FMX_ESTEP_SWEEP] or kern[muxgl.T_FMX_ESTEP]) * 1e-3
         out = {
             "metric": FMX_METRIC, "value": C * npairs * steps / elapsed, "unit": "LLs/s", "n_gpus": ctx.world,
             "steps": steps, "warmup": warmup, "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True,
@@ -740,21 +749,24 @@ def fmx_leg(args, ctx, config, steps, warmup, cpu_baseline=True, cpu_budget_s=10
             "last_iteration": {"nsingle": hist[-1][0], "namb": hist[-1][1], "nchanged": hist[-1][2]},
             # device-event times of the two exchanges per iteration on rank 0 (RCCL only): DESIGN.md 4.3's scaling model
             "exchange_ms_rank0": tm.get("exchange_ms"),
-            "roofline": roofline(fmx_estep_kernel(K), est_s, fmx_bytes_per_entry(K) * my_entries,
-                                 fmx_flops_per_entry(K) * my_entries, fmx_issued_flops_model(K, frac_lin) * my_entries, config,
-                                 scale=my_entries),
         }
-        fl = fmx_floor(K, my_entries, frac_lin, S, est_s * 1e3)
-        rf = out["roofline"]
-        rf["floor"] = fl
-        # roofline.frac means the same in every leg of this line: FP64 flops ISSUED (PMC SQ_INSTS_VALU_{FMA,MUL,ADD}_F64 x 64,
-        # FMA counted twice) / kernel time / 78.6 TFLOP/s, or counter bytes / time / 8 TB/s when that is larger
-        # (roofline.fp64.source says whether the counters or, without a current PMC record, the instruction model supplied the
-        # flops).  The fraction of the recomputable floor of the algorithm as built is its own key: roofline.floor.frac_of_floor.
-        if rf.get("traffic"):
-            rf["hbm"]["traffic_over_compulsory"] = rf["traffic"] / fl["compulsory_bytes"]
-            rf["hbm"]["note"] = ("traffic = PMC FETCH_SIZE x2 + WRITE_SIZE per launch: L2-side fabric requests, Infinity-Cache hits "
-                                 "included -- row gathers that miss the L2, not compulsory HBM bytes")
+        if args.full:
+            # the roofline prices the pair-sweep kernel(s) alone -- the kernels the PMC traffic belongs to -- not the whole
+            # E-step bracket (which also holds the relayout of the posteriors and the reduction of the chunk partials)
+            est_s = float(kern[muxgl.T_FMX_ESTEP_SWEEP] or kern[muxgl.T_FMX_ESTEP]) * 1e-3
+            rf = out["roofline"] = roofline(fmx_estep_kernel(K), est_s, fmx_bytes_per_entry(K) * my_entries,
+                                            fmx_flops_per_entry(K) * my_entries,
+                                            fmx_issued_flops_model(K, frac_lin) * my_entries, config, scale=my_entries)
+            fl = rf["floor"] = fmx_floor(K, my_entries, frac_lin, S, est_s * 1e3)
+            # roofline.frac means the same in every leg of this line: FP64 flops ISSUED (PMC SQ_INSTS_VALU_{FMA,MUL,ADD}_F64
+            # x 64, FMA counted twice) / kernel time / 78.6 TFLOP/s, or counter bytes / time / 8 TB/s when that is larger
+            # (roofline.fp64.source says whether the counters or, without a current PMC record, the instruction model
+            # supplied the flops).  The fraction of the recomputable floor of the algorithm as built is its own key:
+            # roofline.floor.frac_of_floor.
+            if rf.get("traffic"):
+                rf["hbm"]["traffic_over_compulsory"] = rf["traffic"] / fl["compulsory_bytes"]
+                rf["hbm"]["note"] = ("traffic = PMC FETCH_SIZE x2 + WRITE_SIZE per launch: L2-side fabric requests, "
+                                     "Infinity-Cache hits included -- row gathers that miss the L2, not compulsory HBM bytes")
         if ctx.world > 1:
             out["per_rank"] = {"ms_per_iteration": rank_loop_ms, "estep_kernel_ms_last_iteration": rank_estep_ms}
             # DESIGN.md 4.3's model next to the measurement: this rank's kernels + the two exchanges (xGMI: point to
@@ -776,10 +788,10 @@ def fmx_leg(args, ctx, config, steps, warmup, cpu_baseline=True, cpu_budget_s=10
         # near-tie calls of the timed iterations: cells the exact path (csrc/fmx_exact.hip) settled inside the timed region, how
         # many of them it decided differently from the kernels, and cells left open (0: every path settles its own)
         out["exact_path"] = dict(zip(("near_tie_cells", "calls_changed", "unresolved"), eng.fmx_exact_stats()))
-        if cpu_baseline and ctx.world == 1 and not args.no_cpu_baseline:
+        if want_cpu:
             out["cpu_baseline"] = cpu_baseline_fmx(p, K, clust0, budget_s=cpu_budget_s)
             out["cpu_baseline"].update(fmx_parity_sample(eng, p, K, cells))
-        else:
+        elif args.full:
             out["cpu_baseline"] = None
         if args.dump:
             np.savez(args.dump, cells=cells, hist=np.array(hist, dtype=np.int64))
@@ -869,13 +881,18 @@ def main():
                          "repeated 20 times runs ~10 %% below the sustained clock)")
     ap.add_argument("--config", type=int, default=1, help="index into BASELINE.json configs: 1, 2 demuxlet; 3, 4 freemuxlet")
     ap.add_argument("--scale", type=float, default=1.0, help="fraction of the config's cells (debug only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the roofline and floor of the dominant "
+                         "kernel, the CPU baselines with their parity checks, the exact-call pass and, with --config 1, the "
+                         "secondary legs.  Off by default: a plain run only sets up, warms up, times the steps, writes "
+                         "--dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: without the CPU baselines")
     ap.add_argument("--no-legs", "--no-fmx-leg", dest="no_legs", action="store_true",
-                    help="default run: only the headline (configs[1]), none of the secondary legs")
+                    help="--full run of configs[1]: only the headline, none of the secondary legs")
     ap.add_argument("--legs", default=None,
-                    help="default run: secondary legs, in order: BASELINE.json config indices 3, 2, 4 and, with N > 1 ranks, "
-                         "2s = configs[2] as ONE job cut over the ranks (strong scaling).  Default 3,2,4 (N = 1) / "
-                         "3,2,2s,4 (N > 1); given explicitly, the legs also run at --scale != 1 (tests)")
+                    help="--full run of configs[1]: secondary legs, in order: BASELINE.json config indices 3, 2, 4 and, with "
+                         "N > 1 ranks, 2s = configs[2] as ONE job cut over the ranks (strong scaling).  Default 3,2,4 (N = 1) "
+                         "/ 3,2,2s,4 (N > 1); given explicitly, the legs also run at --scale != 1 (tests)")
     ap.add_argument("--fmx-leg-steps", type=int, default=20, help="EM iterations of the configs[3] leg")
     ap.add_argument("--leg-timeout", "--fmx-leg-timeout", dest="leg_timeout", type=float, default=300.0,
                     help="watchdog per secondary leg, seconds")
@@ -904,6 +921,8 @@ def main():
     args = ap.parse_args()
     if args.config not in synth.CONFIGS:
         raise SystemExit("--config must be 1, 2 (demuxlet) or 3, 4 (freemuxlet)")
+    if args.legs is not None and not args.full:
+        raise SystemExit("--legs selects the secondary legs of a --full run")
     if args.steps is None:
         args.steps = {1: 2000, 2: 3, 3: 20, 4: 5}[args.config]
     if args.warmup is None:
@@ -915,7 +934,7 @@ def main():
     if args.config in (1, 2):
         out = demux_leg(args, ctx, args.config, dump_dir=args.dump_outputs)
         legs = args.legs if args.legs is not None else ("3,2,2s,4" if ctx.world > 1 else "3,2,4")
-        if args.config == 1 and not args.no_legs and (args.scale == 1.0 or args.legs is not None):
+        if args.full and args.config == 1 and not args.no_legs and (args.scale == 1.0 or args.legs is not None):
             for cfg in [x.strip() for x in legs.split(",") if x.strip()]:
                 cfg = int(cfg) if cfg.isdigit() else cfg
                 if cfg not in LEGS:

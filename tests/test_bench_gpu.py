@@ -1,11 +1,12 @@
-"""bench.py's one-line JSON contract on a GPU box (short run): the keys the driver reads, the roofline and cpu_baseline
-objects, and that the N > 1 launch path (torch.distributed.run, here two ranks on one device over gloo) prints one line
-from rank 0 with the whole-job aggregate."""
+"""bench.py's one-line JSON contract on a GPU box (short run): the keys the driver reads, what a plain run leaves out and
+what it costs besides its steps, the roofline and cpu_baseline objects of a --full run, and that the N > 1 launch path
+(torch.distributed.run, here two ranks on one device over gloo) prints one line from rank 0 with the whole-job aggregate."""
 import json
 import os
 import socket
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -25,7 +26,7 @@ def run(cmd, timeout=900):
 
 
 def test_single_gpu_line():
-    d = run([sys.executable, BENCH, "--gpus", "1", "--steps", "50", "--warmup", "5", "--ramp-seconds", "0.2"])
+    d = run([sys.executable, BENCH, "--gpus", "1", "--steps", "50", "--warmup", "5", "--ramp-seconds", "0.2", "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -108,6 +109,22 @@ def test_single_gpu_line():
     assert f4["cpu_baseline"]["value"] > 0 and f4["cpu_baseline"]["parity_max_abs_ll_diff"] < 1e-5
 
 
+def test_plain_line_is_lean():
+    """the headline command without --full: the line's headline keys, none of what --full adds, and at most 30 s of the
+    whole run (process start to exit) outside its warmup and timed steps"""
+    t0 = time.perf_counter()
+    d = run([sys.executable, BENCH, "--gpus", "1", "--steps", "2000", "--warmup", "200"])
+    outside_s = time.perf_counter() - t0 - (2000 + 200) * d["ms_per_step"] * 1e-3
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "kernel_ms"):
+        assert k in d, k
+    assert d["steps"] == 2000 and d["warmup"] == 200 and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["metric"] == "cell-sample-pair LLs/sec (singlet+doublet), demuxlet 10k cells×16 samples" and d["unit"] == "LLs/s"
+    assert abs(d["value"] - 10000 * 256 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-9
+    for k in ("roofline", "cpu_baseline", "exact_calls_pass", "freemuxlet_em", "demuxlet_config2", "freemuxlet_config4"):
+        assert k not in d, k
+    assert outside_s < 30.0, outside_s
+
+
 def test_two_rank_launch_line():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -115,7 +132,8 @@ def test_two_rank_launch_line():
     s.close()
     d = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
              "127.0.0.1", "--master-port", str(port), BENCH, "--gpus", "2", "--steps", "30", "--warmup", "3",
-             "--ramp-seconds", "0.1", "--dist-backend", "gloo", "--single-device", "--fmx-leg-steps", "3", "--legs", "3"])
+             "--ramp-seconds", "0.1", "--dist-backend", "gloo", "--single-device", "--fmx-leg-steps", "3", "--legs", "3",
+             "--full"])
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["cpu_baseline"] is None
     fx = d["freemuxlet_em"]  # two ranks, slabs, one in-place all-gather per exchange (gloo staging on this box)
     assert "error" not in fx, fx
@@ -143,7 +161,7 @@ def test_four_ranks_line_explains_itself():
     d = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=4", "--master-addr",
              "127.0.0.1", "--master-port", str(port), BENCH, "--gpus", "4", "--steps", "5", "--warmup", "1",
              "--ramp-seconds", "0", "--dist-backend", "gloo", "--single-device", "--scale", "0.01", "--fmx-leg-steps", "2",
-             "--legs", "3,2s,4", "--no-cpu-baseline"], timeout=900)
+             "--legs", "3,2s,4", "--no-cpu-baseline", "--full"], timeout=900)
     assert d["n_gpus"] == 4 and d["ranks_seen"] == 4 and d["dist"]["world_size"] == 4
     assert len(d["per_rank"]["sweep_kernel_ms"]) == 4 and min(d["per_rank"]["sweep_kernel_ms"]) > 0
     for key in ("freemuxlet_em", "freemuxlet_config4"):
@@ -178,7 +196,7 @@ def test_dense_pileup_sensitivity_line():
 def test_plain_shell_gpus_n_launches_itself():
     """`python bench.py --gpus 2` from a plain shell (the form the driver uses) starts its own two ranks"""
     d = run([sys.executable, BENCH, "--gpus", "2", "--steps", "10", "--warmup", "2", "--ramp-seconds", "0.1",
-             "--dist-backend", "gloo", "--single-device", "--fmx-leg-steps", "2", "--legs", "3", "--no-cpu-baseline"])
+             "--dist-backend", "gloo", "--single-device", "--fmx-leg-steps", "2", "--legs", "3", "--no-cpu-baseline", "--full"])
     assert d["n_gpus"] == 2 and d["steps"] == 10 and d["freemuxlet_em"]["n_gpus"] == 2
     assert "error" not in d["freemuxlet_em"], d["freemuxlet_em"]
 

@@ -8,7 +8,7 @@ O=/root/repo/gpurun_out/octg; rm -rf $O; mkdir -p $O
 for cfg in 3 1; do
   pat=$([ $cfg = 3 ] && echo fmx_estep_oct_kernel || echo demux_oct_kernel)
   for g in $GS; do
-    python bench.py --config $cfg --steps $([ $cfg = 3 ] && echo 60 || echo 600) --warmup 20 --no-cpu-baseline --no-fmx-leg 2>/dev/null | tail -1 > $O/c${cfg}_g$g.json
+    python bench.py --full --config $cfg --steps $([ $cfg = 3 ] && echo 60 || echo 600) --warmup 20 --no-cpu-baseline --no-fmx-leg 2>/dev/null | tail -1 > $O/c${cfg}_g$g.json
     for ctr in FETCH_SIZE WRITE_SIZE; do
       (cd /tmp && timeout 300 rocprofv3 --pmc $ctr --output-format csv -d $O/c${cfg}_g${g}_$ctr -- python /root/repo/bench.py --config $cfg --no-cpu-baseline --no-fmx-leg --steps 3 --warmup 1 --ramp-seconds 0 > $O/c${cfg}_g${g}_$ctr.log 2>&1)
     done
