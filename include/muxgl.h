@@ -168,6 +168,8 @@ enum {
   MUXGL_T_FMXOLD_VOTE = 10, /* freemuxlet-old: one voting pass (c1) */
   MUXGL_T_FMX_ESTEP_SWEEP = 11, /* the pair-sweep kernel(s) alone, inside MUXGL_T_FMX_ESTEP (which also brackets the
                                    relayout of the cluster posteriors and the reduction of the chunk partials) */
+  MUXGL_T_DEMUX_SINGLETS = 12,  /* muxgl_demux_singlets: entry weights + sample sweep (with a table cut into several
+                                   batches also the copies between them) */
   MUXGL_T_COUNT = 16
 };
 
@@ -202,6 +204,18 @@ int muxgl_demux_set_gp(muxgl_handle* h, int32_t V, const double* gp, const uint8
  * (the call fails, naming the reason, otherwise).  Its device memory beyond the pileup and the per-entry likelihoods is a
  * slab budget, 4 GiB or a third of the device's memory if less; MUXGL_DEMUX_SLAB_MB=<n> in the environment sets it. */
 int muxgl_demux_run(muxgl_handle* h, const muxgl_demux_params* p, muxgl_demux_cell* out, double* full_ll);
+
+/* sng[C][V] = llksAB[(j,0,0)] of cmd_cram_demuxlet.cpp:733-747 for every droplet and sample.  Needs muxgl_set_pileup
+ * and muxgl_demux_set_gp, not a previous muxgl_demux_run; any V up to MUXGL_MAX_SAMPLES; one device or a device group.
+ * This is the table the reference's disabled .single / .sing2 writers print (:580, :839-848): what full_ll[c][j][0][0]
+ * holds on the paths that have it.  The slot is (j, k = 0, n = 0) whatever alpha[0] is, and the per-entry likelihoods are
+ * normalised over the whole grid (:686-725), so the call takes the same parameters as muxgl_demux_run (doublet_prior is
+ * not read).  A droplet without entries gets a row of zeros.  The device holds three weights per entry and a slab of the
+ * table (the streamed call's budget: 4 GiB or a third of the device, MUXGL_DEMUX_SLAB_MB); a larger table is swept in
+ * batches of cells, each copied out before the next.  The table is bit-identical from run to run, for any budget, on one
+ * device and on a group.  The records, timings and state of muxgl_demux_run stay as they are (the call's own kernel time
+ * is MUXGL_T_DEMUX_SINGLETS of muxgl_get_timing; it counts as a collecting call of muxgl_get_timing_sum). */
+int muxgl_demux_singlets(muxgl_handle* h, const muxgl_demux_params* p, double* sng);
 
 /* The calls rounding noise could decide, settled in the reference's own arithmetic -- HOST pass, no device work, no
  * handle (popscle_amd/host/exact_calls.hpp).  The kernels' log-likelihoods equal the reference's to ~1e-12, not to the last

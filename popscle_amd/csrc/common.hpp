@@ -545,6 +545,7 @@ struct ring_sel {          // one launch of demux_ring.hip
 // the choosers of path_choice.hpp; a launcher is only called for a job its path takes (0 ok, 1 error)
 int demux_launch(muxgl_handle* h, const muxgl_demux_params* p);
 int demux_stream_launch(muxgl_handle* h, const muxgl_demux_params* p);   // streamed sweep + fold + call
+int demux_singlets_run(muxgl_handle* h, const muxgl_demux_params* p, double* sng);  // demux_singlets.hip: [C][V] to the host
 int demux_entry_pg_launch(muxgl_handle* h, const muxgl_demux_params* p, double* d_pg, bool gen_stream = false,
                           bool by_record = false);
 int demux_ring_lin_launch(muxgl_handle* h, const muxgl_demux_params* p, const wave_item* items, int64_t n_items,
@@ -616,6 +617,7 @@ int group_set_pileup(muxgl_handle* h, int64_t C, int64_t S, int64_t nnz, int64_t
                      const int32_t* entry_snp, const int64_t* entry_rptr, const uint8_t* reads);
 int group_demux_set_gp(muxgl_handle* h, int32_t V, const double* gp, const uint8_t* has_gp);
 int group_demux_run(muxgl_handle* h, const muxgl_demux_params* p, muxgl_demux_cell* out, double* full_ll);
+int group_demux_singlets(muxgl_handle* h, const muxgl_demux_params* p, double* sng);
 const muxgl_demux_cell* group_demux_results(const muxgl_handle* h);
 int group_demux_get_entry_pg(muxgl_handle* h, double* pg);
 int group_fmx_prepare(muxgl_handle* h, const double* af, double* cell_llk0, double* cell_llk2, int32_t* cell_nsnps,

@@ -1,0 +1,272 @@
+// demux_singlets.hip -- muxgl_demux_singlets: the [C][V] table of singlet log-likelihoods, llksAB[(j, 0, 0)] of
+// cmd_cram_demuxlet.cpp:733-747 for every droplet and every sample (what the reference's disabled .single / .sing2 writers
+// print, :580, :839-848).
+//
+//   sng[c][j] = sum over the entries e of c whose marker has genotypes of
+//               log( sum_l sum_m gp[snp_e][j][l] * gp[snp_e][0][m] * pG_e[0][l][m] )
+//
+// Two kernels and a small one for long cells:
+//   * sng_weight_kernel, lane = entry: the per-entry likelihoods of the whole grid (row_entry_pg: their normalisation is
+//     over all alphas, :686-725), then w_l = sum_m gp[snp][0][m] pG[0][l][m], three numbers per entry.  A marker without
+//     genotypes gets w = (1, 1, 1): its row in the device copy of gp is (1, 0, 0) (demux_gp_neutral_rows), so its factor is
+//     exactly 1 for every sample and the sweep has no branch.
+//   * sng_sweep_kernel, lane = sample: f = g_0 w_0 + g_1 w_1 + g_2 w_2 per (entry, sample), multiplied into a product kept
+//     as mantissa x 2^exponent (prodacc), one log per (cell part, sample).  A wave is one work unit: a part of a cell
+//     (at most SNG_PART entries) x a block of 64 samples, the entry wave-uniform.  Below 64 samples a wave holds
+//     G = 64 / VH entries side by side (VH = V rounded up to a power of two, lane = (entry slot, sample)) and the G partial
+//     products of a sample are multiplied in a fixed butterfly at the end.
+//   * sng_join_kernel: the logs of the parts of a cell longer than SNG_PART entries, added in entry order.
+// The cut of a cell depends on the cell alone and every reduction tree is fixed: the table is bit-identical from run to
+// run, for any slab budget, on one device, on a group and through the sharded driver.
+//
+// Memory: [nnz][3] weights and a slab of the table.  When the table exceeds the budget (the streamed call's: 4 GiB or a
+// third of the device, MUXGL_DEMUX_SLAB_MB) the cells are swept in batches and each batch is copied out before the next.
+#include <algorithm>
+#include <cstdlib>
+#include <vector>
+
+#include "demux_entry.hpp"
+
+namespace {
+
+constexpr int64_t SNG_PART = 2048;  // entries per part of a long cell (the wave kernels' cut, common.hpp wave_item)
+constexpr int SNG_UNR = 8;          // entries per lane between two renormalisations, all of their loads in flight: a
+                                    // factor is >= ~1e-11 (pG >= 1e-10 / (1 + 1e-10)), eight cannot underflow
+
+struct sng_alpha {
+  double a[MUXGL_MAX_ALPHA];
+};
+
+// one work item: the entries [e0, e1) of one cell, result row `row` of the slab (rows of cells first, then the rows of
+// the further parts of long cells)
+struct sng_item {
+  int64_t e0, e1, row;
+};
+// a cell of several parts: slab[cell row] += slab[first] + ... + slab[first + count - 1], in this order
+struct sng_cut {
+  int64_t row, first, count;
+};
+
+template <int NA>
+__global__ void __launch_bounds__(256)
+    sng_weight_kernel(int64_t nnz, const int32_t* __restrict__ entry_snp, const int64_t* __restrict__ entry_rptr,
+                      const uint8_t* __restrict__ reads, const double* __restrict__ lut_g, sng_alpha al,
+                      const double* __restrict__ gp, const uint8_t* __restrict__ has_gp, int V, double* __restrict__ wt) {
+  __shared__ double lut[384];
+  for (int i = threadIdx.x; i < 384; i += 256) lut[i] = lut_g[i];
+  __syncthreads();
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= nnz) return;
+  const int32_t s = entry_snp[e];
+  double w0 = 1.0, w1 = 1.0, w2 = 1.0;
+  if (has_gp[s]) {  // (no genotypes: the reference skips the marker, :733)
+    const int64_t r0 = entry_rptr[e], r1 = entry_rptr[e + 1];
+    uint32_t first4 = 0;
+    for (int64_t k = 0; k < 4 && r0 + k < r1; ++k) first4 |= (uint32_t)reads[r0 + k] << (8 * (int)k);
+    double pG[NA * 9];
+    row_entry_pg<NA>(reads, r0, r1, first4, al.a, lut, pG);
+    const double* g = gp + (size_t)s * V * 3;  // sample 0's triple
+    const double h0 = g[0], h1 = g[1], h2 = g[2];
+    w0 = fma(h2, pG[2], fma(h1, pG[1], h0 * pG[0]));
+    w1 = fma(h2, pG[5], fma(h1, pG[4], h0 * pG[3]));
+    w2 = fma(h2, pG[8], fma(h1, pG[7], h0 * pG[6]));
+  }
+  double* o = wt + (size_t)e * 3;
+  o[0] = w0;
+  o[1] = w1;
+  o[2] = w2;
+}
+
+// grid: ceil(n_items * nblk / 4) workgroups of four waves; wave u <-> (item u / nblk, sample block u % nblk), so the
+// waves of a workgroup walk the same entries and read neighbouring pieces of the same genotype rows.
+template <int VH>
+__global__ void __launch_bounds__(256)
+    sng_sweep_kernel(int64_t n_units, int nblk, const sng_item* __restrict__ items, const int32_t* __restrict__ entry_snp,
+                     const double* __restrict__ wt, const double* __restrict__ gp, int V, double* __restrict__ slab) {
+  constexpr int G = 64 / VH;  // entries side by side in a wave
+  const int64_t u = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (u >= n_units) return;
+  const int64_t it = u / nblk;
+  const int blk = (int)(u - it * nblk);
+  const int lane = threadIdx.x & 63;
+  const int sub = G == 1 ? 0 : lane / VH;  // entry slot of the lane
+  const int j = G == 1 ? blk * 64 + lane : lane % VH;
+  const bool jl = j < V;
+  const size_t jo = (size_t)(jl ? j : V - 1) * 3;
+  const int64_t e0 = items[it].e0, e1 = items[it].e1;
+  const size_t V3 = (size_t)V * 3;
+
+  double acc = 1.0;
+  int32_t ex = 0;
+  for (int64_t eb = e0; eb < e1; eb += (int64_t)SNG_UNR * G) {
+    double f[SNG_UNR];
+#pragma unroll
+    for (int i = 0; i < SNG_UNR; ++i) {
+      const int64_t e = eb + (int64_t)i * G + sub;
+      const bool ok = e < e1;
+      const int64_t ec = ok ? e : e1 - 1;  // (a slot past the end reads the last entry again and counts as 1)
+      const double* w = wt + (size_t)ec * 3;
+      const double* g = gp + (size_t)entry_snp[ec] * V3 + jo;
+      const double v = fma(g[2], w[2], fma(g[1], w[1], g[0] * w[0]));
+      f[i] = ok ? v : 1.0;
+    }
+#pragma unroll
+    for (int i = 0; i < SNG_UNR; ++i) acc *= f[i];
+    prodacc_renorm(acc, ex);
+  }
+  if (G > 1) {  // the G partial products of a sample, in a fixed butterfly (a product commutes: both lanes get the same bits)
+#pragma unroll
+    for (int off = VH; off < 64; off <<= 1) {
+      acc *= __shfl_xor(acc, off, 64);
+      ex += __shfl_xor(ex, off, 64);
+    }
+  }
+  if (jl && sub == 0) slab[(size_t)items[it].row * V + j] = prodacc_log(acc, ex);
+}
+
+__global__ void __launch_bounds__(256)
+    sng_join_kernel(int64_t n_cuts, const sng_cut* __restrict__ cuts, int V, double* __restrict__ slab) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_cuts * V) return;
+  const int64_t c = i / V;
+  const int j = (int)(i - c * V);
+  const sng_cut ct = cuts[c];
+  double s = slab[(size_t)ct.row * V + j];
+  for (int64_t k = 0; k < ct.count; ++k) s += slab[(size_t)(ct.first + k) * V + j];
+  slab[(size_t)ct.row * V + j] = s;
+}
+
+template <int NA>
+void launch_weights(muxgl_handle* h, const sng_alpha& al, double* d_wt) {
+  hipLaunchKernelGGL((sng_weight_kernel<NA>), dim3((unsigned)((h->nnz + 255) / 256)), dim3(256), 0, h->stream, h->nnz,
+                     h->d_entry_snp, h->d_entry_rptr, h->d_reads, h->d_lut, al, h->d_gp, h->d_has_gp, h->V, d_wt);
+}
+
+template <int VH>
+void launch_sweep(muxgl_handle* h, int64_t n_items, int nblk, const sng_item* d_items, const double* d_wt, double* d_slab) {
+  const int64_t n_units = n_items * nblk;
+  hipLaunchKernelGGL((sng_sweep_kernel<VH>), dim3((unsigned)((n_units + 3) / 4)), dim3(256), 0, h->stream, n_units, nblk,
+                     d_items, h->d_entry_snp, d_wt, h->d_gp, h->V, d_slab);
+}
+
+// slab budget in bytes, as the streamed call's (demux_stream.hip): MUXGL_DEMUX_SLAB_MB, else 4 GiB bounded by a third of
+// the device's memory
+size_t slab_budget() {
+  if (const char* s = getenv("MUXGL_DEMUX_SLAB_MB")) {
+    const long long mb = atoll(s);
+    if (mb > 0) return (size_t)mb << 20;
+  }
+  size_t fr = 0, tot = 0;
+  size_t b = (size_t)4 << 30;
+  if (hipMemGetInfo(&fr, &tot) == hipSuccess && tot > 0) b = std::min(b, tot / 3);
+  return b;
+}
+
+}  // namespace
+
+int demux_singlets_run(muxgl_handle* h, const muxgl_demux_params* p, double* sng) {
+  const int V = h->V, A = p->n_alpha;
+  const int64_t C = h->C;
+  std::vector<int64_t> cell_ptr((size_t)C + 1);
+  HIPCHK(h, hipMemcpyAsync(cell_ptr.data(), h->d_cell_ptr, sizeof(int64_t) * (size_t)(C + 1), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  auto parts_of = [&](int64_t c) { return std::max<int64_t>(1, (cell_ptr[(size_t)c + 1] - cell_ptr[(size_t)c] + SNG_PART - 1) / SNG_PART); };
+
+  // batches of cells whose rows (one per part) fit the budget; at least one cell
+  const int64_t rows_cap = std::max<int64_t>(1, (int64_t)(slab_budget() / (sizeof(double) * (size_t)V)));
+  int64_t max_rows = 0, max_cells = 0, max_cuts = 0;
+  std::vector<int64_t> batch_end;
+  for (int64_t c0 = 0; c0 < C;) {
+    int64_t rows = 0, c1 = c0, cuts = 0;
+    while (c1 < C && (c1 == c0 || rows + parts_of(c1) <= rows_cap)) {
+      const int64_t np = parts_of(c1);
+      rows += np;
+      cuts += np > 1;
+      ++c1;
+    }
+    batch_end.push_back(c1);
+    max_rows = std::max(max_rows, rows);
+    max_cells = std::max(max_cells, c1 - c0);
+    max_cuts = std::max(max_cuts, cuts);
+    c0 = c1;
+  }
+  if ((double)max_rows * (double)((V + 63) / 64) / 4.0 >= 2147483647.0)
+    MUXGL_FAIL(h, "muxgl_demux_singlets: a batch of %lld rows x %d samples exceeds one launch (lower MUXGL_DEMUX_SLAB_MB)",
+               (long long)max_rows, V);
+
+  int VH = 64;
+  while (VH > 1 && VH / 2 >= V) VH /= 2;
+  const int nblk = (V + 63) / 64;
+  sng_alpha al;
+  for (int i = 0; i < MUXGL_MAX_ALPHA; ++i) al.a[i] = i < A ? p->alpha[i] : p->alpha[0];  // (repeats of alpha[0] change no maximum)
+
+  double* d_wt = nullptr;
+  double* d_slab = nullptr;
+  sng_item* d_items = nullptr;
+  sng_cut* d_cuts = nullptr;
+  std::vector<sng_item> items;
+  std::vector<sng_cut> cuts;
+  auto run = [&]() -> int {
+    if (dev_alloc(h, &d_wt, (size_t)h->nnz * 3)) return 1;
+    if (dev_alloc(h, &d_slab, (size_t)max_rows * V)) return 1;
+    if (dev_alloc(h, &d_items, (size_t)max_rows)) return 1;
+    if (dev_alloc(h, &d_cuts, (size_t)max_cuts)) return 1;
+    tic(h, MUXGL_T_DEMUX_SINGLETS);
+    if (h->nnz > 0) {
+      if (A <= 2) launch_weights<2>(h, al, d_wt);
+      else if (A <= 3) launch_weights<3>(h, al, d_wt);
+      else if (A <= 4) launch_weights<4>(h, al, d_wt);
+      else if (A <= 6) launch_weights<6>(h, al, d_wt);
+      else if (A <= 8) launch_weights<8>(h, al, d_wt);
+      else if (A <= 12) launch_weights<12>(h, al, d_wt);
+      else launch_weights<16>(h, al, d_wt);
+      HIPCHK(h, hipGetLastError());
+    }
+    int64_t c0 = 0;
+    for (const int64_t c1 : batch_end) {
+      const int64_t nc = c1 - c0;
+      items.clear();
+      cuts.clear();
+      int64_t over = nc;  // first free row behind the cells' own
+      for (int64_t c = c0; c < c1; ++c) {
+        const int64_t b = cell_ptr[(size_t)c], e = cell_ptr[(size_t)c + 1], np = parts_of(c);
+        items.push_back(sng_item{b, std::min(e, b + SNG_PART), c - c0});
+        if (np > 1) cuts.push_back(sng_cut{c - c0, over, np - 1});
+        for (int64_t k = 1; k < np; ++k) items.push_back(sng_item{b + k * SNG_PART, std::min(e, b + (k + 1) * SNG_PART), over++});
+      }
+      const int64_t n_items = (int64_t)items.size();
+      // (the copies below come from pageable memory: they have left the vectors when they return)
+      HIPCHK(h, hipMemcpyAsync(d_items, items.data(), sizeof(sng_item) * items.size(), hipMemcpyHostToDevice, h->stream));
+      if (!cuts.empty())
+        HIPCHK(h, hipMemcpyAsync(d_cuts, cuts.data(), sizeof(sng_cut) * cuts.size(), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+      switch (VH) {
+        case 1: launch_sweep<1>(h, n_items, nblk, d_items, d_wt, d_slab); break;
+        case 2: launch_sweep<2>(h, n_items, nblk, d_items, d_wt, d_slab); break;
+        case 4: launch_sweep<4>(h, n_items, nblk, d_items, d_wt, d_slab); break;
+        case 8: launch_sweep<8>(h, n_items, nblk, d_items, d_wt, d_slab); break;
+        case 16: launch_sweep<16>(h, n_items, nblk, d_items, d_wt, d_slab); break;
+        case 32: launch_sweep<32>(h, n_items, nblk, d_items, d_wt, d_slab); break;
+        default: launch_sweep<64>(h, n_items, nblk, d_items, d_wt, d_slab); break;
+      }
+      HIPCHK(h, hipGetLastError());
+      if (!cuts.empty()) {
+        const int64_t n = (int64_t)cuts.size() * V;
+        hipLaunchKernelGGL(sng_join_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (int64_t)cuts.size(),
+                           d_cuts, V, d_slab);
+        HIPCHK(h, hipGetLastError());
+      }
+      if (c1 == C) toc(h, MUXGL_T_DEMUX_SINGLETS);
+      HIPCHK(h, hipMemcpyAsync(sng + (size_t)c0 * V, d_slab, sizeof(double) * (size_t)nc * V, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+      c0 = c1;
+    }
+    return 0;
+  };
+  const int rc = run();
+  dev_free(&d_wt);
+  dev_free(&d_slab);
+  dev_free(&d_items);
+  dev_free(&d_cuts);
+  return rc;
+}

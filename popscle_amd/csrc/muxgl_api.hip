@@ -598,6 +598,19 @@ int muxgl_demux_run(muxgl_handle* h, const muxgl_demux_params* p, muxgl_demux_ce
   return 0;
 }
 
+int muxgl_demux_singlets(muxgl_handle* h, const muxgl_demux_params* p, double* sng) {
+  if (!h) return 1;
+  if (h->group) return group_demux_singlets(h, p, sng);
+  HIPCHK(h, hipSetDevice(h->device));
+  if (check_demux_params(h, p)) return 1;
+  if (!sng) MUXGL_FAIL(h, "muxgl_demux_singlets: NULL output");
+  if (h->C == 0) return 0;
+  // (no clear_timing: the slots of the last muxgl_demux_run keep their values)
+  if (demux_singlets_run(h, p, sng)) return 1;
+  collect_timing(h);
+  return 0;
+}
+
 const muxgl_demux_cell* muxgl_demux_results(const muxgl_handle* h) {
   if (h && h->group) return group_demux_results(h);
   return h ? h->h_dcells : nullptr;

@@ -284,6 +284,23 @@ int group_demux_run(muxgl_handle* h, const muxgl_demux_params* p, muxgl_demux_ce
   return 0;
 }
 
+// every member sweeps its own cells and writes their rows of the caller's [C][V] table
+int group_demux_singlets(muxgl_handle* h, const muxgl_demux_params* p, double* sng) {
+  muxgl_group* g = h->group;
+  if (!p) MUXGL_FAIL(h, "demux params NULL");
+  if (p->n_alpha < 1 || p->n_alpha > MUXGL_MAX_ALPHA) MUXGL_FAIL(h, "n_alpha=%d outside [1,%d]", p->n_alpha, MUXGL_MAX_ALPHA);
+  if (!g->have_pileup) MUXGL_FAIL(h, "no pileup set (muxgl_set_pileup)");
+  if (g->V < 1) MUXGL_FAIL(h, "no GP tensor set (muxgl_demux_set_gp)");
+  if (!sng) MUXGL_FAIL(h, "muxgl_demux_singlets: NULL output");
+  if (for_members(h, [&](int r) {
+        return muxgl_demux_singlets(g->m[(size_t)r], p, sng + (size_t)g->cb[(size_t)r] * (size_t)g->V);
+      }))
+    return 1;
+  g->ms[MUXGL_T_DEMUX_SINGLETS] = 0.f;
+  for (auto* m : g->m) g->ms[MUXGL_T_DEMUX_SINGLETS] = std::max(g->ms[MUXGL_T_DEMUX_SINGLETS], m->ms[MUXGL_T_DEMUX_SINGLETS]);
+  return 0;
+}
+
 const muxgl_demux_cell* group_demux_results(const muxgl_handle* h) { return h->group->h_dcells; }
 
 int group_demux_get_entry_pg(muxgl_handle* h, double* pg) {

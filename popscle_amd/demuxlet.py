@@ -10,9 +10,10 @@ from . import shard
 from .freemuxlet import NoExchange
 
 
-def run_sharded(engine_factory, p, alphas=(0.0, 0.5), doublet_prior=0.5, exchange=None):
+def run_sharded(engine_factory, p, alphas=(0.0, 0.5), doublet_prior=0.5, exchange=None, want_singlets=False):
     """engine_factory() -> object with set_pileup / demux_set_gp / demux_run (muxgl.Engine).  Returns the [C] records of
-    the whole pileup on every rank, in the original cell order."""
+    the whole pileup on every rank, in the original cell order; with want_singlets also the [C][V] table of singlet
+    log-likelihoods (Engine.demux_singlets), gathered the same way: (records, sng)."""
     ex = exchange or NoExchange()
     ranges = shard.cell_shards(p.cell_ptr, ex.world)
     c0, c1 = ranges[ex.rank]
@@ -25,4 +26,10 @@ def run_sharded(engine_factory, p, alphas=(0.0, 0.5), doublet_prior=0.5, exchang
     out = np.zeros(p.C, dtype=cells.dtype)
     for b, e, raw in parts:
         out[b:e] = np.frombuffer(raw, dtype=cells.dtype)
-    return out
+    if not want_singlets:
+        return out
+    V = p.gp.shape[1]
+    sng = np.zeros((p.C, V), dtype=np.float64)
+    for b, e, raw in ex.gather_objects((c0, c1, eng.demux_singlets(alphas).tobytes())):
+        sng[b:e] = np.frombuffer(raw, dtype=np.float64).reshape(e - b, V)
+    return out, sng

@@ -2,6 +2,11 @@
 // running on an MI355X through the C-ABI of libmuxgl (include/muxgl.h).
 //
 //   popscle-amd demuxlet   --plp P --vcf V [--field GT|GP|PL] --out O [...]     mirrors cmdCramDemuxlet (cmd_cram_demuxlet.cpp)
+//       --write-singlets: also <O>.sing2.gz (BGZF), the singlet log-likelihood of every printed droplet against every
+//       sample -- the reference's disabled .sing2 writer (cmd_cram_demuxlet.cpp:580,839-848).  Columns BARCODE, SM_ID,
+//       NUM.SNPS, NUM.READS (the droplet's columns of .best, in place of the reference's RD.TOTL / RD.PASS / RD.UNIQ: the
+//       loader keeps no passed-read count), LLK1 (%.4lf), POSTPRB (%.3lg, equal priors over the samples); the reference's
+//       LLK0 (llks00[0]) is left out: nothing computes llks00 and the reference reads it nowhere else
 //   popscle-amd freemuxlet --plp P --nsample K --out O [...]                   mirrors cmdCramFreemux2 (cmd_cram_freemux2.cpp)
 //   popscle-amd freemuxlet-old --plp P --nsample K --out O [...]               mirrors cmdCramFreemuxlet (cmd_cram_freemuxlet.cpp)
 //   popscle-amd dump-plp   --plp P [--vcf V --field F] --out FILE              loader only: packed pileup to a binary file
@@ -102,9 +107,11 @@ int cmd_demuxlet(int argc, char** argv) {
   std::string sam, tagGroup, tagUMI;
   int32_t dummy_i = 0;
   bool deviceCalls = false;  // (ours) skip the host pass that settles mirrored alpha = 0.5 pairs and near-tie calls as the reference does
+  bool writeSinglets = false;  // (ours) <out>.sing2.gz: the reference's disabled .sing2 writer (:580,839-848)
   Args a;
   cf.add(a);
   a.add_bool("device-calls", &deviceCalls);
+  a.add_bool("write-singlets", &writeSinglets);
   a.add_string("vcf", &vr.path);
   a.add_string("field", &cf.lo.field);
   a.add_double("geno-error-offset", &cf.lo.genoErrorOffset);
@@ -199,6 +206,32 @@ int cmd_demuxlet(int argc, char** argv) {
   }
   w.close();
   tm.lap("demuxlet: write .best");
+  if (writeSinglets) {
+    // .sing2.gz: one row per printed droplet (the order and the filters of .best) and sample, in VCF column order.
+    // POSTPRB is the writer's posterior with equal priors over the samples: a softmax over the droplet's row
+    const size_t V = (size_t)p.nv;
+    std::vector<double> sng((size_t)p.C() * V);
+    check(h, muxgl_demux_singlets(h, &dp, sng.data()), "muxgl_demux_singlets");
+    tm.lap("demuxlet: muxgl_demux_singlets");
+    OutFile ws(cf.outPrefix + ".sing2.gz", true);
+    ws.printf("BARCODE\tSM_ID\tNUM.SNPS\tNUM.READS\tLLK1\tPOSTPRB\n");
+    for (auto it = bc_map.begin(); it != bc_map.end(); ++it) {
+      const int32_t i = it->second;
+      const muxgl_demux_cell& c = cells[(size_t)i];
+      if (p.cell_totl_reads[(size_t)i] < cf.lo.minRead || p.cell_uniq_reads[(size_t)i] < cf.lo.minUMI ||
+          c.nsnps < cf.lo.minSNP || !c.valid)
+        continue;
+      const double* row = sng.data() + (size_t)i * V;
+      double mx = row[0], sum = 0.0;
+      for (size_t j = 1; j < V; ++j) mx = std::max(mx, row[j]);
+      for (size_t j = 0; j < V; ++j) sum += exp(row[j] - mx);
+      for (size_t j = 0; j < V; ++j)
+        ws.printf("%s\t%s\t%u\t%d\t%.4lf\t%.3lg\n", it->first.c_str(), sid(p, (int)j), (unsigned)c.nsnps,
+                  p.cell_uniq_reads[(size_t)i], row[j], exp(row[j] - mx) / sum);
+    }
+    ws.close();
+    tm.lap("demuxlet: write .sing2.gz");
+  }
   notice("Finished writing output files");
   muxgl_destroy(h);
   return 0;
@@ -945,7 +978,10 @@ int cmd_bgzf(int argc, char** argv) {
 
 int main(int argc, char** argv) {
   if (argc < 2) {
-    fprintf(stderr, "usage: popscle-amd <demuxlet|freemuxlet|freemuxlet-old|dump-plp> [options]\n");
+    fprintf(stderr, "usage: popscle-amd <demuxlet|freemuxlet|freemuxlet-old|dump-plp> [options]\n"
+                    "  demuxlet --write-singlets: also <out>.sing2.gz, the singlet log-likelihood of every printed droplet\n"
+                    "    against every sample (BARCODE SM_ID NUM.SNPS NUM.READS LLK1 POSTPRB; the reference's RD.* columns\n"
+                    "    give way to the two counts of .best, its LLK0 is left out)\n");
     return 1;
   }
   try {

@@ -39,6 +39,7 @@ XCHG_PAD = 64
 T_FMX_ENTRY, T_FMX_GP, T_FMX_ESTEP, T_FMX_CALL, T_FMX_MSTEP = 4, 5, 6, 7, 8
 T_FMXOLD_PAIR, T_FMXOLD_VOTE = 9, 10
 T_FMX_ESTEP_SWEEP = 11
+T_DEMUX_SINGLETS = 12
 T_COUNT = 16
 BUF_CGP, BUF_CLUST, BUF_CELLS, BUF_STAT = 0, 1, 2, 3
 
@@ -89,6 +90,7 @@ SYMBOLS = {
     "muxgl_set_pileup": (C.c_int, [_VP, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _VP, _VP, _VP, _VP]),
     "muxgl_demux_set_gp": (C.c_int, [_VP, C.c_int32, _VP, _VP]),
     "muxgl_demux_run": (C.c_int, [_VP, C.POINTER(_DemuxParams), _VP, _VP]),
+    "muxgl_demux_singlets": (C.c_int, [_VP, C.POINTER(_DemuxParams), _VP]),
     "muxgl_demux_results": (_VP, [_VP]),
     "muxgl_demux_exact_calls": (C.c_int, [C.c_int64, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP,
                                           C.POINTER(_DemuxParams), _VP, C.c_int32, _VP]),
@@ -180,6 +182,19 @@ def demux_exact_calls(p, alphas, cells, doublet_prior=0.5, nthreads=0):
     if rc != 0:
         raise MuxglError(f"muxgl_demux_exact_calls failed ({rc})")
     return dict(zip(EXACT_STATS, (int(x) for x in stats)))
+
+
+def singlet_posteriors(sng):
+    """Per-sample posteriors of a [C][V] table of singlet log-likelihoods (Engine.demux_singlets) as the reference's
+    disabled .sing2 writer forms them (cmd_cram_demuxlet.cpp:848): equal priors over the samples, i.e. a softmax over
+    each row, computed with the row maximum subtracted.  A row of zeros (droplet without entries) gives 1 / V."""
+    sng = np.asarray(sng, dtype=np.float64)
+    if sng.ndim != 2:
+        raise ValueError("sng must be [C][V]")
+    if sng.shape[1] == 0:
+        return np.zeros_like(sng)
+    ex = np.exp(sng - sng.max(axis=1, keepdims=True))
+    return ex / ex.sum(axis=1, keepdims=True)
 
 
 def _ptr(a):
@@ -302,6 +317,21 @@ class Engine:
         self.n_alpha = len(alphas)
         if want_full_ll:
             return out, full
+        return out
+
+    def demux_singlets(self, alphas=(0.0, 0.5)):
+        """muxgl_demux_singlets: float64 [C][V], the singlet log-likelihood llksAB[(j, 0, 0)] of every droplet against
+        every sample (full_ll[:, :, 0, 0] where that tensor exists), at any V, without a previous demux_run.  The grid
+        matters: the per-entry likelihoods are normalised over all of its alphas."""
+        if len(alphas) > MAX_ALPHA:
+            raise ValueError("too many alphas")
+        p = _DemuxParams()
+        p.n_alpha = len(alphas)
+        for i, a in enumerate(alphas):
+            p.alpha[i] = float(a)
+        p.doublet_prior = 0.5  # (not read by the call)
+        out = np.zeros((self.C, self.V), dtype=np.float64)
+        self._check(self.lib.muxgl_demux_singlets(self.h, C.byref(p), _ptr(out)))
         return out
 
     def demux_results_view(self):
