@@ -18,6 +18,7 @@
 
 #include "../../include/muxgl.h"
 #include "path_choice.hpp"
+#include "stream_plan.hpp"
 
 constexpr int MUXGL_ROW_CH = 128;   // entries per chunk of the row kernels (16-lane slots)
 constexpr int MUXGL_QUAD_CH = 192;  // entries per chunk of the freemuxlet oct E-step (configs[3], E-step in ms: 128: 1.63,
@@ -330,6 +331,23 @@ static inline int dev_alloc(muxgl_handle* h, T** p, size_t n) {
   dev_free(p);
   if (n == 0) n = 1;
   return dev_alloc_bytes(h, (void**)p, n * sizeof(T));
+}
+
+// a temporary of one call: dev_alloc(h, &t.p, n), freed (back to the handle's cache) when t goes out of scope
+template <typename T>
+struct dev_tmp {
+  T* p = nullptr;
+  dev_tmp() = default;
+  dev_tmp(const dev_tmp&) = delete;
+  dev_tmp& operator=(const dev_tmp&) = delete;
+  ~dev_tmp() { dev_free(&p); }
+};
+
+// slab budget of the streamed paths on the current device (stream_plan.hpp)
+static inline size_t dev_slab_budget(const char* env_mb) {
+  size_t fr = 0, tot = 0;
+  if (hipMemGetInfo(&fr, &tot) != hipSuccess) tot = 0;
+  return stream_plan::slab_budget_bytes(env_mb, tot);
 }
 
 static inline bool timing_off() {  // MUXGL_NO_EVENTS=1: no hipEvent records around the kernels (launch-gap experiments)

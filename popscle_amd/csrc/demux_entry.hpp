@@ -3,6 +3,18 @@
 #pragma once
 #include "common.hpp"
 
+// returns CALL(NA) for the smallest instantiated alpha count NA >= A of the kernels built on row_entry_pg<NA>
+#define DISPATCH_NA(A, CALL)                    \
+  do {                                          \
+    if ((A) <= 2) return CALL(2);               \
+    if ((A) <= 3) return CALL(3);               \
+    if ((A) <= 4) return CALL(4);               \
+    if ((A) <= 6) return CALL(6);               \
+    if ((A) <= 8) return CALL(8);               \
+    if ((A) <= 12) return CALL(12);             \
+    return CALL(16);                            \
+  } while (0)
+
 // cmd_cram_demuxlet.cpp:655-725 for one entry.  lut: [0,128) phred2Err, [128,256) phred2Mat, [256,384) Err/3
 // (muxgl_create); first4 = the entry's first four read bytes (byte k = read k), the rest is read from `reads`.
 template <int NA>

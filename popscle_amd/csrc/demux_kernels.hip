@@ -298,17 +298,6 @@ int launch_entry_pg(muxgl_handle* h, const muxgl_demux_params* p, const alpha_ar
 
 }  // namespace
 
-#define DISPATCH_NA(A, CALL)                    \
-  do {                                          \
-    if ((A) <= 2) return CALL(2);               \
-    if ((A) <= 3) return CALL(3);               \
-    if ((A) <= 4) return CALL(4);               \
-    if ((A) <= 6) return CALL(6);               \
-    if ((A) <= 8) return CALL(8);               \
-    if ((A) <= 12) return CALL(12);             \
-    return CALL(16);                            \
-  } while (0)
-
 // builds the (j,k,nmask) work list: (j,0) pairs first so that the singlet slot n=0 lives in the first wave(s)
 static int build_pairs(muxgl_handle* h, const muxgl_demux_params* p, uint32_t* symmask_out) {
   const int V = h->V, A = p->n_alpha;

@@ -22,7 +22,6 @@
 // Memory: [nnz][3] weights and a slab of the table.  When the table exceeds the budget (the streamed call's: 4 GiB or a
 // third of the device, MUXGL_DEMUX_SLAB_MB) the cells are swept in batches and each batch is copied out before the next.
 #include <algorithm>
-#include <cstdlib>
 #include <vector>
 
 #include "demux_entry.hpp"
@@ -137,9 +136,17 @@ __global__ void __launch_bounds__(256)
 }
 
 template <int NA>
-void launch_weights(muxgl_handle* h, const sng_alpha& al, double* d_wt) {
+int launch_weights(muxgl_handle* h, const sng_alpha& al, double* d_wt) {
   hipLaunchKernelGGL((sng_weight_kernel<NA>), dim3((unsigned)((h->nnz + 255) / 256)), dim3(256), 0, h->stream, h->nnz,
                      h->d_entry_snp, h->d_entry_rptr, h->d_reads, h->d_lut, al, h->d_gp, h->d_has_gp, h->V, d_wt);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int weights_dispatch(muxgl_handle* h, int A, const sng_alpha& al, double* d_wt) {
+#define CALL_W(N) launch_weights<N>(h, al, d_wt)
+  DISPATCH_NA(A, CALL_W);
+#undef CALL_W
 }
 
 template <int VH>
@@ -147,19 +154,6 @@ void launch_sweep(muxgl_handle* h, int64_t n_items, int nblk, const sng_item* d_
   const int64_t n_units = n_items * nblk;
   hipLaunchKernelGGL((sng_sweep_kernel<VH>), dim3((unsigned)((n_units + 3) / 4)), dim3(256), 0, h->stream, n_units, nblk,
                      d_items, h->d_entry_snp, d_wt, h->d_gp, h->V, d_slab);
-}
-
-// slab budget in bytes, as the streamed call's (demux_stream.hip): MUXGL_DEMUX_SLAB_MB, else 4 GiB bounded by a third of
-// the device's memory
-size_t slab_budget() {
-  if (const char* s = getenv("MUXGL_DEMUX_SLAB_MB")) {
-    const long long mb = atoll(s);
-    if (mb > 0) return (size_t)mb << 20;
-  }
-  size_t fr = 0, tot = 0;
-  size_t b = (size_t)4 << 30;
-  if (hipMemGetInfo(&fr, &tot) == hipSuccess && tot > 0) b = std::min(b, tot / 3);
-  return b;
 }
 
 }  // namespace
@@ -173,7 +167,7 @@ int demux_singlets_run(muxgl_handle* h, const muxgl_demux_params* p, double* sng
   auto parts_of = [&](int64_t c) { return std::max<int64_t>(1, (cell_ptr[(size_t)c + 1] - cell_ptr[(size_t)c] + SNG_PART - 1) / SNG_PART); };
 
   // batches of cells whose rows (one per part) fit the budget; at least one cell
-  const int64_t rows_cap = std::max<int64_t>(1, (int64_t)(slab_budget() / (sizeof(double) * (size_t)V)));
+  const int64_t rows_cap = std::max<int64_t>(1, (int64_t)(dev_slab_budget("MUXGL_DEMUX_SLAB_MB") / (sizeof(double) * (size_t)V)));
   int64_t max_rows = 0, max_cells = 0, max_cuts = 0;
   std::vector<int64_t> batch_end;
   for (int64_t c0 = 0; c0 < C;) {
@@ -200,73 +194,55 @@ int demux_singlets_run(muxgl_handle* h, const muxgl_demux_params* p, double* sng
   sng_alpha al;
   for (int i = 0; i < MUXGL_MAX_ALPHA; ++i) al.a[i] = i < A ? p->alpha[i] : p->alpha[0];  // (repeats of alpha[0] change no maximum)
 
-  double* d_wt = nullptr;
-  double* d_slab = nullptr;
-  sng_item* d_items = nullptr;
-  sng_cut* d_cuts = nullptr;
+  dev_tmp<double> d_wt, d_slab;
+  dev_tmp<sng_item> d_items;
+  dev_tmp<sng_cut> d_cuts;
   std::vector<sng_item> items;
   std::vector<sng_cut> cuts;
-  auto run = [&]() -> int {
-    if (dev_alloc(h, &d_wt, (size_t)h->nnz * 3)) return 1;
-    if (dev_alloc(h, &d_slab, (size_t)max_rows * V)) return 1;
-    if (dev_alloc(h, &d_items, (size_t)max_rows)) return 1;
-    if (dev_alloc(h, &d_cuts, (size_t)max_cuts)) return 1;
-    tic(h, MUXGL_T_DEMUX_SINGLETS);
-    if (h->nnz > 0) {
-      if (A <= 2) launch_weights<2>(h, al, d_wt);
-      else if (A <= 3) launch_weights<3>(h, al, d_wt);
-      else if (A <= 4) launch_weights<4>(h, al, d_wt);
-      else if (A <= 6) launch_weights<6>(h, al, d_wt);
-      else if (A <= 8) launch_weights<8>(h, al, d_wt);
-      else if (A <= 12) launch_weights<12>(h, al, d_wt);
-      else launch_weights<16>(h, al, d_wt);
+  if (dev_alloc(h, &d_wt.p, (size_t)h->nnz * 3)) return 1;
+  if (dev_alloc(h, &d_slab.p, (size_t)max_rows * V)) return 1;
+  if (dev_alloc(h, &d_items.p, (size_t)max_rows)) return 1;
+  if (dev_alloc(h, &d_cuts.p, (size_t)max_cuts)) return 1;
+  tic(h, MUXGL_T_DEMUX_SINGLETS);
+  if (h->nnz > 0 && weights_dispatch(h, A, al, d_wt.p)) return 1;
+  int64_t c0 = 0;
+  for (const int64_t c1 : batch_end) {
+    const int64_t nc = c1 - c0;
+    items.clear();
+    cuts.clear();
+    int64_t over = nc;  // first free row behind the cells' own
+    for (int64_t c = c0; c < c1; ++c) {
+      const int64_t b = cell_ptr[(size_t)c], e = cell_ptr[(size_t)c + 1], np = parts_of(c);
+      items.push_back(sng_item{b, std::min(e, b + SNG_PART), c - c0});
+      if (np > 1) cuts.push_back(sng_cut{c - c0, over, np - 1});
+      for (int64_t k = 1; k < np; ++k) items.push_back(sng_item{b + k * SNG_PART, std::min(e, b + (k + 1) * SNG_PART), over++});
+    }
+    const int64_t n_items = (int64_t)items.size();
+    // (the copies below come from pageable memory: they have left the vectors when they return)
+    HIPCHK(h, hipMemcpyAsync(d_items.p, items.data(), sizeof(sng_item) * items.size(), hipMemcpyHostToDevice, h->stream));
+    if (!cuts.empty())
+      HIPCHK(h, hipMemcpyAsync(d_cuts.p, cuts.data(), sizeof(sng_cut) * cuts.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    switch (VH) {
+      case 1: launch_sweep<1>(h, n_items, nblk, d_items.p, d_wt.p, d_slab.p); break;
+      case 2: launch_sweep<2>(h, n_items, nblk, d_items.p, d_wt.p, d_slab.p); break;
+      case 4: launch_sweep<4>(h, n_items, nblk, d_items.p, d_wt.p, d_slab.p); break;
+      case 8: launch_sweep<8>(h, n_items, nblk, d_items.p, d_wt.p, d_slab.p); break;
+      case 16: launch_sweep<16>(h, n_items, nblk, d_items.p, d_wt.p, d_slab.p); break;
+      case 32: launch_sweep<32>(h, n_items, nblk, d_items.p, d_wt.p, d_slab.p); break;
+      default: launch_sweep<64>(h, n_items, nblk, d_items.p, d_wt.p, d_slab.p); break;
+    }
+    HIPCHK(h, hipGetLastError());
+    if (!cuts.empty()) {
+      const int64_t n = (int64_t)cuts.size() * V;
+      hipLaunchKernelGGL(sng_join_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (int64_t)cuts.size(),
+                         d_cuts.p, V, d_slab.p);
       HIPCHK(h, hipGetLastError());
     }
-    int64_t c0 = 0;
-    for (const int64_t c1 : batch_end) {
-      const int64_t nc = c1 - c0;
-      items.clear();
-      cuts.clear();
-      int64_t over = nc;  // first free row behind the cells' own
-      for (int64_t c = c0; c < c1; ++c) {
-        const int64_t b = cell_ptr[(size_t)c], e = cell_ptr[(size_t)c + 1], np = parts_of(c);
-        items.push_back(sng_item{b, std::min(e, b + SNG_PART), c - c0});
-        if (np > 1) cuts.push_back(sng_cut{c - c0, over, np - 1});
-        for (int64_t k = 1; k < np; ++k) items.push_back(sng_item{b + k * SNG_PART, std::min(e, b + (k + 1) * SNG_PART), over++});
-      }
-      const int64_t n_items = (int64_t)items.size();
-      // (the copies below come from pageable memory: they have left the vectors when they return)
-      HIPCHK(h, hipMemcpyAsync(d_items, items.data(), sizeof(sng_item) * items.size(), hipMemcpyHostToDevice, h->stream));
-      if (!cuts.empty())
-        HIPCHK(h, hipMemcpyAsync(d_cuts, cuts.data(), sizeof(sng_cut) * cuts.size(), hipMemcpyHostToDevice, h->stream));
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      switch (VH) {
-        case 1: launch_sweep<1>(h, n_items, nblk, d_items, d_wt, d_slab); break;
-        case 2: launch_sweep<2>(h, n_items, nblk, d_items, d_wt, d_slab); break;
-        case 4: launch_sweep<4>(h, n_items, nblk, d_items, d_wt, d_slab); break;
-        case 8: launch_sweep<8>(h, n_items, nblk, d_items, d_wt, d_slab); break;
-        case 16: launch_sweep<16>(h, n_items, nblk, d_items, d_wt, d_slab); break;
-        case 32: launch_sweep<32>(h, n_items, nblk, d_items, d_wt, d_slab); break;
-        default: launch_sweep<64>(h, n_items, nblk, d_items, d_wt, d_slab); break;
-      }
-      HIPCHK(h, hipGetLastError());
-      if (!cuts.empty()) {
-        const int64_t n = (int64_t)cuts.size() * V;
-        hipLaunchKernelGGL(sng_join_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (int64_t)cuts.size(),
-                           d_cuts, V, d_slab);
-        HIPCHK(h, hipGetLastError());
-      }
-      if (c1 == C) toc(h, MUXGL_T_DEMUX_SINGLETS);
-      HIPCHK(h, hipMemcpyAsync(sng + (size_t)c0 * V, d_slab, sizeof(double) * (size_t)nc * V, hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      c0 = c1;
-    }
-    return 0;
-  };
-  const int rc = run();
-  dev_free(&d_wt);
-  dev_free(&d_slab);
-  dev_free(&d_items);
-  dev_free(&d_cuts);
-  return rc;
+    if (c1 == C) toc(h, MUXGL_T_DEMUX_SINGLETS);
+    HIPCHK(h, hipMemcpyAsync(sng + (size_t)c0 * V, d_slab.p, sizeof(double) * (size_t)nc * V, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    c0 = c1;
+  }
+  return 0;
 }

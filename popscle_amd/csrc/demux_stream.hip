@@ -15,19 +15,16 @@
 // mantissa / exponent form with one log per hypothesis -- in a plainer mapping: lane = sample j of the block, the wave's
 // KT partner samples k are wave-uniform (scalar loads), all alphas of the grid in one launch.
 //
-// State per cell (stream_state): the top-two (value, scan position) of the singlet and of the doublet scan plus the third
-// value of each (muxgl_call::top2), and the evidence sums as (largest term, sum relative to it) for sumLLK and sngLLK.
-// Ordering rule: value descending, then scan position ascending (muxgl_call::key_before), which is what the reference's
-// update rule (bv < v, then nv < v) leaves; it is a total order, so the top-two do not depend on grouping.  Scan
-// positions: j for singlets, (j V + k) A + n for doublets.  An alpha = 0.5 pair is listed once, as (lo, hi), with the
-// value computed in the (hi, lo) orientation; demux_call_decide names its mirror the runner-up.
-// Determinism: a block's partial is reduced in a fixed tree, and a cell's partials are merged into its state in block
-// order, whatever the budget cuts: records are bit-identical across budgets (tests/test_demux_many_samples_gpu.py).
+// State per cell, the fold and why records are bit-identical across budgets: stream_fold.hpp; groups and block list:
+// stream_plan.hpp.  Here the lists are muxgl_call::top2 and the evidence sums those of sumLLK and sngLLK.  Ordering rule:
+// value descending, then scan position ascending (muxgl_call::key_before), which is what the reference's update rule
+// (bv < v, then nv < v) leaves.  Scan positions: j for singlets, (j V + k) A + n for doublets.  An alpha = 0.5 pair is
+// listed once, as (lo, hi), with the value computed in the (hi, lo) orientation; demux_call_decide names its mirror the
+// runner-up.
 #include <algorithm>
-#include <cstdlib>
 #include <vector>
 
-#include "demux_call_body.hpp"
+#include "stream_fold.hpp"
 
 namespace {
 
@@ -36,47 +33,17 @@ using namespace muxgl_call;
 constexpr int SBLK = 64;                     // samples per side of a block of the pair matrix
 constexpr int SLAB_DOUBLES = SBLK * SBLK;    // per alpha and block: [k][j]
 
-struct stream_state {
-  top2 sng, dbl;
-  double M, S, Ms, Ss;  // evidence: largest term, sum of exp(term - M); the same for the singlet terms
+// the lists of the state and their butterfly: DPP pairings (lane_partner)
+struct demux_top2_ops {
+  using list = top2;
+  static __device__ __forceinline__ top2 empty() { return top2{-1e300, -1e300, -1, -1, -1e300}; }
+  static __device__ __forceinline__ top2 merge(const top2& a, const top2& b) { return top2_merge<true>(a, b); }
+  template <int M>
+  static __device__ __forceinline__ top2 partner(const top2& t) { return top2_partner<M, true>(t); }
+  template <int M>
+  static __device__ __forceinline__ double partner(double x) { return lane_partner<M>(x); }
 };
-
-// merge of two partials (a first in block order: the LSE merge is one fixed expression, so the order fixes the bits)
-__device__ __forceinline__ stream_state merge_state(const stream_state& a, const stream_state& b) {
-  stream_state r;
-  r.sng = top2_merge<true>(a.sng, b.sng);
-  r.dbl = top2_merge<true>(a.dbl, b.dbl);
-  r.M = fmax(a.M, b.M);
-  r.S = (a.S > 0.0 ? a.S * exp_nonpos(a.M - r.M) : 0.0) + (b.S > 0.0 ? b.S * exp_nonpos(b.M - r.M) : 0.0);
-  r.Ms = fmax(a.Ms, b.Ms);
-  r.Ss = (a.Ss > 0.0 ? a.Ss * exp_nonpos(a.Ms - r.Ms) : 0.0) + (b.Ss > 0.0 ? b.Ss * exp_nonpos(b.Ms - r.Ms) : 0.0);
-  return r;
-}
-
-__device__ __forceinline__ stream_state empty_state() {
-  stream_state s;
-  s.sng = top2{-1e300, -1e300, -1, -1, -1e300};
-  s.dbl = s.sng;
-  s.M = s.Ms = -__builtin_huge_val();
-  s.S = s.Ss = 0.0;
-  return s;
-}
-
-// one more term of a running (largest term, sum relative to it)
-__device__ __forceinline__ void lse_push(double& M, double& S, double t) {
-  if (!(t > -__builtin_huge_val())) return;  // exp(-inf) adds nothing
-  if (t > M) {
-    S = (S > 0.0 ? S * exp_nonpos(M - t) : 0.0) + 1.0;
-    M = t;
-  } else {
-    S += exp_nonpos(t - M);
-  }
-}
-
-__global__ void __launch_bounds__(256) stream_init_kernel(int64_t n, stream_state* __restrict__ st) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) st[i] = empty_state();
-}
+using stream_state = stream_fold::stream_state<demux_top2_ops>;
 
 // Sweep of one group: grid = (cells of the group, 64 / (4 KT) sub-tiles, blocks of the group).  Lane j of wave w owns
 // sample jbase + j and the KT partners kbase + 4 KT y + KT w + i; NA >= A - 1 accumulators per pair (alphas 1 .. A - 1),
@@ -159,72 +126,43 @@ __global__ void __launch_bounds__(256)
   if (with_singlet) out[lane] = prodacc_log(accS, exS);  // slot (n = 0, k = 0)
 }
 
-template <int M>
-__device__ __forceinline__ stream_state state_partner(const stream_state& s) {
-  stream_state o;
-  o.sng = top2_partner<M, true>(s.sng);
-  o.dbl = top2_partner<M, true>(s.dbl);
-  o.M = lane_partner<M>(s.M);
-  o.S = lane_partner<M>(s.S);
-  o.Ms = lane_partner<M>(s.Ms);
-  o.Ss = lane_partner<M>(s.Ss);
-  return o;
-}
-
-// Fold of one group: one workgroup per cell of the group; the group's blocks in order, each reduced over the workgroup
-// in a fixed tree (thread -> wave butterfly -> the four waves in order) and merged into the cell's state.
+// Fold of one group: one workgroup per cell of the group (stream_fold::fold_blocks); a thread's hypotheses of a block
 __global__ void __launch_bounds__(256)
     stream_fold_kernel(int64_t c0, int32_t b0, int32_t nb, const int32_t* __restrict__ blocks, int nblk,
                        const int64_t* __restrict__ cell_ptr, int V, int nAlpha, call_alpha al,
                        const double* __restrict__ slab, stream_state* __restrict__ state) {
-  __shared__ stream_state parts[4];
   const int64_t c = c0 + blockIdx.x;
   if (cell_ptr[c] == cell_ptr[c + 1]) return;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  stream_state st = state[c];  // (read by every thread, written by thread 0 at the end)
-  for (int z = 0; z < nb; ++z) {
+  stream_fold::fold_blocks(nb, state + c, [&](int z, stream_state& t) {
     const int b = blocks[b0 + z];
     const int X = b / nblk, Y = b - X * nblk;
     const int j = SBLK * X + lane;
     const double* in = slab + ((size_t)blockIdx.x * nb + z) * nAlpha * SLAB_DOUBLES;
-    stream_state t = empty_state();
-    if (j < V) {
-      if (Y == 0 && w == 0) {  // singlet of sample j (:806,828)
-        const double v = in[lane];
-        top2_insert(t.sng, v, j);
-        const double term = v + al.log_single_prior;
-        lse_push(t.M, t.S, term);
-        lse_push(t.Ms, t.Ss, term);
-      }
-      for (int kq = 16 * w; kq < 16 * w + 16; ++kq) {
-        const int k = SBLK * Y + kq;
-        if (k >= V || k == j) continue;
-        for (int n = 1; n < nAlpha; ++n) {
-          const double v = in[((size_t)n * SBLK + kq) * SBLK + lane];
-          if (al.a[n] == 0.5) {  // (hi, lo) orientation only, listed as (lo, hi): see the header
-            if (k > j) continue;
-            lse_push(t.M, t.S, v + al.log_doublet_prior2);  // :812-815
-            top2_insert(t.dbl, v, (k * V + j) * nAlpha + n);
-          } else {
-            lse_push(t.M, t.S, v + al.log_doublet_prior1);
-            top2_insert(t.dbl, v, (j * V + k) * nAlpha + n);
-          }
+    if (j >= V) return;
+    if (Y == 0 && w == 0) {  // singlet of sample j (:806,828)
+      const double v = in[lane];
+      top2_insert(t.sng, v, j);
+      const double term = v + al.log_single_prior;
+      t.all.push(term);
+      t.sgl.push(term);
+    }
+    for (int kq = 16 * w; kq < 16 * w + 16; ++kq) {
+      const int k = SBLK * Y + kq;
+      if (k >= V || k == j) continue;
+      for (int n = 1; n < nAlpha; ++n) {
+        const double v = in[((size_t)n * SBLK + kq) * SBLK + lane];
+        if (al.a[n] == 0.5) {  // (hi, lo) orientation only, listed as (lo, hi): see the header
+          if (k > j) continue;
+          t.all.push(v + al.log_doublet_prior2);  // :812-815
+          top2_insert(t.dbl, v, (k * V + j) * nAlpha + n);
+        } else {
+          t.all.push(v + al.log_doublet_prior1);
+          top2_insert(t.dbl, v, (j * V + k) * nAlpha + n);
         }
       }
     }
-    wave_for<0, 6>([&](auto sc) {
-      constexpr int m = 1 << decltype(sc)::value;
-      t = merge_state(t, state_partner<m>(t));
-    });
-    if (lane == 0) parts[w] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      stream_state r = merge_state(merge_state(parts[0], parts[1]), merge_state(parts[2], parts[3]));
-      st = merge_state(st, r);
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) state[c] = st;
+  });
 }
 
 // the call from the state: one lane per cell (demux_call_decide's note)
@@ -234,7 +172,7 @@ __global__ void __launch_bounds__(64)
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
   const stream_state& s = state[c];
-  const call_partial cp{s.sng, s.dbl, s.M, s.S, s.Ms, s.Ss};
+  const call_partial cp{s.sng, s.dbl, s.all.M, s.all.S, s.sgl.M, s.sgl.S};
   demux_call_decide(cp, (int32_t)(cell_ptr[c + 1] - cell_ptr[c]), V, nAlpha, al, out + c);
 }
 
@@ -264,18 +202,6 @@ int sweep_dispatch(muxgl_handle* h, int64_t c0, int64_t nc, int32_t b0, int32_t 
 
 }  // namespace
 
-// slab budget in bytes: MUXGL_DEMUX_SLAB_MB, else 4 GiB bounded by a third of the device's memory (the handle cache's cap)
-static size_t stream_budget() {
-  if (const char* s = getenv("MUXGL_DEMUX_SLAB_MB")) {
-    const long long mb = atoll(s);
-    if (mb > 0) return (size_t)mb << 20;
-  }
-  size_t fr = 0, tot = 0;
-  size_t b = (size_t)4 << 30;
-  if (hipMemGetInfo(&fr, &tot) == hipSuccess && tot > 0) b = std::min(b, tot / 3);
-  return b;
-}
-
 int demux_stream_launch(muxgl_handle* h, const muxgl_demux_params* p) {
   const int V = h->V, A = p->n_alpha;
   if (A < 2) MUXGL_FAIL(h, "streamed demuxlet call: the alpha grid needs a doublet alpha (n_alpha >= 2)");
@@ -284,66 +210,44 @@ int demux_stream_launch(muxgl_handle* h, const muxgl_demux_params* p) {
   if (h->want_full_ll)
     MUXGL_FAIL(h, "muxgl_demux_run: full_ll is not available on the streamed path (V=%d; more than 255 samples, a job whose "
                   "[C][V][V][A] tensor does not fit the device, or MUXGL_FLAG_FORCE_STREAMED_CALL): pass full_ll = NULL", V);
-  const int nblk = (V + SBLK - 1) / SBLK;
   bool all_sym = true;
   for (int n = 1; n < A; ++n) all_sym = all_sym && p->alpha[n] == 0.5;
   // blocks that hold a hypothesis the call reads: with alpha = 0.5 only the (hi, lo) orientation, and the singlets in Y = 0
-  std::vector<int32_t> blocks;
-  for (int X = 0; X < nblk; ++X)
-    for (int Y = 0; Y < nblk; ++Y)
-      if (!all_sym || X >= Y) blocks.push_back(X * nblk + Y);
+  const int nblk = (V + SBLK - 1) / SBLK;
+  const std::vector<int32_t> blocks = stream_plan::block_list(nblk, all_sym, nblk);  // X * nblk + Y
   const int64_t nb_all = (int64_t)blocks.size();
   const size_t per = (size_t)A * SLAB_DOUBLES * sizeof(double);  // one (cell, block) of the slab
-  const size_t budget = std::max(stream_budget(), per);
-  // groups: all cells x as many blocks as fit; if one block of every cell does not fit, one block x as many cells as fit
-  int64_t gb, gc;
-  if ((size_t)h->C * per <= budget) {
-    gc = h->C;
-    gb = std::min<int64_t>(nb_all, (int64_t)(budget / ((size_t)h->C * per)));
-  } else {
-    gb = 1;
-    gc = (int64_t)(budget / per);
-  }
-  gb = std::min<int64_t>(gb, 65535);
-  gc = std::min<int64_t>(gc, (int64_t)1 << 30);
+  const auto [gc, gb] = stream_plan::cut_groups(h->C, nb_all, per, dev_slab_budget("MUXGL_DEMUX_SLAB_MB"));
 
-  int32_t* d_blocks = nullptr;
-  double* d_pg = nullptr;
-  double* d_slab = nullptr;
-  stream_state* d_state = nullptr;
-  auto run = [&]() -> int {
-    if (dev_alloc(h, &d_blocks, blocks.size())) return 1;
-    if (dev_alloc(h, &d_pg, (size_t)h->nnz * A * 9)) return 1;
-    if (dev_alloc(h, &d_slab, (size_t)gc * gb * A * SLAB_DOUBLES)) return 1;
-    if (dev_alloc(h, &d_state, (size_t)h->C)) return 1;
-    HIPCHK(h, hipMemcpyAsync(d_blocks, blocks.data(), sizeof(int32_t) * blocks.size(), hipMemcpyHostToDevice, h->stream));
-    tic(h, MUXGL_T_DEMUX_SWEEP);
-    if (demux_entry_pg_launch(h, p, d_pg)) return 1;
-    hipLaunchKernelGGL(stream_init_kernel, dim3((unsigned)((h->C + 255) / 256)), dim3(256), 0, h->stream, h->C, d_state);
-    HIPCHK(h, hipGetLastError());
-    const call_alpha al = make_call_alpha(p, V);
-    for (int64_t c0 = 0; c0 < h->C; c0 += gc) {
-      const int64_t nc = std::min(gc, h->C - c0);
-      for (int64_t b0 = 0; b0 < nb_all; b0 += gb) {  // blocks in order: see the header (determinism)
-        const int32_t nb = (int32_t)std::min(gb, nb_all - b0);
-        if (sweep_dispatch(h, c0, nc, (int32_t)b0, nb, d_blocks, nblk, d_pg, A, d_slab)) return 1;
-        hipLaunchKernelGGL(stream_fold_kernel, dim3((unsigned)nc), dim3(256), 0, h->stream, c0, (int32_t)b0, nb, d_blocks,
-                           nblk, h->d_cell_ptr, V, A, al, d_slab, d_state);
-        HIPCHK(h, hipGetLastError());
-      }
+  dev_tmp<int32_t> d_blocks;
+  dev_tmp<double> d_pg, d_slab;
+  dev_tmp<stream_state> d_state;
+  if (dev_alloc(h, &d_blocks.p, blocks.size())) return 1;
+  if (dev_alloc(h, &d_pg.p, (size_t)h->nnz * A * 9)) return 1;
+  if (dev_alloc(h, &d_slab.p, (size_t)gc * gb * A * SLAB_DOUBLES)) return 1;
+  if (dev_alloc(h, &d_state.p, (size_t)h->C)) return 1;
+  HIPCHK(h, hipMemcpyAsync(d_blocks.p, blocks.data(), sizeof(int32_t) * blocks.size(), hipMemcpyHostToDevice, h->stream));
+  tic(h, MUXGL_T_DEMUX_SWEEP);
+  if (demux_entry_pg_launch(h, p, d_pg.p)) return 1;
+  hipLaunchKernelGGL(stream_fold::stream_init_kernel<demux_top2_ops>, dim3((unsigned)((h->C + 255) / 256)), dim3(256), 0,
+                     h->stream, h->C, d_state.p);
+  HIPCHK(h, hipGetLastError());
+  const call_alpha al = make_call_alpha(p, V);
+  for (int64_t c0 = 0; c0 < h->C; c0 += gc) {
+    const int64_t nc = std::min(gc, h->C - c0);
+    for (int64_t b0 = 0; b0 < nb_all; b0 += gb) {  // blocks in order: stream_fold.hpp (determinism)
+      const int32_t nb = (int32_t)std::min(gb, nb_all - b0);
+      if (sweep_dispatch(h, c0, nc, (int32_t)b0, nb, d_blocks.p, nblk, d_pg.p, A, d_slab.p)) return 1;
+      hipLaunchKernelGGL(stream_fold_kernel, dim3((unsigned)nc), dim3(256), 0, h->stream, c0, (int32_t)b0, nb, d_blocks.p,
+                         nblk, h->d_cell_ptr, V, A, al, d_slab.p, d_state.p);
+      HIPCHK(h, hipGetLastError());
     }
-    toc(h, MUXGL_T_DEMUX_SWEEP);
-    tic(h, MUXGL_T_DEMUX_CALL);
-    hipLaunchKernelGGL(stream_call_kernel, dim3((unsigned)((h->C + 63) / 64)), dim3(64), 0, h->stream, h->C, h->d_cell_ptr,
-                       V, A, al, d_state, h->d_dcells);
-    HIPCHK(h, hipGetLastError());
-    toc(h, MUXGL_T_DEMUX_CALL);
-    return 0;
-  };
-  const int rc = run();
-  dev_free(&d_blocks);
-  dev_free(&d_pg);
-  dev_free(&d_slab);
-  dev_free(&d_state);
-  return rc;
+  }
+  toc(h, MUXGL_T_DEMUX_SWEEP);
+  tic(h, MUXGL_T_DEMUX_CALL);
+  hipLaunchKernelGGL(stream_call_kernel, dim3((unsigned)((h->C + 63) / 64)), dim3(64), 0, h->stream, h->C, h->d_cell_ptr,
+                     V, A, al, d_state.p, h->d_dcells);
+  HIPCHK(h, hipGetLastError());
+  toc(h, MUXGL_T_DEMUX_CALL);
+  return 0;
 }

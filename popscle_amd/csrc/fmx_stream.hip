@@ -7,7 +7,8 @@
 // (cells x blocks) at a time whose slab fits a fixed budget; after each group a fold kernel merges the slab into a running
 // state per cell, and the slab is reused.  A last kernel makes the call from that state with the tail every freemuxlet call
 // kernel ends in (fmx_call_finish.inc).  The design of demux_stream.hip, with the entry's nine genotype-pair likelihoods in
-// the role of pG.
+// the role of pG; the two share the groups and the block list (stream_plan.hpp) and the state and its fold
+// (stream_fold.hpp).
 //
 // Reference being replaced: cmd_cram_freemux2.cpp:383-456 (E-step), :458-513 (scans), :515-584 (re-assignment).
 //
@@ -27,17 +28,15 @@
 // Products are mantissa x 2^exponent with one log per (cell, hypothesis); the renormalisation points do not change a bit
 // (scaling by powers of two is exact, and pos_log takes the exponent apart itself).
 //
-// State per cell (fmx_stream_state): fmx_top2 of the singlet and of the doublet scan (value, position p = j(j+1)/2 + k, and
-// the third value), the evidence sums as (largest term, sum of exp(term - largest)) of all hypotheses with their priors and
-// of the singlets without.  Order: value descending, then position ascending (fmx_better) -- the order fmx_top2_push and
-// the reference's strict `>` updates leave, a total order, so grouping cannot change the top two or the third value.
-// A block's partial is reduced in a fixed tree and merged into the state in block order: records are bit-identical
-// whatever the budget.
+// State per cell (stream_fold.hpp, which also says why records are bit-identical whatever the budget): fmx_top2 of the
+// singlet and of the doublet scan (value, position p = j(j+1)/2 + k, and the third value), the evidence sums of all
+// hypotheses with their priors and of the singlets without.  Order: value descending, then position ascending
+// (fmx_better) -- the order fmx_top2_push and the reference's strict `>` updates leave.
 #include <algorithm>
-#include <cstdlib>
 #include <vector>
 
 #include "fmx_call_body.hpp"
+#include "stream_fold.hpp"
 
 namespace {
 
@@ -46,70 +45,27 @@ constexpr int SLAB = CB * CB;       // doubles per (cell, block) of the slab: [s
 constexpr int64_t PART = 2048;      // entries per part of a long cell (demux_wave_plan's WAVE_ITEM)
 constexpr int32_t NO_POS = 0x7fffffff;
 
-struct fmx_stream_state {
-  fmx_top2 sng, dbl;
-  double M, S, Ms, Ss;  // evidence: largest term, sum of exp(term - M); the same for the singlets without their prior
+// the lists of the state and their butterfly: xor pairings
+struct fmx_top2_ops {
+  using list = fmx_top2;
+  static __device__ __forceinline__ fmx_top2 empty() { return fmx_top2{-1e300, -1e300, NO_POS, NO_POS, -1e300}; }
+  static __device__ __forceinline__ fmx_top2 merge(fmx_top2 a, const fmx_top2& b) {  // a first
+    fmx_top2_push(a, b.v1, b.p1);
+    fmx_top2_push(a, b.v2, b.p2);
+    a.v3 = fmax(a.v3, b.v3);  // (b.v1 >= b.v2 >= b.v3 are all in the union: b.v3 can be its third at best)
+    return a;
+  }
+  template <int M>
+  static __device__ __forceinline__ fmx_top2 partner(const fmx_top2& t) {
+    return fmx_top2{__shfl_xor(t.v1, M, 64), __shfl_xor(t.v2, M, 64), __shfl_xor(t.p1, M, 64), __shfl_xor(t.p2, M, 64),
+                    __shfl_xor(t.v3, M, 64)};
+  }
+  template <int M>
+  static __device__ __forceinline__ double partner(double x) { return __shfl_xor(x, M, 64); }
 };
+using fmx_stream_state = stream_fold::stream_state<fmx_top2_ops>;
 constexpr int STATE_DOUBLES = (int)(sizeof(fmx_stream_state) / sizeof(double));
 static_assert(sizeof(fmx_stream_state) % sizeof(double) == 0, "the state is kept in a double buffer");
-
-__device__ __forceinline__ fmx_top2 top2_empty() { return fmx_top2{-1e300, -1e300, NO_POS, NO_POS, -1e300}; }
-
-__device__ __forceinline__ fmx_stream_state state_empty() {
-  fmx_stream_state s;
-  s.sng = s.dbl = top2_empty();
-  s.M = s.Ms = -__builtin_huge_val();
-  s.S = s.Ss = 0.0;
-  return s;
-}
-
-// a merged before b (the LSE merge is one fixed expression, so the order fixes the bits)
-__device__ __forceinline__ fmx_top2 top2_merge(fmx_top2 a, const fmx_top2& b) {
-  fmx_top2_push(a, b.v1, b.p1);
-  fmx_top2_push(a, b.v2, b.p2);
-  a.v3 = fmax(a.v3, b.v3);  // (b.v1 >= b.v2 >= b.v3 are all in the union: b.v3 can be its third at best)
-  return a;
-}
-
-__device__ __forceinline__ fmx_stream_state state_merge(const fmx_stream_state& a, const fmx_stream_state& b) {
-  using muxgl_call::exp_nonpos;
-  fmx_stream_state r;
-  r.sng = top2_merge(a.sng, b.sng);
-  r.dbl = top2_merge(a.dbl, b.dbl);
-  r.M = fmax(a.M, b.M);
-  r.S = (a.S > 0.0 ? a.S * exp_nonpos(a.M - r.M) : 0.0) + (b.S > 0.0 ? b.S * exp_nonpos(b.M - r.M) : 0.0);
-  r.Ms = fmax(a.Ms, b.Ms);
-  r.Ss = (a.Ss > 0.0 ? a.Ss * exp_nonpos(a.Ms - r.Ms) : 0.0) + (b.Ss > 0.0 ? b.Ss * exp_nonpos(b.Ms - r.Ms) : 0.0);
-  return r;
-}
-
-__device__ __forceinline__ void lse_push(double& M, double& S, double t) {
-  using muxgl_call::exp_nonpos;
-  if (!(t > -__builtin_huge_val())) return;
-  if (t > M) {
-    S = (S > 0.0 ? S * exp_nonpos(M - t) : 0.0) + 1.0;
-    M = t;
-  } else {
-    S += exp_nonpos(t - M);
-  }
-}
-
-__device__ __forceinline__ fmx_top2 top2_partner(const fmx_top2& t, int m) {
-  fmx_top2 o;
-  o.v1 = __shfl_xor(t.v1, m, 64), o.p1 = __shfl_xor(t.p1, m, 64);
-  o.v2 = __shfl_xor(t.v2, m, 64), o.p2 = __shfl_xor(t.p2, m, 64);
-  o.v3 = __shfl_xor(t.v3, m, 64);
-  return o;
-}
-
-__device__ __forceinline__ fmx_stream_state state_partner(const fmx_stream_state& s, int m) {
-  fmx_stream_state o;
-  o.sng = top2_partner(s.sng, m);
-  o.dbl = top2_partner(s.dbl, m);
-  o.M = __shfl_xor(s.M, m, 64), o.S = __shfl_xor(s.S, m, 64);
-  o.Ms = __shfl_xor(s.Ms, m, 64), o.Ss = __shfl_xor(s.Ss, m, 64);
-  return o;
-}
 
 __device__ __forceinline__ bool lin_bit(const uint32_t* __restrict__ lin, int64_t e) { return (lin[e >> 5] >> (e & 31)) & 1u; }
 
@@ -266,44 +222,27 @@ __device__ __forceinline__ void block_hyps(int X, int Y, int w, int j, int K, co
   }
 }
 
-// Fold of one group: one workgroup per cell; the group's blocks in order, each reduced over the workgroup in a fixed tree
-// (thread -> wave butterfly -> the four waves in order) and merged into the cell's state
+// Fold of one group: one workgroup per cell of the group (stream_fold::fold_blocks)
 __global__ void __launch_bounds__(256)
     fmx_stream_fold_kernel(int64_t c0, int32_t b0, int32_t nb, const int32_t* __restrict__ blocks, int K,
                            double log_single_prior, double log_double_prior, const double* __restrict__ slab,
                            fmx_stream_state* __restrict__ state) {
-  __shared__ fmx_stream_state parts[4];
-  const int64_t c = c0 + blockIdx.x;
   const int j = threadIdx.x & 63, w = threadIdx.x >> 6;
-  fmx_stream_state st = state[c];  // (read by every thread, written by thread 0 at the end)
-  for (int z = 0; z < nb; ++z) {
+  stream_fold::fold_blocks(nb, state + (c0 + blockIdx.x), [&](int z, fmx_stream_state& t) {
     const int bz = blocks[b0 + z];
     const int X = bz >> 16, Y = bz & 0xffff;
     const double* in = slab + ((size_t)blockIdx.x * nb + z) * SLAB;
-    fmx_stream_state t = state_empty();
     block_hyps(X, Y, w, j, K, in, [&](int p, double v, bool singlet) {
       if (singlet) {
         fmx_top2_push(t.sng, v, p);
-        lse_push(t.M, t.S, v + log_single_prior);
-        lse_push(t.Ms, t.Ss, v);
+        t.all.push(v + log_single_prior);
+        t.sgl.push(v);
       } else {
         fmx_top2_push(t.dbl, v, p);
-        lse_push(t.M, t.S, v + log_double_prior);
+        t.all.push(v + log_double_prior);
       }
     });
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) t = state_merge(t, state_partner(t, m));
-    if (j == 0) parts[w] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) st = state_merge(st, state_merge(state_merge(parts[0], parts[1]), state_merge(parts[2], parts[3])));
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) state[c] = st;
-}
-
-__global__ void __launch_bounds__(256) fmx_stream_init_kernel(int64_t n, fmx_stream_state* __restrict__ st) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) st[i] = state_empty();
+  });
 }
 
 __device__ __forceinline__ int row_of(int p) {
@@ -327,8 +266,8 @@ __global__ void __launch_bounds__(64)
   int32_t sBest = -1, sNext = -1, dBest1 = -1, dBest2 = -1, dNext1 = -1, dNext2 = -1;
   double sngBestLLK = -1e300, sngNextLLK = -1e300, dblBestLLK = -1e300, dblNextLLK = -1e300;
   double sumLLK = -1e300, sngLLK = -1e300;
-  if (s.S > 0.0) sumLLK = s.M + log(s.S);
-  if (s.Ss > 0.0) sngLLK = s.Ms + log_single_prior + log(s.Ss);
+  if (s.all.S > 0.0) sumLLK = s.all.M + log(s.all.S);
+  if (s.sgl.S > 0.0) sngLLK = s.sgl.M + log_single_prior + log(s.sgl.S);
   if (s.sng.p1 != NO_POS) sBest = row_of(s.sng.p1), sngBestLLK = s.sng.v1;
   if (s.sng.p2 != NO_POS) sNext = row_of(s.sng.p2), sngNextLLK = s.sng.v2;
   if (s.dbl.p1 != NO_POS) dBest1 = row_of(s.dbl.p1), dBest2 = s.dbl.p1 - dBest1 * (dBest1 + 1) / 2, dblBestLLK = s.dbl.v1;
@@ -351,26 +290,7 @@ __global__ void __launch_bounds__(256)
 }
 
 // the blocks (X, Y), X >= Y, in sweep order, as X << 16 | Y
-std::vector<int32_t> block_list(int K) {
-  const int nblk = (K + CB - 1) / CB;
-  std::vector<int32_t> b;
-  for (int X = 0; X < nblk; ++X)
-    for (int Y = 0; Y <= X; ++Y) b.push_back(X << 16 | Y);
-  return b;
-}
-
-// slab budget in bytes: MUXGL_FMX_SLAB_MB, else 4 GiB bounded by a third of the device's memory (read at each call, so
-// that a test can change the environment between handles)
-size_t slab_budget() {
-  if (const char* s = getenv("MUXGL_FMX_SLAB_MB")) {
-    const long long mb = atoll(s);
-    if (mb > 0) return (size_t)mb << 20;
-  }
-  size_t fr = 0, tot = 0;
-  size_t b = (size_t)4 << 30;
-  if (hipMemGetInfo(&fr, &tot) == hipSuccess && tot > 0) b = std::min(b, tot / 3);
-  return b;
-}
+std::vector<int32_t> block_list(int K) { return stream_plan::block_list((K + CB - 1) / CB, true, 1 << 16); }
 
 int sweep_launch(muxgl_handle* h, int64_t c0, const int32_t* d_cells, int64_t nc, int32_t b0, int32_t nb,
                  const int32_t* d_blocks, double* d_slab) {
@@ -396,19 +316,8 @@ int fmx_stream_estep_launch(muxgl_handle* h, const muxgl_fmx_params* p, int64_t 
   const std::vector<int32_t> blocks = block_list(K);
   const int64_t nb_all = (int64_t)blocks.size();
   const size_t per = (size_t)SLAB * sizeof(double);  // one (cell, block) of the slab
-  const size_t budget = std::max(slab_budget(), per);
-  // groups (sized here, before anything is enqueued): all cells x as many blocks as fit; if one block of every cell does
-  // not fit, one block x as many cells as fit
-  int64_t gb, gc;
-  if ((size_t)nc * per <= budget) {
-    gc = nc;
-    gb = std::min<int64_t>(nb_all, (int64_t)(budget / ((size_t)nc * per)));
-  } else {
-    gb = 1;
-    gc = (int64_t)(budget / per);
-  }
-  gb = std::min<int64_t>(gb, 65535);
-  gc = std::min<int64_t>(gc, (int64_t)1 << 30);
+  // (sized here, before anything is enqueued)
+  const auto [gc, gb] = stream_plan::cut_groups(nc, nb_all, per, dev_slab_budget("MUXGL_FMX_SLAB_MB"));
   const size_t slab_n = (size_t)gc * gb * SLAB, st_n = (size_t)nc * STATE_DOUBLES;
   if (h->fblocks_k != K) {
     if (dev_alloc(h, &h->d_fblocks, blocks.size())) return 1;
@@ -424,14 +333,15 @@ int fmx_stream_estep_launch(muxgl_handle* h, const muxgl_fmx_params* p, int64_t 
     h->fss_cap = st_n;
   }
   fmx_stream_state* st = reinterpret_cast<fmx_stream_state*>(h->d_fss);
-  hipLaunchKernelGGL(fmx_stream_init_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, h->stream, nc, st);
+  hipLaunchKernelGGL(stream_fold::stream_init_kernel<fmx_top2_ops>, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0,
+                     h->stream, nc, st);
   HIPCHK(h, hipGetLastError());
   const double lsp = log((1.0 - p->doublet_prior) / K);          // cmd_cram_freemux2.cpp:379
   const double ldp = log(p->doublet_prior / K / (K - 1) * 2.0);  // :380
   tic(h, MUXGL_T_FMX_ESTEP_SWEEP);
   for (int64_t g0 = 0; g0 < nc; g0 += gc) {
     const int64_t ng = std::min(gc, nc - g0);
-    for (int64_t b0 = 0; b0 < nb_all; b0 += gb) {  // blocks in order: see the header (determinism)
+    for (int64_t b0 = 0; b0 < nb_all; b0 += gb) {  // blocks in order: stream_fold.hpp (determinism)
       const int32_t nb = (int32_t)std::min(gb, nb_all - b0);
       if (sweep_launch(h, c0 + g0, nullptr, ng, (int32_t)b0, nb, h->d_fblocks, h->d_fslab)) return 1;
       hipLaunchKernelGGL(fmx_stream_fold_kernel, dim3((unsigned)ng), dim3(256), 0, h->stream, g0, (int32_t)b0, nb,
@@ -468,31 +378,24 @@ int fmx_stream_rows(muxgl_handle* h, const std::vector<int32_t>& cells, double* 
   const std::vector<int32_t> blocks = block_list(K);
   const int32_t nb = (int32_t)blocks.size();
   const size_t per_cell = (size_t)nb * SLAB * sizeof(double) + npairs * sizeof(double);
-  const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)(slab_budget() / per_cell)));
-  int32_t *d_blocks = nullptr, *d_cells = nullptr;
-  double *d_slab = nullptr, *d_rows = nullptr;
-  auto run = [&]() -> int {
-    if (dev_alloc(h, &d_blocks, blocks.size()) || dev_alloc(h, &d_cells, (size_t)n) ||
-        dev_alloc(h, &d_slab, (size_t)batch * nb * SLAB) || dev_alloc(h, &d_rows, (size_t)batch * npairs))
-      return 1;
-    HIPCHK(h, hipMemcpyAsync(d_blocks, blocks.data(), sizeof(int32_t) * blocks.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d_cells, cells.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    for (int64_t x0 = 0; x0 < n; x0 += batch) {
-      const int64_t m = std::min(batch, n - x0);
-      if (sweep_launch(h, x0, d_cells, m, 0, nb, d_blocks, d_slab)) return 1;
-      hipLaunchKernelGGL(fmx_stream_rows_kernel, dim3((unsigned)m, (unsigned)nb), dim3(256), 0, h->stream, nb, d_blocks, K,
-                         d_slab, d_rows);
-      HIPCHK(h, hipGetLastError());
-      HIPCHK(h, hipMemcpyAsync(rows + (size_t)x0 * npairs, d_rows, sizeof(double) * (size_t)m * npairs,
-                               hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return 0;
-  };
-  const int rc = run();
-  dev_free(&d_blocks);
-  dev_free(&d_cells);
-  dev_free(&d_slab);
-  dev_free(&d_rows);
-  return rc;
+  const int64_t batch =
+      std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)(dev_slab_budget("MUXGL_FMX_SLAB_MB") / per_cell)));
+  dev_tmp<int32_t> d_blocks, d_cells;
+  dev_tmp<double> d_slab, d_rows;
+  if (dev_alloc(h, &d_blocks.p, blocks.size()) || dev_alloc(h, &d_cells.p, (size_t)n) ||
+      dev_alloc(h, &d_slab.p, (size_t)batch * nb * SLAB) || dev_alloc(h, &d_rows.p, (size_t)batch * npairs))
+    return 1;
+  HIPCHK(h, hipMemcpyAsync(d_blocks.p, blocks.data(), sizeof(int32_t) * blocks.size(), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_cells.p, cells.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  for (int64_t x0 = 0; x0 < n; x0 += batch) {
+    const int64_t m = std::min(batch, n - x0);
+    if (sweep_launch(h, x0, d_cells.p, m, 0, nb, d_blocks.p, d_slab.p)) return 1;
+    hipLaunchKernelGGL(fmx_stream_rows_kernel, dim3((unsigned)m, (unsigned)nb), dim3(256), 0, h->stream, nb, d_blocks.p, K,
+                       d_slab.p, d_rows.p);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(rows + (size_t)x0 * npairs, d_rows.p, sizeof(double) * (size_t)m * npairs,
+                             hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  return 0;
 }
