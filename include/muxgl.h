@@ -170,6 +170,8 @@ enum {
                                    relayout of the cluster posteriors and the reduction of the chunk partials) */
   MUXGL_T_DEMUX_SINGLETS = 12,  /* muxgl_demux_singlets: entry weights + sample sweep (with a table cut into several
                                    batches also the copies between them) */
+  MUXGL_T_FMX_SINGLETS = 13,    /* muxgl_fmx_singlets: (packing of the entry diagonals +) cluster sweep (with a table cut
+                                   into several batches also the copies between them) */
   MUXGL_T_COUNT = 16
 };
 
@@ -304,6 +306,30 @@ int muxgl_fmx_set_clusters(muxgl_handle* h, int32_t K, const int32_t* clust);
  * [C][K(K+1)/2] table, so full_ll must be NULL there: otherwise the call fails with an error. */
 int muxgl_fmx_iterate(muxgl_handle* h, const muxgl_fmx_params* p, muxgl_fmx_cell* out, int32_t* nsingle, int32_t* namb,
                       int32_t* nchanged, double* full_ll);
+
+/* sng[C][K] = llks[j(j+1)/2 + j] of cmd_cram_freemux2.cpp:448-455 for every droplet and cluster, as the LAST E-step of this
+ * handle formed them: sng[c][j] = sum over the entries e of c of log(egl_e[0] q[s_e][j][0] + egl_e[4] q[s_e][j][1] +
+ * egl_e[8] q[s_e][j][2]), egl_e the entry likelihoods of muxgl_fmx_prepare and q the cluster genotype posteriors that
+ * E-step read (MUXGL_BUF_CGP, geno_error mixed in, :402-415) -- so the call takes no parameters.  This is the number
+ * sngBestLLK / sngNextLLK are scanned from (:485-497) and the diagonal of full_ll where that table exists; it does not need
+ * the table, runs at any K up to MUXGL_MAX_CLUSTERS whichever E-step path ran, on one device, a device group and a slabbed or
+ * sharded handle (per-cell output covers the handle's own cells, as muxgl_fmx_iter_fetch's records do; every member of a
+ * group sweeps its own cells).  The M-step and the near-tie path behind an E-step leave the posteriors alone, so the table
+ * belongs to the records of the same iteration: call it after muxgl_fmx_iterate, or after muxgl_fmx_iter_estep (and whatever
+ * follows it) and before the next muxgl_fmx_iter_gp.  It fails, naming the reason, before the first E-step since
+ * muxgl_fmx_set_clusters, after a posterior phase without its E-step, for a NULL output, without a pileup and without
+ * muxgl_fmx_prepare; the handle stays usable.  A droplet without entries gets a row of zeros.
+ * The table is the device's arithmetic throughout (products of factors, one log per cell part and cluster: equal to the
+ * reference's sums of logs to ~1e-11): the records of a near-tie cell carry the values the exact path recomputed in the
+ * reference's arithmetic (muxgl_fmx_exact_stats), the table keeps the device's for those cells too.
+ * It reads state and changes none: records, counters, assignments, cluster pileups and the near-tie bookkeeping stay as
+ * they are.  The device holds a slab of the table (the streamed E-step's budget: 4 GiB or a third of the device,
+ * MUXGL_FMX_SLAB_MB); a larger table is swept in batches of cells, each copied out before the next; nothing proportional to
+ * C x K^2.  The table is bit-identical from call to call, for any budget, on one device, on a group and through the sharded
+ * driver.  Under MUXGL_FLAG_ASYNC_PHASES it returns with the stream drained, like every non-phase call.  Its kernel time
+ * is MUXGL_T_FMX_SINGLETS of muxgl_get_timing (the slots of the last iteration keep their values); it counts as a
+ * collecting call of muxgl_get_timing_sum. */
+int muxgl_fmx_singlets(muxgl_handle* h, double* sng);
 
 /* Near-tie calls of the EM iterations since muxgl_fmx_set_clusters.  The kernels' log-likelihoods equal the reference's to
  * ~1e-12, not to the last bit; a cell where a comparison of cmd_cram_freemux2.cpp:469-497,521-584 has a margin within

@@ -86,6 +86,10 @@ enum { MUXGL_ROLE_FULL = 0, MUXGL_ROLE_ROWS = 1, MUXGL_ROLE_COLS = 2 };
 
 struct muxgl_group;
 
+// muxgl_handle::fmx_sng_state: no E-step since muxgl_fmx_set_clusters; d_cgp holds the posteriors the last E-step read;
+// a posterior phase has rewritten them since
+enum { FMX_SNG_NONE = 0, FMX_SNG_READY = 1, FMX_SNG_STALE = 2 };
+
 // records of the wave E-step's entry streams (fmx_wave.hip)
 struct fmx_lrec {  // a linear entry: glis[g1][g2] = c0 + c1 (g1 + g2)
   double c0, c1;
@@ -197,6 +201,7 @@ struct muxgl_handle {
   muxgl_fmx_cell* h_fcells = nullptr;  // pinned
   double* d_fll = nullptr;        // [C][K(K+1)/2]; not allocated when the E-step is streamed (fmx_stream.hip)
   bool fmx_streamed = false;      // muxgl_fmx_set_clusters chose the streamed E-step (path_choice.hpp)
+  int fmx_sng_state = 0;          // FMX_SNG_*: is d_cgp what the last E-step read? (muxgl_fmx_singlets, fmx_singlets.hip)
   // the streamed E-step's buffers (fmx_stream.hip), kept between iterations: block list, slab, per-cell states
   int32_t* d_fblocks = nullptr;
   int fblocks_k = -1;
@@ -590,6 +595,7 @@ int64_t fmx_wave_fll_rows(const muxgl_handle* h);  // rows of d_fll: C + extra p
 int fmx_stream_estep_launch(muxgl_handle* h, const muxgl_fmx_params* p, int64_t c0, int64_t nc);  // fmx_stream.hip
 int fmx_stream_call_launch(muxgl_handle* h, int64_t c0, int64_t c1, double lsp, double ldp);
 int fmx_stream_rows(muxgl_handle* h, const std::vector<int32_t>& cells, double* rows);  // deep-tie rows, host
+const char* fmx_singlets_refusal(const muxgl_handle* h);  // fmx_singlets.hip: why muxgl_fmx_singlets cannot run now, or NULL
 void fmx_wave_streams_release(muxgl_handle* h);  // the linear/general entry streams and their rank table
 int demux_ensure_ll(muxgl_handle* h, const muxgl_demux_params* p);  // standard LL tensor allocated and zeroed
 int demux_call_wave_launch(muxgl_handle* h, const muxgl_demux_params* p);
@@ -645,6 +651,7 @@ int group_fmx_set_clusters(muxgl_handle* h, int32_t K, const int32_t* clust);
 int group_fmx_iterate(muxgl_handle* h, const muxgl_fmx_params* p, muxgl_fmx_cell* out, int32_t* nsingle, int32_t* namb,
                       int32_t* nchanged, double* full_ll);
 int group_fmx_get_cluster_pileup(muxgl_handle* h, double* gls, int32_t* counts);
+int group_fmx_singlets(muxgl_handle* h, double* sng);
 void group_fmx_exact_stats(const muxgl_handle* h, int64_t* cells, int64_t* changed, int64_t* unresolved);
 void group_peer_stats(const muxgl_handle* h, int32_t* out);
 int group_get_timing(const muxgl_handle* h, float* ms);

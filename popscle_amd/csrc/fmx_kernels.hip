@@ -895,6 +895,7 @@ int muxgl_fmx_set_clusters(muxgl_handle* h, int32_t K, const int32_t* clust) {
   HIPCHK(h, hipMemsetAsync(h->d_xc_epoch, 0, sizeof(int32_t) * (size_t)(C ? C : 1), h->stream));
   h->xs_epoch = 1;
   h->xs_keep = false;
+  h->fmx_sng_state = FMX_SNG_NONE;
   h->fmx_exact_cells = h->fmx_exact_changed = h->fmx_exact_unresolved = 0;
   clear_timing(h);
   tic(h, MUXGL_T_FMX_MSTEP);
@@ -926,6 +927,7 @@ int fmx_phase_gp(muxgl_handle* h, const muxgl_fmx_params* p) {
                        h->K, h->d_af, m->d_cgls, p->geno_error, h->d_cgp);
   toc(h, MUXGL_T_FMX_GP);
   HIPCHK(h, hipGetLastError());
+  if (h->fmx_sng_state == FMX_SNG_READY) h->fmx_sng_state = FMX_SNG_STALE;  // d_cgp is no longer what the last E-step read
   return 0;
 }
 
@@ -1022,6 +1024,7 @@ int fmx_phase_estep(muxgl_handle* h, const muxgl_fmx_params* p) {
   // the three counters, on their way to the host while the caller enqueues the next phase
   HIPCHK(h, hipMemcpyAsync(h->h_fstat, h->d_fstat, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipEventRecord(h->ev_stat, h->stream));
+  h->fmx_sng_state = FMX_SNG_READY;  // muxgl_fmx_singlets: d_cgp is what this E-step read, until the next posterior phase
   return 0;
 }
 

@@ -565,6 +565,23 @@ int group_fmx_get_cluster_pileup(muxgl_handle* h, double* gls, int32_t* counts) 
   return 0;
 }
 
+// every member sweeps its own cells and writes their rows of the caller's [C][K] table
+int group_fmx_singlets(muxgl_handle* h, double* sng) {
+  muxgl_group* g = h->group;
+  if (!g->have_pileup) MUXGL_FAIL(h, "muxgl_fmx_singlets: no pileup set (muxgl_set_pileup)");
+  if (!g->prepared) MUXGL_FAIL(h, "muxgl_fmx_singlets: call muxgl_fmx_prepare first");
+  for (const muxgl_handle* m : g->m)
+    if (const char* why = fmx_singlets_refusal(m)) MUXGL_FAIL(h, "%s", why);
+  if (!sng) MUXGL_FAIL(h, "muxgl_fmx_singlets: NULL output");
+  if (for_members(h, [&](int r) {
+        return muxgl_fmx_singlets(g->m[(size_t)r], sng + (size_t)g->cb[(size_t)r] * (size_t)g->K);
+      }))
+    return 1;
+  g->ms[MUXGL_T_FMX_SINGLETS] = 0.f;
+  for (auto* m : g->m) g->ms[MUXGL_T_FMX_SINGLETS] = std::max(g->ms[MUXGL_T_FMX_SINGLETS], m->ms[MUXGL_T_FMX_SINGLETS]);
+  return 0;
+}
+
 int group_get_timing(const muxgl_handle* h, float* ms) {
   memcpy(ms, h->group->ms, sizeof(float) * MUXGL_T_COUNT);
   return 0;

@@ -168,12 +168,16 @@ def settle_near_ties(engs, gather, doublet_prior, geno_error):
 
 
 def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early_stop=True, exchange=None,
-           exchange_tensor=engine_exchange_tensor, log=None, per=None, timings=None, sync=None, stream_ctx=None):
+           exchange_tensor=engine_exchange_tensor, log=None, per=None, timings=None, sync=None, stream_ctx=None,
+           want_singlets=False):
     """EM loop of cmd_cram_freemux2.cpp:373-605 on a prepared engine.  One rank: a plain engine holding the whole
     pileup.  Several ranks: an engine holding the rank's slabs (load_rank), `exchange` a TorchExchange and
     per = (cells per rank, SNPs per rank) of the equal-slice plan the slabs were cut by.  clust0 spans the whole job.
     Returns (records of ALL cells, complete on every rank; per-iteration stats).  stream_ctx: context manager that
-    makes the engine's stream torch's current one (device-ordered exchanges)."""
+    makes the engine's stream torch's current one (device-ordered exchanges).  want_singlets: also the job-wide [C][K]
+    table of singlet log-likelihoods of the last iteration (Engine.fmx_singlets of every rank's own cells, gathered
+    like the records, in the original cell order): (records, stats, sng) -- the counterpart of
+    demuxlet.run_sharded(want_singlets=True)."""
     ex = exchange or NoExchange()
     t_start = time.perf_counter()
     eng.fmx_set_clusters(K, np.ascontiguousarray(clust0, dtype=np.int32))  # :277-288, own SNP range
@@ -270,4 +274,9 @@ def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early
     out = np.zeros(eng.C_total, dtype=cells.dtype)
     for b, e, raw in parts:
         out[b:e] = np.frombuffer(raw, dtype=cells.dtype)
-    return out, history
+    if not want_singlets:
+        return out, history
+    sng = np.zeros((eng.C_total, K), dtype=np.float64)  # the last E-step's posteriors are still in place: muxgl.h
+    for b, e, raw in ex.gather_objects((c0, c0 + len(cells), eng.fmx_singlets().tobytes())):
+        sng[b:e] = np.frombuffer(raw, dtype=np.float64).reshape(e - b, K)
+    return out, history, sng

@@ -8,6 +8,11 @@
 //       loader keeps no passed-read count), LLK1 (%.4lf), POSTPRB (%.3lg, equal priors over the samples); the reference's
 //       LLK0 (llks00[0]) is left out: nothing computes llks00 and the reference reads it nowhere else
 //   popscle-amd freemuxlet --plp P --nsample K --out O [...]                   mirrors cmdCramFreemux2 (cmd_cram_freemux2.cpp)
+//       --write-singlets: also <O>.clust1.sing2.gz (BGZF), the singlet log-likelihood of every droplet against every
+//       cluster as the last EM iteration formed it (llks[j(j+1)/2 + j], cmd_cram_freemux2.cpp:448-455; the reference
+//       prints only the best and the next).  One row per droplet, in the order of .clust1.samples.gz, and cluster
+//       0 .. K-1.  Columns BARCODE, CLUST, NUM.SNPS, NUM.READS (those of .clust1.samples.gz), LLK1 (%.4lf), POSTPRB
+//       (%.3lg, equal priors over the clusters)
 //   popscle-amd freemuxlet-old --plp P --nsample K --out O [...]               mirrors cmdCramFreemuxlet (cmd_cram_freemuxlet.cpp)
 //   popscle-amd dump-plp   --plp P [--vcf V --field F] --out FILE              loader only: packed pileup to a binary file
 //   popscle-amd synth-plp  --cells C --snps S --samples V --out P              a synthetic data set in the real file formats
@@ -397,11 +402,13 @@ int cmd_freemuxlet(int argc, char** argv) {
   double singletScoreThres = -1e300;
   int32_t nSamples = 0, initIteration = 10, randomSeed = 0, verbose = 0, maxIter = 10;
   bool auxFiles = false, keepInitMissing = false, randomizeSingletScore = false, noEarlyStop = false;
+  bool writeSinglets = false;  // (ours) <out>.clust1.sing2.gz: every droplet against every cluster
   Args a;
   cf.add(a);
   a.add_string("init-cluster", &initClusterFile);
   a.add_int("nsample", &nSamples);
   a.add_bool("aux-files", &auxFiles);
+  a.add_bool("write-singlets", &writeSinglets);
   a.add_int("verbose", &verbose);
   a.add_double("doublet-prior", &doublet_prior);
   a.add_double("geno-error", &geno_error);
@@ -576,6 +583,39 @@ int cmd_freemuxlet(int argc, char** argv) {
   });
   wc1.close();
   tmr.lap("freemuxlet: write .clust1.samples.gz");
+  if (writeSinglets) {
+    // .clust1.sing2.gz: one row per droplet (the order of .clust1.samples.gz) and cluster 0 .. K-1, from the posteriors
+    // of the last E-step (the M-step behind it left them alone).  POSTPRB: equal priors over the clusters, a softmax over
+    // the droplet's row with its maximum subtracted
+    const size_t Kz = (size_t)K;
+    BigVec<double> sng((size_t)C * Kz);
+    check(h, muxgl_fmx_singlets(h, sng.data()), "muxgl_fmx_singlets");
+    tmr.lap("freemuxlet: muxgl_fmx_singlets");
+    std::vector<double> rmax((size_t)C), rsum((size_t)C);
+    parallel_for(C, plp_threads(), [&](int64_t i) {
+      const double* row = sng.data() + (size_t)i * Kz;
+      double mx = row[0], sum = 0.0;
+      for (size_t j = 1; j < Kz; ++j) mx = std::max(mx, row[j]);
+      for (size_t j = 0; j < Kz; ++j) sum += exp(row[j] - mx);
+      rmax[(size_t)i] = mx;
+      rsum[(size_t)i] = sum;
+    });
+    OutFile ws(cf.outPrefix + ".clust1.sing2.gz", true);
+    ws.printf("BARCODE\tCLUST\tNUM.SNPS\tNUM.READS\tLLK1\tPOSTPRB\n");
+    write_rows_parallel(ws, C * (int64_t)K, [&](int64_t r, std::string& o) {
+      const int64_t i = r / K;
+      const int j = (int)(r - i * K);
+      const double v = sng.data()[(size_t)r];
+      const std::string& bc = p.bcs[(size_t)i];
+      char num[160];
+      const int n = snprintf(num, sizeof(num), "\t%d\t%d\t%d\t%.4lf\t%.3lg\n", j, nSNPs[(size_t)i], nReads[(size_t)i], v,
+                             exp(v - rmax[(size_t)i]) / rsum[(size_t)i]);
+      o.append(bc);
+      o.append(num, (size_t)std::min<int>(n, (int)sizeof(num) - 1));
+    });
+    ws.close();
+    tmr.lap("freemuxlet: write .clust1.sing2.gz");
+  }
   muxgl_destroy(h);
   return 0;
 }
@@ -981,7 +1021,9 @@ int main(int argc, char** argv) {
     fprintf(stderr, "usage: popscle-amd <demuxlet|freemuxlet|freemuxlet-old|dump-plp> [options]\n"
                     "  demuxlet --write-singlets: also <out>.sing2.gz, the singlet log-likelihood of every printed droplet\n"
                     "    against every sample (BARCODE SM_ID NUM.SNPS NUM.READS LLK1 POSTPRB; the reference's RD.* columns\n"
-                    "    give way to the two counts of .best, its LLK0 is left out)\n");
+                    "    give way to the two counts of .best, its LLK0 is left out)\n"
+                    "  freemuxlet --write-singlets: also <out>.clust1.sing2.gz, the singlet log-likelihood of every droplet\n"
+                    "    against every cluster in the last iteration (BARCODE CLUST NUM.SNPS NUM.READS LLK1 POSTPRB)\n");
     return 1;
   }
   try {

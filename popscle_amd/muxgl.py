@@ -40,6 +40,7 @@ T_FMX_ENTRY, T_FMX_GP, T_FMX_ESTEP, T_FMX_CALL, T_FMX_MSTEP = 4, 5, 6, 7, 8
 T_FMXOLD_PAIR, T_FMXOLD_VOTE = 9, 10
 T_FMX_ESTEP_SWEEP = 11
 T_DEMUX_SINGLETS = 12
+T_FMX_SINGLETS = 13
 T_COUNT = 16
 BUF_CGP, BUF_CLUST, BUF_CELLS, BUF_STAT = 0, 1, 2, 3
 
@@ -102,6 +103,7 @@ SYMBOLS = {
     "muxgl_fmx_score_stats": (C.c_int, [_VP, _VP]),
     "muxgl_fmx_set_clusters": (C.c_int, [_VP, C.c_int32, _VP]),
     "muxgl_fmx_iterate": (C.c_int, [_VP, C.POINTER(_FmxParams), _VP, _VP, _VP, _VP, _VP]),
+    "muxgl_fmx_singlets": (C.c_int, [_VP, _VP]),
     "muxgl_fmx_get_cluster_pileup": (C.c_int, [_VP, _VP, _VP]),
     "muxgl_fmx_exact_stats": (C.c_int, [_VP, _VP, _VP, _VP]),
     "muxgl_fmx_exact_pending": (C.c_int, [_VP, _VP]),
@@ -185,7 +187,8 @@ def demux_exact_calls(p, alphas, cells, doublet_prior=0.5, nthreads=0):
 
 
 def singlet_posteriors(sng):
-    """Per-sample posteriors of a [C][V] table of singlet log-likelihoods (Engine.demux_singlets) as the reference's
+    """Per-sample posteriors of a [C][V] table of singlet log-likelihoods (Engine.demux_singlets; per-cluster ones of
+    Engine.fmx_singlets' [C][K] table the same way) as the reference's
     disabled .sing2 writer forms them (cmd_cram_demuxlet.cpp:848): equal priors over the samples, i.e. a softmax over
     each row, computed with the row maximum subtracted.  A row of zeros (droplet without entries) gives 1 / V."""
     sng = np.asarray(sng, dtype=np.float64)
@@ -402,6 +405,14 @@ class Engine:
         if want_full_ll:
             return out, stats, full
         return out, stats
+
+    def fmx_singlets(self):
+        """muxgl_fmx_singlets: float64 [C][K], the singlet log-likelihood llks[j(j+1)/2 + j] of every droplet (of the
+        handle's own cells) against every cluster as the last E-step formed it -- the diagonal of fmx_iterate's full_ll
+        where that exists -- at any K, on every E-step path.  singlet_posteriors() turns it into soft assignments."""
+        out = np.zeros((self.C, self.K), dtype=np.float64)
+        self._check(self.lib.muxgl_fmx_singlets(self.h, _ptr(out)))
+        return out
 
     # ---- freemuxlet-old: pairwise distance matrix and voting passes (cmd_cram_freemuxlet.cpp:176-343)
     def fmxold_pair_dist(self, bf_thres=5.41, want_full=False):
