@@ -172,6 +172,8 @@ enum {
                                    batches also the copies between them) */
   MUXGL_T_FMX_SINGLETS = 13,    /* muxgl_fmx_singlets: (packing of the entry diagonals +) cluster sweep (with a table cut
                                    into several batches also the copies between them) */
+  MUXGL_T_DEMUX_INCLUSION = 14, /* muxgl_demux_inclusion: entry likelihoods + pair sweep + marginal fold + finish (with a
+                                   state cut into several batches of cells also the copies between them) */
   MUXGL_T_COUNT = 16
 };
 
@@ -218,6 +220,34 @@ int muxgl_demux_run(muxgl_handle* h, const muxgl_demux_params* p, muxgl_demux_ce
  * device and on a group.  The records, timings and state of muxgl_demux_run stay as they are (the call's own kernel time
  * is MUXGL_T_DEMUX_SINGLETS of muxgl_get_timing; it counts as a collecting call of muxgl_get_timing_sum). */
 int muxgl_demux_singlets(muxgl_handle* h, const muxgl_demux_params* p, double* sng);
+
+/* Per droplet c and sample s: how much evidence there is that s is in the droplet at all, and with whom s pairs best --
+ * the row and column marginals of the pair matrix the reference's disabled .pair writer prints (cmd_cram_demuxlet.cpp:
+ * 852-877).  Over the hypotheses that carry prior mass in :804-821,
+ *   H   = { (j,k,n) : j != k, n >= 1, and k < j where alpha[n] == 0.5 },   value LL(j,k,n) = llksAB[(j,k,n)]
+ *   H_s = { h in H : j == s or k == s }
+ * incl[C][V]  = log( exp(LL(s,0,0) + lsp) + sum_{h in H_s} exp(LL(h) + prior(h)) ), lsp = log_single_prior and prior =
+ *               log_doublet_prior1 (alpha != 0.5) / log_doublet_prior2 (alpha == 0.5) exactly as :793-795
+ * tot[C]      = log of the same sum over all singlets and all of H, WITHOUT the reference's -1e-300 seed (:791), so
+ *               exp(incl - tot) is the posterior that s is in the droplet (sumLLK of the record = logAdd(-1e-300, tot))
+ * dbl[C][V]   = max_{h in H_s} LL(h)   (-1e300 when H_s is empty: V == 1 or a grid without a doublet alpha)
+ * partner, alpha_idx, first [C][V]: the other sample of that hypothesis, its n, and 1 if s is j / 0 if s is k
+ *               (-1, -1, -1 when H_s is empty).  Ties: value descending, then scan position (j V + k) A + n ascending.
+ * Any out pointer may be NULL.  A droplet without entries gets LL = 0 for every hypothesis, like the singlet table.
+ * Needs muxgl_set_pileup and muxgl_demux_set_gp, not a previous muxgl_demux_run; every grid muxgl_demux_run accepts
+ * (also one without a doublet alpha); 1 <= V <= MUXGL_MAX_SAMPLES with V * V * n_alpha < 2^31; one device or a device
+ * group (every member fills the rows of its own cells).  The tables are the device's arithmetic throughout (products of
+ * factors, one log per hypothesis: equal to the reference's sums of logs to ~1e-11); near ties in `partner` are decided
+ * by those values and the order above, not re-resolved in exact arithmetic.
+ * The device holds the per-entry likelihoods ([nnz][n_alpha][9]) and, within the streamed call's budget (4 GiB or a third
+ * of the device, MUXGL_DEMUX_SLAB_MB), a slab of the pair sweep plus the state and the outputs of a batch of whole cells
+ * (60 bytes per cell and sample); the batch is finished and copied out before the next; nothing proportional to C x V^2.
+ * It fails when one cell's state and one 64 x 64 block of the sweep exceed the budget.  All six outputs are bit-identical
+ * from call to call, for any budget, on one device, on a group and through the sharded driver.  The records, full_ll,
+ * timings and state of muxgl_demux_run stay as they are (the call's own kernel time is MUXGL_T_DEMUX_INCLUSION of
+ * muxgl_get_timing; it counts as a collecting call of muxgl_get_timing_sum). */
+int muxgl_demux_inclusion(muxgl_handle* h, const muxgl_demux_params* p, double* incl, double* tot, double* dbl,
+                          int32_t* partner, int32_t* alpha_idx, int32_t* first);
 
 /* The calls rounding noise could decide, settled in the reference's own arithmetic -- HOST pass, no device work, no
  * handle (popscle_amd/host/exact_calls.hpp).  The kernels' log-likelihoods equal the reference's to ~1e-12, not to the last

@@ -569,6 +569,11 @@ struct ring_sel {          // one launch of demux_ring.hip
 int demux_launch(muxgl_handle* h, const muxgl_demux_params* p);
 int demux_stream_launch(muxgl_handle* h, const muxgl_demux_params* p);   // streamed sweep + fold + call
 int demux_singlets_run(muxgl_handle* h, const muxgl_demux_params* p, double* sng);  // demux_singlets.hip: [C][V] to the host
+struct demux_incl_out {  // muxgl_demux_inclusion's outputs (host; any may be NULL), rows of the handle's own cells
+  double *incl, *tot, *dbl;
+  int32_t *partner, *alpha_idx, *first;
+};
+int demux_inclusion_run(muxgl_handle* h, const muxgl_demux_params* p, const demux_incl_out& out);  // demux_incl.hip
 int demux_entry_pg_launch(muxgl_handle* h, const muxgl_demux_params* p, double* d_pg, bool gen_stream = false,
                           bool by_record = false);
 int demux_ring_lin_launch(muxgl_handle* h, const muxgl_demux_params* p, const wave_item* items, int64_t n_items,
@@ -642,6 +647,7 @@ int group_set_pileup(muxgl_handle* h, int64_t C, int64_t S, int64_t nnz, int64_t
 int group_demux_set_gp(muxgl_handle* h, int32_t V, const double* gp, const uint8_t* has_gp);
 int group_demux_run(muxgl_handle* h, const muxgl_demux_params* p, muxgl_demux_cell* out, double* full_ll);
 int group_demux_singlets(muxgl_handle* h, const muxgl_demux_params* p, double* sng);
+int group_demux_inclusion(muxgl_handle* h, const muxgl_demux_params* p, const demux_incl_out& out);
 const muxgl_demux_cell* group_demux_results(const muxgl_handle* h);
 int group_demux_get_entry_pg(muxgl_handle* h, double* pg);
 int group_fmx_prepare(muxgl_handle* h, const double* af, double* cell_llk0, double* cell_llk2, int32_t* cell_nsnps,

@@ -301,6 +301,25 @@ int group_demux_singlets(muxgl_handle* h, const muxgl_demux_params* p, double* s
   return 0;
 }
 
+// every member folds its own cells and writes their rows of the caller's tables
+int group_demux_inclusion(muxgl_handle* h, const muxgl_demux_params* p, const demux_incl_out& out) {
+  muxgl_group* g = h->group;
+  if (!p) MUXGL_FAIL(h, "demux params NULL");
+  if (p->n_alpha < 1 || p->n_alpha > MUXGL_MAX_ALPHA) MUXGL_FAIL(h, "n_alpha=%d outside [1,%d]", p->n_alpha, MUXGL_MAX_ALPHA);
+  if (!g->have_pileup) MUXGL_FAIL(h, "no pileup set (muxgl_set_pileup)");
+  if (g->V < 1) MUXGL_FAIL(h, "no GP tensor set (muxgl_demux_set_gp)");
+  if (for_members(h, [&](int r) {
+        const size_t c = (size_t)g->cb[(size_t)r], o = c * (size_t)g->V;
+        return muxgl_demux_inclusion(g->m[(size_t)r], p, out.incl ? out.incl + o : nullptr, out.tot ? out.tot + c : nullptr,
+                                     out.dbl ? out.dbl + o : nullptr, out.partner ? out.partner + o : nullptr,
+                                     out.alpha_idx ? out.alpha_idx + o : nullptr, out.first ? out.first + o : nullptr);
+      }))
+    return 1;
+  g->ms[MUXGL_T_DEMUX_INCLUSION] = 0.f;
+  for (auto* m : g->m) g->ms[MUXGL_T_DEMUX_INCLUSION] = std::max(g->ms[MUXGL_T_DEMUX_INCLUSION], m->ms[MUXGL_T_DEMUX_INCLUSION]);
+  return 0;
+}
+
 const muxgl_demux_cell* group_demux_results(const muxgl_handle* h) { return h->group->h_dcells; }
 
 int group_demux_get_entry_pg(muxgl_handle* h, double* pg) {

@@ -10,10 +10,13 @@ from . import shard
 from .freemuxlet import NoExchange
 
 
-def run_sharded(engine_factory, p, alphas=(0.0, 0.5), doublet_prior=0.5, exchange=None, want_singlets=False):
+def run_sharded(engine_factory, p, alphas=(0.0, 0.5), doublet_prior=0.5, exchange=None, want_singlets=False,
+                want_inclusion=False):
     """engine_factory() -> object with set_pileup / demux_set_gp / demux_run (muxgl.Engine).  Returns the [C] records of
     the whole pileup on every rank, in the original cell order; with want_singlets also the [C][V] table of singlet
-    log-likelihoods (Engine.demux_singlets), gathered the same way: (records, sng)."""
+    log-likelihoods (Engine.demux_singlets), gathered the same way: (records, sng); with want_inclusion also the dict of
+    per-droplet, per-sample inclusion tables (Engine.demux_inclusion) as the last element: (records, [sng,] inclusion).
+    Cells are independent, so every rank fills the rows of its own cells."""
     ex = exchange or NoExchange()
     ranges = shard.cell_shards(p.cell_ptr, ex.world)
     c0, c1 = ranges[ex.rank]
@@ -26,10 +29,20 @@ def run_sharded(engine_factory, p, alphas=(0.0, 0.5), doublet_prior=0.5, exchang
     out = np.zeros(p.C, dtype=cells.dtype)
     for b, e, raw in parts:
         out[b:e] = np.frombuffer(raw, dtype=cells.dtype)
-    if not want_singlets:
+    if not want_singlets and not want_inclusion:
         return out
+    ret = [out]
     V = p.gp.shape[1]
-    sng = np.zeros((p.C, V), dtype=np.float64)
-    for b, e, raw in ex.gather_objects((c0, c1, eng.demux_singlets(alphas).tobytes())):
-        sng[b:e] = np.frombuffer(raw, dtype=np.float64).reshape(e - b, V)
-    return out, sng
+    if want_singlets:
+        sng = np.zeros((p.C, V), dtype=np.float64)
+        for b, e, raw in ex.gather_objects((c0, c1, eng.demux_singlets(alphas).tobytes())):
+            sng[b:e] = np.frombuffer(raw, dtype=np.float64).reshape(e - b, V)
+        ret.append(sng)
+    if want_inclusion:
+        mine = eng.demux_inclusion(alphas, doublet_prior)
+        inc = {k: np.zeros((p.C,) + v.shape[1:], dtype=v.dtype) for k, v in mine.items()}
+        for b, e, raw in ex.gather_objects((c0, c1, {k: v.tobytes() for k, v in mine.items()})):
+            for k, v in inc.items():
+                v[b:e] = np.frombuffer(raw[k], dtype=v.dtype).reshape((e - b,) + v.shape[1:])
+        ret.append(inc)
+    return tuple(ret)

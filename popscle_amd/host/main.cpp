@@ -7,6 +7,13 @@
 //       NUM.SNPS, NUM.READS (the droplet's columns of .best, in place of the reference's RD.TOTL / RD.PASS / RD.UNIQ: the
 //       loader keeps no passed-read count), LLK1 (%.4lf), POSTPRB (%.3lg, equal priors over the samples); the reference's
 //       LLK0 (llks00[0]) is left out: nothing computes llks00 and the reference reads it nowhere else
+//       --write-inclusion: also <O>.incl.gz (BGZF), one row per printed droplet and sample: the evidence that the sample
+//       is in the droplet, as a singlet or as either half of a doublet, and the doublet it pairs best in -- the row and
+//       column marginals of the reference's disabled .pair writer (cmd_cram_demuxlet.cpp:852-877; muxgl_demux_inclusion).
+//       Columns BARCODE, SM_ID, NUM.SNPS, NUM.READS, LLK.INCL (%.4lf), POSTPRB.INCL (%.3lg, exp(incl - tot)),
+//       DBL.PARTNER (sample id), DBL.ALPHA (%.3lf: the share of the sample's OWN reads in that doublet, alpha if it
+//       is the second, contaminating sample of the pair and 1 - alpha if it is the first, :694-695,734-736), DBL.LLK (%.4lf); the last three are NA where no doublet hypothesis
+//       holds the sample (one sample, or a grid without a doublet alpha)
 //   popscle-amd freemuxlet --plp P --nsample K --out O [...]                   mirrors cmdCramFreemux2 (cmd_cram_freemux2.cpp)
 //       --write-singlets: also <O>.clust1.sing2.gz (BGZF), the singlet log-likelihood of every droplet against every
 //       cluster as the last EM iteration formed it (llks[j(j+1)/2 + j], cmd_cram_freemux2.cpp:448-455; the reference
@@ -113,10 +120,12 @@ int cmd_demuxlet(int argc, char** argv) {
   int32_t dummy_i = 0;
   bool deviceCalls = false;  // (ours) skip the host pass that settles mirrored alpha = 0.5 pairs and near-tie calls as the reference does
   bool writeSinglets = false;  // (ours) <out>.sing2.gz: the reference's disabled .sing2 writer (:580,839-848)
+  bool writeInclusion = false;  // (ours) <out>.incl.gz: per-sample marginals of the disabled .pair writer (:852-877)
   Args a;
   cf.add(a);
   a.add_bool("device-calls", &deviceCalls);
   a.add_bool("write-singlets", &writeSinglets);
+  a.add_bool("write-inclusion", &writeInclusion);
   a.add_string("vcf", &vr.path);
   a.add_string("field", &cf.lo.field);
   a.add_double("geno-error-offset", &cf.lo.genoErrorOffset);
@@ -236,6 +245,37 @@ int cmd_demuxlet(int argc, char** argv) {
     }
     ws.close();
     tm.lap("demuxlet: write .sing2.gz");
+  }
+  if (writeInclusion) {
+    // .incl.gz: one row per printed droplet (the order and the filters of .best) and sample, in VCF column order
+    const size_t V = (size_t)p.nv, n = (size_t)p.C() * V;
+    std::vector<double> incl(n), tot((size_t)p.C()), dbl(n);
+    std::vector<int32_t> partner(n), aidx(n), first(n);
+    check(h, muxgl_demux_inclusion(h, &dp, incl.data(), tot.data(), dbl.data(), partner.data(), aidx.data(), first.data()),
+          "muxgl_demux_inclusion");
+    tm.lap("demuxlet: muxgl_demux_inclusion");
+    OutFile wi(cf.outPrefix + ".incl.gz", true);
+    wi.printf("BARCODE\tSM_ID\tNUM.SNPS\tNUM.READS\tLLK.INCL\tPOSTPRB.INCL\tDBL.PARTNER\tDBL.ALPHA\tDBL.LLK\n");
+    for (auto it = bc_map.begin(); it != bc_map.end(); ++it) {
+      const int32_t i = it->second;
+      const muxgl_demux_cell& c = cells[(size_t)i];
+      if (p.cell_totl_reads[(size_t)i] < cf.lo.minRead || p.cell_uniq_reads[(size_t)i] < cf.lo.minUMI ||
+          c.nsnps < cf.lo.minSNP || !c.valid)
+        continue;
+      for (size_t j = 0; j < V; ++j) {
+        const size_t x = (size_t)i * V + j;
+        wi.printf("%s\t%s\t%u\t%d\t%.4lf\t%.3lg\t", it->first.c_str(), sid(p, (int)j), (unsigned)c.nsnps,
+                  p.cell_uniq_reads[(size_t)i], incl[x], exp(incl[x] - tot[(size_t)i]));
+        if (partner[x] < 0) {
+          wi.printf("NA\tNA\tNA\n");
+        } else {
+          const double a = dp.alpha[aidx[x]];
+          wi.printf("%s\t%.3lf\t%.4lf\n", sid(p, partner[x]), first[x] ? 1.0 - a : a, dbl[x]);
+        }
+      }
+    }
+    wi.close();
+    tm.lap("demuxlet: write .incl.gz");
   }
   notice("Finished writing output files");
   muxgl_destroy(h);
@@ -1022,6 +1062,9 @@ int main(int argc, char** argv) {
                     "  demuxlet --write-singlets: also <out>.sing2.gz, the singlet log-likelihood of every printed droplet\n"
                     "    against every sample (BARCODE SM_ID NUM.SNPS NUM.READS LLK1 POSTPRB; the reference's RD.* columns\n"
                     "    give way to the two counts of .best, its LLK0 is left out)\n"
+                    "  demuxlet --write-inclusion: also <out>.incl.gz, per printed droplet and sample the evidence that the sample\n"
+                    "    is in the droplet and the doublet it pairs best in (BARCODE SM_ID NUM.SNPS NUM.READS LLK.INCL\n"
+                    "    POSTPRB.INCL DBL.PARTNER DBL.ALPHA DBL.LLK)\n"
                     "  freemuxlet --write-singlets: also <out>.clust1.sing2.gz, the singlet log-likelihood of every droplet\n"
                     "    against every cluster in the last iteration (BARCODE CLUST NUM.SNPS NUM.READS LLK1 POSTPRB)\n");
     return 1;

@@ -40,6 +40,7 @@ T_FMX_ENTRY, T_FMX_GP, T_FMX_ESTEP, T_FMX_CALL, T_FMX_MSTEP = 4, 5, 6, 7, 8
 T_FMXOLD_PAIR, T_FMXOLD_VOTE = 9, 10
 T_FMX_ESTEP_SWEEP = 11
 T_DEMUX_SINGLETS = 12
+T_DEMUX_INCLUSION = 14
 T_FMX_SINGLETS = 13
 T_COUNT = 16
 BUF_CGP, BUF_CLUST, BUF_CELLS, BUF_STAT = 0, 1, 2, 3
@@ -92,6 +93,7 @@ SYMBOLS = {
     "muxgl_demux_set_gp": (C.c_int, [_VP, C.c_int32, _VP, _VP]),
     "muxgl_demux_run": (C.c_int, [_VP, C.POINTER(_DemuxParams), _VP, _VP]),
     "muxgl_demux_singlets": (C.c_int, [_VP, C.POINTER(_DemuxParams), _VP]),
+    "muxgl_demux_inclusion": (C.c_int, [_VP, C.POINTER(_DemuxParams), _VP, _VP, _VP, _VP, _VP, _VP]),
     "muxgl_demux_results": (_VP, [_VP]),
     "muxgl_demux_exact_calls": (C.c_int, [C.c_int64, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP,
                                           C.POINTER(_DemuxParams), _VP, C.c_int32, _VP]),
@@ -335,6 +337,33 @@ class Engine:
         p.doublet_prior = 0.5  # (not read by the call)
         out = np.zeros((self.C, self.V), dtype=np.float64)
         self._check(self.lib.muxgl_demux_singlets(self.h, C.byref(p), _ptr(out)))
+        return out
+
+    INCLUSION_FIELDS = ("incl", "tot", "dbl", "partner", "alpha_idx", "first")
+
+    def demux_inclusion(self, alphas=(0.0, 0.5), doublet_prior=0.5, want=INCLUSION_FIELDS):
+        """muxgl_demux_inclusion: dict of arrays over the hypotheses H that carry prior mass (include/muxgl.h):
+        incl float64 [C][V], the log evidence that sample s is in the droplet (singlet s or either half of a doublet);
+        tot float64 [C], the log evidence of everything, so exp(incl - tot[:, None]) is the posterior of inclusion;
+        dbl float64 [C][V], the best doublet log-likelihood with s in it (-1e300: none); partner, alpha_idx, first
+        int32 [C][V]: the other sample of that doublet, its alpha index and whether s is its first sample (-1: none).
+        At any V, without a previous demux_run.  want: the subset of the six to fetch (the others are passed as NULL)."""
+        if len(alphas) > MAX_ALPHA:
+            raise ValueError("too many alphas")
+        unknown = set(want) - set(self.INCLUSION_FIELDS)
+        if unknown:
+            raise ValueError(f"unknown inclusion fields {sorted(unknown)}")
+        p = _DemuxParams()
+        p.n_alpha = len(alphas)
+        for i, a in enumerate(alphas):
+            p.alpha[i] = float(a)
+        p.doublet_prior = float(doublet_prior)
+        out = {}
+        for name in self.INCLUSION_FIELDS:
+            if name in want:
+                shape = (self.C,) if name == "tot" else (self.C, self.V)
+                out[name] = np.zeros(shape, dtype=np.float64 if name in ("incl", "tot", "dbl") else np.int32)
+        self._check(self.lib.muxgl_demux_inclusion(self.h, C.byref(p), *[_ptr(out.get(n)) for n in self.INCLUSION_FIELDS]))
         return out
 
     def demux_results_view(self):
