@@ -103,6 +103,67 @@ def compare_full_ll(got, want, V, alphas, tol=LL_TOL):
     return float(d.max()) if d.size else 0.0
 
 
+def compare_singlet_table(got, want, tol=LL_TOL):
+    """A [C][V] / [C][K] table of singlet log-likelihoods (muxgl_demux_singlets, muxgl_fmx_singlets) against the
+    reference's values of the same slots: every element within `tol`, same-signed infinities equal (the reference's
+    log(0) chain).  Returns the worst finite deviation."""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape and got.dtype == np.float64, (got.shape, want.shape, got.dtype)
+    ok = _close(got, want, tol)
+    with np.errstate(invalid="ignore"):
+        d = np.abs(got - want)
+    d = d[np.isfinite(d)]
+    worst = float(d.max()) if d.size else 0.0
+    assert ok.all(), f"singlet table: {int((~ok).sum())} elements beyond {tol}; worst {worst}"
+    return worst
+
+
+def hypothesis_value(full_ll, s, partner, alpha_idx, first):
+    """LL of the hypothesis the integer fields name for sample s: (s, partner, n) or (partner, s, n)"""
+    c = np.arange(full_ll.shape[0])
+    return np.where(first == 1, full_ll[c, s, partner, alpha_idx], full_ll[c, partner, s, alpha_idx])
+
+
+TOL = LL_TOL
+
+
+def compare_inclusion(got, full, want, what):
+    """The six tables of muxgl_demux_inclusion against `want` = restate(full, alphas, doublet_prior) of
+    tests/test_demux_inclusion.py, `full` the reference's [C][V][V][A] log-likelihoods.  incl, tot and dbl within LL_TOL
+    on every element; the integers: the reference's value of the named hypothesis lies within 2 LL_TOL of the reference's
+    maximum over H_s, and where the reference's best and runner-up are more than 2 LL_TOL apart the three integers are
+    the reference's.  Returns the worst finite deviation per table, and under "pairs" / "decided" how many (cell,
+    sample) pairs have a hypothesis at all / had their integers compared exactly."""
+    worst = {}
+    for k in ("incl", "tot", "dbl"):
+        assert got[k].shape == want[k].shape and got[k].dtype == np.float64
+        with np.errstate(invalid="ignore"):
+            d = np.abs(got[k] - want[k])
+        d = d[np.isfinite(d)]   # (-inf on both sides is equal below)
+        worst[k] = float(d.max()) if d.size else 0.0
+    print(f"inclusion {what}: max |d incl| = {worst['incl']:.3e}, |d tot| = {worst['tot']:.3e}, |d dbl| = {worst['dbl']:.3e}")
+    for k in ("incl", "tot", "dbl"):
+        assert np.all(_close(got[k], want[k], TOL)), (k, worst[k])
+    Cn, V = want["incl"].shape
+    none = want["partner"] < 0
+    for k in ("partner", "alpha_idx", "first"):
+        assert got[k].dtype == np.int32 and np.array_equal(got[k] < 0, none), k
+    decided = 0
+    for s in range(V):
+        m = ~none[:, s]
+        if not m.any():
+            continue
+        v = hypothesis_value(full, s, np.where(m, got["partner"][:, s], 0), np.where(m, got["alpha_idx"][:, s], 0),
+                             got["first"][:, s])
+        assert np.all(np.abs(v - want["dbl"][:, s])[m] <= 2 * TOL), s          # names a hypothesis at the maximum
+        clear = m & (want["gap"][:, s] > 2 * TOL)                               # ... and the reference's own where decided
+        decided += int(clear.sum())
+        for k in ("partner", "alpha_idx", "first"):
+            assert np.array_equal(got[k][clear, s], want[k][clear, s]), (k, s)
+    worst["pairs"], worst["decided"] = int((~none).sum()), decided
+    return worst
+
+
 FMX_LL_FIELDS = ("bestLLK", "nextLLK", "sngBestLLK", "sngNextLLK", "dblBestLLK", "dblNextLLK", "bestPP", "sngPP",
                  "sngOnlyPP", "sumLLK")
 FMX_INT_FIELDS = ("type", "clust", "jBest", "kBest", "jNext", "kNext", "sBest", "sNext", "dBest1", "dBest2", "dNext1",

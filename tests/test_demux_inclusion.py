@@ -12,6 +12,7 @@ import pytest
 
 import oracle_binding as ob
 import ref_binding as rb
+from parity import hypothesis_value  # noqa: F401  (its users import it from here)
 from popscle_amd import build, synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -84,12 +85,6 @@ def restate(full_ll, alphas, doublet_prior):
             with np.errstate(invalid="ignore"):
                 gap[some, s] = (best - second)[some]
     return dict(incl=incl, tot=tot, dbl=dbl, partner=partner, alpha_idx=alpha_idx, first=first, gap=gap)
-
-
-def hypothesis_value(full_ll, s, partner, alpha_idx, first):
-    """LL of the hypothesis the integer fields name for sample s: (s, partner, n) or (partner, s, n)"""
-    c = np.arange(full_ll.shape[0])
-    return np.where(first == 1, full_ll[c, s, partner, alpha_idx], full_ll[c, partner, s, alpha_idx])
 
 
 def reference_run(p, alphas, doublet_prior=0.5):
@@ -250,6 +245,20 @@ def test_a_state_of_several_batches(plan):
         assert 1 <= b <= cells and 1 <= g <= blocks
         assert b * spc + b * g * per <= bud                       # state and slab share the budget
         assert b == cells or (b + 1) * (spc + per) > bud          # as many cells as fit with one block each
+
+
+def test_the_fuzz_shapes_fit_one_megabyte(plan):
+    """tests/test_fuzz_gpu.py asks for the tables under MUXGL_DEMUX_SLAB_MB=1 in a quarter of its cases: one cell's state
+    and one block of slab must fit that for every (V, A) it draws (the widest: 255 * 60 + 64 + 8 + 6 * 32 KB = 212 KB)"""
+    import test_fuzz_gpu as fz
+
+    for V in sorted(set(fz.DEMUX_V)):
+        nblk = (V + 63) // 64
+        for A in sorted({len(g) for g in fz.GRIDS}):
+            got = batches(plan, 60, nblk * nblk, V, A * 4096 * 8, 1 << 20)
+            assert isinstance(got, tuple) and got[0] >= 1 and got[1] >= 1, (V, A, got)
+    assert plan.probe_state_bytes(255) + PER6 == 255 * 60 + 64 + 8 + 6 * 32768 <= (1 << 20) // 4
+    assert batches(plan, 60, 16, 255, PER6, 1 << 20) == (4, 1)   # several batches, a block at a time
 
 
 def test_one_cell_larger_than_the_budget_is_an_error(plan):

@@ -5,7 +5,9 @@ driver, its error paths, and `popscle-amd demuxlet --write-inclusion`.
 
 Bar: parity.LL_TOL (1e-5 absolute) on every element of incl, tot and dbl.  The integers: the reference's value of the
 named hypothesis lies within 2 LL_TOL of the reference's maximum over H_s, and where the reference's best and runner-up
-are more than 2 LL_TOL apart the three integers are the reference's.  Observed deviations: DESIGN.md 4.1d.
+are more than 2 LL_TOL apart the three integers are the reference's (parity.compare_inclusion).  Where every hypothesis
+ties, the integers are tested exactly against the documented order across several 64-sample blocks (section 1b).
+Observed deviations: DESIGN.md 4.1d.
 """
 import ctypes
 import gzip
@@ -20,7 +22,7 @@ import parity
 from popscle_amd import demuxlet, muxgl, plpio, synth
 from test_cli_gpu import BIN, as_pileup
 from test_demux_gpu import _truncate_cells, _with_empty_cells
-from test_demux_inclusion import G1, G2, G3, G6, hypothesis_value, reference_run, restate
+from test_demux_inclusion import G1, G2, G3, G6, reference_run, restate
 
 pytestmark = pytest.mark.gpu
 
@@ -73,35 +75,19 @@ def reference(V, alphas):
     return _REF[key]
 
 
-def assert_against(got, full, want, what):
-    worst = {}
-    for k in ("incl", "tot", "dbl"):
-        assert got[k].shape == want[k].shape and got[k].dtype == np.float64
-        d = np.abs(got[k] - want[k])
-        worst[k] = float(d.max()) if d.size else 0.0
-    print(f"inclusion {what}: max |d incl| = {worst['incl']:.3e}, |d tot| = {worst['tot']:.3e}, |d dbl| = {worst['dbl']:.3e}")
-    for k in ("incl", "tot", "dbl"):
-        assert np.all(parity._close(got[k], want[k], TOL)), (k, worst[k])
-    Cn, V = want["incl"].shape
-    none = want["partner"] < 0
-    for k in ("partner", "alpha_idx", "first"):
-        assert got[k].dtype == np.int32 and np.array_equal(got[k] < 0, none), k
-    for s in range(V):
-        m = ~none[:, s]
-        if not m.any():
-            continue
-        v = hypothesis_value(full, s, np.where(m, got["partner"][:, s], 0), np.where(m, got["alpha_idx"][:, s], 0),
-                             got["first"][:, s])
-        assert np.all(np.abs(v - want["dbl"][:, s])[m] <= 2 * TOL), s          # names a hypothesis at the maximum
-        clear = m & (want["gap"][:, s] > 2 * TOL)                               # ... and the reference's own where decided
-        for k in ("partner", "alpha_idx", "first"):
-            assert np.array_equal(got[k][clear, s], want[k][clear, s]), (k, s)
-    return worst
+assert_against = parity.compare_inclusion
 
 
 # ---- 1. against the reference ------------------------------------------------------------------------------------------
 
 CASES = [(V, g) for g in (G2, G6, G3, G1) for V in (1, 2, 3, 16, 17, 33, 63, 64, 65, 130)] + [(256, G2), (300, G2)]
+# grids the sweep and the fold treat differently: 0.5 not last (the symmetric alpha is tested per n, every block is swept),
+# alpha[0] != 0 (the singlet slot is (j, 0, 0) whatever alpha[0] is), MUXGL_MAX_ALPHA alphas
+G_MID = (0.0, 0.5, 0.2)
+G_NZ = (0.2, 0.5)
+G16 = (0.0, 0.05, 0.1, 0.15, 0.2, 0.25, 0.3, 0.35, 0.4, 0.45, 0.5, 0.6, 0.7, 0.8, 0.9, 0.95)
+assert len(G16) == muxgl.MAX_ALPHA
+CASES += [(V, g) for g in (G_MID, G_NZ, G16) for V in (3, 65)]
 
 
 @pytest.mark.parametrize("V,alphas", CASES)
@@ -134,6 +120,90 @@ def test_no_marker_has_genotypes():
     assert np.allclose(got["incl"], want["incl"], rtol=0, atol=1e-12) and np.allclose(got["tot"], 0.0, rtol=0, atol=1e-12)
     for k in ("partner", "alpha_idx", "first"):   # every hypothesis ties: the earliest scan position
         assert np.array_equal(got[k], want[k]), k
+
+
+# ---- 1b. ties across blocks: the integers follow from the documented order alone (value descending, then scan position
+# (j V + k) A + n ascending), whatever the blocks, waves, roles, groups and batches the hypotheses reach the state through
+
+@pytest.mark.parametrize("alphas", [G2, G3, G_MID])
+@pytest.mark.parametrize("V", [65, 130, 300])
+def test_no_marker_has_genotypes_across_blocks(V, alphas, monkeypatch):
+    """every LL is 0: every hypothesis of H_s ties, so the three integers are the earliest scan position of H_s.  The
+    sums: n equal-magnitude terms, each within ~16 ulp (the exponent's argument is a difference of log priors of
+    magnitude <= 14), so within 16 n 2^-53 <= 4.8e-10 at tot's n = V + V V (A - 1) <= 270 300; held to 1e-9."""
+    monkeypatch.delenv("MUXGL_DEMUX_SLAB_MB", raising=False)
+    A = len(alphas)
+    p = synth.make_pileup(6, 400, V, seed=40 + V, mean_entries=60, min_entries=1, sigma=1.0)
+    p.has_gp = np.zeros_like(p.has_gp)
+    want = restate(np.zeros((p.C, V, V, A)), alphas, 0.5)
+    runs = [inclusion(p, alphas)]
+    if (V, alphas) == (130, G3):   # 1 MB: 130 * 60 + 56 B of state and 3 * 32 KB per block and cell: one batch of the six cells, nine groups of one block
+        monkeypatch.setenv("MUXGL_DEMUX_SLAB_MB", "1")
+        runs.append(inclusion(p, alphas))
+        assert same_bits(*runs)
+    for got in runs:
+        assert np.all(got["dbl"] == 0.0)
+        for k in ("partner", "alpha_idx", "first"):
+            assert np.array_equal(got[k], want[k]), (k, np.argwhere(got[k] != want[k])[:5])
+        assert np.all(parity._close(got["incl"], want["incl"], 1e-9)) and np.all(parity._close(got["tot"], 0.0, 1e-9))
+
+
+@pytest.mark.parametrize("alphas", [G2, G3, G_MID])
+@pytest.mark.parametrize("V", [65, 130])
+def test_every_sample_identical(V, alphas, monkeypatch):
+    """for one n every (j, k) carries the same device value; which n wins is rounding, the rest is the order: sample 0
+    pairs with 1 (as (0, 1, n), or as (1, 0, n) where alpha[n] = 0.5 keeps k < j only), every other sample with 0 (as
+    (0, s, n), or as (s, 0, n) at 0.5)"""
+    monkeypatch.delenv("MUXGL_DEMUX_SLAB_MB", raising=False)
+    base = synth.make_pileup(14, 1500, V, seed=50 + V, mean_entries=40, sigma=1.3, min_entries=1, max_entries=200,
+                             missing_gp_frac=0.03, doublet_frac=0.3)
+    p = _truncate_cells(base, {0: 1, 1: 2, 2: 3, 13: 1})
+    lens = np.diff(p.cell_ptr)
+    assert lens.min() == 1 and lens.max() <= 200 and lens.max() > 60
+    p.gp = np.ascontiguousarray(np.broadcast_to(p.gp[:, :1, :], p.gp.shape))
+    got = inclusion(p, alphas)
+    s = np.arange(V)
+    assert np.all(got["partner"][:, 0] == 1) and np.all(got["partner"][:, 1:] == 0)
+    sym = np.asarray(alphas)[got["alpha_idx"]] == 0.5
+    assert np.array_equal(got["first"], np.where(sym, s[None] > 0, s[None] == 0).astype(np.int32))
+    assert np.all(got["dbl"].view(np.int64) == got["dbl"].view(np.int64)[:, :1])
+    monkeypatch.setenv("MUXGL_DEMUX_SLAB_MB", "1")
+    assert same_bits(got, inclusion(p, alphas))
+
+
+@pytest.mark.parametrize("alphas", [G2, G3, G_MID])
+@pytest.mark.parametrize("V,pairs", [(130, ((3, 70), (64, 129), (10, 20), (100, 101))), (65, ((1, 64), (5, 6), (30, 63)))])
+def test_duplicated_columns(V, pairs, alphas):
+    """samples a < b with the same genotype rows, all others distinct: a hypothesis with b ties the one with a in b's
+    place bit for bit, and that one scans first in either role, so no other sample s names b as its partner -- but for
+    one hypothesis: at alpha = 0.5 only k < j carries prior mass, so for a < s < b the twin of (b, s) is the mirrored
+    (s, a), whose sum is rounded in another order (in the reference's arithmetic too); it may win by rounding"""
+    p = synth.make_pileup(12, 1500, V, seed=70 + V, mean_entries=80, min_entries=5, missing_gp_frac=0.03, doublet_frac=0.3)
+    gp = np.array(p.gp, copy=True)
+    for a, b in pairs:
+        gp[:, b, :] = gp[:, a, :]
+    p.gp = np.ascontiguousarray(gp)
+    cols = np.unique(np.moveaxis(p.gp, 1, 0).reshape(V, -1), axis=0)
+    assert cols.shape[0] == V - len(pairs)          # the premise: no other two samples alike
+    with muxgl.Engine(0) as e:
+        load(e, p)
+        sng = e.demux_singlets(alphas)
+        got = e.demux_inclusion(alphas)
+    paired = {x for ab in pairs for x in ab}
+    others = np.array([s for s in range(V) if s not in paired])
+    sym = np.asarray(alphas)[got["alpha_idx"][:, others]] == 0.5
+    for a, b in pairs:
+        assert sng[:, a].tobytes() == sng[:, b].tobytes(), (a, b)
+        if got["dbl"][:, a].tobytes() != got["dbl"][:, b].tobytes():   # the two copies' best values differ (DESIGN.md 4.1d)
+            import warnings
+
+            warnings.warn(f"V={V} alphas={alphas} pair ({a}, {b}): dbl differs between the two copies; partner check left "
+                          "out for this pair")
+            continue
+        hit = got["partner"][:, others] == b
+        mirrored = sym & (got["first"][:, others] == 0) & ((others > a) & (others < b))[None]   # (b, s, 0.5) against (s, a, 0.5)
+        print(f"V={V} alphas={alphas} pair ({a}, {b}): {int((hit & mirrored).sum())} samples between them name {b} at alpha 0.5")
+        assert not (hit & ~mirrored).any(), (a, b, others[np.argwhere(hit & ~mirrored)[:5, 1]].tolist())
 
 
 def test_zero_cells():

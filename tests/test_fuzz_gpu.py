@@ -6,10 +6,19 @@ qualities, genotype rows that do not sum to one, unusual alpha grids and priors,
 
 Bar: parity.compare_* -- every integer field equal, log-likelihoods within 1e-5 (the asserts below hold them to 1e-7).
 
+Every case also asks the same engine for the per-droplet tables -- muxgl_demux_singlets and the six tables of
+muxgl_demux_inclusion against the reference's full_ll (parity.compare_singlet_table, parity.compare_inclusion on
+test_demux_inclusion.restate), muxgl_fmx_singlets after every iteration against the diagonal of the reference's full_ll
+-- in a quarter of the cases under a slab budget of 1 MB (several batches and groups).  Their bars: TABLE_TOL below.
+A campaign line carries sng_ll, incl_ll, tot_ll, dbl_ll, fmx_sng_ll (the worst |d| of each table) and incl_decided, the
+share of (cell, sample) pairs whose reference gap exceeds 2 LL_TOL: the pairs whose integers were compared exactly.
+
 pytest runs the seeds of FUZZ_SEEDS (a minute); a campaign is
     python tests/test_fuzz_gpu.py --seeds 1000:1400 [--kind demux|fmx] [--log gpurun_out/fuzz.jsonl]
 which prints one JSON line per case and exits 1 at the first failing seed (the seed reproduces the case).
 """
+import contextlib
+import io
 import json
 import os
 import sys
@@ -24,6 +33,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import parity  # noqa: E402
 import ref_binding as rb  # noqa: E402
 from popscle_amd import freemuxlet, muxgl, shard, synth  # noqa: E402
+from test_demux_inclusion import restate  # noqa: E402
 
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(not rb.available(), reason="oracle/_ref/libscdrop_ref.so not built")]
@@ -39,6 +49,38 @@ DEMUX_FLAGS = [0] * 6 + [muxgl.FLAG_FORCE_ROW_KERNEL, muxgl.FLAG_FORCE_WAVE_KERN
                          muxgl.FLAG_FORCE_ROW_KERNEL | muxgl.FLAG_NO_LINEAR_ENTRIES]
 FMX_FLAGS = [0] * 6 + [muxgl.FLAG_FORCE_ROW_KERNEL, muxgl.FLAG_FORCE_WAVE_KERNEL, muxgl.FLAG_NO_LINEAR_ENTRIES,
                        muxgl.FLAG_NO_PIVOT_SUMS, muxgl.FLAG_FORCE_WAVE_KERNEL | muxgl.FLAG_NO_PIVOT_SUMS]
+
+# The bars of the tables (none of them has an exact pass behind it).  parity.compare_* hold them to parity.LL_TOL through
+# parity._close (same-signed infinities equal); on top of that a table whose worst deviation over the campaign
+# `--seeds 1000:1100 --budget-s 600` and over FUZZ_SEEDS stayed within 1e-8 is held to 1e-7 like the rest of this file,
+# else to LL_TOL.  Measured: sng 4.7e-11, incl / tot / dbl 3.0e-11, fmx_sng 1.6e-10 -- all five
+# at 1e-7.  sng: muxgl_demux_singlets; incl, tot, dbl: muxgl_demux_inclusion; fmx_sng: muxgl_fmx_singlets.
+TABLE_TOL = dict(sng=1e-7, incl=1e-7, tot=1e-7, dbl=1e-7, fmx_sng=1e-7)
+RESTATE_BYTES = 5e7   # of full_ll per call of restate (it makes several temporaries of that size): 16 cells at V = 255, A = 6
+
+
+def table_slab_mb(seed, kind):
+    """the slab budget of the table calls alone, from a stream of its own (the cases' draws stay what they were):
+    "1" (MB) in a quarter of the cases, else None (the variable unset: the library's default)"""
+    u = np.random.default_rng([seed, 79]).random(2)[0 if kind == "demux" else 1]
+    return "1" if u < 0.25 else None
+
+
+@contextlib.contextmanager
+def slab_env(name, value):
+    """the environment variable `name` set to `value` (None: unset) inside, what it was outside"""
+    old = os.environ.get(name)
+    try:
+        if value is None:
+            os.environ.pop(name, None)
+        else:
+            os.environ[name] = value
+        yield
+    finally:
+        if old is None:
+            os.environ.pop(name, None)
+        else:
+            os.environ[name] = old
 
 
 def _shape(r, width, per_hyp):
@@ -114,18 +156,45 @@ def _run_demux(eng, info, p):
     eng.demux_set_gp(p.gp, p.has_gp)
     got = eng.demux_run(alphas, dp)                      # the product path (calls made next to the sweep)
     rep = parity.compare_demux(got, want, alphas, p, doublet_prior=dp)
+    st = rep["exact_pass"]
     if info.get("how", "one") == "group":
         assert rep["max_abs_ll_diff"] < 1e-7, rep
-        st = rep["exact_pass"]
-        return dict(ll=rep["max_abs_ll_diff"], looked_at=int(st["cells"]), near=int(st["near_ties"]),
-                    deep=int(st["deep"]), changed=int(st["changed"]), raw_differing=rep["raw_records_differing"])
-    got2, full = eng.demux_run(alphas, dp, want_full_ll=True)   # the tensor path
-    rep2 = parity.compare_demux(got2, want, alphas, p, doublet_prior=dp)
-    worst = parity.compare_full_ll(full, want_ll, V, alphas)
-    assert rep["max_abs_ll_diff"] < 1e-7 and rep2["max_abs_ll_diff"] < 1e-7 and worst < 1e-7, (rep, rep2, worst)
-    st = rep["exact_pass"]
-    return dict(ll=max(rep["max_abs_ll_diff"], worst), looked_at=int(st["cells"]), near=int(st["near_ties"]),
-                deep=int(st["deep"]), changed=int(st["changed"]), raw_differing=rep["raw_records_differing"])
+        out = dict(ll=rep["max_abs_ll_diff"], looked_at=int(st["cells"]), near=int(st["near_ties"]),
+                   deep=int(st["deep"]), changed=int(st["changed"]), raw_differing=rep["raw_records_differing"])
+    else:
+        got2, full = eng.demux_run(alphas, dp, want_full_ll=True)   # the tensor path
+        rep2 = parity.compare_demux(got2, want, alphas, p, doublet_prior=dp)
+        worst = parity.compare_full_ll(full, want_ll, V, alphas)
+        assert rep["max_abs_ll_diff"] < 1e-7 and rep2["max_abs_ll_diff"] < 1e-7 and worst < 1e-7, (rep, rep2, worst)
+        out = dict(ll=max(rep["max_abs_ll_diff"], worst), looked_at=int(st["cells"]), near=int(st["near_ties"]),
+                   deep=int(st["deep"]), changed=int(st["changed"]), raw_differing=rep["raw_records_differing"])
+    out.update(_demux_tables(eng, info, want_ll))
+    return out
+
+
+def _demux_tables(eng, info, want_ll):
+    """the singlet table and the six inclusion tables of the same engine against the reference's full_ll"""
+    alphas, dp, V = info["alphas"], info["dp"], info["V"]
+    slab = table_slab_mb(info["seed"], "demux")
+    with slab_env("MUXGL_DEMUX_SLAB_MB", slab):
+        sng = eng.demux_singlets(alphas)
+        inc = eng.demux_inclusion(alphas, dp)
+    out = dict(table_slab_mb=slab, sng_ll=parity.compare_singlet_table(sng, want_ll[:, :, 0, 0], TABLE_TOL["sng"]))
+    worst, pairs, decided = dict(incl=0.0, tot=0.0, dbl=0.0), 0, 0
+    Cn = want_ll.shape[0]
+    step = int(max(16, RESTATE_BYTES // (V * V * len(alphas) * 8)))
+    for b in range(0, Cn, step):
+        full = want_ll[b:b + step]
+        with contextlib.redirect_stdout(io.StringIO()):   # (a campaign prints one line per case)
+            rep = parity.compare_inclusion({k: v[b:b + step] for k, v in inc.items()}, full, restate(full, alphas, dp),
+                                           f"seed {info['seed']} cells {b}..")
+        worst = {k: max(worst[k], rep[k]) for k in worst}
+        pairs, decided = pairs + rep["pairs"], decided + rep["decided"]
+    for k in worst:
+        assert worst[k] <= TABLE_TOL[k], (k, worst[k])
+    out.update(incl_ll=worst["incl"], tot_ll=worst["tot"], dbl_ll=worst["dbl"],
+               incl_decided=round(decided / pairs, 4) if pairs else None)
+    return out
 
 
 def fmx_case(seed):
@@ -193,7 +262,10 @@ def run_fmx(eng, info, p):
         clust = init
     out = dict(iters=int(ref["n_iter"]), exact_scores=int(eng.fmx_score_stats()),
                greedy_near=[int(x) for x in eng.fmx_greedy_stats()])
-    worst, near = 0.0, 0
+    worst, near, sng_worst = 0.0, 0, 0.0
+    slab = table_slab_mb(info["seed"], "fmx")
+    jd = np.arange(K)
+    jd = jd * (jd + 1) // 2 + jd   # the singlets among the reference's llks[K (K + 1) / 2]
     if how == "shard":
         world = info["world"]
         engs = [muxgl.Engine(0, flags=info["flags"]) for _ in range(world)]
@@ -229,6 +301,9 @@ def run_fmx(eng, info, p):
                 for r, e in enumerate(engs):
                     g, c = e.fmx_cluster_pileup()
                     _check_cplp(g, c, ref["cplp"][it], *s_ranges[r])
+                with slab_env("MUXGL_FMX_SLAB_MB", slab):   # (a rank answers for its own cells)
+                    sng = np.concatenate([e.fmx_singlets()[c_ranges[r][0]:c_ranges[r][1]] for r, e in enumerate(engs)])
+                sng_worst = max(sng_worst, parity.compare_singlet_table(sng, ref["full_ll"][it][:, jd], TABLE_TOL["fmx_sng"]))
             out["exact"] = [int(sum(e.fmx_exact_stats()[k] for e in engs)) for k in range(3)]
         finally:
             for e in engs:
@@ -254,12 +329,15 @@ def run_fmx(eng, info, p):
                 worst, near = max(worst, rep["max_abs_ll_diff"]), near + rep["near_tie_cells"]
                 g, c = run.fmx_cluster_pileup()
                 _check_cplp(g, c, ref["cplp"][it])
+                with slab_env("MUXGL_FMX_SLAB_MB", slab):
+                    sng = run.fmx_singlets()
+                sng_worst = max(sng_worst, parity.compare_singlet_table(sng, ref["full_ll"][it][:, jd], TABLE_TOL["fmx_sng"]))
             out["exact"] = [int(x) for x in run.fmx_exact_stats()]
         finally:
             if own:
                 run.close()
     assert worst < 1e-7, worst
-    out.update(ll=worst, near=near)
+    out.update(ll=worst, near=near, fmx_sng_ll=sng_worst, table_slab_mb=slab)
     return out
 
 
