@@ -98,7 +98,6 @@ __global__ void __launch_bounds__(64)
 
 int demux_stream_launch(muxgl_handle* h, const muxgl_demux_params* p) {
   const int V = h->V, A = p->n_alpha;
-  if (A < 2) MUXGL_FAIL(h, "streamed demuxlet call: the alpha grid needs a doublet alpha (n_alpha >= 2)");
   if ((double)V * V * A >= 2147483648.0)
     MUXGL_FAIL(h, "streamed demuxlet call: V=%d with %d alphas exceeds the int32 scan positions (V*V*n_alpha < 2^31)", V, A);
   if (h->want_full_ll)
@@ -107,8 +106,13 @@ int demux_stream_launch(muxgl_handle* h, const muxgl_demux_params* p) {
   bool all_sym = true;
   for (int n = 1; n < A; ++n) all_sym = all_sym && p->alpha[n] == 0.5;
   // blocks that hold a hypothesis the call reads: with alpha = 0.5 only the (hi, lo) orientation, and the singlets in Y = 0
+  // -- the only blocks of a grid without a doublet alpha (the reference then calls among the singlets alone)
   const int nblk = (V + SBLK - 1) / SBLK;
-  const std::vector<int32_t> blocks = stream_plan::block_list(nblk, all_sym, nblk);  // X * nblk + Y
+  std::vector<int32_t> blocks = stream_plan::block_list(nblk, all_sym, nblk);  // X * nblk + Y
+  if (A == 1) {
+    blocks.clear();
+    for (int X = 0; X < nblk; ++X) blocks.push_back(X * nblk);
+  }
   const int64_t nb_all = (int64_t)blocks.size();
   const size_t per = (size_t)A * SLAB_DOUBLES * sizeof(double);  // one (cell, block) of the slab
   const auto [gc, gb] = stream_plan::cut_groups(h->C, nb_all, per, dev_slab_budget("MUXGL_DEMUX_SLAB_MB"));

@@ -101,7 +101,7 @@ void launch_sweep(muxgl_handle* h, int64_t c0, int64_t nc, int32_t b0, int32_t n
 
 int sweep_dispatch(muxgl_handle* h, int64_t c0, int64_t nc, int32_t b0, int32_t nb, const int32_t* d_blocks, int nblk,
                    const double* d_pg, int A, double* d_slab) {
-  const int na = A - 1;  // alphas 1 .. A - 1 (A >= 2)
+  const int na = A - 1;  // alphas 1 .. A - 1; none: the singlet slots alone (the kernel writes no pair slot)
 #define SW(NA, KT) launch_sweep<NA, KT>(h, c0, nc, b0, nb, d_blocks, nblk, d_pg, A, d_slab)
   if (na <= 1) SW(1, 16);
   else if (na <= 2) SW(2, 8);

@@ -63,8 +63,8 @@ def test_ties_and_deep_bits_occur():
     assert rep["exact_pass"]["deep"] > 0
 
 
-def _same_after_exact(a, b, alphas, p):
-    ea, eb = parity.exact(a, alphas, p), parity.exact(b, alphas, p)
+def _same_after_exact(a, b, alphas, p, doublet_prior=0.5):
+    ea, eb = parity.exact(a, alphas, p, doublet_prior), parity.exact(b, alphas, p, doublet_prior)
     for f in parity.DEMUX_INT_FIELDS:
         assert np.array_equal(ea[f], eb[f]), (f, np.flatnonzero(ea[f] != eb[f])[:5])
     for f in parity.DEMUX_LL_FIELDS:

@@ -16,6 +16,9 @@ share of (cell, sample) pairs whose reference gap exceeds 2 LL_TOL: the pairs wh
 pytest runs the seeds of FUZZ_SEEDS (a minute); a campaign is
     python tests/test_fuzz_gpu.py --seeds 1000:1400 [--kind demux|fmx] [--log gpurun_out/fuzz.jsonl]
 which prints one JSON line per case and exits 1 at the first failing seed (the seed reproduces the case).
+
+The streamed paths (demux_stream.hip, fmx_stream.hip) have cases of their own, stream_demux_case / stream_fmx_case below,
+run by tests/test_fuzz_stream_gpu.py and by `--kind stream-demux|stream-fmx` (profiles/stream_fuzz_campaign.md).
 """
 import contextlib
 import io
@@ -103,12 +106,8 @@ def _pileup(r, seed, C, S, V, ment, mine, sigma, with_gp):
                              missing_gp_frac=float(r.choice([0.0, 0.0, 0.03, 0.5, 1.0])) if with_gp else 0.0, with_gp=with_gp)
 
 
-def demux_case(seed):
-    r = np.random.default_rng([seed, 77])
-    V = int(r.choice(DEMUX_V))
-    alphas = GRIDS[int(r.integers(len(GRIDS)))]
-    C, S, ment, mine, sigma = _shape(r, V, V * V * len(alphas) * 9)
-    p = _pileup(r, 3000 + seed, C, S, V, ment, mine, sigma, True)
+def _gp_mode(r, p, V):
+    """one of the genotype-tensor modes drawn and applied to p.gp; returns its name"""
     mode = str(r.choice(["gt", "gt", "dup", "all_same", "float_rows", "hard"]))
     gp = p.gp
     if mode == "dup" and V > 1:       # some samples are copies of others: exact ties between hypotheses
@@ -124,6 +123,16 @@ def demux_case(seed):
         g = g / g.sum(axis=2, keepdims=True, dtype=np.float32)
         gp = 0.9 * g.astype(np.float64) + 0.1 * g.astype(np.float64).mean(axis=1, keepdims=True)
     p.gp = np.ascontiguousarray(gp)
+    return mode
+
+
+def demux_case(seed):
+    r = np.random.default_rng([seed, 77])
+    V = int(r.choice(DEMUX_V))
+    alphas = GRIDS[int(r.integers(len(GRIDS)))]
+    C, S, ment, mine, sigma = _shape(r, V, V * V * len(alphas) * 9)
+    p = _pileup(r, 3000 + seed, C, S, V, ment, mine, sigma, True)
+    mode = _gp_mode(r, p, V)
     dp = float(r.choice([0.5, 0.5, 0.1, 0.9]))
     flags = int(DEMUX_FLAGS[int(r.integers(len(DEMUX_FLAGS)))])
     how = str(r.choice(["one", "one", "one", "group"]))   # group: a device group of two members on this GPU
@@ -244,12 +253,45 @@ def _check_cplp(g, c, w, s0=None, s1=None):
     assert np.allclose(g[:, sl], w["gls"][:, sl], rtol=1e-11, atol=1e-300)
 
 
-def run_fmx(eng, info, p):
+def fmx_reference(info, p):
+    return rb.RefScl.from_packed(p).freemux2(info["K"], doublet_prior=info["dp"], geno_error=info["ge"],
+                                            frac_init_clust=info.get("frac", 1.0),
+                                            singlet_score_thres=info.get("thres", -1e300), init_clust=info.get("init"),
+                                            full_ll=True, cluster_pileups=True)
+
+
+def _check_raw_tie_order(raw, assigned, K):
+    """The fold's order on exact ties, seen before the exact path settles them (raw: records as a rank fetched them).
+    Clusters without a cell have the same pileup, so a droplet's singlet values against them are the same bits on the
+    device; under (value descending, position ascending) the scans name the lowest such cluster before any other."""
+    empty = np.setdiff1d(np.arange(K), assigned[assigned >= 0])
+    if empty.size < 2:
+        return 0
+    is_empty = np.zeros(K + 1, dtype=bool)   # (slot K: "none", -1)
+    is_empty[empty] = True
+    b, n = raw["sBest"], raw["sNext"]
+    mb, mn = is_empty[b], is_empty[n]
+    assert (b[mb] == empty[0]).all() and (n[mn & mb] == empty[1]).all() and (n[mn & ~mb] == empty[0]).all(), \
+        ("tie order among clusters without a cell", empty[:2], b[mb | mn][:5], n[mb | mn][:5])
+    return int((mb | mn).sum())
+
+
+def run_fmx(eng, info, p, ref=None, trace=None):
+    """ref: fmx_reference(info, p) where the caller has it already.  trace: a list that receives, per iteration, the
+    records, the counters and the cluster pileups (of a rank's own SNPs in a sharded run) as the engine gave them.
+    info["stream"]: the case is expected on the streamed E-step (fmx_stream.hip) -- full_ll is refused, which is the
+    documented sign of that path, and not compared; the run is made under the slab budget info["run_slab"]."""
+    if info.get("stream"):
+        with slab_env("MUXGL_FMX_SLAB_MB", info.get("run_slab")):
+            return _run_fmx(eng, info, p, ref, trace)
+    return _run_fmx(eng, info, p, ref, trace)
+
+
+def _run_fmx(eng, info, p, ref, trace):
     K, dp, ge, how = info["K"], info["dp"], info["ge"], info.get("how", "one")
-    init = info.get("init")
-    ref = rb.RefScl.from_packed(p).freemux2(K, doublet_prior=dp, geno_error=ge, frac_init_clust=info.get("frac", 1.0),
-                                            singlet_score_thres=info.get("thres", -1e300), init_clust=init, full_ll=True,
-                                            cluster_pileups=True)
+    init, stream = info.get("init"), bool(info.get("stream"))
+    if ref is None:
+        ref = fmx_reference(info, p)
     # the start on one device with the whole pileup (the greedy pass is sequential over all cells)
     eng.set_pileup(p.S, p.cell_ptr, p.entry_snp, p.entry_rptr, p.reads)
     llk0, llk2, ns, nr = eng.fmx_prepare(p.af)
@@ -277,6 +319,7 @@ def run_fmx(eng, info, p):
                 e.fmx_prepare(p.af)
                 e.fmx_set_shard(*c_ranges[r], *s_ranges[r])
                 e.fmx_set_clusters(K, clust)
+            assigned = np.asarray(clust)
             for it in range(ref["n_iter"]):
                 for e in engs:
                     e.fmx_iter_gp(dp, ge)
@@ -284,6 +327,9 @@ def run_fmx(eng, info, p):
                 for e in engs:
                     e.fmx_iter_estep(dp, ge)
                 fetched = [e.fmx_iter_fetch() for e in engs]
+                if stream:
+                    out["raw_ties"] = out.get("raw_ties", 0) + sum(
+                        _check_raw_tie_order(cs[c_ranges[r][0]:c_ranges[r][1]], assigned, K) for r, (cs, _) in enumerate(fetched))
                 if sum(e.fmx_exact_pending() for e in engs) > 0:
                     freemuxlet.settle_near_ties(engs, lambda obj: [obj], dp, ge)
                     fetched = [e.fmx_iter_fetch() for e in engs]
@@ -298,13 +344,22 @@ def run_fmx(eng, info, p):
                     stats += np.array(st)
                 rep = _check_iteration(it, ref, cells, stats, K)
                 worst, near = max(worst, rep["max_abs_ll_diff"]), near + rep["near_tie_cells"]
+                assigned = cells["clust"]
+                plps = []
                 for r, e in enumerate(engs):
                     g, c = e.fmx_cluster_pileup()
                     _check_cplp(g, c, ref["cplp"][it], *s_ranges[r])
+                    plps += [g[:, s_ranges[r][0]:s_ranges[r][1]].copy(), c[:, s_ranges[r][0]:s_ranges[r][1]].copy()]
+                if trace is not None:
+                    trace.append((cells, tuple(int(x) for x in stats), plps))
                 with slab_env("MUXGL_FMX_SLAB_MB", slab):   # (a rank answers for its own cells)
                     sng = np.concatenate([e.fmx_singlets()[c_ranges[r][0]:c_ranges[r][1]] for r, e in enumerate(engs)])
                 sng_worst = max(sng_worst, parity.compare_singlet_table(sng, ref["full_ll"][it][:, jd], TABLE_TOL["fmx_sng"]))
             out["exact"] = [int(sum(e.fmx_exact_stats()[k] for e in engs)) for k in range(3)]
+            if stream:   # (asked last: a refused fetch has already taken the iteration's open near ties into the count)
+                for e in engs:
+                    with pytest.raises(muxgl.MuxglError, match="full_ll"):
+                        e.fmx_iter_fetch(want_full_ll=True)
         finally:
             for e in engs:
                 e.close()
@@ -317,8 +372,11 @@ def run_fmx(eng, info, p):
                 # (a device group settles near-tied scores as one device does: the same bits)
                 assert np.array_equal(g0, llk0) and np.array_equal(g2, llk2), "scores of the group / flagged engine differ"
             run.fmx_set_clusters(K, clust)
+            if stream:   # refused before anything runs: the same handle then makes the iterations
+                with pytest.raises(muxgl.MuxglError, match="full_ll"):
+                    run.fmx_iterate(dp, ge, want_full_ll=True)
             for it in range(ref["n_iter"]):
-                if how == "group":
+                if how == "group" or stream:
                     cells, st = run.fmx_iterate(dp, ge)
                 else:
                     cells, st, full = run.fmx_iterate(dp, ge, want_full_ll=True)
@@ -329,6 +387,8 @@ def run_fmx(eng, info, p):
                 worst, near = max(worst, rep["max_abs_ll_diff"]), near + rep["near_tie_cells"]
                 g, c = run.fmx_cluster_pileup()
                 _check_cplp(g, c, ref["cplp"][it])
+                if trace is not None:
+                    trace.append((cells, tuple(int(x) for x in st), [g, c]))
                 with slab_env("MUXGL_FMX_SLAB_MB", slab):
                     sng = run.fmx_singlets()
                 sng_worst = max(sng_worst, parity.compare_singlet_table(sng, ref["full_ll"][it][:, jd], TABLE_TOL["fmx_sng"]))
@@ -341,10 +401,149 @@ def run_fmx(eng, info, p):
     return out
 
 
+# ---- the streamed paths: demux_stream.hip (sweep, top2 fold, call) and fmx_stream.hip (sweep, fold, call, rows of the
+# exact pass).  Widths: the smallest that reach every structural case of a walk over 64 x 64 blocks -- one block, one off
+# a block boundary on either side, a multiple of 64, several blocks; forced by flag up to 255, the product's own choice
+# beyond.  Draws come from streams of their own ([seed, 80], [seed, 81]): demux_case / fmx_case stay what they are.
+STREAM_DEMUX_V = [33, 40, 63, 64, 65, 96, 128, 129, 130, 200, 255]
+STREAM_DEMUX_V_NATURAL = [256, 257, 300, 320]
+STREAM_FMX_K = [33, 40, 63, 64, 65, 100, 128, 129, 200, 255]
+STREAM_FMX_K_NATURAL = [256, 257, 300, 320]
+STREAM_GRIDS = GRIDS + [(0.5, 0.2)]
+
+
+def stream_demux_case(seed):
+    r = np.random.default_rng([seed, 80])
+    natural = bool(r.random() < 0.3)
+    V = int(r.choice(STREAM_DEMUX_V_NATURAL if natural else STREAM_DEMUX_V))
+    alphas = STREAM_GRIDS[int(r.integers(len(STREAM_GRIDS)))]
+    C, S, ment, mine, sigma = _shape(r, V, V * V * len(alphas) * 9)
+    p = _pileup(r, 7000 + seed, C, S, V, ment, mine, sigma, True)
+    mode = _gp_mode(r, p, V)
+    dp = float(r.choice([0.5, 0.1, 0.9]))
+    flags = (0 if natural else muxgl.FLAG_FORCE_STREAMED_CALL) | int(r.choice([0, muxgl.FLAG_NO_LINEAR_ENTRIES]))
+    how = str(r.choice(["one", "one", "one", "group"]))
+    run_slab = "1" if r.random() < 0.5 else None   # MUXGL_DEMUX_SLAB_MB of the run itself (None: the default budget)
+    return dict(kind="stream-demux", seed=seed, V=V, alphas=alphas, C=C, S=S, ment=ment, mode=mode, dp=dp, flags=flags,
+                how=how, run_slab=run_slab, missing_gp=round(1.0 - float(np.mean(p.has_gp)), 3),
+                empty_cells=int(np.sum(np.diff(p.cell_ptr) == 0))), p
+
+
+def stream_fmx_case(seed):
+    r = np.random.default_rng([seed, 81])
+    natural = bool(r.random() < 0.3)
+    K = int(r.choice(STREAM_FMX_K_NATURAL if natural else STREAM_FMX_K))
+    C, S, ment, mine, sigma = _shape(r, 2 * K, K * K * 9 * 6)
+    C = max(C, 3 * K) if K <= 70 else K + 20
+    p = _pileup(r, 9000 + seed, C, S, max(2, int(r.choice([K, max(2, K // 2), K + 1]))), ment, mine, sigma, False)
+    dp = float(r.choice([0.5, 0.1]))
+    ge = float(r.choice([0.1, 0.01]))
+    flags = (0 if natural else muxgl.FLAG_FORCE_STREAMED_ESTEP) | int(r.choice(
+        [0, muxgl.FLAG_NO_LINEAR_ENTRIES, muxgl.FLAG_NO_PIVOT_SUMS, muxgl.FLAG_NO_LINEAR_ENTRIES | muxgl.FLAG_NO_PIVOT_SUMS]))
+    how = str(r.choice(["one", "one", "group", "shard"]))
+    start = str(r.choice(["greedy", "greedy", "partial", "given"]))
+    frac = float(r.choice([0.3, 0.8])) if start == "partial" else 1.0
+    thres = float(r.choice([-1e300, -0.5, 0.0])) if start == "partial" else -1e300
+    init = None
+    if start == "given":   # some cells start without a cluster, some clusters without a cell
+        init = r.integers(-1, K, size=p.C).astype(np.int32)
+    run_slab = "1" if r.random() < 0.5 else None   # MUXGL_FMX_SLAB_MB of the run itself
+    return dict(kind="stream-fmx", seed=seed, K=K, C=C, S=S, ment=ment, dp=dp, ge=ge, flags=flags, how=how,
+                world=int(r.choice([2, 3])), start=start, frac=frac, thres=thres, init=init, run_slab=run_slab,
+                stream=True, empty_cells=int(np.sum(np.diff(p.cell_ptr) == 0))), p
+
+
+def _demux_handle(info, p, flags):
+    e = muxgl.Engine([0, 0] if info["how"] == "group" else 0, flags=flags)
+    e.set_pileup(p.S, p.cell_ptr, p.entry_snp, p.entry_rptr, p.reads)
+    e.demux_set_gp(p.gp, p.has_gp)
+    return e
+
+
+def run_stream_demux(eng, info, p):
+    """the streamed call against the reference; below 256 samples also against the path the job takes without the flag
+    and with the reference's full_ll behind the tables; under a 1 MB slab budget also against the default budget"""
+    from test_demux_many_samples_gpu import _same_after_exact
+
+    alphas, dp, V = info["alphas"], info["dp"], info["V"]
+    forced = bool(info["flags"] & muxgl.FLAG_FORCE_STREAMED_CALL)
+    assert forced == (V <= 255)
+    want, _, want_ll = rb.RefScl.from_packed(p).demux(alphas, doublet_prior=dp, full_ll=forced)
+    with _demux_handle(info, p, info["flags"]) as e:
+        with slab_env("MUXGL_DEMUX_SLAB_MB", info["run_slab"]):
+            with pytest.raises(muxgl.MuxglError, match="full_ll"):   # the documented sign of the streamed path
+                e.demux_run(alphas, dp, want_full_ll=True)
+            got = e.demux_run(alphas, dp)
+        rep = parity.compare_demux(got, want, alphas, p, doublet_prior=dp)
+        assert rep["max_abs_ll_diff"] < 1e-7, rep
+        st = rep["exact_pass"]
+        out = dict(ll=rep["max_abs_ll_diff"], looked_at=int(st["cells"]), near=int(st["near_ties"]), deep=int(st["deep"]),
+                   changed=int(st["changed"]), raw_differing=rep["raw_records_differing"])
+        if info["mode"] == "all_same":
+            # The fold's order on exact ties, before the exact-call pass settles them: every sample has the same rows,
+            # so every singlet is the same product of the same factors, on the device as in the reference, and both
+            # keep the first in scan order (value descending, then position ascending; strict '<')
+            v = want["valid"] == 1
+            assert np.array_equal(got["sBest"][v], want["sBest"][v]) and np.array_equal(got["sNext"][v], want["sNext"][v]), \
+                "raw singlet calls among identical samples"
+        if info["run_slab"] is not None:   # the budget only cuts the groups: the raw records are the same bytes
+            with slab_env("MUXGL_DEMUX_SLAB_MB", None):
+                assert e.demux_run(alphas, dp).tobytes() == got.tobytes(), "records differ between slab budgets"
+        if forced:
+            out.update(_demux_tables(e, info, want_ll))
+        else:   # (no full_ll of the reference at this width: the singlet table against the records' best singlet)
+            with slab_env("MUXGL_DEMUX_SLAB_MB", table_slab_mb(info["seed"], "demux")):
+                sng = e.demux_singlets(alphas)
+            v = want["valid"] == 1
+            out["sng_ll"] = parity.compare_singlet_table(sng[v, want["sBest"][v]][:, None], want["sngBestLLK"][v][:, None],
+                                                         TABLE_TOL["sng"])
+    if forced:
+        with _demux_handle(info, p, info["flags"] & ~muxgl.FLAG_FORCE_STREAMED_CALL) as e:
+            _same_after_exact(got, e.demux_run(alphas, dp), alphas, p, dp)
+    return out
+
+
+def _same_traces(a, b, records):
+    assert len(a) == len(b)
+    for (ca, sa, pa), (cb, sb, pb) in zip(a, b):
+        assert sa == sb, (sa, sb)
+        records(ca, cb)
+        assert len(pa) == len(pb) and all(np.array_equal(x, y) for x, y in zip(pa, pb)), "cluster pileups differ"
+
+
+def _same_bytes(a, b):
+    assert a.tobytes() == b.tobytes(), "records differ between slab budgets"
+
+
+def run_stream_fmx(eng, info, p):
+    """run_fmx's checks on the streamed E-step; below 256 clusters also against the path the job takes without the flag
+    (records by parity.same_records, counters and cluster pileups bit for bit); under a 1 MB slab budget also against
+    the default budget (records byte for byte)"""
+    forced = bool(info["flags"] & muxgl.FLAG_FORCE_STREAMED_ESTEP)
+    assert forced == (info["K"] <= 255) and info["stream"]
+    ref = fmx_reference(info, p)
+    trace = []
+    out = run_fmx(eng, info, p, ref, trace)
+    if info["run_slab"] is not None:
+        again = []
+        run_fmx(eng, dict(info, run_slab=None), p, ref, again)
+        _same_traces(trace, again, _same_bytes)
+    if forced:
+        plain = []
+        run_fmx(eng, dict(info, flags=info["flags"] & ~muxgl.FLAG_FORCE_STREAMED_ESTEP, stream=False), p, ref, plain)
+        _same_traces(trace, plain, parity.same_records)
+    return out
+
+
+CASES = {"demux": (demux_case, run_demux), "fmx": (fmx_case, run_fmx),
+         "stream-demux": (stream_demux_case, run_stream_demux), "stream-fmx": (stream_fmx_case, run_stream_fmx)}
+
+
 def run_case(eng, kind, seed):
-    info, p = (demux_case if kind == "demux" else fmx_case)(seed)
+    case, run = CASES[kind]
+    info, p = case(seed)
     info["nnz"] = int(p.nnz)
-    info.update((run_demux if kind == "demux" else run_fmx)(eng, info, p))
+    info.update(run(eng, info, p))
     info.pop("init", None)
     return info
 
@@ -380,7 +579,7 @@ def main(argv):
 
     ap = argparse.ArgumentParser()
     ap.add_argument("--seeds", default="0:50")
-    ap.add_argument("--kind", default="both", choices=["both", "demux", "fmx"])
+    ap.add_argument("--kind", default="both", choices=["both"] + list(CASES))
     ap.add_argument("--log", default=None)
     ap.add_argument("--keep-going", action="store_true")
     ap.add_argument("--budget-s", type=float, default=1e9, help="stop starting new cases after this many seconds")
@@ -398,7 +597,7 @@ def main(argv):
                 rec = run_case(e, kind, seed)
                 rec["ok"] = True
             except Exception as ex:  # noqa: BLE001  (a campaign reports and goes on or stops, as asked)
-                info, _ = (demux_case if kind == "demux" else fmx_case)(seed)
+                info, _ = CASES[kind][0](seed)
                 info.pop("init", None)
                 rec = dict(info, ok=False, error=f"{type(ex).__name__}: {str(ex)[:600]}",
                            where=traceback.format_exc().strip().splitlines()[-3:])
