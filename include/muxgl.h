@@ -174,6 +174,8 @@ enum {
                                    into several batches also the copies between them) */
   MUXGL_T_DEMUX_INCLUSION = 14, /* muxgl_demux_inclusion: entry likelihoods + pair sweep + marginal fold + finish (with a
                                    state cut into several batches of cells also the copies between them) */
+  MUXGL_T_FMX_INCLUSION = 15,   /* muxgl_fmx_inclusion: pair sweep + marginal fold + finish (with a state cut into
+                                   several batches of cells also the copies between them) */
   MUXGL_T_COUNT = 16
 };
 
@@ -360,6 +362,43 @@ int muxgl_fmx_iterate(muxgl_handle* h, const muxgl_fmx_params* p, muxgl_fmx_cell
  * is MUXGL_T_FMX_SINGLETS of muxgl_get_timing (the slots of the last iteration keep their values); it counts as a
  * collecting call of muxgl_get_timing_sum. */
 int muxgl_fmx_singlets(muxgl_handle* h, double* sng);
+
+/* Per droplet c and cluster s: how much evidence there is that s is in the droplet at all, and with which cluster s pairs
+ * best -- the row and column marginals of the triangle llks[] of cmd_cram_freemux2.cpp:383-456 as the LAST E-step of this
+ * handle formed it (the reference keeps only the best and the next doublet of a droplet, :469-513).  The hypotheses are
+ * those of the scans :469-498: a singlet (j, j) with log_single_prior (lsp, :379), a doublet (j, k), k < j, with
+ * log_double_prior (ldp, :380); LL(j, k) = llks[j(j+1)/2 + k].  For cluster s, H_s = { (s, k) : k < s } + { (j, s) : j > s }.
+ * incl[C][K]    = log( exp(LL(s,s) + lsp) + sum_{h in H_s} exp(LL(h) + ldp) )
+ * tot[C]        = log of the same sum over all singlets and all doublets: the record's sumLLK (whose seed of -1e300 adds
+ *                 nothing), so exp(incl - tot) is the posterior that s is in the droplet
+ * dbl[C][K]     = max_{h in H_s} LL(h)   (-1e300 when H_s is empty, K == 1, or holds no finite value)
+ * partner[C][K] = the other cluster of that hypothesis (-1: none).  Ties: value descending, then position
+ *                 p = hi(hi+1)/2 + lo ascending, the order of the scans.  s is the first (higher) cluster of the pair
+ *                 exactly when partner < s.
+ * Any out pointer may be NULL (all four: the call succeeds and writes nothing).  p->doublet_prior is read; geno_error is
+ * not (it is already mixed into the posteriors the E-step read).  A hypothesis whose LL is -inf (a cluster whose posterior
+ * rows were never filled) adds nothing to a sum and never wins dbl; a sum without a finite term is -inf, never NaN.  A
+ * droplet without entries has LL = 0 for every hypothesis.
+ * State rules, refusals and guarantees are muxgl_fmx_singlets': the tables belong to the records of the same iteration
+ * (call it after muxgl_fmx_iterate, or after muxgl_fmx_iter_estep and before the next muxgl_fmx_iter_gp); it fails, naming
+ * the reason, before the first E-step since muxgl_fmx_set_clusters, after a posterior phase without its E-step, for NULL
+ * p, without a pileup and without muxgl_fmx_prepare, and the handle stays usable; it reads state and changes none
+ * (records, counters, assignments, cluster pileups and the near-tie bookkeeping stay as they are).  1 <= K <=
+ * MUXGL_MAX_CLUSTERS whichever E-step path ran; one device, a device group (every member fills the rows of its own cells)
+ * and a slabbed or sharded handle (per-cell outputs cover the handle's own cells).
+ * The values are the device's arithmetic throughout: the streamed E-step's sweep (products of factors, one log per cell
+ * part and hypothesis, equal to the reference's sums of logs to ~1e-11), also where another E-step path made the records.
+ * Near ties in `partner` are decided by those values and the order above, not re-resolved in exact arithmetic; the
+ * records of a near-tie cell carry the exact path's values, the tables keep the device's for those cells too.
+ * Within the streamed E-step's budget (4 GiB or a third of the device, MUXGL_FMX_SLAB_MB) the device holds a slab of the pair
+ * sweep plus the state and the outputs of a batch of whole cells (52 bytes per cell and cluster); a batch is finished and
+ * copied out before the next; nothing proportional to C x K^2.  It fails, naming the variable, when one cell's state and
+ * one 64 x 64 block of the sweep exceed the budget.  All four outputs are bit-identical from call to call, for any budget,
+ * on one device, on a group and through the sharded driver.  Under MUXGL_FLAG_ASYNC_PHASES it returns with the stream
+ * drained.  Its kernel time is MUXGL_T_FMX_INCLUSION of muxgl_get_timing (the slots of the last iteration keep their
+ * values); it counts as a collecting call of muxgl_get_timing_sum. */
+int muxgl_fmx_inclusion(muxgl_handle* h, const muxgl_fmx_params* p, double* incl, double* tot, double* dbl,
+                        int32_t* partner);
 
 /* Near-tie calls of the EM iterations since muxgl_fmx_set_clusters.  The kernels' log-likelihoods equal the reference's to
  * ~1e-12, not to the last bit; a cell where a comparison of cmd_cram_freemux2.cpp:469-497,521-584 has a margin within

@@ -1,5 +1,5 @@
-// incl_plan.hpp -- the host side of muxgl_demux_inclusion (demux_incl.hip): how the cells are cut into batches whose
-// state shares the slab budget with the sweep's slab.  Plain C++ (no HIP), like stream_plan.hpp, so
+// incl_plan.hpp -- the host side of muxgl_demux_inclusion (demux_incl.hip) and muxgl_fmx_inclusion (fmx_incl.hip): how the
+// cells are cut into batches whose state shares the slab budget with the sweep's slab.  Plain C++ (no HIP), like stream_plan.hpp, so
 // tests/test_demux_inclusion.py compiles it on its own and pins the arithmetic.
 #pragma once
 #include <cstdio>
@@ -42,6 +42,25 @@ inline std::string too_small_message(int V, size_t state_per_cell, size_t slab_p
            "muxgl_demux_inclusion: the state of one cell (%zu bytes at V=%d) and one block of the sweep (%zu bytes) exceed "
            "the slab budget of %zu bytes: raise MUXGL_DEMUX_SLAB_MB",
            state_per_cell, V, slab_per_cell_block, budget);
+  return buf;
+}
+
+// ---- muxgl_fmx_inclusion (fmx_incl.hip): the same cut (cut_batches) over the streamed E-step's budget ---------------------
+
+// bytes the call holds per cell of a batch besides the slab: the state (32 B per cluster: evidence, best value, position),
+// the four outputs the finish kernel writes (8 + 8 + 4 B per cluster, 8 B per cell) and the evidence of `tot` per
+// 64-cluster row block (16 B)
+inline size_t fmx_state_bytes_per_cell(int K) {
+  const size_t nblk = ((size_t)K + 63) / 64;
+  return (size_t)K * (32 + 20) + nblk * 16 + 8;
+}
+
+inline std::string fmx_too_small_message(int K, size_t state_per_cell, size_t slab_per_cell_block, size_t budget) {
+  char buf[320];
+  snprintf(buf, sizeof(buf),
+           "muxgl_fmx_inclusion: the state of one cell (%zu bytes at K=%d) and one block of the sweep (%zu bytes) exceed "
+           "the slab budget of %zu bytes: raise MUXGL_FMX_SLAB_MB",
+           state_per_cell, K, slab_per_cell_block, budget);
   return buf;
 }
 

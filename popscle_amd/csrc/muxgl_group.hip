@@ -601,6 +601,25 @@ int group_fmx_singlets(muxgl_handle* h, double* sng) {
   return 0;
 }
 
+// every member folds its own cells and writes their rows of the caller's tables
+int group_fmx_inclusion(muxgl_handle* h, const muxgl_fmx_params* p, double* incl, double* tot, double* dbl, int32_t* partner) {
+  muxgl_group* g = h->group;
+  if (!p) MUXGL_FAIL(h, "muxgl_fmx_inclusion: fmx params NULL");
+  if (!g->have_pileup) MUXGL_FAIL(h, "muxgl_fmx_inclusion: no pileup set (muxgl_set_pileup)");
+  if (!g->prepared) MUXGL_FAIL(h, "muxgl_fmx_inclusion: call muxgl_fmx_prepare first");
+  for (const muxgl_handle* m : g->m)
+    if (const char* why = fmx_inclusion_refusal(m)) MUXGL_FAIL(h, "%s", why);
+  if (for_members(h, [&](int r) {
+        const size_t c = (size_t)g->cb[(size_t)r], o = c * (size_t)g->K;
+        return muxgl_fmx_inclusion(g->m[(size_t)r], p, incl ? incl + o : nullptr, tot ? tot + c : nullptr,
+                                   dbl ? dbl + o : nullptr, partner ? partner + o : nullptr);
+      }))
+    return 1;
+  g->ms[MUXGL_T_FMX_INCLUSION] = 0.f;
+  for (auto* m : g->m) g->ms[MUXGL_T_FMX_INCLUSION] = std::max(g->ms[MUXGL_T_FMX_INCLUSION], m->ms[MUXGL_T_FMX_INCLUSION]);
+  return 0;
+}
+
 int group_get_timing(const muxgl_handle* h, float* ms) {
   memcpy(ms, h->group->ms, sizeof(float) * MUXGL_T_COUNT);
   return 0;

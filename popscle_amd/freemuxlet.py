@@ -169,7 +169,7 @@ def settle_near_ties(engs, gather, doublet_prior, geno_error):
 
 def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early_stop=True, exchange=None,
            exchange_tensor=engine_exchange_tensor, log=None, per=None, timings=None, sync=None, stream_ctx=None,
-           want_singlets=False):
+           want_singlets=False, want_inclusion=False):
     """EM loop of cmd_cram_freemux2.cpp:373-605 on a prepared engine.  One rank: a plain engine holding the whole
     pileup.  Several ranks: an engine holding the rank's slabs (load_rank), `exchange` a TorchExchange and
     per = (cells per rank, SNPs per rank) of the equal-slice plan the slabs were cut by.  clust0 spans the whole job.
@@ -177,7 +177,9 @@ def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early
     makes the engine's stream torch's current one (device-ordered exchanges).  want_singlets: also the job-wide [C][K]
     table of singlet log-likelihoods of the last iteration (Engine.fmx_singlets of every rank's own cells, gathered
     like the records, in the original cell order): (records, stats, sng) -- the counterpart of
-    demuxlet.run_sharded(want_singlets=True)."""
+    demuxlet.run_sharded(want_singlets=True).  want_inclusion: also the dict of job-wide per-droplet, per-cluster inclusion
+    tables of the last iteration (Engine.fmx_inclusion, gathered the same way) as the last element:
+    (records, stats, [sng,] inclusion)."""
     ex = exchange or NoExchange()
     t_start = time.perf_counter()
     eng.fmx_set_clusters(K, np.ascontiguousarray(clust0, dtype=np.int32))  # :277-288, own SNP range
@@ -274,9 +276,19 @@ def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early
     out = np.zeros(eng.C_total, dtype=cells.dtype)
     for b, e, raw in parts:
         out[b:e] = np.frombuffer(raw, dtype=cells.dtype)
-    if not want_singlets:
+    if not want_singlets and not want_inclusion:
         return out, history
-    sng = np.zeros((eng.C_total, K), dtype=np.float64)  # the last E-step's posteriors are still in place: muxgl.h
-    for b, e, raw in ex.gather_objects((c0, c0 + len(cells), eng.fmx_singlets().tobytes())):
-        sng[b:e] = np.frombuffer(raw, dtype=np.float64).reshape(e - b, K)
-    return out, history, sng
+    res = [out, history]
+    if want_singlets:
+        sng = np.zeros((eng.C_total, K), dtype=np.float64)  # the last E-step's posteriors are still in place: muxgl.h
+        for b, e, raw in ex.gather_objects((c0, c0 + len(cells), eng.fmx_singlets().tobytes())):
+            sng[b:e] = np.frombuffer(raw, dtype=np.float64).reshape(e - b, K)
+        res.append(sng)
+    if want_inclusion:
+        mine = eng.fmx_inclusion(doublet_prior)
+        incl = {n: np.zeros((eng.C_total,) + a.shape[1:], dtype=a.dtype) for n, a in mine.items()}
+        for b, e, raws in ex.gather_objects((c0, c0 + len(cells), {n: a.tobytes() for n, a in mine.items()})):
+            for n, raw in raws.items():
+                incl[n][b:e] = np.frombuffer(raw, dtype=incl[n].dtype).reshape((e - b,) + incl[n].shape[1:])
+        res.append(incl)
+    return tuple(res)

@@ -20,6 +20,12 @@
 //       prints only the best and the next).  One row per droplet, in the order of .clust1.samples.gz, and cluster
 //       0 .. K-1.  Columns BARCODE, CLUST, NUM.SNPS, NUM.READS (those of .clust1.samples.gz), LLK1 (%.4lf), POSTPRB
 //       (%.3lg, equal priors over the clusters)
+//       --write-inclusion: also <O>.clust1.incl.gz (BGZF), one row per droplet of .clust1.samples.gz and cluster 0 .. K-1:
+//       the evidence that the cluster is in the droplet, as a singlet or as either half of a doublet, and the cluster it
+//       pairs best with, from the last EM iteration (muxgl_fmx_inclusion; the reference keeps only the best and the next
+//       doublet, cmd_cram_freemux2.cpp:469-513).  Columns BARCODE, CLUST, NUM.SNPS, NUM.READS, LLK.INCL (%.4lf),
+//       POSTPRB.INCL (%.3lg, exp(incl - tot)), DBL.PARTNER (cluster), DBL.LLK (%.4lf); the last two are NA where no
+//       doublet hypothesis holds the cluster (one cluster)
 //   popscle-amd freemuxlet-old --plp P --nsample K --out O [...]               mirrors cmdCramFreemuxlet (cmd_cram_freemuxlet.cpp)
 //   popscle-amd dump-plp   --plp P [--vcf V --field F] --out FILE              loader only: packed pileup to a binary file
 //   popscle-amd synth-plp  --cells C --snps S --samples V --out P              a synthetic data set in the real file formats
@@ -443,12 +449,14 @@ int cmd_freemuxlet(int argc, char** argv) {
   int32_t nSamples = 0, initIteration = 10, randomSeed = 0, verbose = 0, maxIter = 10;
   bool auxFiles = false, keepInitMissing = false, randomizeSingletScore = false, noEarlyStop = false;
   bool writeSinglets = false;  // (ours) <out>.clust1.sing2.gz: every droplet against every cluster
+  bool writeInclusion = false;  // (ours) <out>.clust1.incl.gz: per-cluster marginals of the last E-step's pair triangle
   Args a;
   cf.add(a);
   a.add_string("init-cluster", &initClusterFile);
   a.add_int("nsample", &nSamples);
   a.add_bool("aux-files", &auxFiles);
   a.add_bool("write-singlets", &writeSinglets);
+  a.add_bool("write-inclusion", &writeInclusion);
   a.add_int("verbose", &verbose);
   a.add_double("doublet-prior", &doublet_prior);
   a.add_double("geno-error", &geno_error);
@@ -655,6 +663,35 @@ int cmd_freemuxlet(int argc, char** argv) {
     });
     ws.close();
     tmr.lap("freemuxlet: write .clust1.sing2.gz");
+  }
+  if (writeInclusion) {
+    // .clust1.incl.gz: one row per droplet (the order of .clust1.samples.gz) and cluster 0 .. K-1, from the posteriors of
+    // the last E-step, like .clust1.sing2.gz
+    const size_t n = (size_t)C * (size_t)K;
+    BigVec<double> incl(n), dbl(n);
+    BigVec<int32_t> partner(n);
+    std::vector<double> tot((size_t)C);
+    check(h, muxgl_fmx_inclusion(h, &fp, incl.data(), tot.data(), dbl.data(), partner.data()), "muxgl_fmx_inclusion");
+    tmr.lap("freemuxlet: muxgl_fmx_inclusion");
+    OutFile wi(cf.outPrefix + ".clust1.incl.gz", true);
+    wi.printf("BARCODE\tCLUST\tNUM.SNPS\tNUM.READS\tLLK.INCL\tPOSTPRB.INCL\tDBL.PARTNER\tDBL.LLK\n");
+    write_rows_parallel(wi, C * (int64_t)K, [&](int64_t r, std::string& o) {
+      const int64_t i = r / K;
+      const int j = (int)(r - i * K);
+      const double v = incl.data()[(size_t)r];
+      char num[240];
+      int m = snprintf(num, sizeof(num), "\t%d\t%d\t%d\t%.4lf\t%.3lg\t", j, nSNPs[(size_t)i], nReads[(size_t)i], v,
+                       exp(v - tot[(size_t)i]));
+      m = std::min<int>(m, (int)sizeof(num) - 1);
+      if (partner.data()[(size_t)r] < 0)
+        m += snprintf(num + m, sizeof(num) - (size_t)m, "NA\tNA\n");
+      else
+        m += snprintf(num + m, sizeof(num) - (size_t)m, "%d\t%.4lf\n", (int)partner.data()[(size_t)r], dbl.data()[(size_t)r]);
+      o.append(p.bcs[(size_t)i]);
+      o.append(num, (size_t)std::min<int>(m, (int)sizeof(num) - 1));
+    });
+    wi.close();
+    tmr.lap("freemuxlet: write .clust1.incl.gz");
   }
   muxgl_destroy(h);
   return 0;
@@ -1066,7 +1103,10 @@ int main(int argc, char** argv) {
                     "    is in the droplet and the doublet it pairs best in (BARCODE SM_ID NUM.SNPS NUM.READS LLK.INCL\n"
                     "    POSTPRB.INCL DBL.PARTNER DBL.ALPHA DBL.LLK)\n"
                     "  freemuxlet --write-singlets: also <out>.clust1.sing2.gz, the singlet log-likelihood of every droplet\n"
-                    "    against every cluster in the last iteration (BARCODE CLUST NUM.SNPS NUM.READS LLK1 POSTPRB)\n");
+                    "    against every cluster in the last iteration (BARCODE CLUST NUM.SNPS NUM.READS LLK1 POSTPRB)\n"
+                    "  freemuxlet --write-inclusion: also <out>.clust1.incl.gz, per droplet and cluster the evidence that the\n"
+                    "    cluster is in the droplet and the cluster it pairs best with, in the last iteration (BARCODE CLUST\n"
+                    "    NUM.SNPS NUM.READS LLK.INCL POSTPRB.INCL DBL.PARTNER DBL.LLK)\n");
     return 1;
   }
   try {

@@ -42,6 +42,7 @@ T_FMX_ESTEP_SWEEP = 11
 T_DEMUX_SINGLETS = 12
 T_DEMUX_INCLUSION = 14
 T_FMX_SINGLETS = 13
+T_FMX_INCLUSION = 15
 T_COUNT = 16
 BUF_CGP, BUF_CLUST, BUF_CELLS, BUF_STAT = 0, 1, 2, 3
 
@@ -106,6 +107,7 @@ SYMBOLS = {
     "muxgl_fmx_set_clusters": (C.c_int, [_VP, C.c_int32, _VP]),
     "muxgl_fmx_iterate": (C.c_int, [_VP, C.POINTER(_FmxParams), _VP, _VP, _VP, _VP, _VP]),
     "muxgl_fmx_singlets": (C.c_int, [_VP, _VP]),
+    "muxgl_fmx_inclusion": (C.c_int, [_VP, C.POINTER(_FmxParams), _VP, _VP, _VP, _VP]),
     "muxgl_fmx_get_cluster_pileup": (C.c_int, [_VP, _VP, _VP]),
     "muxgl_fmx_exact_stats": (C.c_int, [_VP, _VP, _VP, _VP]),
     "muxgl_fmx_exact_pending": (C.c_int, [_VP, _VP]),
@@ -441,6 +443,27 @@ class Engine:
         where that exists -- at any K, on every E-step path.  singlet_posteriors() turns it into soft assignments."""
         out = np.zeros((self.C, self.K), dtype=np.float64)
         self._check(self.lib.muxgl_fmx_singlets(self.h, _ptr(out)))
+        return out
+
+    FMX_INCLUSION_FIELDS = ("incl", "tot", "dbl", "partner")
+
+    def fmx_inclusion(self, doublet_prior=0.5, want=FMX_INCLUSION_FIELDS):
+        """muxgl_fmx_inclusion: dict of arrays over the hypotheses of the last E-step (include/muxgl.h), for the handle's
+        own cells: incl float64 [C][K], the log evidence that cluster s is in the droplet (singlet s or either half of a
+        doublet); tot float64 [C], the log evidence of everything, so exp(incl - tot[:, None]) is the posterior of
+        inclusion; dbl float64 [C][K], the best doublet log-likelihood with s in it (-1e300: none); partner int32 [C][K],
+        the other cluster of that doublet (-1: none).  At any K, on every E-step path.  want: the subset of the four to
+        fetch (the others are passed as NULL)."""
+        unknown = set(want) - set(self.FMX_INCLUSION_FIELDS)
+        if unknown:
+            raise ValueError(f"unknown inclusion fields {sorted(unknown)}")
+        p = _FmxParams(float(doublet_prior), 0.0)  # (geno_error is not read by the call)
+        out = {}
+        for name in self.FMX_INCLUSION_FIELDS:
+            if name in want:
+                shape = (self.C,) if name == "tot" else (self.C, self.K)
+                out[name] = np.zeros(shape, dtype=np.int32 if name == "partner" else np.float64)
+        self._check(self.lib.muxgl_fmx_inclusion(self.h, C.byref(p), *[_ptr(out.get(n)) for n in self.FMX_INCLUSION_FIELDS]))
         return out
 
     # ---- freemuxlet-old: pairwise distance matrix and voting passes (cmd_cram_freemuxlet.cpp:176-343)
