@@ -6,28 +6,20 @@
 // Three steps per group of (cells x 64 x 64 blocks), a group's slab inside the streamed call's budget:
 //   * the sweep of the streamed call (demux_stream_sweep.hpp): slab[cell][block][n][k][j], the call's own per-entry
 //     likelihoods in front of it (demux_entry_pg_launch works at any V).
-//   * incl_fold_kernel, one workgroup per (cell, block of 64 samples B): it OWNS the state of these 64 samples and walks
-//     the group's blocks in order.  A block (X, Y) with X == B is reduced along k into the samples as j (lane = j, wave w
-//     takes 16 partners k, values read as they lie); one with Y == B is reduced along j into the samples as k (lane = k),
-//     read through a padded tile in LDS, which is the transpose.  A diagonal block feeds both roles, rows first.  The
-//     singlet term (j, 0, 0) enters with the row role of block (B, 0).
+//   * incl_fold_kernel, one workgroup per (cell, block of 64 samples B): it OWNS the state of these 64 samples and walks the
+//     group's blocks in order (incl_fold::owner).  A block (X, Y) with X == B is reduced along k into the samples as j
+//     (lane = j, wave w takes 16 partners k, values read as they lie); one with Y == B is reduced along j into the samples
+//     as k (lane = k), read through a padded tile in LDS, which is the transpose.  A diagonal block feeds both roles, rows
+//     first.  The singlet term (j, 0, 0) enters with the row role of block (B, 0).
 //     The issue of a workgroup per (cell, block) with a merge of its own was weighed against this: the owner reads a block
 //     of the slab twice (once per role), but needs no partials in memory and no third kernel, two workgroups never touch
-//     one state, and the merge order below holds by construction.  The sweep computes ~600 FP64 operations per slab
-//     value at 150 entries per cell, so the second read does not show.
+//     one state, and the merge order holds by construction.  The sweep computes ~600 FP64 operations per slab value at
+//     150 entries per cell, so the second read does not show.
 //   * incl_finish_kernel, lane = (cell, sample): M + log S, the best value and its decoded hypothesis.
 //
-// State per (cell, sample), 32 bytes: stream_fold::evidence (M, S) and (best value, scan position).  Scan position
-// (j V + k) A + n names partner, n and role.  `tot` has an evidence per (cell, row block X): every hypothesis is in
-// exactly one row role.
-//
-// Determinism: a thread pushes its hypotheses in a fixed order; a block's partial of a sample is the four waves' as
-// (0 + 1) + (2 + 3); a sample's partials are merged into its state one block at a time in stream_plan::block_list order
-// (rows before columns in a diagonal block); tot's partial of a block is a butterfly over the 64 lanes of that merged row
-// partial, merged per row block in the same order, and the row blocks ascending at the end.  A group only decides how
-// many blocks one launch folds and a batch which cells share the device, so all six outputs are bit-identical from call
-// to call and for any MUXGL_DEMUX_SLAB_MB.  The best hypothesis is taken under a total order (value descending, then scan
-// position ascending).
+// State and determinism: incl_fold.hpp.  The position is the scan position (j V + k) A + n, which names partner, n and
+// role; every hypothesis is in exactly one row role; a thread pushes the singlet first, then k ascending and n ascending
+// (rows), n ascending and j ascending (columns).  All six outputs are bit-identical for any MUXGL_DEMUX_SLAB_MB.
 //
 // Memory: [nnz][A][9] entry likelihoods, and within the budget (incl_plan.hpp) the slab plus state and outputs of a batch
 // of whole cells, finished and copied out before the next.  Nothing proportional to C x V^2.
@@ -35,39 +27,21 @@
 #include <vector>
 
 #include "demux_stream_sweep.hpp"
-#include "incl_plan.hpp"
-#include "stream_fold.hpp"
+#include "incl_fold.hpp"
 
 namespace {
 
 using namespace muxgl_call;
+using incl_fold::TILE_LD;
 using stream_fold::evidence;
 
-constexpr int TILE_LD = SBLK + 1;  // doubles per row of the transposing tile: lanes reading a column hit different banks
-
-struct incl_state {
-  evidence ev;
-  double bv;   // best LL over H_s (-1e300: none)
-  int32_t bp;  // its scan position (j V + k) A + n (-1: none)
-  int32_t pad;
-  static __device__ __forceinline__ incl_state empty() { return {{-__builtin_huge_val(), 0.0}, -1e300, -1, 0}; }
-  __device__ __forceinline__ void push(double v, double prior, int32_t pos) {
-    ev.push(v + prior);
-    if (key_before(v, pos, bv, bp)) bv = v, bp = pos;
-  }
-  static __device__ __forceinline__ incl_state merge(const incl_state& a, const incl_state& b) {  // a first
-    const bool ab = key_before(a.bv, a.bp, b.bv, b.bp);
-    return {evidence::merge(a.ev, b.ev), ab ? a.bv : b.bv, ab ? a.bp : b.bp, 0};
+struct incl_ops {
+  static constexpr int32_t none = -1;
+  static __device__ __forceinline__ bool before(double va, int32_t pa, double vb, int32_t pb) {
+    return key_before(va, pa, vb, pb);
   }
 };
-static_assert(sizeof(incl_state) == 32, "incl_plan::state_bytes_per_cell counts 32 bytes");
-
-__global__ void __launch_bounds__(256)
-    incl_init_kernel(int64_t n_state, int64_t n_tot, incl_state* __restrict__ st, evidence* __restrict__ totb) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n_state) st[i] = incl_state::empty();
-  if (i < n_tot) totb[i] = evidence{-__builtin_huge_val(), 0.0};
-}
+using incl_state = incl_fold::state<incl_ops>;
 
 // grid = (cells of the batch, sample blocks); slab of the group [cell of the batch][nb blocks][A][k][j]
 __global__ void __launch_bounds__(256)
@@ -75,43 +49,15 @@ __global__ void __launch_bounds__(256)
                      const int64_t* __restrict__ cell_ptr, int V, int nAlpha, call_alpha al, const double* __restrict__ slab,
                      incl_state* __restrict__ state, evidence* __restrict__ totb) {
   __shared__ double tile[SBLK * TILE_LD];
-  __shared__ incl_state parts[4][SBLK];
-  const int64_t ci = blockIdx.x;
-  const int B = blockIdx.y;
-  const bool no_entries = cell_ptr[c0 + ci] == cell_ptr[c0 + ci + 1];  // every LL is 0 (the sweep wrote nothing)
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int s = SBLK * B + lane;
-  const bool sl = s < V;
-  const bool owner = w == 0 && sl;
-
-  incl_state st = incl_state::empty();           // of sample s, in wave 0
-  evidence tot = {-__builtin_huge_val(), 0.0};   // of row block B, in thread 0
-  if (owner) st = state[ci * V + s];
-  if (threadIdx.x == 0) tot = totb[ci * nblk + B];
-
-  // the workgroup's partial of one block and role: the waves as (0 + 1) + (2 + 3), then into the state
-  auto reduce = [&](const incl_state& t, bool with_tot) {
-    parts[w][lane] = t;
-    __syncthreads();
-    if (w == 0) {
-      const incl_state r = incl_state::merge(incl_state::merge(parts[0][lane], parts[1][lane]),
-                                             incl_state::merge(parts[2][lane], parts[3][lane]));
-      st = incl_state::merge(st, r);
-      if (with_tot) {  // (lanes without a sample hold the empty evidence)
-        evidence e = r.ev;
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) e = evidence::merge(e, evidence{__shfl_xor(e.M, m, 64), __shfl_xor(e.S, m, 64)});
-        if (lane == 0) tot = evidence::merge(tot, e);
-      }
-    }
-    __syncthreads();
-  };
-
+  const bool no_entries = cell_ptr[c0 + blockIdx.x] == cell_ptr[c0 + blockIdx.x + 1];  // every LL is 0 (no sweep wrote)
+  incl_fold::owner<incl_ops> o(V, nblk, state, totb);
+  const int lane = o.lane, w = o.w, s = o.s, B = o.B;
+  const bool sl = o.sl;
   for (int z = 0; z < nb; ++z) {
     const int b = blocks[b0 + z];
     const int X = b / nblk, Y = b - X * nblk;
     if (X != B && Y != B) continue;  // (uniform over the workgroup)
-    const double* in = slab + ((size_t)ci * nb + z) * nAlpha * SLAB_DOUBLES;
+    const double* in = slab + ((size_t)o.ci * nb + z) * nAlpha * SLAB_DOUBLES;
     if (X == B) {  // s is j: along k
       incl_state t = incl_state::empty();
       if (sl) {
@@ -127,15 +73,13 @@ __global__ void __launch_bounds__(256)
           }
         }
       }
-      reduce(t, true);
+      o.reduce(t, true);
     }
     if (Y == B) {  // s is k: along j, through the tile
       incl_state t = incl_state::empty();
       for (int n = 1; n < nAlpha; ++n) {
         const bool sym = al.a[n] == 0.5;
-        for (int kq = 16 * w; kq < 16 * w + 16; ++kq)
-          tile[kq * TILE_LD + lane] = no_entries ? 0.0 : in[((size_t)n * SBLK + kq) * SBLK + lane];
-        __syncthreads();
+        incl_fold::tile_fill(tile, lane, w, in + (size_t)n * SLAB_DOUBLES, no_entries);
         if (sl) {
           for (int jq = 16 * w; jq < 16 * w + 16; ++jq) {
             const int j = SBLK * X + jq;
@@ -143,16 +87,15 @@ __global__ void __launch_bounds__(256)
             t.push(tile[lane * TILE_LD + jq], sym ? al.log_doublet_prior2 : al.log_doublet_prior1, (j * V + s) * nAlpha + n);
           }
         }
-        __syncthreads();
+        __syncthreads();  // (the next n's tile stores stay behind these reads)
       }
-      reduce(t, false);
+      o.reduce(t, false);
     }
   }
-  if (owner) state[ci * V + s] = st;
-  if (threadIdx.x == 0) totb[ci * nblk + B] = tot;
+  o.store(V, nblk, state, totb);
 }
 
-// lane = (cell of the batch, sample); the lane of sample 0 also joins the cell's row blocks into tot
+// lane = (cell of the batch, sample)
 __global__ void __launch_bounds__(256)
     incl_finish_kernel(int64_t n, int V, int nAlpha, int nblk, const incl_state* __restrict__ state,
                        const evidence* __restrict__ totb, double* __restrict__ incl, double* __restrict__ tot,
@@ -162,36 +105,25 @@ __global__ void __launch_bounds__(256)
   if (i >= n) return;
   const int64_t ci = i / V;
   const int s = (int)(i - ci * V);
-  const incl_state st = state[i];
-  incl[i] = st.ev.M + log(st.ev.S);
-  dbl[i] = st.bv;
+  const int32_t bp = incl_fold::finish_item(i, state, incl, dbl);
   int32_t pr = -1, ai = -1, fi = -1;
-  if (st.bp >= 0) {
-    const int32_t q = st.bp / nAlpha;
+  if (bp >= 0) {
+    const int32_t q = bp / nAlpha;
     const int32_t j = q / V, k = q - j * V;
-    ai = st.bp - q * nAlpha;
+    ai = bp - q * nAlpha;
     fi = j == s ? 1 : 0;
     pr = j == s ? k : j;
   }
   partner[i] = pr;
   alpha_idx[i] = ai;
   first[i] = fi;
-  if (s == 0) {
-    evidence e = totb[ci * nblk];
-    for (int X = 1; X < nblk; ++X) e = evidence::merge(e, totb[ci * nblk + X]);
-    tot[ci] = e.M + log(e.S);
-  }
-}
-
-template <class T>
-int copy_out(muxgl_handle* h, T* dst, const T* d_src, size_t n) {
-  if (dst && n) HIPCHK(h, hipMemcpyAsync(dst, d_src, sizeof(T) * n, hipMemcpyDeviceToHost, h->stream));
-  return 0;
+  incl_fold::finish_tot(ci, s, nblk, totb, tot);
 }
 
 }  // namespace
 
 int demux_inclusion_run(muxgl_handle* h, const muxgl_demux_params* p, const demux_incl_out& out) {
+  using incl_fold::copy_out;
   const int V = h->V, A = p->n_alpha;
   const int64_t C = h->C;
   if ((double)V * V * A >= 2147483648.0)
@@ -226,10 +158,10 @@ int demux_inclusion_run(muxgl_handle* h, const muxgl_demux_params* p, const demu
   for (int64_t c0 = 0; c0 < C; c0 += batch) {
     const int64_t nc = std::min(batch, C - c0);
     const int64_t n = nc * V;
-    hipLaunchKernelGGL(incl_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, nc * nblk, d_state.p,
-                       d_totb.p);
+    hipLaunchKernelGGL(incl_fold::init_kernel<incl_ops>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n,
+                       nc * nblk, d_state.p, d_totb.p);
     HIPCHK(h, hipGetLastError());
-    for (int64_t b0 = 0; b0 < nb_all; b0 += gb) {  // blocks in order (determinism, above)
+    for (int64_t b0 = 0; b0 < nb_all; b0 += gb) {  // blocks in order (determinism: incl_fold.hpp)
       const int32_t nb = (int32_t)std::min(gb, nb_all - b0);
       if (sweep_dispatch(h, c0, nc, (int32_t)b0, nb, d_blocks.p, nblk, d_pg.p, A, d_slab.p)) return 1;
       hipLaunchKernelGGL(incl_fold_kernel, dim3((unsigned)nc, (unsigned)nblk), dim3(256), 0, h->stream, c0, (int32_t)b0, nb,

@@ -8,8 +8,8 @@
 //   * the sweep of the streamed E-step (fmx_stream_sweep.hpp), unchanged in arithmetic and flags, over the cluster
 //     posteriors the last E-step read (d_cgp; fmx_sng_state says whether they still are those): slab[cell][block][slot][lane].
 //   * fmx_incl_fold_kernel, one workgroup per (cell, block of 64 clusters B): it OWNS the state of these 64 clusters and
-//     walks the group's blocks in order (incl_fold_kernel's owner design, demux_incl.hip).  What is read how follows from
-//     the slab's layout, which is not demuxlet's:
+//     walks the group's blocks in order (incl_fold::owner).  What is read how follows from the slab's layout, which is
+//     not demuxlet's:
 //       - an off-diagonal block (X, Y), X > Y, holds [slot k][lane j] = LL(64X + j, 64Y + k).  With X == B the clusters are
 //         the lanes (row role): lane j reads its own column of slots as it lies, wave w the slots 16w .. 16w + 15.  With
 //         Y == B the clusters are the slots (column role): the block goes through a padded tile in LDS, which is the
@@ -22,18 +22,10 @@
 //       - lanes and partners >= K are skipped exactly as block_hyps skips them.
 //   * fmx_incl_finish_kernel, lane = (cell, cluster): M + log S, the best value and its decoded partner.
 //
-// State per (cell, cluster), 32 bytes: stream_fold::evidence (M, S) and (best value, position p = hi(hi+1)/2 + lo of the
-// scans).  `tot` has an evidence per (cell, row block X): every hypothesis is counted once, where it is read in the row
-// role -- in an off-diagonal block that is the role of its higher cluster, in a diagonal block the lane that formed it.
-//
-// Determinism.  A thread pushes its hypotheses in a fixed order (slots / rotations ascending, the singlet last); a block's
-// partial of a cluster is the four waves' as (0 + 1) + (2 + 3); a cluster's partials are merged into its state one block
-// and role at a time, in stream_plan::block_list order, rows before columns in a diagonal block; tot's partial of a block
-// is the xor butterfly (partner 1, 2, .., 32) over the 64 lanes of that merged row partial, merged per row block in the
-// same order, and the row blocks ascending in the finish kernel.  A group only decides how many blocks one launch folds
-// and a batch which cells share the device, so all four outputs are bit-identical from call to call, for any
-// MUXGL_FMX_SLAB_MB, on a group and on slabbed ranks.  The best hypothesis is taken under a total order (value
-// descending, then position ascending: fmx_better), so it does not depend on any grouping at all.
+// State and determinism: incl_fold.hpp.  The position is p = hi(hi+1)/2 + lo of the scans; every hypothesis is counted
+// once in tot, where it is read in the row role -- in an off-diagonal block that is the role of its higher cluster, in a
+// diagonal block the lane that formed it; a thread pushes slots / rotations ascending, the singlet last.  All four
+// outputs are bit-identical for any MUXGL_FMX_SLAB_MB, on a group and on slabbed ranks.
 //
 // Memory: within the budget (incl_plan.hpp) the slab of a group plus state and outputs of a batch of whole cells, finished
 // and copied out before the next.  Nothing proportional to C x K^2.  The call reads state of the handle and writes none.
@@ -42,42 +34,20 @@
 
 #include "fmx_call_body.hpp"
 #include "fmx_stream_sweep.hpp"
-#include "incl_plan.hpp"
-#include "stream_fold.hpp"
+#include "incl_fold.hpp"
 
 namespace {
 
+using incl_fold::TILE_LD;
 using stream_fold::evidence;
 
-constexpr int32_t NO_POS = 0x7fffffff;
-// doubles per row of the transposing tile.  Lane l reads tile[l TILE_LD + q] (ds_read_b64: bank = dword address mod 64 =
-// 2 l + 2 q mod 64 at TILE_LD = 65, per half wave of 32 lanes): 32 lanes on 32 distinct bank pairs, no conflict.
-constexpr int TILE_LD = CB + 1;
-
-struct fincl_state {
-  evidence ev;
-  double bv;   // best LL over H_s (-1e300: none)
-  int32_t bp;  // its position p = hi(hi+1)/2 + lo (NO_POS: none)
-  int32_t pad;
-  static __device__ __forceinline__ fincl_state empty() { return {{-__builtin_huge_val(), 0.0}, -1e300, NO_POS, 0}; }
-  // (a value of -inf adds nothing to the sum and is never better than the empty -1e300)
-  __device__ __forceinline__ void push(double v, double prior, int32_t pos) {
-    ev.push(v + prior);
-    if (fmx_better(v, pos, bv, bp)) bv = v, bp = pos;
-  }
-  static __device__ __forceinline__ fincl_state merge(const fincl_state& a, const fincl_state& b) {  // a first
-    const bool ab = fmx_better(a.bv, a.bp, b.bv, b.bp);
-    return {evidence::merge(a.ev, b.ev), ab ? a.bv : b.bv, ab ? a.bp : b.bp, 0};
+struct fincl_ops {
+  static constexpr int32_t none = 0x7fffffff;
+  static __device__ __forceinline__ bool before(double va, int32_t pa, double vb, int32_t pb) {
+    return fmx_better(va, pa, vb, pb);
   }
 };
-static_assert(sizeof(fincl_state) == 32, "incl_plan::fmx_state_bytes_per_cell counts 32 bytes");
-
-__global__ void __launch_bounds__(256)
-    fmx_incl_init_kernel(int64_t n_state, int64_t n_tot, fincl_state* __restrict__ st, evidence* __restrict__ totb) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n_state) st[i] = fincl_state::empty();
-  if (i < n_tot) totb[i] = evidence{-__builtin_huge_val(), 0.0};
-}
+using fincl_state = incl_fold::state<fincl_ops>;
 
 // grid = (cells of the batch, cluster blocks); slab of the group [cell of the batch][nb blocks][slot][lane]
 __global__ void __launch_bounds__(256)
@@ -85,42 +55,14 @@ __global__ void __launch_bounds__(256)
                          double log_double_prior, const double* __restrict__ slab, fincl_state* __restrict__ state,
                          evidence* __restrict__ totb) {
   __shared__ double tile[CB * TILE_LD];
-  __shared__ fincl_state parts[4][CB];
-  const int64_t ci = blockIdx.x;
-  const int B = blockIdx.y;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int s = CB * B + lane;
-  const bool sl = s < K;
-  const bool owner = w == 0 && sl;
-
-  fincl_state st = fincl_state::empty();        // of cluster s, in wave 0
-  evidence tot = {-__builtin_huge_val(), 0.0};  // of row block B, in thread 0
-  if (owner) st = state[ci * K + s];
-  if (threadIdx.x == 0) tot = totb[ci * nblk + B];
-
-  // the workgroup's partial of one block and role: the waves as (0 + 1) + (2 + 3), then into the state
-  auto reduce = [&](const fincl_state& t, bool with_tot) {
-    parts[w][lane] = t;
-    __syncthreads();
-    if (w == 0) {
-      const fincl_state r = fincl_state::merge(fincl_state::merge(parts[0][lane], parts[1][lane]),
-                                               fincl_state::merge(parts[2][lane], parts[3][lane]));
-      st = fincl_state::merge(st, r);
-      if (with_tot) {  // (lanes without a cluster hold the empty evidence)
-        evidence e = r.ev;
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) e = evidence::merge(e, evidence{__shfl_xor(e.M, m, 64), __shfl_xor(e.S, m, 64)});
-        if (lane == 0) tot = evidence::merge(tot, e);
-      }
-    }
-    __syncthreads();
-  };
-
+  incl_fold::owner<fincl_ops> o(K, nblk, state, totb);
+  const int lane = o.lane, w = o.w, s = o.s, B = o.B;
+  const bool sl = o.sl;
   for (int z = 0; z < nb; ++z) {
     const int bz = blocks[b0 + z];
     const int X = bz >> 16, Y = bz & 0xffff;
     if (X != B && Y != B) continue;  // (uniform over the workgroup)
-    const double* in = slab + ((size_t)ci * nb + z) * SLAB;
+    const double* in = slab + ((size_t)o.ci * nb + z) * SLAB;
     if (X == B) {  // row role: the lane's own values, as block_hyps walks them
       fincl_state t = fincl_state::empty();
       block_hyps(X, Y, w, lane, K, in, [&](int p, double v, bool singlet) {
@@ -129,7 +71,7 @@ __global__ void __launch_bounds__(256)
         else
           t.push(v, log_double_prior, p);
       });
-      reduce(t, true);
+      o.reduce(t, true);
     }
     if (Y == B && X == B) {  // column role of a diagonal block: the pair the lane (s + t) & 63 formed with s
       fincl_state t = fincl_state::empty();
@@ -141,11 +83,10 @@ __global__ void __launch_bounds__(256)
           t.push(in[(r - 1) * CB + jj], log_double_prior, hi * (hi + 1) / 2 + lo);
         }
       }
-      reduce(t, false);
+      o.reduce(t, false);
     } else if (Y == B) {  // column role of an off-diagonal block: s is the slot, through the tile
       fincl_state t = fincl_state::empty();
-      for (int kq = 16 * w; kq < 16 * w + 16; ++kq) tile[kq * TILE_LD + lane] = in[kq * CB + lane];
-      __syncthreads();
+      incl_fold::tile_fill(tile, lane, w, in, false);
       if (sl) {
         for (int jq = 16 * w; jq < 16 * w + 16; ++jq) {
           const int sj = CB * X + jq;
@@ -153,11 +94,10 @@ __global__ void __launch_bounds__(256)
           t.push(tile[lane * TILE_LD + jq], log_double_prior, sj * (sj + 1) / 2 + s);
         }
       }
-      reduce(t, false);  // (its barriers also keep the next block's tile stores behind these reads)
+      o.reduce(t, false);  // (its barriers also keep the next block's tile stores behind these reads)
     }
   }
-  if (owner) state[ci * K + s] = st;
-  if (threadIdx.x == 0) totb[ci * nblk + B] = tot;
+  o.store(K, nblk, state, totb);
 }
 
 __device__ __forceinline__ int row_of(int p) {
@@ -167,8 +107,7 @@ __device__ __forceinline__ int row_of(int p) {
   return r;
 }
 
-// lane = (cell of the batch, cluster); the lane of cluster 0 also joins the cell's row blocks into tot.  A sum without a
-// finite term is -inf
+// lane = (cell of the batch, cluster)
 __global__ void __launch_bounds__(256)
     fmx_incl_finish_kernel(int64_t n, int K, int nblk, const fincl_state* __restrict__ state,
                            const evidence* __restrict__ totb, double* __restrict__ incl, double* __restrict__ tot,
@@ -177,29 +116,18 @@ __global__ void __launch_bounds__(256)
   if (i >= n) return;
   const int64_t ci = i / K;
   const int s = (int)(i - ci * K);
-  const fincl_state st = state[i];
-  incl[i] = st.ev.S > 0.0 ? st.ev.M + log(st.ev.S) : -__builtin_huge_val();
-  dbl[i] = st.bv;
+  const int32_t bp = incl_fold::finish_item(i, state, incl, dbl);
   int32_t pr = -1;
-  if (st.bp != NO_POS) {
-    const int hi = row_of(st.bp), lo = st.bp - hi * (hi + 1) / 2;
+  if (bp != fincl_ops::none) {
+    const int hi = row_of(bp), lo = bp - hi * (hi + 1) / 2;
     pr = hi == s ? lo : hi;
   }
   partner[i] = pr;
-  if (s == 0) {
-    evidence e = totb[ci * nblk];
-    for (int X = 1; X < nblk; ++X) e = evidence::merge(e, totb[ci * nblk + X]);
-    tot[ci] = e.S > 0.0 ? e.M + log(e.S) : -__builtin_huge_val();
-  }
-}
-
-template <class T>
-int copy_out(muxgl_handle* h, T* dst, const T* d_src, size_t n) {
-  if (dst && n) HIPCHK(h, hipMemcpyAsync(dst, d_src, sizeof(T) * n, hipMemcpyDeviceToHost, h->stream));
-  return 0;
+  incl_fold::finish_tot(ci, s, nblk, totb, tot);
 }
 
 int fmx_inclusion_run(muxgl_handle* h, const muxgl_fmx_params* p, double* incl, double* tot, double* dbl, int32_t* partner) {
+  using incl_fold::copy_out;
   const int K = h->K;
   const int64_t C = h->C;
   const int nblk = (K + CB - 1) / CB;
@@ -228,10 +156,10 @@ int fmx_inclusion_run(muxgl_handle* h, const muxgl_fmx_params* p, double* incl, 
   for (int64_t c0 = 0; c0 < C; c0 += batch) {
     const int64_t nc = std::min(batch, C - c0);
     const int64_t n = nc * K;
-    hipLaunchKernelGGL(fmx_incl_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, nc * nblk,
+    hipLaunchKernelGGL(incl_fold::init_kernel<fincl_ops>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, nc * nblk,
                        d_state.p, d_totb.p);
     HIPCHK(h, hipGetLastError());
-    for (int64_t b0 = 0; b0 < nb_all; b0 += gb) {  // blocks in order (determinism, above)
+    for (int64_t b0 = 0; b0 < nb_all; b0 += gb) {  // blocks in order (determinism: incl_fold.hpp)
       const int32_t nb = (int32_t)std::min(gb, nb_all - b0);
       if (sweep_launch(h, c0, nullptr, nc, (int32_t)b0, nb, d_blocks.p, d_slab.p)) return 1;
       hipLaunchKernelGGL(fmx_incl_fold_kernel, dim3((unsigned)nc, (unsigned)nblk), dim3(256), 0, h->stream, (int32_t)b0, nb,

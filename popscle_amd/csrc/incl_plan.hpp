@@ -9,12 +9,12 @@
 
 namespace incl_plan {
 
-// bytes the call holds per cell of a batch besides the slab: the state (32 B per sample: evidence, best value, scan
-// position), the six outputs the finish kernel writes (8 + 8 + 4 + 4 + 4 B per sample, 8 B per cell) and the evidence of
-// `tot` per 64-sample row block (16 B)
-inline size_t state_bytes_per_cell(int V) {
-  const size_t nblk = ((size_t)V + 63) / 64;
-  return (size_t)V * (32 + 28) + nblk * 16 + 8;
+// bytes the call holds per cell of a batch of n items (samples, clusters) besides the slab: the state (32 B per item:
+// evidence, best value, position), the outputs the finish kernel writes (out_bytes_per_item: demuxlet 8 + 8 + 4 + 4 + 4 =
+// 28, freemuxlet 8 + 8 + 4 = 20; and 8 B per cell) and the evidence of `tot` per 64-item row block (16 B)
+inline size_t state_bytes_per_cell(int n, size_t out_bytes_per_item) {
+  const size_t nblk = ((size_t)n + 63) / 64;
+  return (size_t)n * (32 + out_bytes_per_item) + nblk * 16 + 8;
 }
 
 // A batch of whole cells keeps its state on the device while its (cells x blocks) are swept in groups
@@ -35,33 +35,26 @@ inline batches cut_batches(int64_t cells, int64_t blocks, size_t state_per_cell,
   return {true, g.gc, g.gb};  // (g.gc == batch: one block of every cell of the batch fits what the state leaves)
 }
 
-// what the caller reports when cut_batches says no
+// what `call` reports when cut_batches says no: n items, named `letter` (V samples, K clusters), budget variable `env`
+inline std::string too_small_message(const char* call, char letter, int n, size_t state_per_cell, size_t slab_per_cell_block,
+                                     size_t budget, const char* env) {
+  char buf[320];
+  snprintf(buf, sizeof(buf),
+           "%s: the state of one cell (%zu bytes at %c=%d) and one block of the sweep (%zu bytes) exceed the slab budget of "
+           "%zu bytes: raise %s",
+           call, state_per_cell, letter, n, slab_per_cell_block, budget, env);
+  return buf;
+}
+
+// the two calls' bindings of these, which the units and the probes under tests/csrc both use
+inline size_t state_bytes_per_cell(int V) { return state_bytes_per_cell(V, 28); }
+inline size_t fmx_state_bytes_per_cell(int K) { return state_bytes_per_cell(K, 20); }
 inline std::string too_small_message(int V, size_t state_per_cell, size_t slab_per_cell_block, size_t budget) {
-  char buf[320];
-  snprintf(buf, sizeof(buf),
-           "muxgl_demux_inclusion: the state of one cell (%zu bytes at V=%d) and one block of the sweep (%zu bytes) exceed "
-           "the slab budget of %zu bytes: raise MUXGL_DEMUX_SLAB_MB",
-           state_per_cell, V, slab_per_cell_block, budget);
-  return buf;
+  return too_small_message("muxgl_demux_inclusion", 'V', V, state_per_cell, slab_per_cell_block, budget,
+                           "MUXGL_DEMUX_SLAB_MB");
 }
-
-// ---- muxgl_fmx_inclusion (fmx_incl.hip): the same cut (cut_batches) over the streamed E-step's budget ---------------------
-
-// bytes the call holds per cell of a batch besides the slab: the state (32 B per cluster: evidence, best value, position),
-// the four outputs the finish kernel writes (8 + 8 + 4 B per cluster, 8 B per cell) and the evidence of `tot` per
-// 64-cluster row block (16 B)
-inline size_t fmx_state_bytes_per_cell(int K) {
-  const size_t nblk = ((size_t)K + 63) / 64;
-  return (size_t)K * (32 + 20) + nblk * 16 + 8;
-}
-
 inline std::string fmx_too_small_message(int K, size_t state_per_cell, size_t slab_per_cell_block, size_t budget) {
-  char buf[320];
-  snprintf(buf, sizeof(buf),
-           "muxgl_fmx_inclusion: the state of one cell (%zu bytes at K=%d) and one block of the sweep (%zu bytes) exceed "
-           "the slab budget of %zu bytes: raise MUXGL_FMX_SLAB_MB",
-           state_per_cell, K, slab_per_cell_block, budget);
-  return buf;
+  return too_small_message("muxgl_fmx_inclusion", 'K', K, state_per_cell, slab_per_cell_block, budget, "MUXGL_FMX_SLAB_MB");
 }
 
 }  // namespace incl_plan
