@@ -441,6 +441,40 @@ int muxgl_fmx_exact_finish(muxgl_handle* h, const muxgl_fmx_params* p, const int
 /* cluster pileups for the .clust1.vcf.gz writer (cmd_cram_freemux2.cpp:608-658): gls[K][S][9], counts[K][S][3] */
 int muxgl_fmx_get_cluster_pileup(muxgl_handle* h, double* gls, int32_t* counts);
 
+/* Which cluster is which donor: the cluster pileups scored against the donors' genotypes, demuxlet's singlet likelihood
+ * (cmd_cram_demuxlet.cpp:733-747) with a cluster in the place of a droplet.  With gls[K][S][9], counts[K][S][3]
+ * exactly as muxgl_fmx_get_cluster_pileup returns them at the moment of the call, gp[S][V][3] / has_gp[S] of
+ * muxgl_demux_set_gp and af[S] of muxgl_fmx_prepare:
+ *   U(k)      = { s : has_gp[s] != 0 and counts[k][s][0] > 0 }
+ *   L_g       = gls[k][s][4 g], g = 0, 1, 2   (the diagonal, as the E-step reads it, cmd_cram_freemux2.cpp:402-404)
+ *   ll[K][V]  = sum over s in U(k) of log(L_0 gp[s][v][0] + L_1 gp[s][v][1] + L_2 gp[s][v][2])
+ *   ll0[K]    = sum over s in U(k) of log(L_0 (1-af)(1-af) + L_1 2 af (1-af) + L_2 af af)   (gp0s of :388-390: an unrelated
+ *               individual), so ll[k][v] - ll0[k] is the log Bayes factor "cluster k is donor v" against "somebody from
+ *               the population": positive for a match
+ *   nsnps[K]  = |U(k)|
+ * A cluster without cells has U = {}: ll = ll0 = 0, nsnps = 0.  A factor that is exactly 0 makes that score -inf, never
+ * NaN.  Membership in U is decided by has_gp and the read count, never by the content of a gp row (the device copy holds
+ * (1,0,0) in the rows of markers without genotypes).  Any output may be NULL (all three: the call succeeds and writes
+ * nothing).  kernel_ms (NULL allowed) receives the hipEvent time of the call's kernels, from a pair of events the call
+ * creates and destroys itself: no slot of muxgl_get_timing / muxgl_get_timing_sum is touched and the call is not a
+ * collecting one.
+ * It needs muxgl_set_pileup, muxgl_fmx_prepare, muxgl_fmx_set_clusters (from then on the pileups exist) and
+ * muxgl_demux_set_gp (after the muxgl_set_pileup in force) on the same handle, and scores the pileups as they are now:
+ * after muxgl_fmx_set_clusters the initial ones, after muxgl_fmx_iterate what .clust1.vcf.gz prints.  1 <= K <=
+ * MUXGL_MAX_CLUSTERS, 1 <= V <= MUXGL_MAX_SAMPLES.  One device, whole pileup: it fails, naming the reason and leaving the
+ * handle usable, on a device group, a slabbed handle and a handle whose muxgl_fmx_set_shard range is not everything (their
+ * cluster pileups are cut by SNP range, and ranges summed in rank order would round differently), for a NULL handle and
+ * when one of the four prerequisites is missing.
+ * It reads state and changes none: records, counters, assignments, cluster pileups, MUXGL_BUF_CGP, the near-tie
+ * bookkeeping and whether muxgl_fmx_singlets / muxgl_fmx_inclusion may run stay bit for bit what they were.  Under
+ * MUXGL_FLAG_ASYNC_PHASES it returns with the stream drained.
+ * The values are the device's arithmetic (products of factors, one log per cluster, donor and part of 2048 consecutive
+ * SNPs, the parts added in ascending SNP order: equal to the sums of logs to ~1e-11).  Device memory beyond the inputs is
+ * per cluster of a batch: those logs, the read counts of its S markers and its results; batches of clusters are sized to
+ * the streamed E-step's budget (4 GiB or a third of the device, MUXGL_FMX_SLAB_MB) and each is copied out before the next;
+ * nothing proportional to K x S x V.  All three outputs are bit-identical from call to call and for any budget. */
+int muxgl_fmx_match_donors(muxgl_handle* h, double* ll /*[K][V]*/, double* ll0 /*[K]*/, int32_t* nsnps /*[K]*/, float* kernel_ms);
+
 /* ---- freemuxlet-old (`popscle freemuxlet-old`, cmd_cram_freemuxlet.cpp): the parts that differ from freemux2.  The
  *      entry pileups, scores and the EM loop are the calls above (geno_error = 0 except in the tenth and last
  *      iteration, no early stop: cmd_cram_freemuxlet.cpp:457,485,500); what is particular to the old command is its

@@ -292,3 +292,43 @@ def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early
                 incl[n][b:e] = np.frombuffer(raw, dtype=incl[n].dtype).reshape((e - b,) + incl[n].shape[1:])
         res.append(incl)
     return tuple(res)
+
+
+def match_table(ll, ll0, nsnps=None):
+    """Best donors of the clusters from Engine.fmx_match_donors' tables (pure numpy).  ll [K][V], ll0 [K]; llr = ll -
+    ll0[:, None] is the log Bayes factor "cluster k is donor v" against "somebody from the population".  Returns a dict,
+    per cluster: best, next int32 (the donors with the largest and second largest llr; ties go to the lower donor index;
+    next = -1 with a single donor), best_llr, next_llr float64 (NaN where there is none), post float64 [K][V] (softmax of
+    ll over the donors with equal priors, the row maximum subtracted) and reciprocal bool (cluster k is also the best
+    cluster, lowest index on ties, of its best donor).  A cluster with nsnps == 0 (given nsnps; else: a row of ll and ll0
+    that is all zero) has no evidence: best = next = -1, not reciprocal, and is nobody's best cluster."""
+    ll = np.asarray(ll, dtype=np.float64)
+    ll0 = np.asarray(ll0, dtype=np.float64)
+    if ll.ndim != 2 or ll0.shape != ll.shape[:1]:
+        raise ValueError("ll must be [K][V] and ll0 [K]")
+    K, V = ll.shape
+    empty = (np.asarray(nsnps) == 0) if nsnps is not None else (np.all(ll == 0.0, axis=1) & (ll0 == 0.0))
+    with np.errstate(invalid="ignore"):
+        llr = ll - ll0[:, None]
+    llr = np.where(np.isnan(llr), -np.inf, llr)  # (-inf - -inf: no evidence for that donor either)
+    best = np.full(K, -1, dtype=np.int32)
+    nxt = np.full(K, -1, dtype=np.int32)
+    best_llr = np.full(K, np.nan)
+    next_llr = np.full(K, np.nan)
+    for k in range(K):
+        if empty[k] or V == 0:
+            continue
+        order = np.argsort(-llr[k], kind="stable")  # descending, ties by ascending donor index
+        best[k], best_llr[k] = order[0], llr[k, order[0]]
+        if V > 1:
+            nxt[k], next_llr[k] = order[1], llr[k, order[1]]
+    with np.errstate(invalid="ignore", over="ignore"):
+        mx = ll.max(axis=1, keepdims=True) if V else np.zeros((K, 1))
+        ex = np.exp(np.where(np.isneginf(mx), 0.0, ll - mx))
+        post = ex / ex.sum(axis=1, keepdims=True) if V else ex
+    best_clust = np.full(V, -1, dtype=np.int64)  # per donor: the cluster with the largest llr among those with evidence
+    live = np.flatnonzero(~empty)
+    if live.size and V:
+        best_clust = live[np.argmax(llr[live], axis=0)]  # (argmax: first = lowest cluster index on ties)
+    reciprocal = np.array([best[k] >= 0 and best_clust[best[k]] == k for k in range(K)], dtype=bool)
+    return dict(best=best, next=nxt, best_llr=best_llr, next_llr=next_llr, post=post, reciprocal=reciprocal)

@@ -26,6 +26,15 @@
 //       doublet, cmd_cram_freemux2.cpp:469-513).  Columns BARCODE, CLUST, NUM.SNPS, NUM.READS, LLK.INCL (%.4lf),
 //       POSTPRB.INCL (%.3lg, exp(incl - tot)), DBL.PARTNER (cluster), DBL.LLK (%.4lf); the last two are NA where no
 //       doublet hypothesis holds the cluster (one cluster)
+//       --match-vcf FILE: which cluster is which donor.  FILE holds genotypes of some or all pooled donors; it is read with
+//       demuxlet's genotype flags and their meanings (--field, --sm, --sm-list, --geno-error-offset, --geno-error-coeff,
+//       --r2-info, --min-mac, --min-callrate; known to freemuxlet only next to --match-vcf) by the demuxlet loader, and after
+//       the EM the final cluster pileups are scored against the donors on the device (muxgl_fmx_match_donors).  Writes
+//       <O>.clust1.match.gz (BGZF), one row per cluster and donor: CLUST, SM_ID, NUM.SNPS (markers the cluster has reads at
+//       and the donors have genotypes at), LLK, LLK0 (an unrelated individual at the allele frequencies), LLR = LLK - LLK0
+//       (%.4lf), POSTPRB (%.3lg, equal priors over the donors); and <O>.clust1.match.best.gz, one row per cluster: CLUST,
+//       NUM.SNPS, BEST.SM_ID, BEST.LLR, NEXT.SM_ID, NEXT.LLR, DIFF.LLR, RECIPROCAL (1: the cluster is also the best
+//       cluster of its best donor), NA where there is none.  One device only: refused with --devices naming several
 //   popscle-amd freemuxlet-old --plp P --nsample K --out O [...]               mirrors cmdCramFreemuxlet (cmd_cram_freemuxlet.cpp)
 //   popscle-amd dump-plp   --plp P [--vcf V --field F] --out FILE              loader only: packed pileup to a binary file
 //   popscle-amd synth-plp  --cells C --snps S --samples V --out P              a synthetic data set in the real file formats
@@ -450,8 +459,24 @@ int cmd_freemuxlet(int argc, char** argv) {
   bool auxFiles = false, keepInitMissing = false, randomizeSingletScore = false, noEarlyStop = false;
   bool writeSinglets = false;  // (ours) <out>.clust1.sing2.gz: every droplet against every cluster
   bool writeInclusion = false;  // (ours) <out>.clust1.incl.gz: per-cluster marginals of the last E-step's pair triangle
+  VcfReader vr;  // (ours) --match-vcf: genotypes of pooled donors the final clusters are scored against
+  std::vector<std::string> smIDs;
+  std::string smList;
   Args a;
   cf.add(a);
+  a.add_string("match-vcf", &vr.path);
+  bool wantMatch = false;
+  for (int i = 0; i < argc; ++i) wantMatch = wantMatch || !strcmp(argv[i], "--match-vcf");
+  if (wantMatch) {  // demuxlet's genotype flags, with their meanings; unknown to freemuxlet otherwise, as in the reference
+    a.add_string("field", &cf.lo.field);
+    a.add_double("geno-error-offset", &cf.lo.genoErrorOffset);
+    a.add_double("geno-error-coeff", &cf.lo.genoErrorCoeffR2);
+    a.add_string("r2-info", &cf.lo.r2info);
+    a.add_int("min-mac", &vr.vfilt.minMAC);
+    a.add_double("min-callrate", &vr.vfilt.minCallRate);
+    a.add_multi_string("sm", &smIDs);
+    a.add_string("sm-list", &smList);
+  }
   a.add_string("init-cluster", &initClusterFile);
   a.add_int("nsample", &nSamples);
   a.add_bool("aux-files", &auxFiles);
@@ -473,10 +498,24 @@ int cmd_freemuxlet(int argc, char** argv) {
   if (nSamples < 0 || nSamples > MUXGL_MAX_CLUSTERS)
     fatal("freemuxlet: --nsample %d outside [1, %d], the clusters the library supports (MUXGL_MAX_CLUSTERS)", nSamples,
           MUXGL_MAX_CLUSTERS);
+  if (wantMatch && vr.path.empty()) fatal("freemuxlet: --match-vcf needs a file name");
+  if (wantMatch && cf.grouped())
+    fatal("freemuxlet: --match-vcf is not available with --devices naming more than one device: a group's cluster pileups "
+          "are cut by SNP range (muxgl_fmx_match_donors scores the whole pileup on one device); run it on one device");
 
   Pileup p;
   StageTimer tmr;
-  load_from_plp(cf.plpPrefix, cf.lo, nullptr, p);
+  if (wantMatch) {  // the demuxlet loader: its merge-join with the markers and its GP construction (the pileup is the same)
+    vr.wanted = smIDs;
+    if (!smList.empty()) {
+      TsvReader t(smList);
+      while (t.read_line() > 0) vr.wanted.push_back(t.str_field_at(0));
+    }
+    vr.init();
+    load_from_plp(cf.plpPrefix, cf.lo, &vr, p);
+  } else {
+    load_from_plp(cf.plpPrefix, cf.lo, nullptr, p);
+  }
   tmr.lap("freemuxlet: load");
   const int64_t C = p.C(), S = p.S();
   const int K = nSamples;
@@ -692,6 +731,65 @@ int cmd_freemuxlet(int argc, char** argv) {
     });
     wi.close();
     tmr.lap("freemuxlet: write .clust1.incl.gz");
+  }
+  if (wantMatch) {
+    // .clust1.match.gz / .clust1.match.best.gz: the final cluster pileups (what .clust1.vcf.gz printed) against the donors
+    const size_t V = (size_t)p.nv, Kz = (size_t)K;
+    check(h, muxgl_demux_set_gp(h, p.nv, p.gp.data(), p.has_gp.data()), "muxgl_demux_set_gp");
+    std::vector<double> mll(Kz * V), mll0(Kz);
+    std::vector<int32_t> mns(Kz);
+    float kms = 0.f;
+    check(h, muxgl_fmx_match_donors(h, mll.data(), mll0.data(), mns.data(), &kms), "muxgl_fmx_match_donors");
+    tmr.lap("freemuxlet: muxgl_demux_set_gp + muxgl_fmx_match_donors");
+    auto llr = [&](size_t k, size_t v) {
+      const double d = mll[k * V + v] - mll0[k];
+      return std::isnan(d) ? -INFINITY : d;  // (-inf against -inf: no evidence for that donor either)
+    };
+    // best and next donor of every cluster (ties: lower donor index), best cluster of every donor (ties: lower cluster)
+    std::vector<int> best(Kz, -1), next(Kz, -1), bestClust(V, -1);
+    for (size_t k = 0; k < Kz; ++k) {
+      if (mns[k] == 0) continue;
+      for (size_t v = 0; v < V; ++v) {
+        if (best[k] < 0 || llr(k, v) > llr(k, (size_t)best[k])) {
+          next[k] = best[k];
+          best[k] = (int)v;
+        } else if (next[k] < 0 || llr(k, v) > llr(k, (size_t)next[k])) {
+          next[k] = (int)v;
+        }
+      }
+      for (size_t v = 0; v < V; ++v)
+        if (bestClust[v] < 0 || llr(k, v) > llr((size_t)bestClust[v], v)) bestClust[v] = (int)k;
+    }
+    OutFile wm(cf.outPrefix + ".clust1.match.gz", true);
+    wm.printf("CLUST\tSM_ID\tNUM.SNPS\tLLK\tLLK0\tLLR\tPOSTPRB\n");
+    for (size_t k = 0; k < Kz; ++k) {
+      const double* row = mll.data() + k * V;
+      double mx = row[0], sum = 0.0;
+      for (size_t v = 1; v < V; ++v) mx = std::max(mx, row[v]);
+      if (std::isinf(mx)) mx = 0.0;  // (every donor at -inf)
+      for (size_t v = 0; v < V; ++v) sum += exp(row[v] - mx);
+      for (size_t v = 0; v < V; ++v)
+        wm.printf("%d\t%s\t%d\t%.4lf\t%.4lf\t%.4lf\t%.3lg\n", (int)k, sid(p, (int)v), mns[k], row[v], mll0[k], llr(k, v),
+                  sum > 0.0 ? exp(row[v] - mx) / sum : 1.0 / (double)V);
+    }
+    wm.close();
+    OutFile wb(cf.outPrefix + ".clust1.match.best.gz", true);
+    wb.printf("CLUST\tNUM.SNPS\tBEST.SM_ID\tBEST.LLR\tNEXT.SM_ID\tNEXT.LLR\tDIFF.LLR\tRECIPROCAL\n");
+    for (size_t k = 0; k < Kz; ++k) {
+      wb.printf("%d\t%d\t", (int)k, mns[k]);
+      if (best[k] < 0) {
+        wb.printf("NA\tNA\tNA\tNA\tNA\tNA\n");
+        continue;
+      }
+      wb.printf("%s\t%.4lf\t", sid(p, best[k]), llr(k, (size_t)best[k]));
+      if (next[k] < 0) wb.printf("NA\tNA\tNA\t");
+      else
+        wb.printf("%s\t%.4lf\t%.4lf\t", sid(p, next[k]), llr(k, (size_t)next[k]),
+                  llr(k, (size_t)best[k]) - llr(k, (size_t)next[k]));
+      wb.printf("%d\n", bestClust[(size_t)best[k]] == (int)k ? 1 : 0);
+    }
+    wb.close();
+    tmr.lap("freemuxlet: write .clust1.match.gz + .clust1.match.best.gz");
   }
   muxgl_destroy(h);
   return 0;
@@ -1104,6 +1202,8 @@ int main(int argc, char** argv) {
                     "    POSTPRB.INCL DBL.PARTNER DBL.ALPHA DBL.LLK)\n"
                     "  freemuxlet --write-singlets: also <out>.clust1.sing2.gz, the singlet log-likelihood of every droplet\n"
                     "    against every cluster in the last iteration (BARCODE CLUST NUM.SNPS NUM.READS LLK1 POSTPRB)\n"
+                    "  freemuxlet --match-vcf FILE [demuxlet's genotype flags]: also <out>.clust1.match.gz and .clust1.match.best.gz,\n"
+                    "      the final clusters scored against the donors' genotypes in FILE (one device)\n"
                     "  freemuxlet --write-inclusion: also <out>.clust1.incl.gz, per droplet and cluster the evidence that the\n"
                     "    cluster is in the droplet and the cluster it pairs best with, in the last iteration (BARCODE CLUST\n"
                     "    NUM.SNPS NUM.READS LLK.INCL POSTPRB.INCL DBL.PARTNER DBL.LLK)\n");

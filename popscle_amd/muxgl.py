@@ -109,6 +109,7 @@ SYMBOLS = {
     "muxgl_fmx_singlets": (C.c_int, [_VP, _VP]),
     "muxgl_fmx_inclusion": (C.c_int, [_VP, C.POINTER(_FmxParams), _VP, _VP, _VP, _VP]),
     "muxgl_fmx_get_cluster_pileup": (C.c_int, [_VP, _VP, _VP]),
+    "muxgl_fmx_match_donors": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
     "muxgl_fmx_exact_stats": (C.c_int, [_VP, _VP, _VP, _VP]),
     "muxgl_fmx_exact_pending": (C.c_int, [_VP, _VP]),
     "muxgl_fmx_exact_hint": (C.c_int, [_VP, C.c_int32]),
@@ -581,6 +582,30 @@ class Engine:
         cnt = np.zeros((self.K, self.S, 3), dtype=np.int32)
         self._check(self.lib.muxgl_fmx_get_cluster_pileup(self.h, _ptr(gls), _ptr(cnt)))
         return gls, cnt
+
+    FMX_MATCH_FIELDS = ("ll", "ll0", "nsnps")
+
+    def fmx_match_donors(self, want=FMX_MATCH_FIELDS):
+        """muxgl_fmx_match_donors: the cluster pileups as they are now scored against the donors of demux_set_gp
+        (include/muxgl.h).  dict of ll float64 [K][V], the log-likelihood of cluster k being donor v over the markers the
+        cluster has reads at and the donors have genotypes at; ll0 float64 [K], the same for an unrelated individual at
+        the allele frequencies (ll - ll0[:, None] is the log Bayes factor of a match); nsnps int32 [K], those markers'
+        number; and kernel_ms, the event time of the call's kernels.  want: the subset of the three to fetch (the others
+        are passed as NULL).  freemuxlet.match_table() turns ll and ll0 into best donors."""
+        unknown = set(want) - set(self.FMX_MATCH_FIELDS)
+        if unknown:
+            raise ValueError(f"unknown match fields {sorted(unknown)}")
+        out = {}
+        if "ll" in want:
+            out["ll"] = np.zeros((self.K, self.V), dtype=np.float64)
+        if "ll0" in want:
+            out["ll0"] = np.zeros(self.K, dtype=np.float64)
+        if "nsnps" in want:
+            out["nsnps"] = np.zeros(self.K, dtype=np.int32)
+        ms = C.c_float(0.0)
+        self._check(self.lib.muxgl_fmx_match_donors(self.h, *[_ptr(out.get(n)) for n in self.FMX_MATCH_FIELDS], C.byref(ms)))
+        out["kernel_ms"] = float(ms.value)
+        return out
 
     # ---- measurement
     def timing_sum(self, reset=False):
