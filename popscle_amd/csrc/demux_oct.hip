@@ -21,8 +21,8 @@
 //     p = l/2, independent of m (3 distinct likelihoods per entry instead of 9), and for alpha = 0.5 it is
 //     p = (l+m)/4 (5 distinct instead of 9).  Phase 1 therefore carries 8 products per read instead of 18, and the
 //     singlet slot factorises into (sum_l g_j[l] q0[l]) * (g_0[0]+g_0[1]+g_0[2]).
-//   * products leave the kernel as (mantissa, exponent) pairs; the finish kernel multiplies the chunk partials
-//     of a cell in chunk order and takes ONE log per hypothesis and cell.
+//   * products leave the kernel as (mantissa, exponent) pairs packed into eight bytes (oct_pack); the finish kernel
+//     multiplies the chunk partials of a cell in chunk order and takes ONE log per hypothesis and cell.
 //   * entries with at most one usable read (three quarters of a typical pileup) are linear in the genotypes: a chunk's
 //     records are partitioned (oct_partition_kernel), the linear ones are swept first by a loop of their own from rows of
 //     moments (s, rho) -- one FMA and the product update per hypothesis, the sums s folded in at the end.  Their
@@ -70,6 +70,33 @@ struct og {
   static constexpr uint32_t MROW = 32u * P;       // bytes of a marker's row of moments (s, rho) x 2P samples (unit sums: half)
   static constexpr int TROW = 6 * P;              // doubles of a marker's row of triples
 };
+
+// A chunk's partial product m 2^E, m = frexp's mantissa in [0.5, 1), in eight bytes: the mantissa's sign and exponent
+// field are constant (0x3FE), so those twelve bits carry E + OCT_EBIAS for E in [-OCT_EBIAS, OCT_EFIELD_ESC - 1 - OCT_EBIAS]
+// = [-4093, 1] (1: a product of exactly 1, or one an ulp above it).  Field value OCT_EFIELD_ESC is the escape: the
+// twelve bits of the mantissa's own word and E (20 bits, signed: a chunk is <= 192 factors >= 2^-1074, |E| < 2^18) are in
+// part_e then, which nobody writes or reads otherwise.  Lossless for every double, so a hypothesis' product and its
+// log are what they were with twelve-byte partials.  (A chunk deep enough to escape: 192 entries of several reads each
+// against a genotype they contradict; a mantissa that is not in [0.5, 1): a product of 0.)
+constexpr int OCT_EBIAS = 4093;
+constexpr uint32_t OCT_EFIELD_ESC = 4095u;
+__device__ __forceinline__ void oct_pack(double m, int32_t E, size_t o, uint2* __restrict__ part, int32_t* __restrict__ part_e) {
+  const uint32_t hi = (uint32_t)__double2hiint(m), lo = (uint32_t)__double2loint(m);
+  const bool plain = (hi >> 20) == 0x3FEu && (uint32_t)(E + OCT_EBIAS) < OCT_EFIELD_ESC;
+  part[o] = uint2{lo, (hi & 0xFFFFFu) | ((plain ? (uint32_t)(E + OCT_EBIAS) : OCT_EFIELD_ESC) << 20)};
+  if (!plain) part_e[o] = (int32_t)(((uint32_t)E & 0xFFFFFu) | ((hi >> 20) << 20));
+}
+// the mantissa and E + OCT_EBIAS of the partial w at index o
+__device__ __forceinline__ void oct_unpack(uint2 w, size_t o, const int32_t* __restrict__ part_e, double& m, int32_t& eb) {
+  uint32_t top = 0x3FEu;
+  eb = (int32_t)(w.y >> 20);
+  if (w.y >= (OCT_EFIELD_ESC << 20)) {
+    const int32_t pe = part_e[o];
+    top = (uint32_t)pe >> 20;
+    eb = ((int32_t)((uint32_t)pe << 12) >> 12) + OCT_EBIAS;
+  }
+  m = __hiloint2double((int)((w.y & 0xFFFFFu) | (top << 20)), (int)w.x);
+}
 
 template <int CTRL>
 __device__ __forceinline__ double dpp_rot(double x) {
@@ -205,7 +232,7 @@ __global__ void __launch_bounds__(64, P == 8 ? OCT_WAVES : 2)
                      const int32_t* __restrict__ order, const uint8_t* __restrict__ reads,
                      const double* __restrict__ gpo, const double* __restrict__ gmo,
                      const double* __restrict__ gp0s, int32_t S_dummy, const double* __restrict__ lut_g,
-                     const int32_t* __restrict__ chunk_pos, double* __restrict__ part_m, int32_t* __restrict__ part_e) {
+                     const int32_t* __restrict__ chunk_pos, uint2* __restrict__ part, int32_t* __restrict__ part_e) {
   __shared__ double lut[384];
   __shared__ __align__(16) double ablut[O_NLUT * 4];
   using G = og<P>;
@@ -668,17 +695,15 @@ __global__ void __launch_bounds__(64, P == 8 ? OCT_WAVES : 2)
       for (int a = 0; a < ON_ACC; ++a) {
         int e;
         const double m = frexp(acc[a], &e);
-        part_m[((size_t)qpos * ON_ACC + a) * P + p] = m;
-        part_e[((size_t)qpos * ON_ACC + a) * P + p] = exs[a] + e + exa[a];
+        oct_pack(m, exs[a] + e + exa[a], ((size_t)qpos * ON_ACC + a) * P + p, part, part_e);
       }
     }
   }
 }
 
-// Decodes accumulator idx = a * P + p into its hypothesis (j, k); false for slots nobody reads (pairs held twice,
-// j / k >= V).
+// Decodes accumulator idx = a * P + p into its hypothesis (j, k); false for slots nobody reads (pairs held twice).
 template <int P>
-__device__ __forceinline__ bool oct_decode(int idx, const int32_t* __restrict__ pmap, int V, int& j, int& k) {
+__device__ __forceinline__ bool oct_decode(int idx, const int32_t* __restrict__ pmap, int& j, int& k) {
   using G = og<P>;
   const int a = idx / P, p = idx % P;
   bool publish = true;
@@ -707,50 +732,93 @@ __device__ __forceinline__ bool oct_decode(int idx, const int32_t* __restrict__ 
       publish = p < pf;
     }
   }
-  return publish && j < V && k < V;
+  return publish;
 }
+
+// The slot table: for every accumulator slot idx its hypothesis as j | k << 8 | max(j, k) << 16, the third byte 255 for a
+// slot nobody reads -- so a slot counts at V samples iff that byte is < V, and the table depends on P alone.  Filled once
+// (behind the positions it is derived from, oct_launch_t); the readers find a slot's hypothesis with one load that
+// depends on nothing, where decoding in place cost two divisions, a branch tree and a load of pmap in front of the
+// first load of a partial.
+template <int P>
+__global__ void __launch_bounds__(64) oct_slot_kernel(const int32_t* __restrict__ pmap, int32_t* __restrict__ slots) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= og<P>::N_HYP) return;
+  int j, k;
+  const bool publish = oct_decode<P>(idx, pmap, j, k);
+  slots[idx] = j | (k << 8) | ((publish ? (j > k ? j : k) : 255) << 16);
+}
+constexpr int32_t OCT_SLOT_NONE = 255 << 16;
+__device__ __forceinline__ bool oct_slot_live(int32_t s, int V) { return ((s >> 16) & 0xff) < V; }
 
 // log(m 2^e), spelled with an explicit fma: the reduce kernel and the finish kernel must give the same bits, and whether
 // "a + b * c" is contracted is the compiler's choice per site
 __device__ __forceinline__ double oct_log(double m, int64_t e) { return pos_log(m, (double)e); }
 
-// Multiplies the chunk partials of one cell in chunk order: ONE log per hypothesis.  A chunk's partials sit at the chunk's
-// position ci in its cell's list (the sweep writes them there, oct_chunk_pos_kernel), so a cell's are consecutive and a
-// reader needs no chunk ids.
-template <int P>
-__device__ __forceinline__ bool oct_hypothesis(int idx, int64_t c0, int64_t c1, const double* __restrict__ part_m,
-                                               const int32_t* __restrict__ part_e, const int32_t* __restrict__ pmap, int V,
-                                               int& j, int& k, double& v) {
-  constexpr int O_NHYP = og<P>::N_HYP;
-  if (!oct_decode<P>(idx, pmap, V, j, k)) return false;
-  // eight chunks per trip: the sixteen loads are independent and in flight together, the products stay in chunk order
-  double m = 1.0;
-  int64_t e = 0;
+// Multiplies the chunk partials of one cell in chunk order, for the NH slots off[] of a thread at once: ONE log per
+// hypothesis follows.  A chunk's partials sit at the chunk's position in its cell's list (the sweep writes them there,
+// oct_chunk_pos_kernel), so a cell's are consecutive -- pb points at its first chunk's -- and a reader needs no chunk
+// ids.  n is uniform over the wave (a wave serves one cell), so the trips and their loads are under scalar control:
+// U chunks a trip, U x NH independent loads in flight, the last trip with exactly the loads that exist -- no predicated
+// load, no select.  hm / he: the products' mantissas and the sums of E + OCT_EBIAS.
+template <int NH, int U, int O_NHYP, int R>
+__device__ __forceinline__ void oct_fold_trip(const uint2* __restrict__ pb, const int32_t* __restrict__ pe, int64_t ci,
+                                              const int (&off)[NH], double (&hm)[NH], int64_t (&he)[NH]) {
+  uint2 w[NH][R];
+  uint32_t top = 0;
+#pragma unroll
+  for (int i = 0; i < NH; ++i)
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+      w[i][u] = pb[(size_t)(ci + u) * O_NHYP + off[i]];
+      top = w[i][u].y > top ? w[i][u].y : top;
+    }
+  if (__builtin_expect(top < (OCT_EFIELD_ESC << 20), 1)) {  // no escape among the thread's R x NH partials
+#pragma unroll
+    for (int i = 0; i < NH; ++i) {
+      uint32_t es = 0;
+#pragma unroll
+      for (int u = 0; u < R; ++u) {
+        hm[i] *= __hiloint2double((int)((w[i][u].y & 0xFFFFFu) | 0x3FE00000u), (int)w[i][u].x);
+        es += w[i][u].y >> 20;
+      }
+      he[i] += es;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < NH; ++i)
+#pragma unroll
+      for (int u = 0; u < R; ++u) {
+        double m;
+        int32_t eb;
+        oct_unpack(w[i][u], (size_t)(ci + u) * O_NHYP + off[i], pe, m, eb);
+        hm[i] *= m;
+        he[i] += eb;
+      }
+  }
+}
+template <int NH, int U, int O_NHYP>
+__device__ __forceinline__ void oct_fold(const uint2* __restrict__ pb, const int32_t* __restrict__ pe, int64_t n,
+                                         const int (&off)[NH], double (&hm)[NH], int64_t (&he)[NH]) {
+  static_assert(U == 4 || U == 8, "the last trip is spelled per remainder");
+  int64_t ci = 0;
   int cnt = 0;
-  for (int64_t ci = c0; ci < c1; ci += 8) {
-    double pm[8];
-    int32_t pe[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const bool ok = ci + u < c1;
-      const size_t o = (size_t)(ok ? ci + u : c0) * O_NHYP + idx;
-      pm[u] = ok ? part_m[o] : 1.0;
-      pe[u] = ok ? part_e[o] : 0;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      m *= pm[u];
-      e += pe[u];
-    }
-    if (++cnt == 64) {  // mantissas are in [0.5,1): 512 factors cannot underflow
+  for (; ci + U <= n; ci += U) {
+    oct_fold_trip<NH, U, O_NHYP, U>(pb, pe, ci, off, hm, he);
+    if (++cnt == 512 / U) {  // mantissas are in [0.5,1): 512 factors (and a last trip) cannot underflow
       cnt = 0;
-      int ee;
-      m = frexp(m, &ee);
-      e += ee;
+#pragma unroll
+      for (int i = 0; i < NH; ++i) {
+        int ee;
+        hm[i] = frexp(hm[i], &ee);
+        he[i] += ee;
+      }
     }
   }
-  v = oct_log(m, e);
-  return true;
+  wave_for<1, U>([&](auto rc) {
+    constexpr int R = decltype(rc)::value;
+    if (n - ci == R) oct_fold_trip<NH, U, O_NHYP, R>(pb, pe, ci, off, hm, he);
+  });
 }
 
 // position of every chunk in its cell's list (the inverse of cell_chunks)
@@ -763,18 +831,34 @@ __global__ void __launch_bounds__(256)
 // writes ll[c][j][k][n] (+ mirror) of one cell to the LL tensor in HBM (needed when the caller asks for the tensor)
 template <int P>
 __global__ void __launch_bounds__(192)
-    demux_oct_reduce_kernel(const int64_t* __restrict__ cell_chunk_ptr, const double* __restrict__ part_m,
-                            const int32_t* __restrict__ part_e, const int32_t* __restrict__ pmap, int V,
+    demux_oct_reduce_kernel(const int64_t* __restrict__ cell_chunk_ptr, const uint2* __restrict__ part,
+                            const int32_t* __restrict__ part_e, const int32_t* __restrict__ slots, int V,
                             double* __restrict__ ll) {
+  constexpr int O_NHYP = og<P>::N_HYP, NH = (O_NHYP + 191) / 192;
   const int64_t c = blockIdx.x;
   const int64_t c0 = cell_chunk_ptr[c], c1 = cell_chunk_ptr[c + 1];
   if (c0 == c1) return;
   double* out = ll + (size_t)c * V * V * 2;
-  for (int idx = threadIdx.x; idx < og<P>::N_HYP; idx += 192) {
-    int j, k;
-    double v;
-    if (!oct_hypothesis<P>(idx, c0, c1, part_m, part_e, pmap, V, j, k, v)) continue;
-    if (idx < 2 * P) {
+  int32_t hs[NH];
+  int off[NH];
+  double hm[NH];
+  int64_t he[NH];
+#pragma unroll
+  for (int i = 0; i < NH; ++i) {
+    const int idx = (int)threadIdx.x + i * 192;
+    hs[i] = idx < O_NHYP ? slots[idx] : OCT_SLOT_NONE;
+    off[i] = oct_slot_live(hs[i], V) ? idx : 0;  // (a valid address either way)
+    hm[i] = 1.0;
+    he[i] = 0;
+  }
+  // eight chunks per trip: the loads are independent and in flight together, the products stay in chunk order
+  oct_fold<NH, 8, O_NHYP>(part + (size_t)c0 * O_NHYP, part_e + (size_t)c0 * O_NHYP, c1 - c0, off, hm, he);
+#pragma unroll
+  for (int i = 0; i < NH; ++i) {
+    if (!oct_slot_live(hs[i], V)) continue;
+    const int j = hs[i] & 0xff, k = (hs[i] >> 8) & 0xff;
+    const double v = oct_log(hm[i], he[i] - (int64_t)OCT_EBIAS * (c1 - c0));
+    if (i == 0 && (int)threadIdx.x < 2 * P) {
       out[((size_t)j * V + k) * 2 + 0] = v;  // singlet: alpha index 0
     } else {
       out[((size_t)j * V + k) * 2 + 1] = v;
@@ -787,102 +871,72 @@ __global__ void __launch_bounds__(192)
 // (demux_call_body.hpp) follows at once: no LL tensor round trip through HBM, one launch less, and the 160-byte
 // records go straight to the caller's pinned host buffer (16-byte stores of consecutive lanes), which removes the
 // separate device-to-host copy.
-#ifndef QF_CELLS_N
-#define QF_CELLS_N 4
-#endif
+// A wave per cell at P = 8, four waves per cell at P = 16.  Measured (profiles/oct_finish_lean.md): two thirds of the
+// kernel's time scale with the number of cells and one third is a fixed chain (0.064 ms for 10 000 cells, 0.043 ms for
+// 5 000), so both count: few instructions per cell, and few dependent steps -- a slot's hypothesis from ONE load that
+// depends on nothing, a cell's partials consecutive (no chunk ids), a thread's NH slots walked TOGETHER, four chunks a trip.
+// (Workgroups that take two cell groups in turn, all resident at once, were measured and dropped: the compiler keeps the
+// scans' constants in registers across that loop, and held to five waves per SIMD it spills: 0.083 ms against 0.058 ms.)
 template <int P>
 __global__ void __launch_bounds__(256)
     demux_oct_finish_kernel(int64_t C, const int64_t* __restrict__ cell_ptr, const int64_t* __restrict__ cell_chunk_ptr,
-                            const double* __restrict__ part_m, const int32_t* __restrict__ part_e,
-                            const int32_t* __restrict__ pmap, int V,
+                            const uint2* __restrict__ part, const int32_t* __restrict__ part_e,
+                            const int32_t* __restrict__ slots, int V,
                             muxgl_call::call_alpha al, double doublet_prior, muxgl_demux_cell* __restrict__ out) {
-  constexpr int QF_CELLS = P == 8 ? QF_CELLS_N : 1, THREADS = 256, O_NHYP = og<P>::N_HYP;
-  static_assert(P == 16 || QF_CELLS * 64 == THREADS, "a wave per cell at P = 8");
+  constexpr int THREADS = 256, TC = P == 8 ? 64 : 256, QF_CELLS = THREADS / TC, O_NHYP = og<P>::N_HYP;  // TC: threads per cell
   constexpr int LD = 4 * P + 1;  // row stride of the tiles in doubles (2P samples x 2 alphas): odd, so that the lanes of a cell's
                                  // call, which read the same column of their rows at once, meet different LDS banks
   __shared__ double llt[QF_CELLS][2 * P * LD];
   __shared__ __align__(16) muxgl_demux_cell rec[QF_CELLS];
-  __shared__ int64_t ccp[QF_CELLS + 1];
   static_assert(sizeof(muxgl_demux_cell) % 16 == 0, "records are copied out in 16-byte pieces");
-  const int64_t cbase = (int64_t)blockIdx.x * QF_CELLS;
   const int tid = threadIdx.x;
-  if (tid <= QF_CELLS) ccp[tid] = cell_chunk_ptr[cbase + tid <= C ? cbase + tid : C];
-  for (int t = tid; t < QF_CELLS * 2 * P * LD; t += THREADS) (&llt[0][0])[t] = 0.0;
-  __syncthreads();
-  // The kernel's time is a chain of dependent latencies (measured: the same 65 us for 5 000 cells as for 10 000), so the
-  // chain is kept short: the chunk ranges of the workgroup's cells come from ONE load (above), a cell's partials are
-  // consecutive (no chunk ids), and a thread's hypotheses -- NH of the workgroup's QF_CELLS x N_HYP -- are walked TOGETHER,
-  // four chunks a trip: 2 x 4 x NH loads in flight instead of one hypothesis after the other (three dependent trips each).
-  constexpr int NH = (QF_CELLS * O_NHYP + THREADS - 1) / THREADS;
-  int hj[NH], hk[NH], hidx[NH], hlc[NH];
-  int64_t h0[NH];
-  int hn[NH];
+  const int lc = __builtin_amdgcn_readfirstlane(tid / TC), t = tid % TC;  // the thread's cell of the group: one per wave
+  // a thread's NH slots of its cell: where their partials are in a chunk's block, and where their logs go in the tile
+  // ((j, k) and, of a pair, its mirror)
+  constexpr int NH = (O_NHYP + TC - 1) / TC;
+  int off[NH], at[NH], atm[NH];
   bool hv[NH];
-  double hm[NH];
-  int64_t he[NH];
-  int nmax = 0;
 #pragma unroll
   for (int i = 0; i < NH; ++i) {
-    const int w = tid + i * THREADS;
-    const int lc = w < QF_CELLS * O_NHYP ? w / O_NHYP : 0;
-    hlc[i] = lc;
-    hidx[i] = w - lc * O_NHYP;
-    h0[i] = ccp[lc];
-    hn[i] = (int)(ccp[lc + 1] - ccp[lc]);
-    hv[i] = w < QF_CELLS * O_NHYP && hn[i] > 0 && oct_decode<P>(hidx[i] < O_NHYP ? hidx[i] : 0, pmap, V, hj[i], hk[i]);
-    if (!hv[i]) hn[i] = 0, hidx[i] = 0;
-    hm[i] = 1.0;
-    he[i] = 0;
-    nmax = hn[i] > nmax ? hn[i] : nmax;
+    const int idx = t + i * TC;
+    const int32_t s = idx < O_NHYP ? slots[idx] : OCT_SLOT_NONE;
+    const int j = s & 0xff, k = (s >> 8) & 0xff;
+    hv[i] = oct_slot_live(s, V);
+    off[i] = hv[i] ? idx : 0;  // (a valid address either way; the tile has no place for the others)
+    const bool single = i == 0 && t < 2 * P;  // idx < 2 P: alpha index 0
+    at[i] = j * LD + k * 2 + (single ? 0 : 1);
+    atm[i] = single ? at[i] : k * LD + j * 2 + 1;
   }
-  int cnt = 0;
-  for (int ci = 0; ci < nmax; ci += 4) {
-    double pm[NH][4];
-    int32_t pe[NH][4];
-#pragma unroll
-    for (int i = 0; i < NH; ++i)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const bool ok = ci + u < hn[i];
-        const size_t o = (ok ? (size_t)(h0[i] + ci + u) * O_NHYP : 0) + hidx[i];  // (a valid address either way)
-        const double vm = part_m[o];
-        const int32_t ve = part_e[o];
-        pm[i][u] = ok ? vm : 1.0;
-        pe[i][u] = ok ? ve : 0;
-      }
-#pragma unroll
-    for (int i = 0; i < NH; ++i)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        hm[i] *= pm[i][u];
-        he[i] += pe[i][u];
-      }
-    if (++cnt == 128) {  // mantissas are in [0.5,1): 512 factors cannot underflow (as oct_hypothesis)
-      cnt = 0;
-#pragma unroll
-      for (int i = 0; i < NH; ++i) {
-        int ee;
-        hm[i] = frexp(hm[i], &ee);
-        he[i] += ee;
-      }
-    }
+  const int64_t cbase = (int64_t)blockIdx.x * QF_CELLS, c = cbase + lc;
+  int64_t c0 = 0, n = 0;
+  if (c < C) {
+    c0 = cell_chunk_ptr[c];
+    n = cell_chunk_ptr[c + 1] - c0;
   }
+  if (n > 0) {
+    double hm[NH];
+    int64_t he[NH];
 #pragma unroll
-  for (int i = 0; i < NH; ++i) {
-    if (!hv[i]) continue;
-    const double v = oct_log(hm[i], he[i]);
-    if (hidx[i] < 2 * P) {
-      llt[hlc[i]][hj[i] * LD + hk[i] * 2 + 0] = v;
-    } else {
-      llt[hlc[i]][hj[i] * LD + hk[i] * 2 + 1] = v;
-      llt[hlc[i]][hk[i] * LD + hj[i] * 2 + 1] = v;
+    for (int i = 0; i < NH; ++i) {
+      hm[i] = 1.0;
+      he[i] = 0;
     }
+    // four chunks a trip: 4 x NH loads in flight, one or two trips for a typical cell
+    oct_fold<NH, 4, O_NHYP>(part + (size_t)c0 * O_NHYP, part_e + (size_t)c0 * O_NHYP, n, off, hm, he);
+#pragma unroll
+    for (int i = 0; i < NH; ++i) {
+      if (!hv[i]) continue;
+      const double v = oct_log(hm[i], he[i] - (int64_t)OCT_EBIAS * n);
+      llt[lc][at[i]] = v;
+      llt[lc][atm[i]] = v;
+    }
+  } else {  // a cell without entries (or none: the last group's tail) reads as zeros; a cell with entries writes every
+            // element the scans read -- row[0] and row[2 k + 1], k != row, below V -- so its tile needs no fill
+    for (int x = t; x < 2 * P * LD; x += TC) llt[lc][x] = 0.0;
   }
   __syncthreads();
   if constexpr (P == 8) {  // a wave per cell for the scans (sixteen rows x four ranges of columns); the cells' decisions side by side
     __shared__ muxgl_call::call_partial parts[QF_CELLS];
-    const int lc = tid >> 6;
-    const int64_t c = cbase + lc;
     const muxgl_call::call_partial cp = muxgl_call::demux_call_scan<16, 4>(tid & 63, c < C, V, 2, al, llt[lc], LD);
     if ((tid & 63) == 0) parts[lc] = cp;
     __syncthreads();
@@ -939,12 +993,15 @@ template <int P>
 int oct_launch_t(muxgl_handle* h, const muxgl_demux_params* p) {
   constexpr int O_SLOTS = og<P>::SLOTS, O_NHYP = og<P>::N_HYP;
   muxgl_row_state* st = h->qrow;
-  if (!st->d_tmap || st->tmap_p != P) {  // positions met by the rotations
-    if (dev_alloc(h, &st->d_tmap, (size_t)(P / 2) * P)) return 1;
+  constexpr int N_PMAP = (P / 2) * P;
+  if (!st->d_tmap || st->tmap_p != P) {  // positions met by the rotations, and behind them the slot table made from them
+    if (dev_alloc(h, &st->d_tmap, (size_t)N_PMAP + O_NHYP)) return 1;
     hipLaunchKernelGGL(oct_pmap_kernel<P>, dim3(1), dim3(64), 0, h->stream, st->d_tmap);
+    hipLaunchKernelGGL(oct_slot_kernel<P>, dim3((O_NHYP + 63) / 64), dim3(64), 0, h->stream, st->d_tmap, st->d_tmap + N_PMAP);
     HIPCHK(h, hipGetLastError());
     st->tmap_p = P;
   }
+  const int32_t* d_slots = st->d_tmap + N_PMAP;
   const size_t need = (size_t)st->n_chunks * O_NHYP;
   if (need > st->part_cap) {
     if (dev_alloc(h, &st->d_part, need)) return 1;
@@ -954,6 +1011,7 @@ int oct_launch_t(muxgl_handle* h, const muxgl_demux_params* p) {
     if (dev_alloc(h, &st->d_part_e, need)) return 1;
     st->part_e_cap = need;
   }
+  uint2* d_part = reinterpret_cast<uint2*>(st->d_part);  // eight-byte partials (oct_pack)
   if (!st->d_chunk_pos) {  // where a chunk's partials go (oct_hypothesis)
     if (dev_alloc(h, &st->d_chunk_pos, (size_t)(st->n_chunks ? st->n_chunks : 1))) return 1;
     if (st->n_chunks)
@@ -1016,19 +1074,20 @@ int oct_launch_t(muxgl_handle* h, const muxgl_demux_params* p) {
                        use_lin ? st->d_qent_lin : h->d_qent, st->d_orec, st->d_unit_ptr,
                        use_lin ? st->d_chunk_nlin : (const int32_t*)nullptr,
                        use_lin ? st->d_quad_order : (const int32_t*)nullptr, h->d_reads,
-                       h->d_gpq, h->d_gmq, h->d_gp0s, (int32_t)h->S, h->d_lut, st->d_chunk_pos, st->d_part, st->d_part_e);
+                       h->d_gpq, h->d_gmq, h->d_gp0s, (int32_t)h->S, h->d_lut, st->d_chunk_pos, d_part, st->d_part_e);
     HIPCHK(h, hipGetLastError());
   }
   toc_tic(h, MUXGL_T_DEMUX_SWEEP, MUXGL_T_DEMUX_REDUCE);
   if (h->want_full_ll) {
     hipLaunchKernelGGL(demux_oct_reduce_kernel<P>, dim3((unsigned)h->C), dim3(192), 0, h->stream, st->d_cell_chunk_ptr,
-                       st->d_part, st->d_part_e, st->d_tmap, h->V, h->d_ll);
+                       d_part, st->d_part_e, d_slots, h->V, h->d_ll);
   } else {  // reduce + call fused, records written to the pinned host buffer
     const muxgl_call::call_alpha al = muxgl_call::make_call_alpha(p, h->V);
-    constexpr int QF_CELLS = P == 8 ? QF_CELLS_N : 1;
-    hipLaunchKernelGGL(demux_oct_finish_kernel<P>, dim3((unsigned)((h->C + QF_CELLS - 1) / QF_CELLS)), dim3(256), 0,
-                       h->stream, h->C, h->d_cell_ptr, st->d_cell_chunk_ptr, st->d_part, st->d_part_e, st->d_tmap, h->V, al,
-                       p->doublet_prior, h->h_dcells);
+    constexpr int QF_CELLS = P == 8 ? 4 : 1;
+    const int64_t n_groups = (h->C + QF_CELLS - 1) / QF_CELLS;
+    if (n_groups)
+      hipLaunchKernelGGL(demux_oct_finish_kernel<P>, dim3((unsigned)n_groups), dim3(256), 0, h->stream, h->C, h->d_cell_ptr,
+                         st->d_cell_chunk_ptr, d_part, st->d_part_e, d_slots, h->V, al, p->doublet_prior, h->h_dcells);
     h->records_on_host = true;
   }
   HIPCHK(h, hipGetLastError());
