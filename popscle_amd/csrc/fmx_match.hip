@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "match_plan.hpp"
 
 namespace {
 
@@ -222,16 +223,15 @@ int fmx_match_run(muxgl_handle* h, double* ll, double* ll0, int32_t* nsnps, floa
     return 0;
   }
   const bool want_hwe = ll0 || nsnps;
-  const int NP = (int)((S + FMM_PART - 1) / FMM_PART);
-  // bytes of a cluster in a batch: logs of the parts (donors, HWE), counts of the parts, read counts, results
-  const double per_k = (ll ? 8.0 * NP * V + 8.0 * V : 0.0) + 12.0 * NP + 4.0 * (double)S + 12.0;
-  const int kb_cap = (int)std::min<double>((double)K, std::max(1.0, (double)dev_slab_budget("MUXGL_FMX_SLAB_MB") / per_k));
+  // the cut of the call (match_plan.hpp): parts, bytes of a cluster in a batch, clusters of a batch
+  const int NP = match_plan::parts(S, FMM_PART);
+  const double per_k = match_plan::bytes_per_cluster(S, V, NP, ll != nullptr);
+  const int kb_cap = match_plan::clusters_per_batch(K, per_k, dev_slab_budget("MUXGL_FMX_SLAB_MB"));
   const int T = match_tile();
   const int nblk = (V + 63) / 64;
   if ((double)NP * nblk * ((kb_cap + T - 1) / T) / 4.0 >= 2147483647.0)
     MUXGL_FAIL(h, "muxgl_fmx_match_donors: a batch of %d clusters exceeds one launch (lower MUXGL_FMX_SLAB_MB)", kb_cap);
-  int VH = 64;
-  while (VH > 1 && VH / 2 >= V) VH /= 2;
+  const int VH = match_plan::lane_width(V);
 
   dev_tmp<double> d_part, d_part0, d_out, d_out0;
   dev_tmp<int32_t> d_nreads, d_partn, d_outn;

@@ -5,8 +5,13 @@ tests/test_fmx_gpu.py).
 
 Bar: parity.LL_TOL (1e-5 absolute) on every finite element, -inf where the restatement has -inf, nsnps equal; every test
 prints the worst deviation it saw (DESIGN.md 4.2e has the largest).
+
+Section 1b runs every instantiation of fmm_sweep_kernel (every donor width VH at every tile size T, and the HWE sweep)
+and holds the tile sizes to each other bit for bit; section 4 has batches of clusters that the tile does not divide.
+The grid of 1b is also what tests/test_fmx_match.py test_grid_and_fuzz_seeds_reach_every_variant counts, without a GPU.
 """
 import gzip
+import itertools
 import os
 import re
 import subprocess
@@ -19,11 +24,15 @@ import parity
 from match_ref import restate_match
 from popscle_amd import freemuxlet, muxgl, plpio, synth
 from test_cli_gpu import BIN, tokens_match
+from test_fmx_match import GRID_K, GRID_V, SHORT_V, TILES, grid_s, load_plan_probe, match_plan
+from test_fuzz_gpu import slab_env
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-P = int(re.search(r"FMM_PART\s*=\s*(\d+)", open(os.path.join(ROOT, "popscle_amd", "csrc", "fmx_match.hip")).read()).group(1))
+SRC = open(os.path.join(ROOT, "popscle_amd", "csrc", "fmx_match.hip")).read()
+P = int(re.search(r"FMM_PART\s*=\s*(\d+)", SRC).group(1))
+UNR = int(re.search(r"FMM_UNR\s*=\s*(\d+)", SRC).group(1))
 
 
 def prepared(p, devs=0, flags=0):
@@ -51,11 +60,10 @@ def holed(p, seed, frac=0.2):
     return gp, has_gp
 
 
-def assert_match(e, gp, has_gp, af, what, got=None):
-    """the call against the restatement of the handle's own pileup; returns (got, worst deviation)"""
-    got = got or e.fmx_match_donors()
-    gls, cnt = e.fmx_cluster_pileup()
-    ll, ll0, nsnps = restate_match(gls, cnt, gp, has_gp, af)
+def compare(got, want, what):
+    """got: the call's dict; want: (ll, ll0, nsnps) of the restatement.  Every element: nsnps equal, -inf exactly where the
+    restatement has it, no NaN or +inf, every finite element within parity.LL_TOL.  Returns the worst deviation."""
+    ll, ll0, nsnps = want
     assert got["ll"].shape == ll.shape and got["ll0"].shape == ll0.shape and got["nsnps"].dtype == np.int32
     assert np.array_equal(got["nsnps"], nsnps)
     worst = 0.0
@@ -65,11 +73,17 @@ def assert_match(e, gp, has_gp, af, what, got=None):
         fin = np.isfinite(w)
         if fin.any():
             worst = max(worst, float(np.max(np.abs(g[fin] - w[fin]))))
-    print(f"fmx match {what}: K={ll.shape[0]} V={ll.shape[1]} S={gls.shape[1]}, max |dLL| = {worst:.3e}, "
-          f"kernel {got['kernel_ms']:.3f} ms")
+    print(f"fmx match {what}: K={ll.shape[0]} V={ll.shape[1]}, max |dLL| = {worst:.3e}, kernel {got['kernel_ms']:.3f} ms")
     assert worst <= parity.LL_TOL
     assert np.all(got["ll"][nsnps == 0] == 0.0) and np.all(got["ll0"][nsnps == 0] == 0.0)
-    return got, worst
+    return worst
+
+
+def assert_match(e, gp, has_gp, af, what, got=None):
+    """the call against the restatement of the handle's own pileup; returns (got, worst deviation)"""
+    got = got or e.fmx_match_donors()
+    gls, cnt = e.fmx_cluster_pileup()
+    return got, compare(got, restate_match(gls, cnt, gp, has_gp, af), f"{what}, S={gls.shape[1]}")
 
 
 # ---- 1. shapes: every cut of donors (lanes, blocks), clusters (tile remainder) and markers (parts) ------------------------
@@ -98,6 +112,61 @@ def test_shapes_vs_restatement(V, K, S):
 
 def _small(V=5, K=5, S=300, seed=7100, **kw):
     return synth.make_pileup(80, S, V, seed=seed, mean_entries=80, min_entries=5, with_gp=True, **kw)
+
+
+# ---- 1b. every instantiation of the sweep, and the tile sizes against each other bit for bit ----------------------------
+
+# GRID_S = 2 P + 5: three parts, the last of five markers; SHORT_S = 1, UNR - 1, 64 UNR + 1 (below one part: below or just
+# past one unrolled group at G = 1 and at G = 64) and P + 1 (two parts, the second of one marker)
+GRID_S, SHORT_S = grid_s(P, UNR)
+FIELDS = ("ll", "ll0", "nsnps")
+
+
+def _same_bytes(a, b, what):
+    for n in FIELDS:
+        if n in a or n in b:
+            assert a[n].tobytes() == b[n].tobytes(), f"{n} differs: {what}"
+
+
+def _tiles_agree(V, S, subsets):
+    plan = load_plan_probe()
+    vh = match_plan(plan, S, V, GRID_K, P)["vh"]
+    G = 64 // vh
+    if S == GRID_S:   # the last part's only unrolled group is partial at every G; the parts before it have whole groups only
+        assert (S - 2 * P) % (UNR * G) != 0 and 0 < S - 2 * P < UNR and P % (UNR * 64) == 0
+    p = synth.make_pileup(60, S, V, seed=7600 + V + S, mean_entries=max(1, S // 5), min_entries=1, reads_lambda=0.6,
+                          doublet_frac=0.1, with_gp=True)
+    gp, has_gp = holed(p, V + S) if S > 1 else (p.gp, p.has_gp)
+    with prepared(p) as e:
+        e.fmx_set_clusters(GRID_K, spread_init(p.C, GRID_K))
+        e.demux_set_gp(gp, has_gp)
+        with slab_env("MUXGL_FMX_MATCH_TILE", None):
+            base, _ = assert_match(e, gp, has_gp, p.af, f"grid VH={vh}, default tile")
+        assert base["nsnps"][GRID_K - 1] == 0 and (S < 100 or (base["nsnps"][:GRID_K - 1] > 0).all())
+        for t in TILES:
+            with slab_env("MUXGL_FMX_MATCH_TILE", str(t)):
+                _same_bytes(e.fmx_match_donors(), base, f"tile {t} against the default, V={V} S={S}")
+        if subsets:
+            for t in (None, "8"):
+                with slab_env("MUXGL_FMX_MATCH_TILE", t):
+                    for n in range(1, 4):
+                        for want in itertools.combinations(FIELDS, n):
+                            only = e.fmx_match_donors(want=want)
+                            assert set(only) == set(want) | {"kernel_ms"}
+                            _same_bytes(only, {k: base[k] for k in want}, f"want={want}, tile {t}, V={V}")
+
+
+@pytest.mark.parametrize("V", GRID_V)
+def test_every_donor_width_at_every_tile_size(V):
+    """K = 11 (a remainder of 1, 3, 3 clusters at tiles of 2, 4, 8), three parts with a tail of five markers: the default
+    call against the restatement, every tile size against the default in the bytes of all three outputs; at 17 and 65
+    donors also every subset of the outputs, at the default tile and at 8"""
+    _tiles_agree(V, GRID_S, subsets=V in (17, 65))
+
+
+@pytest.mark.parametrize("V,S", [(V, S) for S in SHORT_S for V in SHORT_V])
+def test_short_marker_axes_at_every_tile_size(V, S):
+    _tiles_agree(V, S, subsets=False)
 
 
 def test_no_marker_with_genotypes():
@@ -303,6 +372,71 @@ def test_budget_does_not_matter(tmp_path):
     assert outs[0]["ll"].shape == (5, 65) and np.isfinite(outs[0]["ll"]).all() and (outs[0]["nsnps"] > 0).all()
     for n in ("ll", "ll0", "nsnps"):
         assert outs[0][n].tobytes() == outs[1][n].tobytes()
+
+
+_CHILD_MANY = r"""
+import os, sys, numpy as np
+sys.path[:0] = [sys.argv[1], os.path.join(sys.argv[1], "tests")]
+from match_ref import restate_match
+from popscle_amd import muxgl, synth
+from test_fmx_match import load_plan_probe, match_plan
+K, V, S, P, out = int(sys.argv[2]), 9, int(sys.argv[3]), int(sys.argv[4]), sys.argv[5]
+mb = os.environ.get("MUXGL_FMX_SLAB_MB")
+if mb:   # the batch the kernel's own byte count gives under this budget: several batches, the last one short, and a
+    # batch that tiles of 4 and 8 clusters do not divide (else the last tile of a batch has no slot to leave unwritten)
+    plan = match_plan(load_plan_probe(), S, V, K, P, budget=int(mb) << 20)
+    kb = plan["kb"]
+    assert plan["np"] == 3 and 16000 < plan["per_k"] < 17500 and kb == 62, plan
+    assert kb != 1 and kb < K and kb % 4 != 0 and kb % 8 != 0 and K % kb != 0, (kb, K)
+p = synth.make_pileup(50, S, V, seed=7302 + K, mean_entries=40, min_entries=20, max_entries=80, with_gp=True)
+has_gp = p.has_gp.copy()
+has_gp[::5] = 0
+gp = p.gp.copy()
+gp[has_gp == 0] = np.nan
+res = {}
+with muxgl.Engine(0) as e:
+    e.set_pileup(p.S, p.cell_ptr, p.entry_snp, p.entry_rptr, p.reads)
+    e.fmx_prepare(p.af)
+    e.fmx_set_clusters(K, ((np.arange(p.C) * 7) % K).astype(np.int32))   # dealt round: most clusters one cell or none
+    e.demux_set_gp(gp, has_gp)
+    for tile in ("4", "8"):
+        os.environ["MUXGL_FMX_MATCH_TILE"] = tile
+        r = e.fmx_match_donors()
+        res.update({f"{n}_t{tile}": r[n] for n in ("ll", "ll0", "nsnps")})
+    if not mb:   # the restatement of the handle's own pileups, for the parent to hold the table to
+        gls, cnt = e.fmx_cluster_pileup()
+        res["want_ll"], res["want_ll0"], res["want_nsnps"] = restate_match(gls, cnt, gp, has_gp, p.af)
+np.savez(out, **res)
+"""
+
+
+@pytest.mark.parametrize("K", [130, 300])
+def test_many_clusters_in_batches_the_tile_does_not_divide(tmp_path, K):
+    """K clusters of one cell or none, 9 donors, three parts: under MUXGL_FMX_SLAB_MB=1 the call takes batches of 62
+    clusters (stated by the child from match_plan.hpp before it runs), so at tiles of 4 and 8 the last tile of every
+    batch re-reads the batch's last cluster and must not store it, and a short batch follows the full ones.  The bytes
+    are those of the default budget (one batch) at either tile, and that table is held to the restatement."""
+    outs = []
+    for mb in (1, 0):
+        env = dict(os.environ)
+        env.pop("MUXGL_FMX_SLAB_MB", None)
+        env.pop("MUXGL_FMX_MATCH_TILE", None)
+        if mb:
+            env["MUXGL_FMX_SLAB_MB"] = str(mb)
+        out = str(tmp_path / f"many{mb}.npz")
+        r = subprocess.run([sys.executable, "-c", _CHILD_MANY, ROOT, str(K), str(GRID_S), str(P), out], env=env,
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        outs.append(np.load(out))
+    small, full = outs
+    for n in FIELDS:
+        assert full[f"{n}_t4"].tobytes() == full[f"{n}_t8"].tobytes(), f"{n}: tiles 4 and 8 differ, one batch"
+        for t in (4, 8):
+            assert small[f"{n}_t{t}"].tobytes() == full[f"{n}_t4"].tobytes(), f"{n}: tile {t} under 1 MB differs from one batch"
+    got = {n: full[f"{n}_t4"] for n in FIELDS}
+    got["kernel_ms"] = 0.0
+    compare(got, (full["want_ll"], full["want_ll0"], full["want_nsnps"]), f"K={K} in batches of 62")
+    assert got["ll"].shape == (K, 9) and 40 <= (got["nsnps"] > 0).sum() <= 50 and (got["nsnps"] == 0).sum() >= K - 50
 
 
 # ---- 5. refusals ----------------------------------------------------------------------------------------------------------

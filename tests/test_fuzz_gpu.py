@@ -13,6 +13,15 @@ test_demux_inclusion.restate), muxgl_fmx_singlets after every iteration against 
 A campaign line carries sng_ll, incl_ll, tot_ll, dbl_ll, fmx_sng_ll (the worst |d| of each table) and incl_decided, the
 share of (cell, sample) pairs whose reference gap exceeds 2 LL_TOL: the pairs whose integers were compared exactly.
 
+Every freemuxlet case (fmx_case; not the streamed ones) also scores its clusters against a donor panel drawn for it
+(match_case below) with muxgl_fmx_match_donors, at a tile size drawn per case and under the case's table budget, and
+holds the table to tests/match_ref.py restate_match twice: fed the handle's own fmx_cluster_pileup(), after every
+iteration where the case runs on one handle, and fed the reference's cluster pileups of the last iteration, which does
+not pass through the library's M-step.  Device groups and sharded handles refuse the call by name; their last
+assignment is scored on the module's plain engine.  A campaign line of --kind fmx carries match_ll, match_ref_ll (the
+worst |d| against either), match_v, match_tile, match_mode, match_dup, match_missing and match_neginf (the -inf of
+the last table).
+
 pytest runs the seeds of FUZZ_SEEDS (a minute); a campaign is
     python tests/test_fuzz_gpu.py --seeds 1000:1400 [--kind demux|fmx] [--log gpurun_out/fuzz.jsonl]
 which prints one JSON line per case and exits 1 at the first failing seed (the seed reproduces the case).
@@ -26,6 +35,7 @@ import json
 import os
 import sys
 import time
+import types
 
 import numpy as np
 import pytest
@@ -35,6 +45,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import parity  # noqa: E402
 import ref_binding as rb  # noqa: E402
+from match_ref import restate_match  # noqa: E402
 from popscle_amd import freemuxlet, muxgl, shard, synth  # noqa: E402
 from test_demux_inclusion import restate  # noqa: E402
 
@@ -58,7 +69,11 @@ FMX_FLAGS = [0] * 6 + [muxgl.FLAG_FORCE_ROW_KERNEL, muxgl.FLAG_FORCE_WAVE_KERNEL
 # `--seeds 1000:1100 --budget-s 600` and over FUZZ_SEEDS stayed within 1e-8 is held to 1e-7 like the rest of this file,
 # else to LL_TOL.  Measured: sng 4.7e-11, incl / tot / dbl 3.0e-11, fmx_sng 1.6e-10 -- all five
 # at 1e-7.  sng: muxgl_demux_singlets; incl, tot, dbl: muxgl_demux_inclusion; fmx_sng: muxgl_fmx_singlets.
-TABLE_TOL = dict(sng=1e-7, incl=1e-7, tot=1e-7, dbl=1e-7, fmx_sng=1e-7)
+# match, match_ref: muxgl_fmx_match_donors against restate_match of the handle's own and of the reference's cluster
+# pileups (campaign `--seeds 1000:1100 --kind fmx --budget-s 600`): 1.8e-12 and 1.8e-12 over the campaign,
+# 1.5e-11 and 1.5e-11 over FUZZ_SEEDS (seed 3, 16 000 markers) -- both at 1e-7.  match_ref could have been as far off as
+# |U| x 1e-11 = 1.6e-7 (the library's pileups are held to the reference's at rtol 1e-11); it is not.
+TABLE_TOL = dict(sng=1e-7, incl=1e-7, tot=1e-7, dbl=1e-7, fmx_sng=1e-7, match=1e-7, match_ref=1e-7)
 RESTATE_BYTES = 5e7   # of full_ll per call of restate (it makes several temporaries of that size): 16 cells at V = 255, A = 6
 
 
@@ -206,6 +221,104 @@ def _demux_tables(eng, info, want_ll):
     return out
 
 
+# ---- the donor panel a freemuxlet case's clusters are scored against (muxgl_fmx_match_donors, fmx_match.hip) ---------------
+# Widths: every lane width of the sweep (1, 2, 4, 8, 16, 32, 64 lanes per SNP slot), one off a power of two on either
+# side, two and three donor blocks.  Draws come from a stream of their own ([seed, 82]): fmx_case stays what it is.
+MATCH_V = [1, 2, 3, 5, 8, 12, 16, 17, 24, 32, 33, 64, 65, 130]
+MATCH_TILES = (1, 2, 4, 8)
+# The restatement takes one log and one fsum term per (cluster, donor, marker of U), about 0.1 us each, and a case asks
+# for it up to twelve times (ten iterations at most, the reference's pileups, the plain engine).  K x V x S x 12 stays
+# under MATCH_WORK: the panel of the widest K x S is narrowed, no element of a table is left out.
+MATCH_WORK = 2e7
+MATCH_CALLS = 12
+
+
+def match_case(seed, info, p):
+    """the panel of a freemuxlet case: V donors whose genotypes are columns of p.truth["G"] taken with replacement
+    (duplicated donors are common: their columns of ll must be the same bytes), padded with random genotypes where the
+    panel is wider than the pileup's donors; rows through _gp_mode or, one time in five, the mode "zeros" (a share of
+    triples with one or two hard zeros, three triples zero in all three places: -inf wherever a cluster covers them);
+    markers without genotypes drawn as _pileup draws missing_gp_frac (1.0: every output zero), their rows NaN.
+    V is redrawn among the widths that fit MATCH_WORK where the first draw does not (the widest K x S only)."""
+    r = np.random.default_rng([seed, 82])
+    K, S = info["K"], p.S
+    V = int(r.choice(MATCH_V))
+    cap = max(1, int(MATCH_WORK // (MATCH_CALLS * K * S)))
+    narrow = int(r.choice([v for v in MATCH_V if v <= cap]))   # (drawn in every case: the stream does not depend on the cap)
+    if V > cap:
+        V = narrow
+    tile = int(r.choice(MATCH_TILES))
+    G = p.truth["G"].astype(np.int64)
+    take = min(V, G.shape[1])
+    Gm = np.concatenate([G[:, r.integers(G.shape[1], size=take)], r.integers(0, 3, size=(S, V - take))], axis=1)
+    frac = float(r.choice([0.0, 0.0, 0.03, 0.5, 1.0]))
+    has_gp = np.ones(S, dtype=np.uint8)
+    has_gp[r.random(S) < frac] = 0
+    q = types.SimpleNamespace(S=S, gp=synth.gt_to_gp(Gm, 0.1), truth={"G": Gm})
+    if r.random() < 0.2:
+        mode, gp = "zeros", q.gp
+        z = r.random((S, V)) < 0.3
+        first = r.integers(0, 3, size=(S, V))
+        second = (first + r.integers(0, 3, size=(S, V))) % 3       # (the same place one time in three: one zero, else two)
+        i, j = np.nonzero(z)
+        gp[i, j, first[z]] = 0.0
+        gp[i, j, second[z]] = 0.0
+        gp[r.integers(S, size=3), r.integers(V, size=3), :] = 0.0
+    else:
+        mode = _gp_mode(r, q, V)
+    gp = np.ascontiguousarray(q.gp)
+    cols = np.ascontiguousarray(gp[has_gp != 0].transpose(1, 0, 2))   # [V][markers with genotypes][3]
+    seen, twin = {}, np.arange(V)
+    for v in range(V):
+        twin[v] = seen.setdefault(cols[v].tobytes(), v)              # the first donor with the same bytes
+    gp[has_gp == 0] = np.nan
+    return dict(V=V, tile=tile, mode=mode, gp=gp, has_gp=has_gp, twin=twin, dup_pairs=int((twin != np.arange(V)).sum()),
+                missing=frac, slab=table_slab_mb(seed, "fmx"))
+
+
+def _match_call(e, m):
+    """the call at the case's tile size and budget; a duplicated donor's column is its twin's, byte for byte"""
+    with slab_env("MUXGL_FMX_SLAB_MB", m["slab"]), slab_env("MUXGL_FMX_MATCH_TILE", str(m["tile"])):
+        got = e.fmx_match_donors()
+    assert got["ll"].shape[1] == m["V"]
+    assert got["ll"].tobytes() == np.ascontiguousarray(got["ll"][:, m["twin"]]).tobytes(), "columns of duplicated donors differ"
+    return got
+
+
+def _match_worst(got, gls, cnt, m, af, tol, what):
+    """every element against restate_match: nsnps equal, -inf exactly where the restatement has it, NaN and +inf nowhere,
+    every finite element within tol; the worst deviation"""
+    ll, ll0, nsnps = restate_match(gls, cnt, m["gp"], m["has_gp"], af)
+    assert np.array_equal(got["nsnps"], nsnps), (what, "nsnps")
+    worst = 0.0
+    for g, w in ((got["ll"], ll), (got["ll0"], ll0)):
+        assert g.shape == w.shape and not np.isnan(g).any() and not np.isposinf(g).any(), what
+        assert np.array_equal(np.isneginf(g), np.isneginf(w)), (what, "-inf")
+        fin = np.isfinite(w)
+        if fin.any():
+            worst = max(worst, float(np.max(np.abs(g[fin] - w[fin]))))
+    assert worst <= tol, (what, worst)
+    return worst
+
+
+def _ref_cplp(w):
+    """(gls, counts) of a cluster pileup of the reference, as Engine.fmx_cluster_pileup() shapes them (_check_cplp)"""
+    return w["gls"], np.stack([w["nreads"], w["nref"], w["nalt"]], axis=-1)
+
+
+def _match_elsewhere(eng, m, clust, K, p, w):
+    """a group or a set of ranks does not answer the call: the assignment `clust` (the last iteration's) loaded into the
+    plain engine, which holds the case's pileup since the start, and scored there; (match, match_ref)"""
+    eng.fmx_set_clusters(K, np.ascontiguousarray(clust, dtype=np.int32))
+    eng.demux_set_gp(m["gp"], m["has_gp"])
+    got = _match_call(eng, m)
+    g, c = eng.fmx_cluster_pileup()
+    _check_cplp(g, c, w)
+    return (_match_worst(got, g, c, m, p.af, TABLE_TOL["match"], "plain engine, own pileups"),
+            _match_worst(got, *_ref_cplp(w), m, p.af, TABLE_TOL["match_ref"], "plain engine, reference's pileups"),
+            int(np.isneginf(got["ll"]).sum()))
+
+
 def fmx_case(seed):
     r = np.random.default_rng([seed, 78])
     K = int(r.choice(FMX_K))
@@ -306,6 +419,8 @@ def _run_fmx(eng, info, p, ref, trace):
                greedy_near=[int(x) for x in eng.fmx_greedy_stats()])
     worst, near, sng_worst = 0.0, 0, 0.0
     slab = table_slab_mb(info["seed"], "fmx")
+    m = match_case(info["seed"], info, p) if info.get("kind") == "fmx" else None   # (the streamed cases: no panel)
+    match_worst = match_ref_worst = match_neginf = None
     jd = np.arange(K)
     jd = jd * (jd + 1) // 2 + jd   # the singlets among the reference's llks[K (K + 1) / 2]
     if how == "shard":
@@ -319,6 +434,11 @@ def _run_fmx(eng, info, p, ref, trace):
                 e.fmx_prepare(p.af)
                 e.fmx_set_shard(*c_ranges[r], *s_ranges[r])
                 e.fmx_set_clusters(K, clust)
+            if m is not None:   # refused by name on a rank whose range is not everything; the ranks run on as before
+                part = next(r for r in range(world) if (*c_ranges[r], *s_ranges[r]) != (0, p.C, 0, p.S))
+                engs[part].demux_set_gp(m["gp"], m["has_gp"])
+                with pytest.raises(muxgl.MuxglError, match="muxgl_fmx_match_donors: not available on a sharded handle"):
+                    engs[part].fmx_match_donors()
             assigned = np.asarray(clust)
             for it in range(ref["n_iter"]):
                 for e in engs:
@@ -356,6 +476,9 @@ def _run_fmx(eng, info, p, ref, trace):
                     sng = np.concatenate([e.fmx_singlets()[c_ranges[r][0]:c_ranges[r][1]] for r, e in enumerate(engs)])
                 sng_worst = max(sng_worst, parity.compare_singlet_table(sng, ref["full_ll"][it][:, jd], TABLE_TOL["fmx_sng"]))
             out["exact"] = [int(sum(e.fmx_exact_stats()[k] for e in engs)) for k in range(3)]
+            if m is not None and ref["n_iter"] > 0:
+                match_worst, match_ref_worst, match_neginf = _match_elsewhere(eng, m, cells["clust"], K, p,
+                                                                              ref["cplp"][ref["n_iter"] - 1])
             if stream:   # (asked last: a refused fetch has already taken the iteration's open near ties into the count)
                 for e in engs:
                     with pytest.raises(muxgl.MuxglError, match="full_ll"):
@@ -372,6 +495,11 @@ def _run_fmx(eng, info, p, ref, trace):
                 # (a device group settles near-tied scores as one device does: the same bits)
                 assert np.array_equal(g0, llk0) and np.array_equal(g2, llk2), "scores of the group / flagged engine differ"
             run.fmx_set_clusters(K, clust)
+            if m is not None:
+                run.demux_set_gp(m["gp"], m["has_gp"])   # once: the iterations below must still be the reference's
+                if how == "group":
+                    with pytest.raises(muxgl.MuxglError, match="muxgl_fmx_match_donors: not available on a device group"):
+                        run.fmx_match_donors()
             if stream:   # refused before anything runs: the same handle then makes the iterations
                 with pytest.raises(muxgl.MuxglError, match="full_ll"):
                     run.fmx_iterate(dp, ge, want_full_ll=True)
@@ -392,12 +520,26 @@ def _run_fmx(eng, info, p, ref, trace):
                 with slab_env("MUXGL_FMX_SLAB_MB", slab):
                     sng = run.fmx_singlets()
                 sng_worst = max(sng_worst, parity.compare_singlet_table(sng, ref["full_ll"][it][:, jd], TABLE_TOL["fmx_sng"]))
+                if m is not None and how == "one":   # the table of this iteration's pileups, on the running handle
+                    got = _match_call(run, m)
+                    match_worst = max(match_worst or 0.0, _match_worst(got, g, c, m, p.af, TABLE_TOL["match"],
+                                                                       f"iteration {it}, own pileups"))
+                    if it == ref["n_iter"] - 1:
+                        match_neginf = int(np.isneginf(got["ll"]).sum())
+                        match_ref_worst = _match_worst(got, *_ref_cplp(ref["cplp"][it]), m, p.af, TABLE_TOL["match_ref"],
+                                                       f"iteration {it}, reference's pileups")
             out["exact"] = [int(x) for x in run.fmx_exact_stats()]
+            if m is not None and how == "group" and ref["n_iter"] > 0:
+                match_worst, match_ref_worst, match_neginf = _match_elsewhere(eng, m, cells["clust"], K, p,
+                                                                              ref["cplp"][ref["n_iter"] - 1])
         finally:
             if own:
                 run.close()
     assert worst < 1e-7, worst
     out.update(ll=worst, near=near, fmx_sng_ll=sng_worst, table_slab_mb=slab)
+    if m is not None:
+        out.update(match_ll=match_worst, match_ref_ll=match_ref_worst, match_v=m["V"], match_tile=m["tile"],
+                   match_mode=m["mode"], match_dup=m["dup_pairs"], match_missing=m["missing"], match_neginf=match_neginf)
     return out
 
 
