@@ -475,6 +475,41 @@ int muxgl_fmx_get_cluster_pileup(muxgl_handle* h, double* gls, int32_t* counts);
  * nothing proportional to K x S x V.  All three outputs are bit-identical from call to call and for any budget. */
 int muxgl_fmx_match_donors(muxgl_handle* h, double* ll /*[K][V]*/, double* ll0 /*[K]*/, int32_t* nsnps /*[K]*/, float* kernel_ms);
 
+/* Did the run split one donor over two clusters: every pair of cluster pileups scored as "one individual" against "two
+ * unrelated individuals", the pairwise Bayes factor of freemuxlet-old (cmd_cram_freemuxlet.cpp:186-221, dropD.llk2, .llk0,
+ * .nsnps) with clusters in the place of droplets.  The pair a > b is stored at a (a - 1) / 2 + b, the indexing of
+ * muxgl_dropd.  With gls[K][S][9], counts[K][S][3] exactly as muxgl_fmx_get_cluster_pileup returns them at the moment of
+ * the call and af[S] of muxgl_fmx_prepare:
+ *   U(k)       = { s : counts[k][s][0] > 0 },  L_k,g = gls[k][s][4 g],  p = ((1-af)^2, 2 af (1-af), af^2)   (gps, :200-203)
+ *   nsnps[a,b] = |U(a) n U(b)|
+ *   llk2[a,b]  = sum over s in U(a) n U(b) of log( sum_g p_g L_a,g L_b,g )                         (lk2 of :206)
+ *   llk0[a,b]  = sum over the same s of log( sum_gi sum_gj p_gi p_gj L_a,gi L_b,gj )               (lk0 of :208), formed as
+ *                (sum_g p_g L_a,g) (sum_g p_g L_b,g)
+ * llk2 - llk0 is the log Bayes factor "a and b are one donor" against "two unrelated donors": positive for a split donor
+ * (the reference's threshold is --bf-thres, 5.41).
+ * The rules of muxgl_fmx_match_donors carry over word for word.  A cluster without cells has U = {}: each of its pairs
+ * gets 0, 0, 0.  K = 1 has no pair and the call succeeds.  No NaN and no +inf; a factor that is exactly 0 gives -inf,
+ * which cannot arise for af in [0, 1] because the merge clamps every pileup element to 1e-6.  Any output may be NULL (all
+ * three: the call succeeds and writes nothing).  kernel_ms (NULL allowed) receives the hipEvent time of the call's
+ * kernels, from a pair of events the call creates and destroys itself: no slot of muxgl_get_timing /
+ * muxgl_get_timing_sum is touched and the call is not a collecting one.
+ * It needs muxgl_set_pileup, muxgl_fmx_prepare and muxgl_fmx_set_clusters on the same handle (no GP tensor), and scores
+ * the pileups as they are now.  One device, whole pileup: it fails, naming the reason and leaving the handle usable, on a
+ * device group, a slabbed handle and a handle whose muxgl_fmx_set_shard range is not everything (their cluster pileups are
+ * cut by SNP range, and ranges summed in rank order would round differently), for a NULL handle and when one of the three
+ * prerequisites is missing.
+ * It reads state and changes none: records, counters, assignments, cluster pileups, MUXGL_BUF_CGP, the near-tie
+ * bookkeeping and whether muxgl_fmx_singlets / muxgl_fmx_inclusion may run stay bit for bit what they were.  Under
+ * MUXGL_FLAG_ASYNC_PHASES it returns with the stream drained.
+ * The values are the device's arithmetic (products of factors, one log per pair, product and part of 2048 consecutive
+ * SNPs, the parts added in ascending SNP order).  Device memory beyond the inputs: one membership bit per (SNP, cluster),
+ * one block of 64 partner clusters packed as 1536 S bytes, the triangle of results (20 bytes per pair), and per row cluster
+ * of a batch the logs and counts of its parts, batches sized to the streamed E-step's budget (MUXGL_FMX_SLAB_MB); nothing
+ * proportional to K x K x S.  All three outputs are bit-identical from call to call, for any budget and tile size
+ * (MUXGL_FMX_PAIRS_TILE). */
+int muxgl_fmx_cluster_pairs(muxgl_handle* h, double* llk2 /*[K(K-1)/2]*/, double* llk0 /*[K(K-1)/2]*/,
+                            int32_t* nsnps /*[K(K-1)/2]*/, float* kernel_ms);
+
 /* ---- freemuxlet-old (`popscle freemuxlet-old`, cmd_cram_freemuxlet.cpp): the parts that differ from freemux2.  The
  *      entry pileups, scores and the EM loop are the calls above (geno_error = 0 except in the tenth and last
  *      iteration, no early stop: cmd_cram_freemuxlet.cpp:457,485,500); what is particular to the old command is its

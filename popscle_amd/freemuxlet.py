@@ -332,3 +332,57 @@ def match_table(ll, ll0, nsnps=None):
         best_clust = live[np.argmax(llr[live], axis=0)]  # (argmax: first = lowest cluster index on ties)
     reciprocal = np.array([best[k] >= 0 and best_clust[best[k]] == k for k in range(K)], dtype=bool)
     return dict(best=best, next=nxt, best_llr=best_llr, next_llr=next_llr, post=post, reciprocal=reciprocal)
+
+
+def cluster_pair_table(llk2, llk0, nsnps=None, thres=5.41):
+    """Which clusters are one donor, from Engine.fmx_cluster_pairs' tables (pure numpy).  llk2, llk0 [K (K - 1) / 2] with the
+    pair a > b at a (a - 1) / 2 + b; thres is the reference's --bf-thres default.  Returns a dict: diff float64 [K][K], the
+    symmetric matrix of llk2 - llk0 (the log Bayes factor "one donor" against "two unrelated donors") with a NaN diagonal;
+    partner int32 [K] and partner_diff float64 [K], per cluster the other cluster with the largest diff and that diff;
+    group int32 [K] and groups (a list of lists of cluster indices), the connected components of the pairs with diff >
+    thres.  Tie rules: equal diffs go to the lower partner index; a diff equal to thres does not link; a pair without a
+    shared marker (nsnps == 0 where nsnps is given, else llk2 == llk0 == 0) carries no evidence, never links and is nobody's
+    partner, so a cluster whose pairs are all of that kind (one without cells) has partner -1, partner_diff NaN and a
+    group of its own; -inf - -inf counts as -inf.  Groups are numbered in the order of their smallest member and list
+    their members in ascending order."""
+    llk2 = np.asarray(llk2, dtype=np.float64).ravel()
+    llk0 = np.asarray(llk0, dtype=np.float64).ravel()
+    n = llk2.size
+    K = int(round((1.0 + np.sqrt(1.0 + 8.0 * n)) / 2.0))
+    if llk0.size != n or K * (K - 1) // 2 != n:
+        raise ValueError("llk2 and llk0 must both be [K (K - 1) / 2]")
+    if nsnps is not None and np.asarray(nsnps).size != n:
+        raise ValueError("nsnps must be [K (K - 1) / 2]")
+    none = (np.asarray(nsnps).ravel() == 0) if nsnps is not None else ((llk2 == 0.0) & (llk0 == 0.0))
+    with np.errstate(invalid="ignore"):
+        d = llk2 - llk0
+    d = np.where(np.isnan(d), -np.inf, d)
+    a, b = np.tril_indices(K, -1)  # row-major over the lower triangle: exactly the order a (a - 1) / 2 + b
+    diff = np.full((K, K), np.nan)
+    diff[a, b] = diff[b, a] = d
+    seen = np.zeros((K, K), dtype=bool)
+    seen[a, b] = seen[b, a] = ~none
+    partner = np.full(K, -1, dtype=np.int32)
+    partner_diff = np.full(K, np.nan)
+    for k in range(K):
+        cand = np.flatnonzero(seen[k])
+        if cand.size:
+            partner[k] = cand[np.argmax(diff[k, cand])]  # (argmax: the first, i.e. the lowest index, on ties)
+            partner_diff[k] = diff[k, partner[k]]
+    root = list(range(K))
+
+    def find(x):
+        while root[x] != x:
+            root[x] = root[root[x]]
+            x = root[x]
+        return x
+
+    for i in np.flatnonzero(~none & (d > thres)):
+        ra, rb = find(int(a[i])), find(int(b[i]))
+        if ra != rb:
+            root[max(ra, rb)] = min(ra, rb)  # (the root of a group is its smallest member)
+    roots = [find(k) for k in range(K)]
+    order = sorted(set(roots))
+    group = np.array([order.index(r) for r in roots], dtype=np.int32)
+    groups = [[k for k in range(K) if roots[k] == r] for r in order]
+    return dict(diff=diff, partner=partner, partner_diff=partner_diff, group=group, groups=groups)

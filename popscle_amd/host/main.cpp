@@ -26,6 +26,11 @@
 //       doublet, cmd_cram_freemux2.cpp:469-513).  Columns BARCODE, CLUST, NUM.SNPS, NUM.READS, LLK.INCL (%.4lf),
 //       POSTPRB.INCL (%.3lg, exp(incl - tot)), DBL.PARTNER (cluster), DBL.LLK (%.4lf); the last two are NA where no
 //       doublet hypothesis holds the cluster (one cluster)
+//       --write-cluster-pairs: did the run split one donor over two clusters.  After the EM every pair of final cluster
+//       pileups is scored as one donor against two unrelated donors on the device (muxgl_fmx_cluster_pairs).  Writes
+//       <O>.clust1.ldist.gz (BGZF), one row per pair a > b in ascending (a, b) order: ID1, ID2, NSNP (markers both have
+//       reads at), LLK0, LLK2, LDIFF = LLK2 - LLK0 (%.2lf), DIFF.SNP (%.4lf): the reference's .ldist.gz row
+//       (cmd_cram_freemuxlet.cpp:268) without its read-count columns.  One device only
 //       --match-vcf FILE: which cluster is which donor.  FILE holds genotypes of some or all pooled donors; it is read with
 //       demuxlet's genotype flags and their meanings (--field, --sm, --sm-list, --geno-error-offset, --geno-error-coeff,
 //       --r2-info, --min-mac, --min-callrate; known to freemuxlet only next to --match-vcf) by the demuxlet loader, and after
@@ -459,6 +464,7 @@ int cmd_freemuxlet(int argc, char** argv) {
   bool auxFiles = false, keepInitMissing = false, randomizeSingletScore = false, noEarlyStop = false;
   bool writeSinglets = false;  // (ours) <out>.clust1.sing2.gz: every droplet against every cluster
   bool writeInclusion = false;  // (ours) <out>.clust1.incl.gz: per-cluster marginals of the last E-step's pair triangle
+  bool writeClusterPairs = false;  // (ours) <out>.clust1.ldist.gz: every pair of final clusters as one donor or two
   VcfReader vr;  // (ours) --match-vcf: genotypes of pooled donors the final clusters are scored against
   std::vector<std::string> smIDs;
   std::string smList;
@@ -482,6 +488,7 @@ int cmd_freemuxlet(int argc, char** argv) {
   a.add_bool("aux-files", &auxFiles);
   a.add_bool("write-singlets", &writeSinglets);
   a.add_bool("write-inclusion", &writeInclusion);
+  a.add_bool("write-cluster-pairs", &writeClusterPairs);
   a.add_int("verbose", &verbose);
   a.add_double("doublet-prior", &doublet_prior);
   a.add_double("geno-error", &geno_error);
@@ -502,6 +509,9 @@ int cmd_freemuxlet(int argc, char** argv) {
   if (wantMatch && cf.grouped())
     fatal("freemuxlet: --match-vcf is not available with --devices naming more than one device: a group's cluster pileups "
           "are cut by SNP range (muxgl_fmx_match_donors scores the whole pileup on one device); run it on one device");
+  if (writeClusterPairs && cf.grouped())
+    fatal("freemuxlet: --write-cluster-pairs is not available with --devices naming more than one device: "
+          "muxgl_fmx_cluster_pairs: not available on a device group (use a one-device handle)");
 
   Pileup p;
   StageTimer tmr;
@@ -790,6 +800,24 @@ int cmd_freemuxlet(int argc, char** argv) {
     }
     wb.close();
     tmr.lap("freemuxlet: write .clust1.match.gz + .clust1.match.best.gz");
+  }
+  if (writeClusterPairs) {
+    // .clust1.ldist.gz: the final cluster pileups against each other, the row of the reference's .ldist.gz
+    // (cmd_cram_freemuxlet.cpp:268) without its read-count columns, one row per pair a > b in ascending (a, b) order
+    const size_t Kz = (size_t)K, np = Kz * (Kz - 1) / 2;
+    std::vector<double> l2(np), l0(np);
+    std::vector<int32_t> ns(np);
+    float kms = 0.f;
+    check(h, muxgl_fmx_cluster_pairs(h, l2.data(), l0.data(), ns.data(), &kms), "muxgl_fmx_cluster_pairs");
+    tmr.lap("freemuxlet: muxgl_fmx_cluster_pairs");
+    OutFile wp(cf.outPrefix + ".clust1.ldist.gz", true);
+    wp.printf("ID1\tID2\tNSNP\tLLK0\tLLK2\tLDIFF\tDIFF.SNP\n");
+    for (size_t a = 1, i = 0; a < Kz; ++a)
+      for (size_t b = 0; b < a; ++b, ++i)
+        wp.printf("%d\t%d\t%d\t%.2lf\t%.2lf\t%.2lf\t%.4lf\n", (int)a, (int)b, ns[i], l0[i], l2[i], l2[i] - l0[i],
+                  (l2[i] - l0[i]) / (ns[i] + 1e-6));
+    wp.close();
+    tmr.lap("freemuxlet: write .clust1.ldist.gz");
   }
   muxgl_destroy(h);
   return 0;
@@ -1204,6 +1232,8 @@ int main(int argc, char** argv) {
                     "    against every cluster in the last iteration (BARCODE CLUST NUM.SNPS NUM.READS LLK1 POSTPRB)\n"
                     "  freemuxlet --match-vcf FILE [demuxlet's genotype flags]: also <out>.clust1.match.gz and .clust1.match.best.gz,\n"
                     "      the final clusters scored against the donors' genotypes in FILE (one device)\n"
+                    "  freemuxlet --write-cluster-pairs: also <out>.clust1.ldist.gz, every pair of final clusters as one donor\n"
+                    "    against two unrelated donors (ID1 ID2 NSNP LLK0 LLK2 LDIFF DIFF.SNP; one device)\n"
                     "  freemuxlet --write-inclusion: also <out>.clust1.incl.gz, per droplet and cluster the evidence that the\n"
                     "    cluster is in the droplet and the cluster it pairs best with, in the last iteration (BARCODE CLUST\n"
                     "    NUM.SNPS NUM.READS LLK.INCL POSTPRB.INCL DBL.PARTNER DBL.LLK)\n");

@@ -110,6 +110,7 @@ SYMBOLS = {
     "muxgl_fmx_inclusion": (C.c_int, [_VP, C.POINTER(_FmxParams), _VP, _VP, _VP, _VP]),
     "muxgl_fmx_get_cluster_pileup": (C.c_int, [_VP, _VP, _VP]),
     "muxgl_fmx_match_donors": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    "muxgl_fmx_cluster_pairs": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
     "muxgl_fmx_exact_stats": (C.c_int, [_VP, _VP, _VP, _VP]),
     "muxgl_fmx_exact_pending": (C.c_int, [_VP, _VP]),
     "muxgl_fmx_exact_hint": (C.c_int, [_VP, C.c_int32]),
@@ -604,6 +605,24 @@ class Engine:
             out["nsnps"] = np.zeros(self.K, dtype=np.int32)
         ms = C.c_float(0.0)
         self._check(self.lib.muxgl_fmx_match_donors(self.h, *[_ptr(out.get(n)) for n in self.FMX_MATCH_FIELDS], C.byref(ms)))
+        out["kernel_ms"] = float(ms.value)
+        return out
+
+    FMX_PAIRS_FIELDS = ("llk2", "llk0", "nsnps")
+
+    def fmx_cluster_pairs(self, want=FMX_PAIRS_FIELDS):
+        """muxgl_fmx_cluster_pairs: every pair of the cluster pileups as they are now scored as one donor against two
+        unrelated donors (include/muxgl.h).  dict of llk2, llk0 float64 and nsnps int32, each [K (K - 1) / 2] with the
+        pair a > b at a (a - 1) / 2 + b (llk2 - llk0 is the log Bayes factor of "one donor", over the nsnps markers both
+        clusters have reads at), and kernel_ms, the event time of the call's kernels.  want: the subset of the three to
+        fetch (the others are passed as NULL).  freemuxlet.cluster_pair_table() turns them into a matrix and groups."""
+        unknown = set(want) - set(self.FMX_PAIRS_FIELDS)
+        if unknown:
+            raise ValueError(f"unknown pair fields {sorted(unknown)}")
+        n = self.K * (self.K - 1) // 2
+        out = {f: np.zeros(n, dtype=np.int32 if f == "nsnps" else np.float64) for f in self.FMX_PAIRS_FIELDS if f in want}
+        ms = C.c_float(0.0)
+        self._check(self.lib.muxgl_fmx_cluster_pairs(self.h, *[_ptr(out.get(f)) for f in self.FMX_PAIRS_FIELDS], C.byref(ms)))
         out["kernel_ms"] = float(ms.value)
         return out
 
