@@ -155,8 +155,14 @@ typedef struct {
 /* kernel timings of the most recent *_run / *_iterate call, milliseconds, measured with hipEvents recorded on the
  * stream the kernels were launched on */
 enum {
-  MUXGL_T_DEMUX_REDUCE = 0, /* row path only: chunk partial log-likelihoods summed per cell */
-  MUXGL_T_DEMUX_SWEEP = 1,  /* per-entry likelihoods (a4,a5) fused with the sample-pair x alpha sweep (a6) */
+  MUXGL_T_DEMUX_REDUCE = 0, /* row and default-grid paths: chunk partials folded per cell (default grid: and the call).
+                               Where the default-grid path runs its cells as two groups on two streams (below,
+                               muxgl_demux_oct_split) the first group's share runs underneath the second group's sweep:
+                               the slot is then what remained of the step's device time behind the end of the last
+                               sweep, i.e. the exposed part */
+  MUXGL_T_DEMUX_SWEEP = 1,  /* per-entry likelihoods (a4,a5) fused with the sample-pair x alpha sweep (a6); with two cell
+                               groups: from the start of the step to the end of the later of the two sweeps (the later
+                               of two elapsed times, taken on the host).  SWEEP and REDUCE never overlap */
   MUXGL_T_DEMUX_CALL = 2,  /* evidence sums, best/next scans, call (a7-a9) */
   MUXGL_T_DEMUX_D2H = 3,   /* per-cell records to host */
   MUXGL_T_FMX_ENTRY = 4,   /* entry 9-GL pileup + cell scores (b1,b2) */
@@ -274,6 +280,15 @@ int muxgl_demux_exact_calls(int64_t C, int32_t V, const int64_t* cell_ptr, const
 
 /* pinned host view of the last run's [C] records (valid until the next run or destroy) */
 const muxgl_demux_cell* muxgl_demux_results(const muxgl_handle* h);
+
+/* What the most recent muxgl_demux_run did on the default-grid path (V <= 32, alpha {0, 0.5}), for tests and tuning:
+ * info[0] = the first cell of the second cell group of the plan (0: one group), info[1] = the cell groups that run used
+ * (1 or 2; 1 as well when the LL tensor was asked for, and always under MUXGL_FLAG_NO_LINEAR_ENTRIES, whose plan has no
+ * launch order), info[2] = the sweep units the device holds at once (one residency round), info[3] = the plan's units.
+ * The boundary follows from info[2] and the plan; the environment variable MUXGL_OCT_SPLIT=<cell index>, read when the
+ * plan is built (first run after muxgl_set_pileup / muxgl_demux_set_gp), places it explicitly, 0 forces one group.
+ * Records do not depend on it.  Zeros before the first run, on other paths' plans and for a device group. */
+int muxgl_demux_oct_split(const muxgl_handle* h, int64_t* info);
 
 /* per-entry pGs[nnz][n_alpha*9] of the last run (cmd_cram_demuxlet.cpp:655-725), for parity tests */
 int muxgl_demux_get_entry_pg(muxgl_handle* h, double* pg);

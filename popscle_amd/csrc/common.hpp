@@ -78,6 +78,12 @@ struct muxgl_row_state {
   int32_t* d_chunk_pos = nullptr;       // position of every chunk in its cell's list: where the oct kernel leaves its partials
   size_t part_cap = 0, part_e_cap = 0;
   int64_t n_chunks = 0;
+  // oct sweep as a pipeline of two cell groups (demux_oct.hip, built with d_quad_order): cells [0, oct_cut) and the rest;
+  // 0: one group.  Group g's units are [oct_unit0[g], oct_unit0[g + 1]), each range a multiple of eight.
+  int64_t oct_cut = 0;
+  int64_t oct_unit0[3] = {0, 0, 0};
+  int64_t oct_round = 0;                // units of one residency round of the sweep kernel on this device
+  int oct_groups_run = 0;               // cell groups of the last run (1 or 2)
 };
 
 // what a handle's pileup is (muxgl_fmx_set_column_slab / device groups): the whole pileup, the cell-major row slab of a
@@ -111,6 +117,13 @@ struct muxgl_handle {
   int device = 0;
   hipStream_t stream = nullptr;
   bool owns_stream = true;
+  // the sweep of the oct path's second cell group (demux_oct.hip) runs on a stream of the handle's own, forked from
+  // `stream` and joined back into it before the launcher returns: every other call sees one stream.  Stream and events
+  // are made by the first two-group run (a handle that never takes that path has none) and go with the handle
+  hipStream_t stream2 = nullptr;
+  hipEvent_t ev_fork = nullptr;    // the fork where no timing event is recorded (MUXGL_NO_EVENTS)
+  hipEvent_t ev_sweep2 = nullptr;  // end of the second group's sweep: a time stamp, and the join
+  bool split_timed = false;  // the brackets SWEEP / REDUCE of this run are those of a two-group run (collect_timing)
   std::string err;
   int role = MUXGL_ROLE_FULL;
   muxgl_handle* col = nullptr;         // column slab of a slabbed handle (owned; same device, same stream)
@@ -377,6 +390,7 @@ static inline void toc(muxgl_handle* h, int id) {
   (void)hipEventRecord(h->ev[2 * id + 1], h->stream);
 }
 static inline void clear_timing(muxgl_handle* h) {
+  h->split_timed = false;
   for (int i = 0; i < MUXGL_T_COUNT; ++i) {
     h->ev_used[i] = false;
     h->ms[i] = 0.f;
@@ -387,6 +401,25 @@ static inline void clear_timing(muxgl_handle* h) {
 // the elapsed-time query succeeds; ms[] keeps the last value of every slot until clear_timing.  ms_calls counts the
 // collecting calls (include/muxgl.h says which entry points those are).
 static inline void collect_timing(muxgl_handle* h) {
+  if (h->split_timed) {
+    // The oct sweep ran as two cell groups on two streams (demux_oct.hip).  With A = the start (start event of SWEEP),
+    // E1 / E2 = the ends of the two sweeps (stop event of SWEEP, ev_sweep2) and F = the end of the step behind the join
+    // (stop event of REDUCE): SWEEP = max(E1, E2) - A, the later of two elapsed times taken here on the host -- no wait
+    // on the device orders the first group's finish behind the second group's sweep --, REDUCE = F - A - SWEEP.
+    h->split_timed = false;
+    h->ev_used[MUXGL_T_DEMUX_SWEEP] = h->ev_used[MUXGL_T_DEMUX_REDUCE] = false;
+    float t1 = 0.f, t2 = 0.f, tf = 0.f;
+    hipEvent_t a = h->ev[2 * MUXGL_T_DEMUX_SWEEP];
+    if (hipEventElapsedTime(&t1, a, h->ev[2 * MUXGL_T_DEMUX_SWEEP + 1]) == hipSuccess &&
+        hipEventElapsedTime(&t2, a, h->ev_sweep2) == hipSuccess &&
+        hipEventElapsedTime(&tf, a, h->ev[2 * MUXGL_T_DEMUX_REDUCE + 1]) == hipSuccess) {
+      const float ts = t1 > t2 ? t1 : t2, tr = tf > ts ? tf - ts : 0.f;
+      h->ms[MUXGL_T_DEMUX_SWEEP] = ts;
+      h->ms_sum[MUXGL_T_DEMUX_SWEEP] += (double)ts;
+      h->ms[MUXGL_T_DEMUX_REDUCE] = tr;
+      h->ms_sum[MUXGL_T_DEMUX_REDUCE] += (double)tr;
+    }
+  }
   for (int i = 0; i < MUXGL_T_COUNT; ++i) {
     if (h->ev_used[i]) {
       h->ev_used[i] = false;
@@ -585,6 +618,7 @@ int demux_row_launch(muxgl_handle* h, const muxgl_demux_params* p);
 void demux_row_free(muxgl_handle* h);
 int demux_row_build(muxgl_handle* h, muxgl_row_state** st, int64_t c0, int64_t c1, int ch);
 int demux_oct_launch(muxgl_handle* h, const muxgl_demux_params* p);
+int demux_oct_split_info(const muxgl_handle* h, int64_t* out);  // muxgl_demux_oct_split
 int demux_row2_launch(muxgl_handle* h, const muxgl_demux_params* p);  // (demux_row2.hip)
 double row2_part_bytes(const muxgl_row_state* st);  // chunk partials of the two-per-lane row kernels (demux_row2.hip)
 int demux_call16_launch(muxgl_handle* h, const muxgl_demux_params* p);
@@ -610,7 +644,8 @@ int demux_gp_neutral_rows(muxgl_handle* h, int V);  // d_gp rows of markers with
 void demux_row_release(muxgl_row_state** st);
 int plan_build_chunks(muxgl_handle* h, muxgl_row_state* st, int64_t cb, int64_t ce, int ch);  // chunk tables (plan_kernels.hip)
 int plan_build_qent(muxgl_handle* h);       // packed entry records of the quad kernel, on the device (plan_kernels.hip)
-int quad_launch_order(muxgl_handle* h, const row_chunk* d_chunks, const int32_t* d_nlin, int64_t n, int32_t** order);
+int quad_launch_order(muxgl_handle* h, const row_chunk* d_chunks, const int32_t* d_nlin, int64_t n, int32_t** order,
+                      int64_t cut = 0);  // cut > 0: the chunks of cells below `cut` first
 int plan_build_lin(muxgl_handle* h);        // d_lin (plan_kernels.hip)
 int plan_build_bit_streams(muxgl_handle* h, const uint32_t* bits, int64_t** rank, fmx_grec** rec_set, fmx_grec** rec_clr,
                            int64_t* n_set);

@@ -154,21 +154,35 @@ __global__ void __launch_bounds__(64)
 
 // Launch order: a wave's trip counts are the maxima over its chunks, so within every bucket of QUAD_BUCKET
 // consecutive chunks of the plan's order (ascending first SNP -- the rows gathered by co-resident workgroups stay a
-// sliding window at that grain) the chunks are sorted by their number of non-linear batches.
+// sliding window at that grain) the chunks are sorted by their number of non-linear batches.  Above the bucket: the
+// chunk's cell group (cut > 0: cells below `cut` first, oct_launch_t); inside a group the order is the same.
 constexpr int QUAD_BUCKET = 1024;
 __global__ void __launch_bounds__(256)
-    quad_order_key_kernel(int n_chunks, int bucket, const row_chunk* __restrict__ chunks,
+    quad_order_key_kernel(int n_chunks, int bucket, int cut, const row_chunk* __restrict__ chunks,
                           const int32_t* __restrict__ chunk_nlin, uint64_t* __restrict__ key, int32_t* __restrict__ iota) {
   const int w = blockIdx.x * blockDim.x + threadIdx.x;
   if (w >= n_chunks) return;
   const int nl = chunk_nlin[w], len = chunks[w].len;
   const uint64_t bg = (uint64_t)min(len - nl, 1023), bl = (uint64_t)min(nl, 1023);
-  key[w] = ((uint64_t)(w / bucket) << 40) | ((1023u - bg) << 30) | ((1023u - bl) << 20) | (uint64_t)(w % bucket);
+  const uint64_t grp = (cut > 0 && chunks[w].cell >= cut) ? 1u : 0u;
+  key[w] = (grp << 62) | ((uint64_t)(w / bucket) << 40) | ((1023u - bg) << 30) | ((1023u - bl) << 20) | (uint64_t)(w % bucket);
   iota[w] = w;
 }
 
+// The launch order by unit slot: the sorted order holds the n1 chunks of the first cell group, then the others; the
+// second group's units start at slot w2 (a unit boundary behind the first group's, padded to eight units).  No unit
+// holds chunks of two groups; a slot without a chunk holds n_chunks.  (One group: n1 = n_chunks.)
+__global__ void __launch_bounds__(256)
+    oct_pad_order_kernel(int n_slots, int n_chunks, int n1, int w2, const int32_t* __restrict__ sorted,
+                         int32_t* __restrict__ order) {
+  const int w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= n_slots) return;
+  const int i = w < w2 ? (w < n1 ? w : n_chunks) : w - w2 + n1;
+  order[w] = i < n_chunks ? sorted[i] : n_chunks;
+}
+
 // Steps of a unit's linear loop: the longest linear list among its eight chunks, rounded to the loop's unrolling, plus
-// the read-ahead (0 for a unit without linear entries).
+// the read-ahead (0 for a unit without linear entries).  order: by unit slot (oct_pad_order_kernel).
 __global__ void __launch_bounds__(256)
     oct_unit_steps_kernel(int n_units, int n_chunks, int slots, const int32_t* __restrict__ order,
                           const int32_t* __restrict__ nlin, int32_t* __restrict__ steps) {
@@ -176,8 +190,8 @@ __global__ void __launch_bounds__(256)
   if (u >= n_units) return;
   int m = 0;
   for (int k = 0; k < slots; ++k) {
-    const int w = u * slots + k;
-    if (w < n_chunks) m = max(m, nlin[order[w]]);
+    const int q = order[u * slots + k];
+    if (q < n_chunks) m = max(m, nlin[q]);
   }
   steps[u] = m > 0 ? (m + 2) / 3 * 3 + O_LPAD : 0;
 }
@@ -192,11 +206,10 @@ __global__ void __launch_bounds__(256)
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int u = t / slots, slot = t % slots;
   if (u >= n_units) return;
-  const int w = u * slots + slot;
+  const int q = order[u * slots + slot];
   int64_t e0 = 0;
   int nl = 0;
-  if (w < n_chunks) {
-    const int q = order[w];
+  if (q < n_chunks) {
     e0 = chunks[q].e0;
     nl = nlin[q];
   }
@@ -229,7 +242,7 @@ __global__ void __launch_bounds__(64, P == 8 ? OCT_WAVES : 2)
     demux_oct_kernel(const row_chunk* __restrict__ chunks, int n_chunks, const quad_entry* __restrict__ qent,
                      const uint2* __restrict__ orec, const int64_t* __restrict__ unit_ptr,
                      const int32_t* __restrict__ chunk_nlin,
-                     const int32_t* __restrict__ order, const uint8_t* __restrict__ reads,
+                     const int32_t* __restrict__ order, int unit_base, const uint8_t* __restrict__ reads,
                      const double* __restrict__ gpo, const double* __restrict__ gmo,
                      const double* __restrict__ gp0s, int32_t S_dummy, const double* __restrict__ lut_g,
                      const int32_t* __restrict__ chunk_pos, uint2* __restrict__ part, int32_t* __restrict__ part_e) {
@@ -268,10 +281,12 @@ __global__ void __launch_bounds__(64, P == 8 ? OCT_WAVES : 2)
   }
   __syncthreads();  // the tables are complete
 
-  const int unit = xcd_swizzle(blockIdx.x, gridDim.x >> 3);  // eight chunks that are neighbours in the launch order
+  // eight chunks that are neighbours in the launch order; the launch covers the units of one cell group, from unit_base
+  const int unit = unit_base + xcd_swizzle(blockIdx.x, gridDim.x >> 3);
   const int wq = unit * O_SLOTS + slot;
   const uint32_t p16 = (uint32_t)p * 16u;
-  const int q = wq < n_chunks ? (order ? order[wq] : wq) : n_chunks;
+  // (order: by unit slot, n_chunks where a slot is empty -- oct_pad_order_kernel; without it the slots are the chunks)
+  const int q = order ? order[wq] : (wq < n_chunks ? wq : n_chunks);
   int64_t e0 = 0;
   int len = 0;
   int32_t qpos = 0;  // where the chunk's partials go: its position in its cell's list
@@ -879,7 +894,8 @@ __global__ void __launch_bounds__(192)
 // scans' constants in registers across that loop, and held to five waves per SIMD it spills: 0.083 ms against 0.058 ms.)
 template <int P>
 __global__ void __launch_bounds__(256)
-    demux_oct_finish_kernel(int64_t C, const int64_t* __restrict__ cell_ptr, const int64_t* __restrict__ cell_chunk_ptr,
+    demux_oct_finish_kernel(int64_t c_first, int64_t C /* cells [c_first, C) */, const int64_t* __restrict__ cell_ptr,
+                            const int64_t* __restrict__ cell_chunk_ptr,
                             const uint2* __restrict__ part, const int32_t* __restrict__ part_e,
                             const int32_t* __restrict__ slots, int V,
                             muxgl_call::call_alpha al, double doublet_prior, muxgl_demux_cell* __restrict__ out) {
@@ -907,7 +923,7 @@ __global__ void __launch_bounds__(256)
     at[i] = j * LD + k * 2 + (single ? 0 : 1);
     atm[i] = single ? at[i] : k * LD + j * 2 + 1;
   }
-  const int64_t cbase = (int64_t)blockIdx.x * QF_CELLS, c = cbase + lc;
+  const int64_t cbase = c_first + (int64_t)blockIdx.x * QF_CELLS, c = cbase + lc;
   int64_t c0 = 0, n = 0;
   if (c < C) {
     c0 = cell_chunk_ptr[c];
@@ -950,14 +966,15 @@ __global__ void __launch_bounds__(256)
   }
   __syncthreads();
   constexpr int NQ = (int)(sizeof(muxgl_demux_cell) / 16);
-  if (tid < QF_CELLS * NQ && cbase + tid / NQ < C)
+  if (tid < QF_CELLS * NQ && cbase + tid / NQ < C)  // (a record is a multiple of 16 bytes: aligned from any first cell)
     reinterpret_cast<uint4*>(out + cbase)[tid] = reinterpret_cast<const uint4*>(&rec[0])[tid];
 }
 
 }  // namespace
 
 // the launch order of the chunks of the oct / quad kernels (quad_order_key_kernel), shared with fmx_oct.hip
-int quad_launch_order(muxgl_handle* h, const row_chunk* d_chunks, const int32_t* d_nlin, int64_t n, int32_t** order) {
+int quad_launch_order(muxgl_handle* h, const row_chunk* d_chunks, const int32_t* d_nlin, int64_t n, int32_t** order,
+                      int64_t cut) {
   int32_t* d_iota = nullptr;
   uint64_t *d_key = nullptr, *d_key2 = nullptr;
   void* d_tmp = nullptr;
@@ -976,8 +993,8 @@ int quad_launch_order(muxgl_handle* h, const row_chunk* d_chunks, const int32_t*
   int bucket = QUAD_BUCKET;
   if (const char* ev = getenv("MUXGL_QUAD_BUCKET")) bucket = atoi(ev) > 0 ? atoi(ev) : bucket;  // (tuning)
   if (bucket > (1 << 20)) bucket = 1 << 20;
-  hipLaunchKernelGGL(quad_order_key_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (int)n, bucket, d_chunks,
-                     d_nlin, d_key, d_iota);
+  hipLaunchKernelGGL(quad_order_key_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (int)n, bucket,
+                     (int)cut, d_chunks, d_nlin, d_key, d_iota);
   size_t tmp_bytes = 0;
   hipError_t e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_key, d_key2, d_iota, *order, (size_t)n, 0u, 64u, h->stream);
   if (e == hipSuccess) e = dev_malloc_retry((void**)&d_tmp, tmp_bytes ? tmp_bytes : 1);
@@ -1020,41 +1037,93 @@ int oct_launch_t(muxgl_handle* h, const muxgl_demux_params* p) {
     HIPCHK(h, hipGetLastError());
   }
   const bool use_lin = h->d_lin && h->d_gmq && !(h->flags & MUXGL_FLAG_NO_LINEAR_ENTRIES);
-  const unsigned blocks = (unsigned)((((st->n_chunks + O_SLOTS - 1) / O_SLOTS) + 7) / 8 * 8);  // multiple of 8 for xcd_swizzle
+  auto kern = h->gp_unit_sums ? demux_oct_kernel<P, true> : demux_oct_kernel<P, false>;
+  auto pad8 = [](int64_t chunks) { return ((chunks + O_SLOTS - 1) / O_SLOTS + 7) / 8 * 8; };  // units, a multiple of 8 for xcd_swizzle
   if (use_lin && !st->d_chunk_nlin && st->n_chunks) {  // once per pileup and GP tensor: every chunk's linear entries first
     quad_lrec* d_lrec = nullptr;  // chunk-major records, repacked below
-    int32_t* d_steps = nullptr;
+    int32_t *d_steps = nullptr, *d_sorted = nullptr;
     auto cleanup = [&]() {
       dev_free(&d_lrec);
       dev_free(&d_steps);
+      dev_free(&d_sorted);
     };
+    auto drop_plan = [&]() {  // a failure below leaves no half-built plan behind: the next run starts over
+      cleanup();
+      dev_free(&st->d_qent_lin);
+      dev_free(&st->d_chunk_nlin);
+      dev_free(&st->d_quad_order);
+      dev_free(&st->d_unit_ptr);
+      dev_free(&st->d_orec);
+    };
+    // The cell groups of the pipeline below: cells [0, cut) and the rest; cut = 0: one group.  The two sweeps are on
+    // the device together and share its slots; what the split gains is the first group's finish run underneath the
+    // second sweep, and it gains only where that finish lands in the sweep's drain: the sweep is bound by VALU issue
+    // (DESIGN 6), so a finish that runs in the middle of it lengthens it by what it saves, and a first group that ends
+    // after the second one leaves BOTH finishes exposed, a whole fixed chain slower than one group.  Measured over
+    // pileups of 1.1 to 5.5 residency rounds of the sweep kernel (profiles/oct_split.md, section 3): a gain of 8 to 13 us
+    // between OCT_SPLIT_ROUNDS_LO and OCT_SPLIT_ROUNDS_HI rounds with OCT_SPLIT_LEAD of the chunks in the first group,
+    // nothing or a loss outside, a loss of 20 to 55 us for a first group of two thirds and more.  So: two groups inside
+    // that window, the first OCT_SPLIT_LEAD of the chunks; one group everywhere else -- also where the chunks are
+    // less than half full on average: those pileups (many small cells) were measured at 174 entries per chunk of 192,
+    // and with nearly empty chunks the step is mostly finish, which the split only cuts in two.
+    // MUXGL_OCT_SPLIT=<cell> places the boundary (tuning, tests), 0 forces one group.
+    constexpr double OCT_SPLIT_ROUNDS_LO = 1.5, OCT_SPLIT_ROUNDS_HI = 2.3, OCT_SPLIT_LEAD = 0.55;
+    std::vector<int64_t> ccp((size_t)h->C + 1);
+    int per_cu = 0, n_cu = 0;
+    hipError_t e = hipMemcpyAsync(ccp.data(), st->d_cell_chunk_ptr, sizeof(int64_t) * ccp.size(), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64, 0);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device);
+    if (e != hipSuccess) MUXGL_FAIL(h, "demux_oct_launch: %s", hipGetErrorString(e));
+    const int64_t round = (int64_t)per_cu * n_cu, n_units_all = (st->n_chunks + O_SLOTS - 1) / O_SLOTS;
+    int64_t cut = 0;
+    if (const char* ev = getenv("MUXGL_OCT_SPLIT")) {
+      cut = atoll(ev);
+      if (cut < 0 || cut >= h->C) cut = 0;  // (a boundary behind the last cell leaves nothing for the second group)
+    } else if (round > 0 && (double)n_units_all >= OCT_SPLIT_ROUNDS_LO * (double)round &&
+               (double)n_units_all <= OCT_SPLIT_ROUNDS_HI * (double)round &&
+               h->nnz >= st->n_chunks * (MUXGL_OCT_CH / 2)) {  // (chunks half full at least: see above)
+      const int64_t lead = (int64_t)(OCT_SPLIT_LEAD * (double)st->n_chunks);  // chunks of the first group, at most
+      cut = std::upper_bound(ccp.begin(), ccp.end(), lead) - ccp.begin() - 1;  // the last cell boundary at or below that
+      if (cut <= 0 || cut >= h->C) cut = 0;
+    }
+    const int64_t n1 = cut > 0 ? ccp[(size_t)cut] : st->n_chunks;
+    st->oct_cut = cut;
+    st->oct_round = round;
+    st->oct_unit0[0] = 0;
+    st->oct_unit0[1] = pad8(n1);
+    st->oct_unit0[2] = st->oct_unit0[1] + (cut > 0 ? pad8(st->n_chunks - n1) : 0);
+    if (st->oct_unit0[2] * O_SLOTS > INT32_MAX) MUXGL_FAIL(h, "demux_oct_launch: too many chunks");
     if (dev_alloc(h, &st->d_qent_lin, (size_t)h->nnz) || dev_alloc(h, &st->d_chunk_nlin, (size_t)st->n_chunks) ||
         dev_alloc(h, &d_lrec, (size_t)h->nnz)) {
-      cleanup();
+      drop_plan();
       return 1;
     }
     hipLaunchKernelGGL(oct_partition_kernel, dim3((unsigned)((st->n_chunks + 63) / 64)), dim3(64), 0, h->stream,
                        (int)st->n_chunks, st->d_chunks, h->d_qent, h->d_lin, h->d_reads, h->d_gp0s, st->d_qent_lin,
                        d_lrec, st->d_chunk_nlin);
-    if (hipGetLastError() != hipSuccess || quad_launch_order(h, st->d_chunks, st->d_chunk_nlin, st->n_chunks, &st->d_quad_order)) {
-      cleanup();
+    if (hipGetLastError() != hipSuccess || quad_launch_order(h, st->d_chunks, st->d_chunk_nlin, st->n_chunks, &d_sorted, cut)) {
+      drop_plan();
       MUXGL_FAIL(h, "demux_oct_launch: partition failed");
     }
     // the linear entries' records, step-major per unit (what the sweep streams)
-    const int n_units = (int)blocks;
+    const int n_units = (int)st->oct_unit0[2];
+    const int n_slots = n_units * O_SLOTS;
     std::vector<int32_t> steps((size_t)n_units);
     std::vector<int64_t> uptr((size_t)n_units + 1, 0);
-    if (dev_alloc(h, &d_steps, (size_t)n_units)) {
-      cleanup();
+    if (dev_alloc(h, &d_steps, (size_t)n_units) || dev_alloc(h, &st->d_quad_order, (size_t)n_slots)) {
+      drop_plan();
       return 1;
     }
+    hipLaunchKernelGGL(oct_pad_order_kernel, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, h->stream, n_slots,
+                       (int)st->n_chunks, (int)n1, (int)st->oct_unit0[1] * O_SLOTS, d_sorted, st->d_quad_order);
     hipLaunchKernelGGL(oct_unit_steps_kernel, dim3((unsigned)((n_units + 255) / 256)), dim3(256), 0, h->stream, n_units,
                        (int)st->n_chunks, O_SLOTS, st->d_quad_order, st->d_chunk_nlin, d_steps);
-    hipError_t e = hipMemcpyAsync(steps.data(), d_steps, sizeof(int32_t) * (size_t)n_units, hipMemcpyDeviceToHost, h->stream);
+    e = hipMemcpyAsync(steps.data(), d_steps, sizeof(int32_t) * (size_t)n_units, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     for (int u = 0; u < n_units; ++u) uptr[(size_t)u + 1] = uptr[(size_t)u] + (int64_t)steps[(size_t)u] * O_SLOTS;
     if (e != hipSuccess || dev_alloc(h, &st->d_unit_ptr, uptr.size()) || dev_alloc(h, &st->d_orec, (size_t)uptr.back() + 1)) {
-      cleanup();
+      drop_plan();
       MUXGL_FAIL(h, "demux_oct_launch: record tables");
     }
     e = hipMemcpyAsync(st->d_unit_ptr, uptr.data(), sizeof(int64_t) * uptr.size(), hipMemcpyHostToDevice, h->stream);
@@ -1064,30 +1133,95 @@ int oct_launch_t(muxgl_handle* h, const muxgl_demux_params* p) {
     if (e == hipSuccess) e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // (uptr is a host buffer; d_lrec is freed)
     cleanup();
+    if (e != hipSuccess) {
+      drop_plan();
+      MUXGL_FAIL(h, "demux_oct_launch: %s", hipGetErrorString(e));
+    }
+  }
+  // The plan's units and cell groups.  Without the linear form (MUXGL_FLAG_NO_LINEAR_ENTRIES) there is no launch order
+  // to put a group key into: one group.  The LL tensor's reduce kernel takes one group as well (the plan is the same).
+  const bool planned = use_lin && st->d_chunk_nlin;
+  const int64_t units_all = planned ? st->oct_unit0[2] : pad8(st->n_chunks);
+  const int64_t cut = planned && !h->want_full_ll ? st->oct_cut : 0;
+  st->oct_groups_run = cut > 0 ? 2 : 1;
+  auto sweep = [&](hipStream_t s, int64_t u0, int64_t u1) {
+    if (u1 > u0)
+      hipLaunchKernelGGL(kern, dim3((unsigned)(u1 - u0)), dim3(64), 0, s, st->d_chunks, (int)st->n_chunks,
+                         use_lin ? st->d_qent_lin : h->d_qent, st->d_orec, st->d_unit_ptr,
+                         use_lin ? st->d_chunk_nlin : (const int32_t*)nullptr,
+                         use_lin ? st->d_quad_order : (const int32_t*)nullptr, (int)u0, h->d_reads,
+                         h->d_gpq, h->d_gmq, h->d_gp0s, (int32_t)h->S, h->d_lut, st->d_chunk_pos, d_part, st->d_part_e);
+  };
+  const muxgl_call::call_alpha al = muxgl_call::make_call_alpha(p, h->V);
+  auto finish = [&](hipStream_t s, int64_t c0, int64_t c1) {  // reduce + call fused, records written to the pinned host buffer
+    constexpr int QF_CELLS = P == 8 ? 4 : 1;
+    const int64_t n_groups = (c1 - c0 + QF_CELLS - 1) / QF_CELLS;
+    if (n_groups > 0)
+      hipLaunchKernelGGL(demux_oct_finish_kernel<P>, dim3((unsigned)n_groups), dim3(256), 0, s, c0, c1, h->d_cell_ptr,
+                         st->d_cell_chunk_ptr, d_part, st->d_part_e, d_slots, h->V, al, p->doublet_prior, h->h_dcells);
+  };
+  if (cut > 0) {
+    // Two cell groups as a pipeline: the sweep of the cells from `cut` on runs on stream2 beside the handle's stream, which
+    // carries the first group's sweep and both finishes.  The two sweeps are on the device together (the first gets
+    // there first and ends first; the dispatcher fills freed slots as it does for one launch, so the sweep as a whole
+    // is no shorter); the first group's finish (its fixed chain of dependent steps, the write-back of its partials)
+    // runs underneath the longer-running second sweep; only the second group's finish is exposed.  A chunk's partials go to its cell's place (chunk_pos) and
+    // a cell's record to its own: the groups share every buffer without overlap.  stream2 is forked from the handle's
+    // stream by the step's first event and joined back into it by the wait in front of the second finish, whatever
+    // happens in between: what follows on the handle's stream is ordered behind both groups.
+    // (Measured and dropped, profiles/oct_split.md: the second group's finish on stream2 as well and the join at the end
+    // -- the step then ends with two dependent hand-overs between queues instead of none; the first group on stream2;
+    // a lower or higher priority for stream2.)
+    hipError_t e = hipSuccess;
+    if (!h->stream2) {  // the first two-group run of this handle (muxgl_destroy releases them)
+      e = hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking);
+      if (e != hipSuccess) h->stream2 = nullptr;
+      if (e == hipSuccess && !h->ev_fork) e = hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming);
+      if (e == hipSuccess && !h->ev_sweep2) e = hipEventCreate(&h->ev_sweep2);
+      if (e != hipSuccess) {
+        if (h->stream2) (void)hipStreamDestroy(h->stream2);
+        h->stream2 = nullptr;
+        MUXGL_FAIL(h, "demux_oct_launch: second stream: %s", hipGetErrorString(e));
+      }
+    }
+    tic(h, MUXGL_T_DEMUX_SWEEP);
+    hipEvent_t fork = h->ev[2 * MUXGL_T_DEMUX_SWEEP];
+    if (timing_off()) e = hipEventRecord(fork = h->ev_fork, h->stream);
     if (e != hipSuccess) MUXGL_FAIL(h, "demux_oct_launch: %s", hipGetErrorString(e));
+    sweep(h->stream, st->oct_unit0[0], st->oct_unit0[1]);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamWaitEvent(h->stream2, fork, 0);
+    if (e != hipSuccess) MUXGL_FAIL(h, "demux_oct_launch: %s", hipGetErrorString(e));
+    sweep(h->stream2, st->oct_unit0[1], st->oct_unit0[2]);
+    e = hipGetLastError();
+    hipError_t ej = hipEventRecord(h->ev_sweep2, h->stream2);  // the end of the second sweep: a time stamp, and the join
+    toc(h, MUXGL_T_DEMUX_SWEEP);                                // the end of the first
+    if (e == hipSuccess && ej == hipSuccess) {
+      finish(h->stream, 0, cut);
+      e = hipGetLastError();
+    }
+    if (ej == hipSuccess) ej = hipStreamWaitEvent(h->stream, h->ev_sweep2, 0);
+    if (ej != hipSuccess) (void)hipStreamSynchronize(h->stream2);  // (no join on the device: join here)
+    if (e == hipSuccess) e = ej;
+    if (e == hipSuccess) {
+      finish(h->stream, cut, h->C);
+      e = hipGetLastError();
+    }
+    if (e != hipSuccess) MUXGL_FAIL(h, "demux_oct_launch: %s", hipGetErrorString(e));
+    toc(h, MUXGL_T_DEMUX_REDUCE);
+    h->split_timed = !timing_off();
+    h->records_on_host = true;
+    return 0;
   }
   tic(h, MUXGL_T_DEMUX_SWEEP);
-  if (blocks) {
-    auto kern = h->gp_unit_sums ? demux_oct_kernel<P, true> : demux_oct_kernel<P, false>;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), 0,
-                       h->stream, st->d_chunks, (int)st->n_chunks,
-                       use_lin ? st->d_qent_lin : h->d_qent, st->d_orec, st->d_unit_ptr,
-                       use_lin ? st->d_chunk_nlin : (const int32_t*)nullptr,
-                       use_lin ? st->d_quad_order : (const int32_t*)nullptr, h->d_reads,
-                       h->d_gpq, h->d_gmq, h->d_gp0s, (int32_t)h->S, h->d_lut, st->d_chunk_pos, d_part, st->d_part_e);
-    HIPCHK(h, hipGetLastError());
-  }
+  sweep(h->stream, 0, units_all);
+  HIPCHK(h, hipGetLastError());
   toc_tic(h, MUXGL_T_DEMUX_SWEEP, MUXGL_T_DEMUX_REDUCE);
   if (h->want_full_ll) {
     hipLaunchKernelGGL(demux_oct_reduce_kernel<P>, dim3((unsigned)h->C), dim3(192), 0, h->stream, st->d_cell_chunk_ptr,
                        d_part, st->d_part_e, d_slots, h->V, h->d_ll);
-  } else {  // reduce + call fused, records written to the pinned host buffer
-    const muxgl_call::call_alpha al = muxgl_call::make_call_alpha(p, h->V);
-    constexpr int QF_CELLS = P == 8 ? 4 : 1;
-    const int64_t n_groups = (h->C + QF_CELLS - 1) / QF_CELLS;
-    if (n_groups)
-      hipLaunchKernelGGL(demux_oct_finish_kernel<P>, dim3((unsigned)n_groups), dim3(256), 0, h->stream, h->C, h->d_cell_ptr,
-                         st->d_cell_chunk_ptr, d_part, st->d_part_e, d_slots, h->V, al, p->doublet_prior, h->h_dcells);
+  } else {
+    finish(h->stream, 0, h->C);
     h->records_on_host = true;
   }
   HIPCHK(h, hipGetLastError());
@@ -1095,6 +1229,17 @@ int oct_launch_t(muxgl_handle* h, const muxgl_demux_params* p) {
   return 0;
 }
 }  // namespace
+
+// what the last run of the default-grid path did with its cells (include/muxgl.h)
+int demux_oct_split_info(const muxgl_handle* h, int64_t* out) {
+  const muxgl_row_state* st = h->qrow;
+  const bool planned = st && st->d_chunk_nlin;
+  out[0] = planned ? st->oct_cut : 0;
+  out[1] = st ? st->oct_groups_run : 0;
+  out[2] = planned ? st->oct_round : 0;
+  out[3] = planned ? st->oct_unit0[2] : 0;
+  return 0;
+}
 
 // the default grid {0, 0.5} at V <= 32 (path_choice.hpp): eight lanes per entry up to 16 samples, sixteen beyond
 int demux_oct_launch(muxgl_handle* h, const muxgl_demux_params* p) {

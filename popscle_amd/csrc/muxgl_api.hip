@@ -442,6 +442,9 @@ void muxgl_destroy(muxgl_handle* h) {
   if (h->h_fcells) (void)hipHostFree(h->h_fcells);
   if (h->h_fstat) (void)hipHostFree(h->h_fstat);
   if (h->ev_stat) (void)hipEventDestroy(h->ev_stat);
+  if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
+  if (h->ev_sweep2) (void)hipEventDestroy(h->ev_sweep2);
+  if (h->stream2) (void)hipStreamDestroy(h->stream2);
   for (int i = 0; i < 2 * MUXGL_T_COUNT; ++i)
     if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
   dev_pool_release(h, true);  // the cached blocks go back to the driver; blocks still out lose their owner
@@ -609,6 +612,15 @@ int muxgl_demux_singlets(muxgl_handle* h, const muxgl_demux_params* p, double* s
   if (demux_singlets_run(h, p, sng)) return 1;
   collect_timing(h);
   return 0;
+}
+
+int muxgl_demux_oct_split(const muxgl_handle* h, int64_t* info) {
+  if (!h || !info) return 1;
+  if (h->group) {
+    info[0] = info[1] = info[2] = info[3] = 0;
+    return 0;
+  }
+  return demux_oct_split_info(h, info);
 }
 
 const muxgl_demux_cell* muxgl_demux_results(const muxgl_handle* h) {

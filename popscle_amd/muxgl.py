@@ -96,6 +96,7 @@ SYMBOLS = {
     "muxgl_demux_singlets": (C.c_int, [_VP, C.POINTER(_DemuxParams), _VP]),
     "muxgl_demux_inclusion": (C.c_int, [_VP, C.POINTER(_DemuxParams), _VP, _VP, _VP, _VP, _VP, _VP]),
     "muxgl_demux_results": (_VP, [_VP]),
+    "muxgl_demux_oct_split": (C.c_int, [_VP, _VP]),
     "muxgl_demux_exact_calls": (C.c_int, [C.c_int64, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP,
                                           C.POINTER(_DemuxParams), _VP, C.c_int32, _VP]),
     "muxgl_demux_get_entry_pg": (C.c_int, [_VP, _VP]),
@@ -375,6 +376,12 @@ class Engine:
         p = self.lib.muxgl_demux_results(self.h)
         buf = (C.c_char * (self.C * DEMUX_CELL.itemsize)).from_address(p)
         return np.frombuffer(buf, dtype=DEMUX_CELL, count=self.C)
+
+    def demux_oct_split(self):
+        """muxgl_demux_oct_split: dict(cut, groups, round_units, units) of the last demux_run on the default-grid path"""
+        info = np.zeros(4, dtype=np.int64)
+        self._check(self.lib.muxgl_demux_oct_split(self.h, _ptr(info)))
+        return dict(zip(("cut", "groups", "round_units", "units"), (int(x) for x in info)))
 
     def demux_entry_pg(self):
         pg = np.zeros((self.nnz, self.n_alpha, 3, 3), dtype=np.float64)
