@@ -257,6 +257,36 @@ int muxgl_demux_singlets(muxgl_handle* h, const muxgl_demux_params* p, double* s
 int muxgl_demux_inclusion(muxgl_handle* h, const muxgl_demux_params* p, double* incl, double* tot, double* dbl,
                           int32_t* partner, int32_t* alpha_idx, int32_t* first);
 
+/* Every droplet against a donor that is NOT in the panel: the half-unspecified and unspecified doublet likelihoods the
+ * reference accumulates and never prints (llksA0 / llks00, cmd_cram_demuxlet.cpp:749-773; the commented-out header of
+ * :628 still lists their columns).  With pG_e[n][l][m] the per-entry likelihood of :655-725, normalised over the whole
+ * grid (so the call takes the parameters of muxgl_demux_run; doublet_prior is not read), u[s][.] the unknown donor's
+ * genotype prior at marker s, and the sums over the entries e of droplet c whose marker s_e has genotypes:
+ *   ll_ju[C][V][n_alpha]: ll_ju[c][j][n] = sum_e log sum_l sum_m gp[s_e][j][l] * u[s_e][m] * pG_e[n][l][m]
+ *                         (llksA0: sample j with share 1 - alpha[n], the unknown donor with share alpha[n])
+ *   ll_uj[C][V][n_alpha]: ll_uj[c][k][n] = sum_e log sum_l sum_m u[s_e][l] * gp[s_e][k][m] * pG_e[n][l][m]
+ *                         (the other orientation, which the reference does not form: the same hypothesis as ll_ju only
+ *                         where alpha[n] == 0.5)
+ *   ll_uu[C][n_alpha]:    ll_uu[c][n]    = sum_e log sum_l sum_m u[s_e][l] * u[s_e][m] * pG_e[n][l][m]      (llks00)
+ * gp0 == NULL: u is the reference's panel mean (:428-440), the rows gp[s][0..V-1] added in sample order, then divided by
+ * V, computed on the device.  gp0 != NULL: the caller's prior [S][3] (Hardy-Weinberg from an allele frequency, say);
+ * the values in rows of markers without genotypes do not matter.  A marker without genotypes contributes a factor of
+ * exactly 1 everywhere (:733), a droplet without entries gets zeros, and slot n = 0 is kept like every other slot (the
+ * singlet slot of :799,806).  Needs muxgl_set_pileup and muxgl_demux_set_gp, not a previous muxgl_demux_run; any V up
+ * to MUXGL_MAX_SAMPLES (there is no pair grid: V * V * n_alpha may exceed 2^31) and any n_alpha up to MUXGL_MAX_ALPHA; one
+ * device or a device group (every member fills the rows of its own cells).  Any subset of the three tables may be NULL;
+ * with all three NULL the call fails, naming the reason, and the handle stays usable.  kernel_ms (NULL allowed) receives
+ * the hipEvent time of the call's kernels, from a pair of events the call makes for itself (a group: the slowest
+ * member's): the records, full_ll, timing slots and state of muxgl_demux_run stay as they are.
+ * Device memory: nothing proportional to nnz x n_alpha is held for the whole pileup.  The cells are swept in batches of
+ * whole cells whose 6 n_alpha weights per entry, slab rows and table rows fit the streamed call's budget (4 GiB or a
+ * third of the device, MUXGL_DEMUX_SLAB_MB); each batch is copied out before the next; the call fails, naming the
+ * reason, when one cell alone exceeds the budget.  All three tables are bit-identical from call to call, for any budget,
+ * for any subset of requested tables, on one device, on a group and through the sharded driver. */
+int muxgl_demux_unknown(muxgl_handle* h, const muxgl_demux_params* p, const double* gp0 /* NULL, or [S][3] */,
+                        double* ll_ju /* NULL or [C][V][n_alpha] */, double* ll_uj /* NULL or [C][V][n_alpha] */,
+                        double* ll_uu /* NULL or [C][n_alpha] */, float* kernel_ms /* NULL or one float */);
+
 /* The calls rounding noise could decide, settled in the reference's own arithmetic -- HOST pass, no device work, no
  * handle (popscle_amd/host/exact_calls.hpp).  The kernels' log-likelihoods equal the reference's to ~1e-12, not to the last
  * bit, and every decision of cmd_cram_demuxlet.cpp:827-837,883-906,925-988 compares two of them.  For the cells of

@@ -602,6 +602,9 @@ struct ring_sel {          // one launch of demux_ring.hip
 int demux_launch(muxgl_handle* h, const muxgl_demux_params* p);
 int demux_stream_launch(muxgl_handle* h, const muxgl_demux_params* p);   // streamed sweep + fold + call
 int demux_singlets_run(muxgl_handle* h, const muxgl_demux_params* p, double* sng);  // demux_singlets.hip: [C][V] to the host
+// demux_unknown.hip: the three tables of muxgl_demux_unknown to the host (any may be NULL), rows of the handle's own cells
+int demux_unknown_run(muxgl_handle* h, const muxgl_demux_params* p, const double* gp0, double* ll_ju, double* ll_uj,
+                      double* ll_uu, float* kernel_ms);
 struct demux_incl_out {  // muxgl_demux_inclusion's outputs (host; any may be NULL), rows of the handle's own cells
   double *incl, *tot, *dbl;
   int32_t *partner, *alpha_idx, *first;
@@ -684,6 +687,8 @@ int group_demux_set_gp(muxgl_handle* h, int32_t V, const double* gp, const uint8
 int group_demux_run(muxgl_handle* h, const muxgl_demux_params* p, muxgl_demux_cell* out, double* full_ll);
 int group_demux_singlets(muxgl_handle* h, const muxgl_demux_params* p, double* sng);
 int group_demux_inclusion(muxgl_handle* h, const muxgl_demux_params* p, const demux_incl_out& out);
+int group_demux_unknown(muxgl_handle* h, const muxgl_demux_params* p, const double* gp0, double* ll_ju, double* ll_uj,
+                        double* ll_uu, float* kernel_ms);
 const muxgl_demux_cell* group_demux_results(const muxgl_handle* h);
 int group_demux_get_entry_pg(muxgl_handle* h, double* pg);
 int group_fmx_prepare(muxgl_handle* h, const double* af, double* cell_llk0, double* cell_llk2, int32_t* cell_nsnps,

@@ -614,6 +614,19 @@ int muxgl_demux_singlets(muxgl_handle* h, const muxgl_demux_params* p, double* s
   return 0;
 }
 
+int muxgl_demux_unknown(muxgl_handle* h, const muxgl_demux_params* p, const double* gp0, double* ll_ju, double* ll_uj,
+                        double* ll_uu, float* kernel_ms) {
+  if (!h) return 1;
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (h->group) return group_demux_unknown(h, p, gp0, ll_ju, ll_uj, ll_uu, kernel_ms);
+  HIPCHK(h, hipSetDevice(h->device));
+  if (check_demux_params(h, p)) return 1;
+  if (!ll_ju && !ll_uj && !ll_uu) MUXGL_FAIL(h, "muxgl_demux_unknown: all three outputs are NULL");
+  if (h->C == 0) return 0;
+  // (no clear_timing, no timing slot: records, timings and state of the last muxgl_demux_run keep their values)
+  return demux_unknown_run(h, p, gp0, ll_ju, ll_uj, ll_uu, kernel_ms);
+}
+
 int muxgl_demux_oct_split(const muxgl_handle* h, int64_t* info) {
   if (!h || !info) return 1;
   if (h->group) {

@@ -320,6 +320,26 @@ int group_demux_inclusion(muxgl_handle* h, const muxgl_demux_params* p, const de
   return 0;
 }
 
+// every member sweeps its own cells and writes their rows of the caller's tables; kernel_ms: the slowest member's
+int group_demux_unknown(muxgl_handle* h, const muxgl_demux_params* p, const double* gp0, double* ll_ju, double* ll_uj,
+                        double* ll_uu, float* kernel_ms) {
+  muxgl_group* g = h->group;
+  if (!p) MUXGL_FAIL(h, "demux params NULL");
+  if (p->n_alpha < 1 || p->n_alpha > MUXGL_MAX_ALPHA) MUXGL_FAIL(h, "n_alpha=%d outside [1,%d]", p->n_alpha, MUXGL_MAX_ALPHA);
+  if (!g->have_pileup) MUXGL_FAIL(h, "no pileup set (muxgl_set_pileup)");
+  if (g->V < 1) MUXGL_FAIL(h, "no GP tensor set (muxgl_demux_set_gp)");
+  if (!ll_ju && !ll_uj && !ll_uu) MUXGL_FAIL(h, "muxgl_demux_unknown: all three outputs are NULL");
+  std::vector<float> ms((size_t)g->n, 0.f);
+  if (for_members(h, [&](int r) {
+        const size_t c = (size_t)g->cb[(size_t)r], o = c * (size_t)g->V * (size_t)p->n_alpha;
+        return muxgl_demux_unknown(g->m[(size_t)r], p, gp0, ll_ju ? ll_ju + o : nullptr, ll_uj ? ll_uj + o : nullptr,
+                                   ll_uu ? ll_uu + c * (size_t)p->n_alpha : nullptr, kernel_ms ? &ms[(size_t)r] : nullptr);
+      }))
+    return 1;
+  if (kernel_ms) *kernel_ms = *std::max_element(ms.begin(), ms.end());
+  return 0;
+}
+
 const muxgl_demux_cell* group_demux_results(const muxgl_handle* h) { return h->group->h_dcells; }
 
 int group_demux_get_entry_pg(muxgl_handle* h, double* pg) {

@@ -11,11 +11,12 @@ from .freemuxlet import NoExchange
 
 
 def run_sharded(engine_factory, p, alphas=(0.0, 0.5), doublet_prior=0.5, exchange=None, want_singlets=False,
-                want_inclusion=False):
+                want_inclusion=False, *, want_unknown=False):
     """engine_factory() -> object with set_pileup / demux_set_gp / demux_run (muxgl.Engine).  Returns the [C] records of
     the whole pileup on every rank, in the original cell order; with want_singlets also the [C][V] table of singlet
     log-likelihoods (Engine.demux_singlets), gathered the same way: (records, sng); with want_inclusion also the dict of
-    per-droplet, per-sample inclusion tables (Engine.demux_inclusion) as the last element: (records, [sng,] inclusion).
+    per-droplet, per-sample inclusion tables (Engine.demux_inclusion): (records, [sng,] inclusion); with want_unknown
+    (keyword only) also the dict of the three tables of Engine.demux_unknown (panel mean) as the last element.
     Cells are independent, so every rank fills the rows of its own cells."""
     ex = exchange or NoExchange()
     ranges = shard.cell_shards(p.cell_ptr, ex.world)
@@ -29,7 +30,7 @@ def run_sharded(engine_factory, p, alphas=(0.0, 0.5), doublet_prior=0.5, exchang
     out = np.zeros(p.C, dtype=cells.dtype)
     for b, e, raw in parts:
         out[b:e] = np.frombuffer(raw, dtype=cells.dtype)
-    if not want_singlets and not want_inclusion:
+    if not want_singlets and not want_inclusion and not want_unknown:
         return out
     ret = [out]
     V = p.gp.shape[1]
@@ -45,4 +46,11 @@ def run_sharded(engine_factory, p, alphas=(0.0, 0.5), doublet_prior=0.5, exchang
             for k, v in inc.items():
                 v[b:e] = np.frombuffer(raw[k], dtype=v.dtype).reshape((e - b,) + v.shape[1:])
         ret.append(inc)
+    if want_unknown:
+        mine = {k: v for k, v in eng.demux_unknown(alphas).items() if k != "kernel_ms"}
+        unk = {k: np.zeros((p.C,) + v.shape[1:], dtype=v.dtype) for k, v in mine.items()}
+        for b, e, raw in ex.gather_objects((c0, c1, {k: v.tobytes() for k, v in mine.items()})):
+            for k, v in unk.items():
+                v[b:e] = np.frombuffer(raw[k], dtype=v.dtype).reshape((e - b,) + v.shape[1:])
+        ret.append(unk)
     return tuple(ret)

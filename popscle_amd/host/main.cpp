@@ -14,6 +14,13 @@
 //       DBL.PARTNER (sample id), DBL.ALPHA (%.3lf: the share of the sample's OWN reads in that doublet, alpha if it
 //       is the second, contaminating sample of the pair and 1 - alpha if it is the first, :694-695,734-736), DBL.LLK (%.4lf); the last three are NA where no doublet hypothesis
 //       holds the sample (one sample, or a grid without a doublet alpha)
+//       --write-unknown: also <O>.unk.gz (BGZF), one row per printed droplet: how well a donor that is NOT in the VCF
+//       explains it -- the half-unspecified and unspecified doublet likelihoods the reference accumulates and never prints
+//       (llksA0 / llks00, cmd_cram_demuxlet.cpp:749-773; muxgl_demux_unknown with the panel mean of :428-440 as the
+//       unknown donor's genotype prior).  Columns BARCODE, NUM.SNPS, NUM.READS, BEST.LLK (of .best, %.4lf), UNK.SNG.LLK
+//       (one unknown donor), UNK.DBL.ALPHA (%.2lf), UNK.DBL.LLK (two unknown donors, the best alpha), HALF.GUESS (SM,*,alpha:
+//       the known donor has share 1 - alpha; *,SM,alpha: share alpha), HALF.LLK, DIFF.LLK.PANEL.UNK (BEST.LLK minus the
+//       largest of the three); LLKs %.4lf; NA where a column has no hypothesis (a grid of one alpha)
 //   popscle-amd freemuxlet --plp P --nsample K --out O [...]                   mirrors cmdCramFreemux2 (cmd_cram_freemux2.cpp)
 //       --write-singlets: also <O>.clust1.sing2.gz (BGZF), the singlet log-likelihood of every droplet against every
 //       cluster as the last EM iteration formed it (llks[j(j+1)/2 + j], cmd_cram_freemux2.cpp:448-455; the reference
@@ -141,8 +148,10 @@ int cmd_demuxlet(int argc, char** argv) {
   bool deviceCalls = false;  // (ours) skip the host pass that settles mirrored alpha = 0.5 pairs and near-tie calls as the reference does
   bool writeSinglets = false;  // (ours) <out>.sing2.gz: the reference's disabled .sing2 writer (:580,839-848)
   bool writeInclusion = false;  // (ours) <out>.incl.gz: per-sample marginals of the disabled .pair writer (:852-877)
+  bool writeUnknown = false;  // (ours) <out>.unk.gz: the droplet against a donor missing from the VCF (llksA0 / llks00, :749-773)
   Args a;
   cf.add(a);
+  a.add_bool("write-unknown", &writeUnknown);
   a.add_bool("device-calls", &deviceCalls);
   a.add_bool("write-singlets", &writeSinglets);
   a.add_bool("write-inclusion", &writeInclusion);
@@ -296,6 +305,53 @@ int cmd_demuxlet(int argc, char** argv) {
     }
     wi.close();
     tm.lap("demuxlet: write .incl.gz");
+  }
+  if (writeUnknown) {
+    // .unk.gz: one row per printed droplet (the order and the filters of .best).  The best hypothesis with one panel
+    // sample: (j, n >= 1, known donor first) and, where alpha[n] != 0.5, (k, n >= 1, known donor second) -- at 0.5 the
+    // two are one hypothesis, the reference's k < j rule for mirrored pairs (:812-815); ties by value, then (sample, n,
+    // known donor first) ascending
+    const size_t V = (size_t)p.nv, A = (size_t)dp.n_alpha;
+    std::vector<double> ju((size_t)p.C() * V * A), uj((size_t)p.C() * V * A), uu((size_t)p.C() * A);
+    check(h, muxgl_demux_unknown(h, &dp, nullptr, ju.data(), uj.data(), uu.data(), nullptr), "muxgl_demux_unknown");
+    tm.lap("demuxlet: muxgl_demux_unknown");
+    OutFile wu(cf.outPrefix + ".unk.gz", true);
+    wu.printf("BARCODE\tNUM.SNPS\tNUM.READS\tBEST.LLK\tUNK.SNG.LLK\tUNK.DBL.ALPHA\tUNK.DBL.LLK\tHALF.GUESS\tHALF.LLK\t"
+              "DIFF.LLK.PANEL.UNK\n");
+    for (auto it = bc_map.begin(); it != bc_map.end(); ++it) {
+      const int32_t i = it->second;
+      const muxgl_demux_cell& c = cells[(size_t)i];
+      if (p.cell_totl_reads[(size_t)i] < cf.lo.minRead || p.cell_uniq_reads[(size_t)i] < cf.lo.minUMI ||
+          c.nsnps < cf.lo.minSNP || !c.valid)
+        continue;
+      const double* r2 = uu.data() + (size_t)i * A;
+      double top = r2[0], dblv = -1e300, halfv = -1e300;
+      int dn = -1, hj = -1, hn = -1, hmajor = -1;
+      for (size_t n = 1; n < A; ++n)
+        if (r2[n] > dblv) dblv = r2[n], dn = (int)n;
+      for (size_t j = 0; j < V; ++j)
+        for (size_t n = 1; n < A; ++n) {
+          const size_t x = ((size_t)i * V + j) * A + n;
+          if (ju[x] > halfv) halfv = ju[x], hj = (int)j, hn = (int)n, hmajor = 1;
+          if (dp.alpha[n] != 0.5 && uj[x] > halfv) halfv = uj[x], hj = (int)j, hn = (int)n, hmajor = 0;
+        }
+      wu.printf("%s\t%u\t%d\t%.4lf\t%.4lf\t", it->first.c_str(), (unsigned)c.nsnps, p.cell_uniq_reads[(size_t)i], c.bestLLK, r2[0]);
+      if (dn < 0) {
+        wu.printf("NA\tNA\t");
+      } else {
+        wu.printf("%.2lf\t%.4lf\t", dp.alpha[dn], dblv);
+        top = std::max(top, dblv);
+      }
+      if (hj < 0) {
+        wu.printf("NA\tNA\t");
+      } else {
+        wu.printf("%s,%s,%.2lf\t%.4lf\t", hmajor ? sid(p, hj) : "*", hmajor ? "*" : sid(p, hj), dp.alpha[hn], halfv);
+        top = std::max(top, halfv);
+      }
+      wu.printf("%.4lf\n", c.bestLLK - top);
+    }
+    wu.close();
+    tm.lap("demuxlet: write .unk.gz");
   }
   notice("Finished writing output files");
   muxgl_destroy(h);
@@ -1228,6 +1284,9 @@ int main(int argc, char** argv) {
                     "  demuxlet --write-inclusion: also <out>.incl.gz, per printed droplet and sample the evidence that the sample\n"
                     "    is in the droplet and the doublet it pairs best in (BARCODE SM_ID NUM.SNPS NUM.READS LLK.INCL\n"
                     "    POSTPRB.INCL DBL.PARTNER DBL.ALPHA DBL.LLK)\n"
+                    "  demuxlet --write-unknown: also <out>.unk.gz, per printed droplet how well a donor missing from the VCF\n"
+                    "    explains it (BARCODE NUM.SNPS NUM.READS BEST.LLK UNK.SNG.LLK UNK.DBL.ALPHA UNK.DBL.LLK HALF.GUESS\n"
+                    "    HALF.LLK DIFF.LLK.PANEL.UNK)\n"
                     "  freemuxlet --write-singlets: also <out>.clust1.sing2.gz, the singlet log-likelihood of every droplet\n"
                     "    against every cluster in the last iteration (BARCODE CLUST NUM.SNPS NUM.READS LLK1 POSTPRB)\n"
                     "  freemuxlet --match-vcf FILE [demuxlet's genotype flags]: also <out>.clust1.match.gz and .clust1.match.best.gz,\n"

@@ -95,6 +95,7 @@ SYMBOLS = {
     "muxgl_demux_run": (C.c_int, [_VP, C.POINTER(_DemuxParams), _VP, _VP]),
     "muxgl_demux_singlets": (C.c_int, [_VP, C.POINTER(_DemuxParams), _VP]),
     "muxgl_demux_inclusion": (C.c_int, [_VP, C.POINTER(_DemuxParams), _VP, _VP, _VP, _VP, _VP, _VP]),
+    "muxgl_demux_unknown": (C.c_int, [_VP, C.POINTER(_DemuxParams), _VP, _VP, _VP, _VP, _VP]),
     "muxgl_demux_results": (_VP, [_VP]),
     "muxgl_demux_oct_split": (C.c_int, [_VP, _VP]),
     "muxgl_demux_exact_calls": (C.c_int, [C.c_int64, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP,
@@ -205,6 +206,45 @@ def singlet_posteriors(sng):
         return np.zeros_like(sng)
     ex = np.exp(sng - sng.max(axis=1, keepdims=True))
     return ex / ex.sum(axis=1, keepdims=True)
+
+
+def unknown_summary(tables, alphas):
+    """Per droplet, the best hypotheses with a donor that is not in the panel, from the tables of Engine.demux_unknown
+    (dict with ju, uj [C][V][A] and uu [C][A]).  Pure numpy.  Returns a dict of [C] arrays:
+    uu_sng = uu[:, 0]; uu_dbl, uu_alpha_idx: the maximum of uu[:, n >= 1] and its n, first n on ties (-1e300 and -1 when
+    the grid has one alpha); half_llk, half_sample, half_alpha_idx, half_known_major: the best hypothesis with one panel
+    sample -- the candidates are (j, n >= 1, ju), sample j with share 1 - alpha[n] (half_known_major = 1), and
+    (k, n >= 1, uj) only where alpha[n] != 0.5 (half_known_major = 0; at 0.5 it is the same hypothesis as ju, the
+    reference's k < j rule for mirrored pairs, cmd_cram_demuxlet.cpp:812-815).  Ties: value descending, then (sample, n,
+    ju before uj) ascending.  -1e300 and -1 where there is no candidate."""
+    ju = np.asarray(tables["ju"], dtype=np.float64)
+    uj = np.asarray(tables["uj"], dtype=np.float64)
+    uu = np.asarray(tables["uu"], dtype=np.float64)
+    al = np.asarray(alphas, dtype=np.float64)
+    A = al.size
+    if ju.ndim != 3 or ju.shape != uj.shape or uu.shape != (ju.shape[0], A) or ju.shape[2] != A or A < 1:
+        raise ValueError("tables must be ju, uj [C][V][A] and uu [C][A] with A = len(alphas)")
+    Cn, V = ju.shape[:2]
+    out = {"uu_sng": uu[:, 0].copy(), "uu_dbl": np.full(Cn, -1e300), "uu_alpha_idx": np.full(Cn, -1, dtype=np.int32),
+           "half_llk": np.full(Cn, -1e300), "half_sample": np.full(Cn, -1, dtype=np.int32),
+           "half_alpha_idx": np.full(Cn, -1, dtype=np.int32), "half_known_major": np.full(Cn, -1, dtype=np.int32)}
+    if A < 2 or Cn == 0:
+        return out
+    k = np.argmax(uu[:, 1:], axis=1)  # (first maximum)
+    out["uu_alpha_idx"][:] = k + 1
+    out["uu_dbl"][:] = uu[np.arange(Cn), k + 1]
+    # candidates in tie order: sample, then n, then ju before uj
+    cand = np.stack([ju[:, :, 1:], np.where(al[1:] != 0.5, uj[:, :, 1:], -np.inf)], axis=3).reshape(Cn, -1)
+    cand = np.where(np.isnan(cand), -np.inf, cand)
+    if cand.shape[1]:
+        b = np.argmax(cand, axis=1)
+        v = cand[np.arange(Cn), b]
+        some = v > -np.inf
+        out["half_llk"][some] = v[some]
+        out["half_sample"][some] = (b // (2 * (A - 1)))[some]
+        out["half_alpha_idx"][some] = ((b // 2) % (A - 1) + 1)[some]
+        out["half_known_major"][some] = (1 - b % 2)[some]
+    return out
 
 
 def _ptr(a):
@@ -369,6 +409,40 @@ class Engine:
                 shape = (self.C,) if name == "tot" else (self.C, self.V)
                 out[name] = np.zeros(shape, dtype=np.float64 if name in ("incl", "tot", "dbl") else np.int32)
         self._check(self.lib.muxgl_demux_inclusion(self.h, C.byref(p), *[_ptr(out.get(n)) for n in self.INCLUSION_FIELDS]))
+        return out
+
+    UNKNOWN_FIELDS = ("ju", "uj", "uu")
+
+    def demux_unknown(self, alphas=(0.0, 0.5), gp0=None, want=UNKNOWN_FIELDS):
+        """muxgl_demux_unknown: every droplet against a donor that is not in the panel (include/muxgl.h).  dict of
+        ju float64 [C][V][A], sample j (share 1 - alpha) with the unknown donor (share alpha), the reference's llksA0;
+        uj float64 [C][V][A], the other orientation; uu float64 [C][A], two unknown donors, the reference's llks00; and
+        kernel_ms, the event time of the call's kernels.  gp0: the unknown donor's genotype prior [S][3], or None for the
+        panel mean.  want: the subset of the three to fetch (the others are passed as NULL).  At any V, without a previous
+        demux_run.  unknown_summary() turns the tables into per-droplet calls."""
+        if len(alphas) > MAX_ALPHA:
+            raise ValueError("too many alphas")
+        unknown = set(want) - set(self.UNKNOWN_FIELDS)
+        if unknown:
+            raise ValueError(f"unknown fields {sorted(unknown)}")
+        p = _DemuxParams()
+        p.n_alpha = len(alphas)
+        for i, a in enumerate(alphas):
+            p.alpha[i] = float(a)
+        p.doublet_prior = 0.5  # (not read by the call)
+        if gp0 is not None:
+            gp0 = _arr(gp0, np.float64, "gp0")
+            if gp0.shape != (self.S, 3):
+                raise ValueError("gp0 must be [S][3]")
+        A = len(alphas)
+        out = {}
+        for name in self.UNKNOWN_FIELDS:
+            if name in want:
+                out[name] = np.zeros((self.C, A) if name == "uu" else (self.C, self.V, A), dtype=np.float64)
+        ms = C.c_float(0.0)
+        self._check(self.lib.muxgl_demux_unknown(self.h, C.byref(p), _ptr(gp0), *[_ptr(out.get(n)) for n in self.UNKNOWN_FIELDS],
+                                                  C.byref(ms)))
+        out["kernel_ms"] = float(ms.value)
         return out
 
     def demux_results_view(self):
