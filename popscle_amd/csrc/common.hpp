@@ -303,6 +303,20 @@ struct host_timer {
                                      __FILE__, __LINE__);                                       \
   } while (0)
 
+// CALL(W) for the lane width W of a sweep whose lanes are (entry slot, column): the columns rounded up to a power of two,
+// 64 from 33 columns on (match_plan::lane_width), in the manner of demux_entry.hpp's DISPATCH_NA.  It names the seven
+// widths a unit instantiates (fmx_pairs.hip has no width 1 and keeps a switch of its own).
+#define DISPATCH_WIDTH(W, CALL) \
+  switch (W) {                  \
+    case 1: CALL(1); break;     \
+    case 2: CALL(2); break;     \
+    case 4: CALL(4); break;     \
+    case 8: CALL(8); break;     \
+    case 16: CALL(16); break;   \
+    case 32: CALL(32); break;   \
+    default: CALL(64); break;   \
+  }
+
 // ---- device memory: dev_alloc / dev_free with a per-handle cache of large blocks -----------------------------------------
 // The phases of a run allocate and free tens of GB each (entry likelihoods, the greedy start's tables, cluster pileups);
 // hipMalloc of memory that was in use before costs ~30 ms per GB on these boxes (the driver clears it) and hipFree drains
@@ -372,6 +386,41 @@ static inline bool timing_off() {  // MUXGL_NO_EVENTS=1: no hipEvent records aro
   static const bool off = getenv("MUXGL_NO_EVENTS") != nullptr;
   return off;
 }
+// A call's own event pair, for the calls that report their kernel time through a `kernel_ms` argument and leave the
+// handle's timing slots alone.  The events exist only when kernel_ms is wanted and timing is on; start / stop record
+// them around the kernels, add() (behind a stream synchronise) adds the bracket to *kernel_ms; they are destroyed on
+// every way out of the call.
+struct call_events {
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  float* ms = nullptr;
+  call_events() = default;
+  call_events(const call_events&) = delete;
+  call_events& operator=(const call_events&) = delete;
+  ~call_events() {
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+  }
+  int create(muxgl_handle* h, float* kernel_ms, const char* who) {
+    if (!kernel_ms || timing_off()) return 0;
+    HIPCHK(h, hipEventCreate(&ev0));
+    if (hipEventCreate(&ev1) != hipSuccess) MUXGL_FAIL(h, "%s: hipEventCreate failed", who);
+    ms = kernel_ms;
+    return 0;
+  }
+  int start(muxgl_handle* h) {
+    if (ms) HIPCHK(h, hipEventRecord(ev0, h->stream));
+    return 0;
+  }
+  int stop(muxgl_handle* h) {
+    if (ms) HIPCHK(h, hipEventRecord(ev1, h->stream));
+    return 0;
+  }
+  void add() {
+    float t = 0.f;
+    if (ms && hipEventElapsedTime(&t, ev0, ev1) == hipSuccess) *ms += t;
+  }
+};
+
 static inline void tic(muxgl_handle* h, int id) {
   if (timing_off()) return;
   (void)hipEventRecord(h->ev[2 * id], h->stream);

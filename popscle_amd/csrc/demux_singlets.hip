@@ -12,12 +12,13 @@
 //     exactly 1 for every sample and the sweep has no branch.
 //   * sng_sweep_kernel, lane = sample: f = g_0 w_0 + g_1 w_1 + g_2 w_2 per (entry, sample), multiplied into a product kept
 //     as mantissa x 2^exponent (prodacc), one log per (cell part, sample).  A wave is one work unit: a part of a cell
-//     (at most SNG_PART entries) x a block of 64 samples, the entry wave-uniform.  Below 64 samples a wave holds
+//     (at most 2048 entries) x a block of 64 samples, the entry wave-uniform.  Below 64 samples a wave holds
 //     G = 64 / VH entries side by side (VH = V rounded up to a power of two, lane = (entry slot, sample)) and the G partial
 //     products of a sample are multiplied in a fixed butterfly at the end.
-//   * sng_join_kernel: the logs of the parts of a cell longer than SNG_PART entries, added in entry order.
-// The cut of a cell depends on the cell alone and every reduction tree is fixed: the table is bit-identical from run to
-// run, for any slab budget, on one device, on a group and through the sharded driver.
+//   * table_join_kernel (table_call.hpp): the logs of the parts of a long cell, added in entry order.
+// Which cell goes into which batch, its cut into parts (fixed parts of 2048 entries) and the order of the work items
+// are table_plan.hpp's.  The cut of a cell depends on the cell alone and every reduction tree is fixed: the table is
+// bit-identical from run to run, for any slab budget, on one device, on a group and through the sharded driver.
 //
 // Memory: [nnz][3] weights and a slab of the table.  When the table exceeds the budget (the streamed call's: 4 GiB or a
 // third of the device, MUXGL_DEMUX_SLAB_MB) the cells are swept in batches and each batch is copied out before the next.
@@ -25,10 +26,10 @@
 #include <vector>
 
 #include "demux_entry.hpp"
+#include "table_call.hpp"
 
 namespace {
 
-constexpr int64_t SNG_PART = 2048;  // entries per part of a long cell (the wave kernels' cut, common.hpp wave_item)
 constexpr int SNG_UNR = 8;          // entries per lane between two renormalisations, all of their loads in flight: a
                                     // factor is >= ~1e-11 (pG >= 1e-10 / (1 + 1e-10)), eight cannot underflow
 
@@ -36,15 +37,7 @@ struct sng_alpha {
   double a[MUXGL_MAX_ALPHA];
 };
 
-// one work item: the entries [e0, e1) of one cell, result row `row` of the slab (rows of cells first, then the rows of
-// the further parts of long cells)
-struct sng_item {
-  int64_t e0, e1, row;
-};
-// a cell of several parts: slab[cell row] += slab[first] + ... + slab[first + count - 1], in this order
-struct sng_cut {
-  int64_t row, first, count;
-};
+using sng_item = table_plan::item;  // the entries [e0, e1) of one cell, result row `row` of the slab
 
 template <int NA>
 __global__ void __launch_bounds__(256)
@@ -123,18 +116,6 @@ __global__ void __launch_bounds__(256)
   if (jl && sub == 0) slab[(size_t)items[it].row * V + j] = prodacc_log(acc, ex);
 }
 
-__global__ void __launch_bounds__(256)
-    sng_join_kernel(int64_t n_cuts, const sng_cut* __restrict__ cuts, int V, double* __restrict__ slab) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n_cuts * V) return;
-  const int64_t c = i / V;
-  const int j = (int)(i - c * V);
-  const sng_cut ct = cuts[c];
-  double s = slab[(size_t)ct.row * V + j];
-  for (int64_t k = 0; k < ct.count; ++k) s += slab[(size_t)(ct.first + k) * V + j];
-  slab[(size_t)ct.row * V + j] = s;
-}
-
 template <int NA>
 int launch_weights(muxgl_handle* h, const sng_alpha& al, double* d_wt) {
   hipLaunchKernelGGL((sng_weight_kernel<NA>), dim3((unsigned)((h->nnz + 255) / 256)), dim3(256), 0, h->stream, h->nnz,
@@ -164,79 +145,45 @@ int demux_singlets_run(muxgl_handle* h, const muxgl_demux_params* p, double* sng
   std::vector<int64_t> cell_ptr((size_t)C + 1);
   HIPCHK(h, hipMemcpyAsync(cell_ptr.data(), h->d_cell_ptr, sizeof(int64_t) * (size_t)(C + 1), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  auto parts_of = [&](int64_t c) { return std::max<int64_t>(1, (cell_ptr[(size_t)c + 1] - cell_ptr[(size_t)c] + SNG_PART - 1) / SNG_PART); };
 
-  // batches of cells whose rows (one per part) fit the budget; at least one cell
+  // batches of cells whose rows (one per part) fit the budget (table_plan.hpp)
   const int64_t rows_cap = std::max<int64_t>(1, (int64_t)(dev_slab_budget("MUXGL_DEMUX_SLAB_MB") / (sizeof(double) * (size_t)V)));
-  int64_t max_rows = 0, max_cells = 0, max_cuts = 0;
-  std::vector<int64_t> batch_end;
-  for (int64_t c0 = 0; c0 < C;) {
-    int64_t rows = 0, c1 = c0, cuts = 0;
-    while (c1 < C && (c1 == c0 || rows + parts_of(c1) <= rows_cap)) {
-      const int64_t np = parts_of(c1);
-      rows += np;
-      cuts += np > 1;
-      ++c1;
-    }
-    batch_end.push_back(c1);
-    max_rows = std::max(max_rows, rows);
-    max_cells = std::max(max_cells, c1 - c0);
-    max_cuts = std::max(max_cuts, cuts);
-    c0 = c1;
-  }
-  if ((double)max_rows * (double)((V + 63) / 64) / 4.0 >= 2147483647.0)
+  const table_plan::batches bt = table_plan::plan(cell_ptr.data(), C, (size_t)rows_cap, [](int64_t, int64_t np) { return (size_t)np; });
+  const int nblk = (V + 63) / 64;
+  if (table_plan::exceeds_one_launch((double)bt.max_rows * (double)nblk, 4.0))
     MUXGL_FAIL(h, "muxgl_demux_singlets: a batch of %lld rows x %d samples exceeds one launch (lower MUXGL_DEMUX_SLAB_MB)",
-               (long long)max_rows, V);
+               (long long)bt.max_rows, V);
 
   int VH = 64;
   while (VH > 1 && VH / 2 >= V) VH /= 2;
-  const int nblk = (V + 63) / 64;
   sng_alpha al;
   for (int i = 0; i < MUXGL_MAX_ALPHA; ++i) al.a[i] = i < A ? p->alpha[i] : p->alpha[0];  // (repeats of alpha[0] change no maximum)
 
   dev_tmp<double> d_wt, d_slab;
   dev_tmp<sng_item> d_items;
-  dev_tmp<sng_cut> d_cuts;
+  dev_tmp<table_plan::cut> d_cuts;
   std::vector<sng_item> items;
-  std::vector<sng_cut> cuts;
+  std::vector<table_plan::cut> cuts;
   if (dev_alloc(h, &d_wt.p, (size_t)h->nnz * 3)) return 1;
-  if (dev_alloc(h, &d_slab.p, (size_t)max_rows * V)) return 1;
-  if (dev_alloc(h, &d_items.p, (size_t)max_rows)) return 1;
-  if (dev_alloc(h, &d_cuts.p, (size_t)max_cuts)) return 1;
+  if (dev_alloc(h, &d_slab.p, (size_t)bt.max_rows * V)) return 1;
+  if (dev_alloc(h, &d_items.p, (size_t)bt.max_rows)) return 1;
+  if (dev_alloc(h, &d_cuts.p, (size_t)bt.max_cuts)) return 1;
   tic(h, MUXGL_T_DEMUX_SINGLETS);
   if (h->nnz > 0 && weights_dispatch(h, A, al, d_wt.p)) return 1;
   int64_t c0 = 0;
-  for (const int64_t c1 : batch_end) {
+  for (const int64_t c1 : bt.end) {
     const int64_t nc = c1 - c0;
-    items.clear();
-    cuts.clear();
-    int64_t over = nc;  // first free row behind the cells' own
-    for (int64_t c = c0; c < c1; ++c) {
-      const int64_t b = cell_ptr[(size_t)c], e = cell_ptr[(size_t)c + 1], np = parts_of(c);
-      items.push_back(sng_item{b, std::min(e, b + SNG_PART), c - c0});
-      if (np > 1) cuts.push_back(sng_cut{c - c0, over, np - 1});
-      for (int64_t k = 1; k < np; ++k) items.push_back(sng_item{b + k * SNG_PART, std::min(e, b + (k + 1) * SNG_PART), over++});
-    }
+    table_plan::fill(cell_ptr.data(), c0, c1, table_plan::fixed_begin, items, &cuts, nullptr);
     const int64_t n_items = (int64_t)items.size();
-    // (the copies below come from pageable memory: they have left the vectors when they return)
-    HIPCHK(h, hipMemcpyAsync(d_items.p, items.data(), sizeof(sng_item) * items.size(), hipMemcpyHostToDevice, h->stream));
-    if (!cuts.empty())
-      HIPCHK(h, hipMemcpyAsync(d_cuts.p, cuts.data(), sizeof(sng_cut) * cuts.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    switch (VH) {
-      case 1: launch_sweep<1>(h, n_items, nblk, d_items.p, d_wt.p, d_slab.p); break;
-      case 2: launch_sweep<2>(h, n_items, nblk, d_items.p, d_wt.p, d_slab.p); break;
-      case 4: launch_sweep<4>(h, n_items, nblk, d_items.p, d_wt.p, d_slab.p); break;
-      case 8: launch_sweep<8>(h, n_items, nblk, d_items.p, d_wt.p, d_slab.p); break;
-      case 16: launch_sweep<16>(h, n_items, nblk, d_items.p, d_wt.p, d_slab.p); break;
-      case 32: launch_sweep<32>(h, n_items, nblk, d_items.p, d_wt.p, d_slab.p); break;
-      default: launch_sweep<64>(h, n_items, nblk, d_items.p, d_wt.p, d_slab.p); break;
-    }
+    if (table_upload(h, items, d_items.p, cuts, d_cuts.p)) return 1;
+#define CALL_S(W) launch_sweep<W>(h, n_items, nblk, d_items.p, d_wt.p, d_slab.p)
+    DISPATCH_WIDTH(VH, CALL_S);
+#undef CALL_S
     HIPCHK(h, hipGetLastError());
     if (!cuts.empty()) {
       const int64_t n = (int64_t)cuts.size() * V;
-      hipLaunchKernelGGL(sng_join_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (int64_t)cuts.size(),
-                         d_cuts.p, V, d_slab.p);
+      hipLaunchKernelGGL(table_join_kernel<double>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
+                         (int64_t)cuts.size(), d_cuts.p, V, d_slab.p);
       HIPCHK(h, hipGetLastError());
     }
     if (c1 == C) toc(h, MUXGL_T_DEMUX_SINGLETS);

@@ -15,7 +15,7 @@
 //     its rows of gp and u are (1, 0, 0), so its factor is exactly 1 everywhere and the sweep has no branch.
 //   * unk_sweep_kernel, lane = column of the slab: the V samples and, as column V, u itself (its "ju" dot is ll_uu).
 //     Two dots per (entry, column, alpha), multiplied into products kept as mantissa x 2^exponent, one log per (cell
-//     part, column, alpha, orientation).  A wave is one work unit: a part of a cell (at most UNK_PART entries) x a block
+//     part, column, alpha, orientation).  A wave is one work unit: a part of a cell (at most 2048 entries) x a block
 //     of 64 columns x a chunk of CH <= 3 alphas -- the accumulators of a whole 16-alpha grid do not fit a lane beside
 //     the loads in flight.  Every accumulator belongs to one (alpha, orientation), so the chunking changes no bit.
 //     Below 64 columns a wave holds G = 64 / VH entries side by side, multiplied in a fixed butterfly at the end.
@@ -23,33 +23,28 @@
 //     (VH = 1, 64 entries side by side) -- one launch over V + 1 columns would idle half the lanes at 8, 16 or 32
 //     samples and spend a whole second block on one column at 64.
 //   * unk_emit_kernel: the logs of the parts of a cell added in entry order and written in the caller's layout.
-// The cut of a cell depends on the cell alone and every reduction tree is fixed: the tables are bit-identical from call
-// to call, for any budget, for any subset of outputs, on one device, on a group and through the sharded driver.
+// Which cell goes into which batch, its cut into parts (fixed parts of 2048 entries) and the order of the work items
+// are table_plan.hpp's.  The cut of a cell depends on the cell alone and every reduction tree is fixed: the tables are
+// bit-identical from call to call, for any budget, for any subset of outputs, on one device, on a group and through the
+// sharded driver.
 //
 // Memory: nothing proportional to nnz x n_alpha is held for the whole pileup.  Cells are swept in batches of whole cells
-// whose weights ([entries][n_alpha][6]), slab rows and output rows fit the streamed call's budget (4 GiB or a third of
-// the device, MUXGL_DEMUX_SLAB_MB); each batch is copied out before the next.
+// whose weights ([entries][n_alpha][6]), slab rows and output rows (table_plan::unknown_bytes) fit the streamed call's
+// budget (4 GiB or a third of the device, MUXGL_DEMUX_SLAB_MB); each batch is copied out before the next.
 #include <algorithm>
 #include <vector>
 
 #include "demux_entry.hpp"
+#include "table_call.hpp"
 
 namespace {
-
-constexpr int64_t UNK_PART = 2048;  // entries per part of a long cell (the cut of demux_singlets.hip)
 
 struct unk_alpha {
   double a[MUXGL_MAX_ALPHA];
 };
-// one work item: the entries [e0, e1) of one cell, result row `row` of the slab (rows of cells first, then the rows of
-// the further parts of long cells)
-struct unk_item {
-  int64_t e0, e1, row;
-};
+using unk_item = table_plan::item;  // the entries [e0, e1) of one cell, result row `row` of the slab
 // the further parts of a cell: its value = slab[cell row] + slab[first] + ... + slab[first + count - 1], in this order
-struct unk_cell {
-  int64_t first, count;
-};
+using unk_cell = table_plan::cell;
 
 __global__ void __launch_bounds__(256)
     unk_mean_kernel(int64_t S, const double* __restrict__ gp, const uint8_t* __restrict__ has_gp, int V, double* __restrict__ u) {
@@ -270,15 +265,9 @@ template <int CH>
 void sweep_dispatch_vh(muxgl_handle* h, int A, int nch, int j0, int ncol, const unk_batch& b) {
   int VH = 64;
   while (VH > 1 && VH / 2 >= ncol) VH /= 2;
-  switch (VH) {
-    case 1: launch_sweep<1, CH>(h, A, nch, j0, ncol, b); break;
-    case 2: launch_sweep<2, CH>(h, A, nch, j0, ncol, b); break;
-    case 4: launch_sweep<4, CH>(h, A, nch, j0, ncol, b); break;
-    case 8: launch_sweep<8, CH>(h, A, nch, j0, ncol, b); break;
-    case 16: launch_sweep<16, CH>(h, A, nch, j0, ncol, b); break;
-    case 32: launch_sweep<32, CH>(h, A, nch, j0, ncol, b); break;
-    default: launch_sweep<64, CH>(h, A, nch, j0, ncol, b); break;
-  }
+#define CALL_S(W) launch_sweep<W, CH>(h, A, nch, j0, ncol, b)
+  DISPATCH_WIDTH(VH, CALL_S);
+#undef CALL_S
 }
 
 int sweep_dispatch(muxgl_handle* h, int CH, int A, int nch, int j0, int ncol, const unk_batch& b) {
@@ -300,43 +289,24 @@ int demux_unknown_run(muxgl_handle* h, const muxgl_demux_params* p, const double
   std::vector<int64_t> cell_ptr((size_t)C + 1);
   HIPCHK(h, hipMemcpyAsync(cell_ptr.data(), h->d_cell_ptr, sizeof(int64_t) * (size_t)(C + 1), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  auto len_of = [&](int64_t c) { return cell_ptr[(size_t)c + 1] - cell_ptr[(size_t)c]; };
-  auto parts_of = [&](int64_t c) { return std::max<int64_t>(1, (len_of(c) + UNK_PART - 1) / UNK_PART); };
-  // device bytes of a cell: its entries' weights, its slab rows (one per part) and its rows of the three tables
-  const size_t row_bytes = sizeof(double) * (size_t)A * 2 * VC;
-  auto bytes_of = [&](int64_t c) {
-    return (size_t)len_of(c) * A * 6 * sizeof(double) + (size_t)parts_of(c) * (row_bytes + sizeof(unk_item)) + row_bytes +
-           sizeof(unk_cell);
-  };
 
-  // batches of whole cells that fit the budget
+  // batches of whole cells whose device bytes fit the budget (table_plan.hpp)
   const size_t budget = dev_slab_budget("MUXGL_DEMUX_SLAB_MB");
-  int64_t max_rows = 0, max_cells = 0, max_entries = 0;
-  std::vector<int64_t> batch_end;
-  for (int64_t c0 = 0; c0 < C;) {
-    if (bytes_of(c0) > budget)
-      MUXGL_FAIL(h, "muxgl_demux_unknown: droplet %lld alone (%lld entries x %d alphas x %d samples: %.1f MB) exceeds the "
-                    "budget of %.1f MB (raise MUXGL_DEMUX_SLAB_MB)",
-                 (long long)(h->cell_base + c0), (long long)len_of(c0), A, V, (double)bytes_of(c0) / 1048576.0,
-                 (double)budget / 1048576.0);
-    size_t bytes = 0;
-    int64_t rows = 0, c1 = c0;
-    while (c1 < C && (c1 == c0 || bytes + bytes_of(c1) <= budget)) {
-      bytes += bytes_of(c1);
-      rows += parts_of(c1);
-      ++c1;
-    }
-    batch_end.push_back(c1);
-    max_rows = std::max(max_rows, rows);
-    max_cells = std::max(max_cells, c1 - c0);
-    max_entries = std::max(max_entries, cell_ptr[(size_t)c1] - cell_ptr[(size_t)c0]);
-    c0 = c1;
+  auto bytes_of = [&](int64_t len, int64_t np) { return table_plan::unknown_bytes(len, np, A, VC); };
+  const table_plan::batches bt = table_plan::plan(cell_ptr.data(), C, budget, bytes_of);
+  if (bt.over >= 0) {
+    const int64_t len = cell_ptr[(size_t)bt.over + 1] - cell_ptr[(size_t)bt.over];
+    MUXGL_FAIL(h, "muxgl_demux_unknown: droplet %lld alone (%lld entries x %d alphas x %d samples: %.1f MB) exceeds the "
+                  "budget of %.1f MB (raise MUXGL_DEMUX_SLAB_MB)",
+               (long long)(h->cell_base + bt.over), (long long)len, A, V,
+               (double)bytes_of(len, table_plan::parts(len)) / 1048576.0, (double)budget / 1048576.0);
   }
   const int nblk = (V + 63) / 64;
   const int nch = (A + 2) / 3, CH = (A + nch - 1) / nch;  // chunks of the grid, alphas per chunk (1..3)
-  if ((double)max_rows * nblk * nch / 4.0 >= 2147483647.0 || (double)max_cells * VC * A / 256.0 >= 2147483647.0)
+  if (table_plan::exceeds_one_launch((double)bt.max_rows * nblk * nch, 4.0) ||
+      table_plan::exceeds_one_launch((double)bt.max_cells * VC * A, 256.0))
     MUXGL_FAIL(h, "muxgl_demux_unknown: a batch of %lld rows x %d samples x %d alphas exceeds one launch (lower MUXGL_DEMUX_SLAB_MB)",
-               (long long)max_rows, V, A);
+               (long long)bt.max_rows, V, A);
   unk_alpha al;
   for (int i = 0; i < MUXGL_MAX_ALPHA; ++i) al.a[i] = i < A ? p->alpha[i] : p->alpha[0];  // (repeats of alpha[0] change no maximum)
 
@@ -344,65 +314,27 @@ int demux_unknown_run(muxgl_handle* h, const muxgl_demux_params* p, const double
   dev_tmp<unk_item> d_items;
   dev_tmp<unk_cell> d_cells;
   if (dev_alloc(h, &d_u.p, (size_t)S * 3)) return 1;
-  if (dev_alloc(h, &d_wt.p, (size_t)max_entries * A * 6)) return 1;
-  if (dev_alloc(h, &d_slab.p, (size_t)max_rows * A * 2 * VC)) return 1;
-  if (dev_alloc(h, &d_ju.p, (size_t)max_cells * V * A)) return 1;
-  if (dev_alloc(h, &d_uj.p, (size_t)max_cells * V * A)) return 1;
-  if (dev_alloc(h, &d_uu.p, (size_t)max_cells * A)) return 1;
-  if (dev_alloc(h, &d_items.p, (size_t)max_rows)) return 1;
-  if (dev_alloc(h, &d_cells.p, (size_t)max_cells)) return 1;
-
-  // (events of the call's own: the handle's timing slots keep their values)
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  const bool timed = kernel_ms && !timing_off();
-  if (timed) {
-    HIPCHK(h, hipEventCreate(&ev0));
-    if (hipEventCreate(&ev1) != hipSuccess) {
-      (void)hipEventDestroy(ev0);
-      MUXGL_FAIL(h, "muxgl_demux_unknown: hipEventCreate failed");
-    }
-  }
-  struct ev_guard {
-    hipEvent_t a, b;
-    ~ev_guard() {
-      if (a) (void)hipEventDestroy(a);
-      if (b) (void)hipEventDestroy(b);
-    }
-  } guard{ev0, ev1};
+  if (dev_alloc(h, &d_wt.p, (size_t)bt.max_entries * A * 6)) return 1;
+  if (dev_alloc(h, &d_slab.p, (size_t)bt.max_rows * A * 2 * VC)) return 1;
+  if (dev_alloc(h, &d_ju.p, (size_t)bt.max_cells * V * A)) return 1;
+  if (dev_alloc(h, &d_uj.p, (size_t)bt.max_cells * V * A)) return 1;
+  if (dev_alloc(h, &d_uu.p, (size_t)bt.max_cells * A)) return 1;
+  if (dev_alloc(h, &d_items.p, (size_t)bt.max_rows)) return 1;
+  if (dev_alloc(h, &d_cells.p, (size_t)bt.max_cells)) return 1;
+  call_events ev;  // (the handle's timing slots keep their values)
+  if (ev.create(h, kernel_ms, "muxgl_demux_unknown")) return 1;
 
   if (gp0 && S > 0) HIPCHK(h, hipMemcpyAsync(d_u.p, gp0, sizeof(double) * (size_t)S * 3, hipMemcpyHostToDevice, h->stream));
   std::vector<unk_item> items;
   std::vector<unk_cell> cells;
   int64_t c0 = 0;
-  for (const int64_t c1 : batch_end) {
+  for (const int64_t c1 : bt.end) {
     const int64_t nc = c1 - c0;
-    items.clear();
-    cells.clear();
-    int64_t over = nc;  // first free row behind the cells' own
-    for (int64_t c = c0; c < c1; ++c) {
-      const int64_t b = cell_ptr[(size_t)c], e = cell_ptr[(size_t)c + 1], np = parts_of(c);
-      items.push_back(unk_item{b, std::min(e, b + UNK_PART), c - c0});
-      cells.push_back(unk_cell{over, np - 1});
-      for (int64_t k = 1; k < np; ++k) items.push_back(unk_item{b + k * UNK_PART, std::min(e, b + (k + 1) * UNK_PART), over++});
-    }
-    unk_batch bt;
-    bt.eb0 = cell_ptr[(size_t)c0];
-    bt.eb1 = cell_ptr[(size_t)c1];
-    bt.n_items = (int64_t)items.size();
-    bt.nc = nc;
-    bt.d_items = d_items.p;
-    bt.d_cells = d_cells.p;
-    bt.d_wt = d_wt.p;
-    bt.d_slab = d_slab.p;
-    bt.d_ju = d_ju.p;
-    bt.d_uj = d_uj.p;
-    bt.d_uu = d_uu.p;
-    bt.d_u = d_u.p;
-    // (the copies below come from pageable memory: they have left the vectors when they return)
-    HIPCHK(h, hipMemcpyAsync(d_items.p, items.data(), sizeof(unk_item) * items.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d_cells.p, cells.data(), sizeof(unk_cell) * cells.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (timed) HIPCHK(h, hipEventRecord(ev0, h->stream));
+    table_plan::fill(cell_ptr.data(), c0, c1, table_plan::fixed_begin, items, nullptr, &cells);
+    const unk_batch b = {cell_ptr[(size_t)c0], cell_ptr[(size_t)c1], (int64_t)items.size(), nc, d_items.p, d_cells.p, d_wt.p,
+                         d_slab.p, d_ju.p, d_uj.p, d_uu.p, d_u.p};
+    if (table_upload(h, items, d_items.p, cells, d_cells.p)) return 1;
+    if (ev.start(h)) return 1;
     if (c0 == 0 && S > 0) {  // the unknown donor's prior, once per call
       if (gp0)
         hipLaunchKernelGGL(unk_neutral_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, h->stream, S, h->d_has_gp, d_u.p);
@@ -411,26 +343,23 @@ int demux_unknown_run(muxgl_handle* h, const muxgl_demux_params* p, const double
                            V, d_u.p);
       HIPCHK(h, hipGetLastError());
     }
-    if (bt.eb1 > bt.eb0 && weights_dispatch(h, A, al, bt)) return 1;
-    if (sweep_dispatch(h, CH, A, nch, 0, V, bt)) return 1;  // the samples
-    if (sweep_dispatch(h, CH, A, nch, V, 1, bt)) return 1;  // the unknown donor's own column
+    if (b.eb1 > b.eb0 && weights_dispatch(h, A, al, b)) return 1;
+    if (sweep_dispatch(h, CH, A, nch, 0, V, b)) return 1;  // the samples
+    if (sweep_dispatch(h, CH, A, nch, V, 1, b)) return 1;  // the unknown donor's own column
     {
       const int64_t n = nc * VC * A;
       hipLaunchKernelGGL(unk_emit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, nc, d_cells.p, V, A,
                          d_slab.p, d_ju.p, d_uj.p, d_uu.p);
       HIPCHK(h, hipGetLastError());
     }
-    if (timed) HIPCHK(h, hipEventRecord(ev1, h->stream));
+    if (ev.stop(h)) return 1;
     const size_t nva = sizeof(double) * (size_t)nc * V * A;
     if (ll_ju) HIPCHK(h, hipMemcpyAsync(ll_ju + (size_t)c0 * V * A, d_ju.p, nva, hipMemcpyDeviceToHost, h->stream));
     if (ll_uj) HIPCHK(h, hipMemcpyAsync(ll_uj + (size_t)c0 * V * A, d_uj.p, nva, hipMemcpyDeviceToHost, h->stream));
     if (ll_uu)
       HIPCHK(h, hipMemcpyAsync(ll_uu + (size_t)c0 * A, d_uu.p, sizeof(double) * (size_t)nc * A, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (timed) {
-      float t = 0.f;
-      if (hipEventElapsedTime(&t, ev0, ev1) == hipSuccess) *kernel_ms += t;
-    }
+    ev.add();
     c0 = c1;
   }
   return 0;

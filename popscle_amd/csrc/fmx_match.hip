@@ -188,15 +188,9 @@ void launch_sweep(muxgl_handle* h, const fmm_args& a) {
 
 template <int T>
 void launch_donors(muxgl_handle* h, int VH, const fmm_args& a) {
-  switch (VH) {
-    case 1: launch_sweep<1, T, false>(h, a); break;
-    case 2: launch_sweep<2, T, false>(h, a); break;
-    case 4: launch_sweep<4, T, false>(h, a); break;
-    case 8: launch_sweep<8, T, false>(h, a); break;
-    case 16: launch_sweep<16, T, false>(h, a); break;
-    case 32: launch_sweep<32, T, false>(h, a); break;
-    default: launch_sweep<64, T, false>(h, a); break;
-  }
+#define CALL_S(W) launch_sweep<W, T, false>(h, a)
+  DISPATCH_WIDTH(VH, CALL_S);
+#undef CALL_S
 }
 
 // clusters per wave (DESIGN.md 4.2e has the measurement behind the default); MUXGL_FMX_MATCH_TILE=1|2|4|8 for the probe,
@@ -240,27 +234,12 @@ int fmx_match_run(muxgl_handle* h, double* ll, double* ll0, int32_t* nsnps, floa
                    dev_alloc(h, &d_out0.p, (size_t)kb_cap) || dev_alloc(h, &d_outn.p, (size_t)kb_cap)))
     return 1;
   if (dev_alloc(h, &d_nreads.p, (size_t)kb_cap * S)) return 1;
-  // (events of the call's own: the handle's timing slots keep their values)
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  const bool timed = kernel_ms && !timing_off();
-  if (timed) {
-    HIPCHK(h, hipEventCreate(&ev0));
-    if (hipEventCreate(&ev1) != hipSuccess) {
-      (void)hipEventDestroy(ev0);
-      MUXGL_FAIL(h, "muxgl_fmx_match_donors: hipEventCreate failed");
-    }
-  }
-  struct ev_guard {
-    hipEvent_t a, b;
-    ~ev_guard() {
-      if (a) (void)hipEventDestroy(a);
-      if (b) (void)hipEventDestroy(b);
-    }
-  } guard{ev0, ev1};
+  call_events ev;  // (the handle's timing slots keep their values)
+  if (ev.create(h, kernel_ms, "muxgl_fmx_match_donors")) return 1;
 
   for (int k0 = 0; k0 < K; k0 += kb_cap) {
     const int kb = std::min(kb_cap, K - k0);
-    if (timed) HIPCHK(h, hipEventRecord(ev0, h->stream));
+    if (ev.start(h)) return 1;
     HIPCHK(h, hipMemsetAsync(d_nreads.p, 0, sizeof(int32_t) * (size_t)kb * S, h->stream));
     if (h->nnz) {
       const int64_t blocks = std::min<int64_t>((h->nnz + 255) / 256, 16384);
@@ -292,16 +271,13 @@ int fmx_match_run(muxgl_handle* h, double* ll, double* ll0, int32_t* nsnps, floa
                          d_part0.p, d_partn.p, d_out0.p, d_outn.p);
       HIPCHK(h, hipGetLastError());
     }
-    if (timed) HIPCHK(h, hipEventRecord(ev1, h->stream));
+    if (ev.stop(h)) return 1;
     if (ll)
       HIPCHK(h, hipMemcpyAsync(ll + (size_t)k0 * V, d_out.p, sizeof(double) * (size_t)kb * V, hipMemcpyDeviceToHost, h->stream));
     if (ll0) HIPCHK(h, hipMemcpyAsync(ll0 + k0, d_out0.p, sizeof(double) * (size_t)kb, hipMemcpyDeviceToHost, h->stream));
     if (nsnps) HIPCHK(h, hipMemcpyAsync(nsnps + k0, d_outn.p, sizeof(int32_t) * (size_t)kb, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (timed) {
-      float t = 0.f;
-      if (hipEventElapsedTime(&t, ev0, ev1) == hipSuccess) *kernel_ms += t;
-    }
+    ev.add();
   }
   return 0;
 }

@@ -231,7 +231,7 @@ void launch_sweep(muxgl_handle* h, const fcp_args& a) {
 
 template <int T>
 void launch_width(muxgl_handle* h, int KH, const fcp_args& a) {
-  switch (KH) {
+  switch (KH) {  // (no width 1, pairs_plan::lane_width: not common.hpp's DISPATCH_WIDTH)
     case 2: launch_sweep<2, T>(h, a); break;
     case 4: launch_sweep<4, T>(h, a); break;
     case 8: launch_sweep<8, T>(h, a); break;
@@ -283,25 +283,10 @@ int fmx_pairs_run(muxgl_handle* h, double* llk2, double* llk0, int32_t* nsnps, f
       dev_alloc(h, &d_part2.p, part_n) || dev_alloc(h, &d_part0.p, part_n) || dev_alloc(h, &d_partn.p, part_n) ||
       dev_alloc(h, &d_tri2.p, npair) || dev_alloc(h, &d_tri0.p, npair) || dev_alloc(h, &d_trin.p, npair))
     return 1;
-  // (events of the call's own: the handle's timing slots keep their values)
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  const bool timed = kernel_ms && !timing_off();
-  if (timed) {
-    HIPCHK(h, hipEventCreate(&ev0));
-    if (hipEventCreate(&ev1) != hipSuccess) {
-      (void)hipEventDestroy(ev0);
-      MUXGL_FAIL(h, "muxgl_fmx_cluster_pairs: hipEventCreate failed");
-    }
-  }
-  struct ev_guard {
-    hipEvent_t a, b;
-    ~ev_guard() {
-      if (a) (void)hipEventDestroy(a);
-      if (b) (void)hipEventDestroy(b);
-    }
-  } guard{ev0, ev1};
+  call_events ev;  // (the handle's timing slots keep their values)
+  if (ev.create(h, kernel_ms, "muxgl_fmx_cluster_pairs")) return 1;
 
-  if (timed) HIPCHK(h, hipEventRecord(ev0, h->stream));
+  if (ev.start(h)) return 1;
   HIPCHK(h, hipMemsetAsync(d_memb.p, 0, sizeof(u64) * (size_t)S * W, h->stream));
   if (h->nnz) {
     const int64_t blocks = std::min<int64_t>((h->nnz + 255) / 256, 16384);
@@ -329,15 +314,12 @@ int fmx_pairs_run(muxgl_handle* h, double* llk2, double* llk0, int32_t* nsnps, f
       HIPCHK(h, hipGetLastError());
     }
   }
-  if (timed) HIPCHK(h, hipEventRecord(ev1, h->stream));
+  if (ev.stop(h)) return 1;
   if (llk2) HIPCHK(h, hipMemcpyAsync(llk2, d_tri2.p, sizeof(double) * npair, hipMemcpyDeviceToHost, h->stream));
   if (llk0) HIPCHK(h, hipMemcpyAsync(llk0, d_tri0.p, sizeof(double) * npair, hipMemcpyDeviceToHost, h->stream));
   if (nsnps) HIPCHK(h, hipMemcpyAsync(nsnps, d_trin.p, sizeof(int32_t) * npair, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (timed) {
-    float t = 0.f;
-    if (hipEventElapsedTime(&t, ev0, ev1) == hipSuccess) *kernel_ms = t;
-  }
+  ev.add();  // (*kernel_ms is 0 so far)
   return 0;
 }
 

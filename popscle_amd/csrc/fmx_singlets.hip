@@ -17,26 +17,25 @@
 //     cell x a block of 64 clusters, the entry wave-uniform (its diagonal comes through scalar loads).  Below 64 clusters
 //     a wave holds G = 64 / KH entries side by side (KH = K rounded up to a power of two, lane = (entry slot, cluster))
 //     and the G partial products of a cluster are multiplied in a fixed butterfly at the end.
-//   * fsg_join_kernel: the logs of the parts of a long cell, added in entry order.
-// A cell of more than 2048 entries is cut into the equal parts of the wave plan (as fmx_stream.hip's sweep_block cuts
-// it).  The cut depends on the cell alone and every reduction tree is fixed: the table is bit-identical from call to
-// call, for any slab budget, on one device, on a group and through the sharded driver.
+//   * table_join_kernel (table_call.hpp): the logs of the parts of a long cell, added in entry order.
+// Which cell goes into which batch, its cut into parts (the equal parts of the wave plan, as fmx_stream.hip's
+// sweep_block cuts a cell) and the order of the work items are table_plan.hpp's.  The cut depends on the cell alone and
+// every reduction tree is fixed: the table is bit-identical from call to call, for any slab budget, on one device, on a
+// group and through the sharded driver.
 //
-// The diagonal is read straight from d_egls (3 of 9 doubles at a 72-byte stride) or from a copy packed into [nnz][3] at
-// the start of the call (MUXGL_FMX_SNG_DIAG=egls|packed; DESIGN.md 4.2c has the measurement behind the default).
+// The diagonal is read straight from d_egls (3 of 9 doubles at a 72-byte stride; DESIGN.md 4.2c has the measurement
+// against a packed [nnz][3] copy, a path that is gone).
 //
-// Memory: a slab of the table (the streamed E-step's budget: 4 GiB or a third of the device, MUXGL_FMX_SLAB_MB), the
-// work items, and [nnz][3] when the diagonal is packed.  When the table exceeds the budget the cells are swept in
-// batches and each batch is copied out before the next.  Nothing proportional to C x K^2.
+// Memory: a slab of the table (the streamed E-step's budget: 4 GiB or a third of the device, MUXGL_FMX_SLAB_MB) and the
+// work items.  When the table exceeds the budget the cells are swept in batches and each batch is copied out before the
+// next.  Nothing proportional to C x K^2.
 #include <algorithm>
-#include <cstring>
 #include <vector>
 
-#include "common.hpp"
+#include "table_call.hpp"
 
 namespace {
 
-constexpr int64_t FSG_PART = 2048;  // entries per part of a long cell (the wave kernels' cut, common.hpp wave_item)
 // Entries per lane between two renormalisations, all of their loads in flight.  The smallest factor this path can see:
 // a factor is a combination sum_l q_l d_l of the entry's diagonal with a posterior triple that sums to 1 (within a few
 // ulp, with or without the geno_error mixing of :402-415: a single q_l may be tiny or exactly 0 at geno_error = 0, their
@@ -47,34 +46,17 @@ constexpr int64_t FSG_PART = 2048;  // entries per part of a long cell (the wave
 // product 0 and the log -inf, the reference's log(0) chain; frexp(0) = 0, so no NaN on the way.
 constexpr int FSG_UNR = 8;
 
-// one work item: the entries [e0, e1) of one cell, result row `row` of the slab (rows of cells first, then the rows of
-// the further parts of long cells)
-struct fsg_item {
-  int64_t e0, e1, row;
-};
-// a cell of several parts: slab[cell row] += slab[first] + ... + slab[first + count - 1], in this order
-struct fsg_cut {
-  int64_t row, first, count;
-};
-
-__global__ void __launch_bounds__(256)
-    fsg_pack_kernel(int64_t nnz, const double* __restrict__ egls, double* __restrict__ diag) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= nnz * 3) return;
-  const int64_t e = i / 3;
-  const int l = (int)(i - e * 3);
-  diag[i] = egls[(size_t)e * 9 + 4 * l];
-}
+using fsg_item = table_plan::item;  // the entries [e0, e1) of one cell, result row `row` of the slab
 
 // grid: ceil(n_items * nblk / 4) workgroups of four waves; wave u <-> (item u / nblk, cluster block u % nblk), so the
 // waves of a workgroup walk the same entries and read neighbouring pieces of the same posterior rows.
-// PACKED: diag is [nnz][3]; else it is d_egls, [nnz][9], the diagonal at 0, 4, 8.
-template <int KH, bool PACKED>
+// diag is d_egls, [nnz][9], the diagonal at 0, 4, 8.
+template <int KH>
 __global__ void __launch_bounds__(256)
     fsg_sweep_kernel(int64_t n_units, int nblk, const fsg_item* __restrict__ items, const int32_t* __restrict__ entry_snp,
                      const double* __restrict__ diag, const double* __restrict__ cgp, int K, double* __restrict__ slab) {
   constexpr int G = 64 / KH;  // entries side by side in a wave
-  constexpr int DS = PACKED ? 3 : 9, D1 = PACKED ? 1 : 4, D2 = PACKED ? 2 : 8;
+  constexpr int DS = 9, D1 = 4, D2 = 8;
   const int64_t u = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   if (u >= n_units) return;
   const int64_t it = u / nblk;
@@ -115,37 +97,11 @@ __global__ void __launch_bounds__(256)
   if (jl && sub == 0) slab[(size_t)items[it].row * K + j] = prodacc_log(acc, ex);
 }
 
-__global__ void __launch_bounds__(256)
-    fsg_join_kernel(int64_t n_cuts, const fsg_cut* __restrict__ cuts, int K, double* __restrict__ slab) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n_cuts * K) return;
-  const int64_t c = i / K;
-  const int j = (int)(i - c * K);
-  const fsg_cut ct = cuts[c];
-  double s = slab[(size_t)ct.row * K + j];
-  for (int64_t k = 0; k < ct.count; ++k) s += slab[(size_t)(ct.first + k) * K + j];
-  slab[(size_t)ct.row * K + j] = s;
-}
-
 template <int KH>
-void launch_sweep(muxgl_handle* h, bool packed, int64_t n_items, int nblk, const fsg_item* d_items, const double* d_diag,
-                  double* d_slab) {
+void launch_sweep(muxgl_handle* h, int64_t n_items, int nblk, const fsg_item* d_items, double* d_slab) {
   const int64_t n_units = n_items * nblk;
-  const dim3 grid((unsigned)((n_units + 3) / 4));
-  if (packed)
-    hipLaunchKernelGGL((fsg_sweep_kernel<KH, true>), grid, dim3(256), 0, h->stream, n_units, nblk, d_items, h->d_entry_snp,
-                       d_diag, h->d_cgp, h->K, d_slab);
-  else
-    hipLaunchKernelGGL((fsg_sweep_kernel<KH, false>), grid, dim3(256), 0, h->stream, n_units, nblk, d_items, h->d_entry_snp,
-                       h->d_egls, h->d_cgp, h->K, d_slab);
-}
-
-// which copy of the diagonal the sweep reads (header comment); the environment is read at each call
-bool diag_packed() {
-  const char* s = getenv("MUXGL_FMX_SNG_DIAG");
-  if (s && !strcmp(s, "packed")) return true;
-  if (s && !strcmp(s, "egls")) return false;
-  return false;
+  hipLaunchKernelGGL((fsg_sweep_kernel<KH>), dim3((unsigned)((n_units + 3) / 4)), dim3(256), 0, h->stream, n_units, nblk,
+                     d_items, h->d_entry_snp, h->d_egls, h->d_cgp, h->K, d_slab);
 }
 
 int fmx_singlets_run(muxgl_handle* h, double* sng) {
@@ -154,81 +110,40 @@ int fmx_singlets_run(muxgl_handle* h, double* sng) {
   std::vector<int64_t> cell_ptr((size_t)C + 1);
   HIPCHK(h, hipMemcpyAsync(cell_ptr.data(), h->d_cell_ptr, sizeof(int64_t) * (size_t)(C + 1), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  auto len_of = [&](int64_t c) { return cell_ptr[(size_t)c + 1] - cell_ptr[(size_t)c]; };
-  auto parts_of = [&](int64_t c) { return len_of(c) > FSG_PART ? (len_of(c) + FSG_PART - 1) / FSG_PART : (int64_t)1; };
 
-  // batches of cells whose rows (one per part) fit the budget; at least one cell
+  // batches of cells whose rows (one per part) fit the budget (table_plan.hpp)
   const int64_t rows_cap = std::max<int64_t>(1, (int64_t)(dev_slab_budget("MUXGL_FMX_SLAB_MB") / (sizeof(double) * (size_t)K)));
-  int64_t max_rows = 0, max_cuts = 0;
-  std::vector<int64_t> batch_end;
-  for (int64_t c0 = 0; c0 < C;) {
-    int64_t rows = 0, c1 = c0, cuts = 0;
-    while (c1 < C && (c1 == c0 || rows + parts_of(c1) <= rows_cap)) {
-      const int64_t np = parts_of(c1);
-      rows += np;
-      cuts += np > 1;
-      ++c1;
-    }
-    batch_end.push_back(c1);
-    max_rows = std::max(max_rows, rows);
-    max_cuts = std::max(max_cuts, cuts);
-    c0 = c1;
-  }
+  const table_plan::batches bt = table_plan::plan(cell_ptr.data(), C, (size_t)rows_cap, [](int64_t, int64_t np) { return (size_t)np; });
   const int nblk = (K + 63) / 64;
-  if ((double)max_rows * (double)nblk / 4.0 >= 2147483647.0)
+  if (table_plan::exceeds_one_launch((double)bt.max_rows * (double)nblk, 4.0))
     MUXGL_FAIL(h, "muxgl_fmx_singlets: a batch of %lld rows x %d clusters exceeds one launch (lower MUXGL_FMX_SLAB_MB)",
-               (long long)max_rows, K);
+               (long long)bt.max_rows, K);
   int KH = 64;
   while (KH > 1 && KH / 2 >= K) KH /= 2;
-  const bool packed = diag_packed();
 
-  dev_tmp<double> d_diag, d_slab;
+  dev_tmp<double> d_slab;
   dev_tmp<fsg_item> d_items;
-  dev_tmp<fsg_cut> d_cuts;
+  dev_tmp<table_plan::cut> d_cuts;
   std::vector<fsg_item> items;
-  std::vector<fsg_cut> cuts;
-  if (packed && dev_alloc(h, &d_diag.p, (size_t)h->nnz * 3)) return 1;
-  if (dev_alloc(h, &d_slab.p, (size_t)max_rows * K)) return 1;
-  if (dev_alloc(h, &d_items.p, (size_t)max_rows)) return 1;
-  if (dev_alloc(h, &d_cuts.p, (size_t)max_cuts)) return 1;
+  std::vector<table_plan::cut> cuts;
+  if (dev_alloc(h, &d_slab.p, (size_t)bt.max_rows * K)) return 1;
+  if (dev_alloc(h, &d_items.p, (size_t)bt.max_rows)) return 1;
+  if (dev_alloc(h, &d_cuts.p, (size_t)bt.max_cuts)) return 1;
   tic(h, MUXGL_T_FMX_SINGLETS);
-  if (packed && h->nnz > 0) {
-    const int64_t n = h->nnz * 3;
-    hipLaunchKernelGGL(fsg_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->nnz, h->d_egls, d_diag.p);
-    HIPCHK(h, hipGetLastError());
-  }
   int64_t c0 = 0;
-  for (const int64_t c1 : batch_end) {
+  for (const int64_t c1 : bt.end) {
     const int64_t nc = c1 - c0;
-    items.clear();
-    cuts.clear();
-    int64_t over = nc;  // first free row behind the cells' own
-    for (int64_t c = c0; c < c1; ++c) {
-      const int64_t b = cell_ptr[(size_t)c], n = len_of(c), np = parts_of(c);
-      items.push_back(fsg_item{b, b + n / np, c - c0});
-      if (np > 1) cuts.push_back(fsg_cut{c - c0, over, np - 1});
-      for (int64_t k = 1; k < np; ++k) items.push_back(fsg_item{b + n * k / np, b + n * (k + 1) / np, over++});
-    }
+    table_plan::fill(cell_ptr.data(), c0, c1, table_plan::equal_begin, items, &cuts, nullptr);
     const int64_t n_items = (int64_t)items.size();
-    // (the copies below come from pageable memory: they have left the vectors when they return)
-    HIPCHK(h, hipMemcpyAsync(d_items.p, items.data(), sizeof(fsg_item) * items.size(), hipMemcpyHostToDevice, h->stream));
-    if (!cuts.empty())
-      HIPCHK(h, hipMemcpyAsync(d_cuts.p, cuts.data(), sizeof(fsg_cut) * cuts.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    switch (KH) {
-      case 1: launch_sweep<1>(h, packed, n_items, nblk, d_items.p, d_diag.p, d_slab.p); break;
-      case 2: launch_sweep<2>(h, packed, n_items, nblk, d_items.p, d_diag.p, d_slab.p); break;
-      case 4: launch_sweep<4>(h, packed, n_items, nblk, d_items.p, d_diag.p, d_slab.p); break;
-      case 8: launch_sweep<8>(h, packed, n_items, nblk, d_items.p, d_diag.p, d_slab.p); break;
-      case 16: launch_sweep<16>(h, packed, n_items, nblk, d_items.p, d_diag.p, d_slab.p); break;
-      case 32: launch_sweep<32>(h, packed, n_items, nblk, d_items.p, d_diag.p, d_slab.p); break;
-      default: launch_sweep<64>(h, packed, n_items, nblk, d_items.p, d_diag.p, d_slab.p); break;
-    }
+    if (table_upload(h, items, d_items.p, cuts, d_cuts.p)) return 1;
+#define CALL_S(W) launch_sweep<W>(h, n_items, nblk, d_items.p, d_slab.p)
+    DISPATCH_WIDTH(KH, CALL_S);
+#undef CALL_S
     HIPCHK(h, hipGetLastError());
     if (!cuts.empty()) {
       const int64_t n = (int64_t)cuts.size() * K;
-      hipLaunchKernelGGL(fsg_join_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (int64_t)cuts.size(),
-                         d_cuts.p, K, d_slab.p);
+      hipLaunchKernelGGL(table_join_kernel<double>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
+                         (int64_t)cuts.size(), d_cuts.p, K, d_slab.p);
       HIPCHK(h, hipGetLastError());
     }
     if (c1 == C) toc(h, MUXGL_T_FMX_SINGLETS);

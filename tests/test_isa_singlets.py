@@ -16,5 +16,7 @@ def test_sweep_kernel_uses_no_scratch_and_no_agprs(tmp_path_factory):
         assert meta["num_vgpr"] <= 128, (name, meta)  # four waves per SIMD at least
         assert "scratch_" not in body and "s_swappc" not in body
         assert len(re.findall(r"global_load_dwordx[24]", body)) >= 8, name  # the entries of a block, loaded side by side
-    for name, (body, meta) in kernels(text, "sng_join_kernel").items():
+    js = kernels(text, "table_join_kernel")
+    assert len(js) == 1
+    for name, (body, meta) in js.items():
         assert meta["private_seg_size"] == 0

@@ -6,9 +6,8 @@ One JSON line per shape.  Every shape runs in a child process of its own under `
 probe stops at the first child that fails: nothing is started on a device another step has just left in doubt.
 
 Per shape, after two EM iterations from a greedy start (spread clusters beyond 64): kernel_ms = MUXGL_T_FMX_SINGLETS of
-`repeats` calls after one untimed call, as median / min / max, once per way of reading the entry diagonal
-(MUXGL_FMX_SNG_DIAG=egls: straight from the [nnz][9] likelihoods; packed: from a [nnz][3] copy made inside the call and
-the bracket); wall_ms = host clock around the whole call, its copy of the table to the host included (the default way);
+`repeats` calls after one untimed call, as median / min / max; wall_ms = host clock around the whole call, its copy of
+the table to the host included, median;
 estep_ms / iter_ms = MUXGL_T_FMX_ESTEP and the sum of the GP, E-step, call and M-step slots of the iteration before;
 roof_frac = nnz x K x 24 bytes (every posterior row once per entry) / kernel time / 8 TB/s.  Where full_ll exists
 (K <= 255, table at most --full-ll-max-gb) full_ll_wall_ms = muxgl_fmx_iterate(..., full_ll) with its copy to the host,
@@ -60,23 +59,13 @@ def run_case(name, repeats, full_ll_max_gb):
         ms = e.timing()
         estep = float(ms[muxgl.T_FMX_ESTEP])
         it_ms = float(ms[muxgl.T_FMX_GP] + ms[muxgl.T_FMX_ESTEP] + ms[muxgl.T_FMX_CALL] + ms[muxgl.T_FMX_MSTEP])
-        kern, tables = {}, {}
-        for how in ("egls", "packed"):
-            os.environ["MUXGL_FMX_SNG_DIAG"] = how
-            e.fmx_singlets()
-            ks = []
-            for _ in range(repeats):
-                tables[how] = e.fmx_singlets()
-                ks.append(float(e.timing()[muxgl.T_FMX_SINGLETS]))
-            kern[how] = ks
-        del os.environ["MUXGL_FMX_SNG_DIAG"]
-        assert tables["egls"].tobytes() == tables["packed"].tobytes()
-        wall = []
+        e.fmx_singlets()
+        kern, wall = [], []
         for _ in range(repeats):
             t0 = time.perf_counter()
             sng = e.fmx_singlets()
             wall.append((time.perf_counter() - t0) * 1e3)
-        default_ms = float(e.timing()[muxgl.T_FMX_SINGLETS])
+            kern.append(float(e.timing()[muxgl.T_FMX_SINGLETS]))
         npairs = K * (K + 1) // 2
         tensor_gb = p.C * npairs * 8 / 1e9
         full_ms, full_dev = None, None
@@ -89,16 +78,12 @@ def run_case(name, repeats, full_ll_max_gb):
             j = np.arange(K)
             full_dev = float(np.max(np.abs(full[:, j * (j + 1) // 2 + j] - sng)))
             del full
-    med = {h: float(np.median(v)) for h, v in kern.items()}
-    best = min(med.values())
+    med = float(np.median(kern))
     r = dict(case=name, C=int(p.C), S=int(p.S), K=int(K), nnz=int(p.nnz), repeats=repeats,
-             kernel_ms_egls=round(med["egls"], 4), kernel_ms_egls_min=round(min(kern["egls"]), 4),
-             kernel_ms_egls_max=round(max(kern["egls"]), 4),
-             kernel_ms_packed=round(med["packed"], 4), kernel_ms_packed_min=round(min(kern["packed"]), 4),
-             kernel_ms_packed_max=round(max(kern["packed"]), 4), kernel_ms_default=round(default_ms, 4),
+             kernel_ms=round(med, 4), kernel_ms_min=round(min(kern), 4), kernel_ms_max=round(max(kern), 4),
              wall_ms=round(float(np.median(wall)), 3), estep_ms=round(estep, 4), iter_ms=round(it_ms, 4),
              iterate_wall_ms=round(iterate_wall, 3), table_gb=round(p.C * K * 8 / 1e9, 4), tensor_gb=round(tensor_gb, 2),
-             row_bytes_gb=round(p.nnz * K * 24 / 1e9, 3), roof_frac=round(p.nnz * K * 24.0 / (best * 1e-3) / HBM_ROOF, 4),
+             row_bytes_gb=round(p.nnz * K * 24 / 1e9, 3), roof_frac=round(p.nnz * K * 24.0 / (med * 1e-3) / HBM_ROOF, 4),
              full_ll_wall_ms=None if full_ms is None else round(full_ms, 1), max_abs_diff_vs_full_ll=full_dev)
     print(json.dumps(r), flush=True)
 
