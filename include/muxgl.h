@@ -198,7 +198,10 @@ int muxgl_version(void);
 int muxgl_group_peer_stats(const muxgl_handle* h, int32_t* out);
 
 /* ---- pileup hand-over: replaces the in-memory result of sc_dropseq_lib_t::load_from_plp
- *      (sc_drop_seq.cpp:103-384; containers sc_drop_seq.h:130-184).  Copies to device memory. --------------------- */
+ *      (sc_drop_seq.cpp:103-384; containers sc_drop_seq.h:130-184).  Copies to device memory.
+ *      A new pileup drops everything that was made for the previous one: the GP tensor of muxgl_demux_set_gp (every
+ *      demuxlet call and muxgl_fmx_match_donors fail with "no GP tensor set" until it is handed over again for the new
+ *      SNP set), the grid of the last muxgl_demux_run, and the freemuxlet state from muxgl_fmx_prepare on. ---------- */
 int muxgl_set_pileup(muxgl_handle* h, int64_t C, int64_t S, int64_t nnz, int64_t R, const int64_t* cell_ptr,
                      const int32_t* entry_snp, const int64_t* entry_rptr, const uint8_t* reads);
 

@@ -665,6 +665,7 @@ int demux_ring_lin_launch(muxgl_handle* h, const muxgl_demux_params* p, const wa
                           const double* gm, int na, const ring_sel& sel, double* llw, const double* pgt = nullptr,
                           bool pg_by_record = false);
 void demux_ring_release(muxgl_handle* h);
+void demux_panel_release(muxgl_handle* h);  // muxgl_api.hip: the GP tensor and what was made from it; V = 0
 int demux_row_plan(muxgl_handle* h);
 int demux_row_launch(muxgl_handle* h, const muxgl_demux_params* p);
 void demux_row_free(muxgl_handle* h);

@@ -263,6 +263,30 @@ int muxgl_validate_pileup(muxgl_handle* h, int64_t C, int64_t S, int64_t nnz, in
   return 0;
 }
 
+// The GP tensor of muxgl_demux_set_gp and everything made from it go: a handle without a panel (V = 0) refuses every call
+// that reads one.  Called for a new panel and for a new pileup, whose SNP ids the old rows do not belong to.
+void demux_panel_release(muxgl_handle* h) {
+  dev_free(&h->d_gp);
+  dev_free(&h->d_has_gp);
+  dev_free(&h->d_gpq);
+  dev_free(&h->d_gp0s);
+  dev_free(&h->d_gmq);
+  demux_ring_release(h);  // (its records name the neutral table row for markers without genotypes)
+  if (h->qrow) {  // the oct kernel's partitioned records carry has_gp (quad_lrec::code): rebuilt on the next run
+    dev_free(&h->qrow->d_qent_lin);
+    dev_free(&h->qrow->d_chunk_nlin);
+    dev_free(&h->qrow->d_orec);
+    dev_free(&h->qrow->d_unit_ptr);
+    dev_free(&h->qrow->d_quad_order);
+  }
+  h->V = 0;
+  h->gp_min_sum = 1.0;
+  h->gp_unit_sums = false;
+  h->have_dp = false;
+  h->pairs_valid = false;
+  h->ll_zeroed = false;
+}
+
 // Hand-over of a packed pileup in one of three roles: the whole pileup (every derived table), a rank's row slab (the same,
 // its cells only), or a column slab (all cells, the entries of a SNP range; it only ever feeds the SNP-major view of the
 // ordered M-step, so the chunk plans, the wave plan and the packed quad records are skipped).
@@ -287,6 +311,7 @@ int muxgl_set_pileup_role(muxgl_handle* h, int role, int64_t C, int64_t S, int64
     muxgl_destroy(h->col);
     h->col = nullptr;
   }
+  if (role != MUXGL_ROLE_COLS) demux_panel_release(h);  // the panel was laid out for the previous pileup's SNPs
   h->role = role;
   h->C_total = C;
   h->cell_base = 0;
@@ -466,22 +491,12 @@ int muxgl_demux_set_gp(muxgl_handle* h, int32_t V, const double* gp, const uint8
   if (V < 1 || V > MUXGL_MAX_SAMPLES) MUXGL_FAIL(h, "muxgl_demux_set_gp: V=%d outside [1,%d]", V, MUXGL_MAX_SAMPLES);
   if (!gp || !has_gp) MUXGL_FAIL(h, "muxgl_demux_set_gp: NULL array");
   if (h->S <= 0 && h->nnz > 0) MUXGL_FAIL(h, "muxgl_demux_set_gp: call muxgl_set_pileup first");
+  demux_panel_release(h);  // the previous panel and whatever was derived from it
   const size_t n = (size_t)h->S * V * 3;
   if (dev_alloc(h, &h->d_gp, n)) return 1;
   if (dev_alloc(h, &h->d_has_gp, (size_t)h->S)) return 1;
   if (n) HIPCHK(h, hipMemcpyAsync(h->d_gp, gp, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
   if (h->S) HIPCHK(h, hipMemcpyAsync(h->d_has_gp, has_gp, (size_t)h->S, hipMemcpyHostToDevice, h->stream));
-  dev_free(&h->d_gpq);
-  dev_free(&h->d_gp0s);
-  dev_free(&h->d_gmq);
-  demux_ring_release(h);  // (its records name the neutral table row for markers without genotypes)
-  if (h->qrow) {  // the oct kernel's partitioned records carry has_gp (quad_lrec::code): rebuilt on the next run
-    dev_free(&h->qrow->d_qent_lin);
-    dev_free(&h->qrow->d_chunk_nlin);
-    dev_free(&h->qrow->d_orec);
-    dev_free(&h->qrow->d_unit_ptr);
-    dev_free(&h->qrow->d_quad_order);
-  }
   h->gp_min_sum = 1.0;
   if (V > 32 && h->S > 0) {
     // smallest triple sum: the one-kernel sweep of demux_ring.hip multiplies g_j x pG x g_k into its products directly and
@@ -584,7 +599,17 @@ int muxgl_demux_run(muxgl_handle* h, const muxgl_demux_params* p, muxgl_demux_ce
   clear_timing(h);
   if (h->C > 0) {
     h->want_full_ll = full_ll != nullptr;
-    if (demux_launch(h, p)) return 1;
+    const bool had_dp = h->have_dp;
+    const muxgl_demux_params old_dp = h->last_dp;
+    if (demux_launch(h, p)) {
+      // a refused run is no run: muxgl_demux_get_entry_pg keeps reporting the grid of the last run that was made (a
+      // caller's buffer is sized for that one), and whatever was keyed by the grid is made again
+      h->have_dp = had_dp;
+      h->last_dp = old_dp;
+      h->pairs_valid = false;
+      h->ll_zeroed = false;
+      return 1;
+    }
     if (!h->records_on_host) {
       tic(h, MUXGL_T_DEMUX_D2H);
       HIPCHK(h, hipMemcpyAsync(h->h_dcells, h->d_dcells, sizeof(muxgl_demux_cell) * (size_t)h->C,

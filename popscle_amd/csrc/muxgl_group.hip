@@ -168,6 +168,8 @@ int group_set_pileup(muxgl_handle* h, int64_t C, int64_t S, int64_t nnz, int64_t
   g->nnz = nnz;
   g->R = R;
   g->K = 0;
+  g->V = h->V = 0;  // the members drop their panel with their pileup (demux_panel_release) ...
+  g->n_alpha = 0;   // ... and the grid of the last run
   // cells: contiguous ranges balanced by entries (the work unit of every sweep)
   g->cb = cuts_by_prefix(cell_ptr, C, g->n);
   g->eb.assign((size_t)g->n + 1, 0);
@@ -262,6 +264,7 @@ int group_demux_set_gp(muxgl_handle* h, int32_t V, const double* gp, const uint8
   if (for_members(h, [&](int r) { return muxgl_demux_set_gp(g->m[(size_t)r], V, gp, has_gp); })) return 1;
   g->V = V;
   h->V = V;
+  g->n_alpha = 0;  // (as the members' have_dp: muxgl_demux_get_entry_pg wants a run on this panel)
   return 0;
 }
 

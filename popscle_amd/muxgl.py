@@ -322,6 +322,7 @@ class Engine:
                                                _ptr(entry_rptr), _ptr(reads)))
         self.C, self.S, self.nnz, self.R = C_, int(S), nnz, R
         self.C_total, self.cell_base = C_, 0
+        self.V = self.K = self.n_alpha = 0   # the library drops the panel, the last grid and the clusters with the pileup
 
     def fmx_set_column_slab(self, C_total, c0, s0, s1, cell_ptr, entry_snp, entry_rptr, reads):
         """attach the column slab (all C_total cells, entries with s0 <= SNP < s1) to a handle holding a row slab"""
@@ -348,6 +349,7 @@ class Engine:
             raise ValueError("gp must be [S][V][3] and has_gp [S]")
         self._check(self.lib.muxgl_demux_set_gp(self.h, gp.shape[1], _ptr(gp), _ptr(has_gp)))
         self.V = gp.shape[1]
+        self.n_alpha = 0   # (demux_entry_pg wants a run on this panel)
 
     def demux_run(self, alphas=(0.0, 0.5), doublet_prior=0.5, want_cells=True, want_full_ll=False):
         key = (tuple(alphas), float(doublet_prior))

@@ -33,6 +33,7 @@ def test_config2_shape_demuxlet():
         assert rep["max_abs_ll_diff"] < 1e-6
         # the same cells alone: bit-identical records, and the full hypothesis tensor against the oracle's
         eng.set_pileup(sub.S, sub.cell_ptr, sub.entry_snp, sub.entry_rptr, sub.reads)
+        eng.demux_set_gp(sub.gp, sub.has_gp)   # (a new pileup drops the panel)
         got, gfull = eng.demux_run(alphas, 0.5, want_full_ll=True)
         assert got.tobytes() == cells[pick].tobytes()
         assert parity.compare_full_ll(gfull, wfull, cfg["V"], alphas) < 1e-6
@@ -66,6 +67,7 @@ def test_config2_full_size_demuxlet():
         pick = np.unique(np.concatenate([pick, longest]))
         sub = p.subset_cells(pick)
         eng.set_pileup(sub.S, sub.cell_ptr, sub.entry_snp, sub.entry_rptr, sub.reads)
+        eng.demux_set_gp(sub.gp, sub.has_gp)   # (a new pileup drops the panel)
         got, gfull = eng.demux_run(alphas, 0.5, want_full_ll=True)
     assert got.tobytes() == cells[pick].tobytes()
     n5 = alphas.index(0.5)
