@@ -448,6 +448,50 @@ int muxgl_fmx_singlets(muxgl_handle* h, double* sng);
 int muxgl_fmx_inclusion(muxgl_handle* h, const muxgl_fmx_params* p, double* incl, double* tot, double* dbl,
                         int32_t* partner);
 
+/* Every droplet against a donor that NO cluster holds -- a donor spread over clusters that are not theirs because
+ * --nsample is too small, or one with too few cells for the greedy start to give them a cluster.  A cluster without cells
+ * has a pileup of ones and its posterior row at a marker is the Hardy-Weinberg triple gp0s of cmd_cram_freemux2.cpp:388-390:
+ * the reference run with K + 2 clusters, two of them empty, holds these numbers in its llks[] triangle.  With g = egl_e[9]
+ * the entry likelihoods of muxgl_fmx_prepare, q[s][j][.] the cluster posteriors the last E-step read (MUXGL_BUF_CGP,
+ * geno_error mixed in), u[s][.] the unknown donor's genotype prior at marker s, and the sums over the entries e of droplet
+ * c in entry order:
+ *   ll_ju[C][K]: ll_ju[c][j] = sum_e log sum_g1 sum_g2 g[3 g1 + g2] * u[s_e][g1] * q[s_e][j][g2]
+ *                (cluster j plus the unknown donor: slot (K, j), :440-446, the unknown donor the higher-numbered cluster)
+ *   ll_u[C]:     ll_u[c]     = sum_e log sum_g g[4 g] * u[s_e][g]                     (the unknown donor alone: slot (K, K))
+ *   ll_uu[C]:    ll_uu[c]    = sum_e log sum_g1 sum_g2 g[3 g1 + g2] * u[s_e][g1] * u[s_e][g2]
+ *                (two unknown donors: slot (K + 1, K))
+ * gp0 == NULL: u[s] = ((1-af)(1-af), 2 af (1-af), af af), formed exactly as :388-390 from the af of muxgl_fmx_prepare, on
+ * the device.  gp0 != NULL: the caller's rows [S][3] (a specific donor's genotypes, say).  Every row must be a probability
+ * triple -- entries in [0, 1], sum within 1e-6 of 1; this is checked on the host before any device work and the call
+ * fails naming the first offending marker.  The reference's empty cluster goes through the division by its sum and the
+ * geno_error mixing with itself (:406-415) and equals u only to an ulp; the call uses u as defined here.
+ * With gp0 == NULL, ll_u and ll_uu are the quantities behind cell_llk2 / cell_llk0 of muxgl_fmx_prepare; the call forms
+ * them itself (so they exist for a caller's prior and on a slabbed rank), and they are the device's sums (products of
+ * factors, one log per cell part), not the exactly recomputed ones muxgl_fmx_prepare returns for near-tied cells.
+ * State rules and refusals are muxgl_fmx_singlets': call it after muxgl_fmx_iterate, or after muxgl_fmx_iter_estep and
+ * before the next muxgl_fmx_iter_gp; it fails, naming the reason, before the first E-step since muxgl_fmx_set_clusters,
+ * after a posterior phase without its E-step, without a pileup and without muxgl_fmx_prepare, and the handle stays usable.
+ * It reads state and changes none: records, counters, assignments, cluster pileups, MUXGL_BUF_CGP, the near-tie
+ * bookkeeping and whether the other table calls may run stay as they are; it caches nothing on the handle.  Under
+ * MUXGL_FLAG_ASYNC_PHASES it returns with the stream drained.
+ * 1 <= K <= MUXGL_MAX_CLUSTERS whichever E-step path ran; one device, a device group (every member fills the rows of its
+ * own cells) and a slabbed or sharded handle (the outputs cover the handle's own cells).
+ * Any subset of the three outputs may be NULL; with all three NULL the call fails, naming the reason, and the handle stays
+ * usable.  A droplet without entries gets zeros.  A factor of exactly 0 (a one-hot gp0 against posterior rows that were
+ * never filled) gives -inf, never NaN.
+ * kernel_ms (NULL allowed) receives the hipEvent time of the call's kernels, from a pair of events the call makes for
+ * itself (a group: the slowest member's): no timing slot of muxgl_get_timing is touched and the call is not a collecting
+ * call of muxgl_get_timing_sum.
+ * Device memory: the cells are swept in batches of whole cells whose 40 bytes of weights per entry, slab rows (K + 2
+ * doubles per cell part) and table rows fit the streamed E-step's budget (4 GiB or a third of the device,
+ * MUXGL_FMX_SLAB_MB); each batch is copied out before the next; the call fails, naming the variable, when one cell alone
+ * exceeds the budget.  The outputs are bit-identical from call to call, for any MUXGL_FMX_SLAB_MB, for any subset of
+ * outputs, on one device, on a group and through the sharded driver, and for a gp0 holding the Hardy-Weinberg rows formed
+ * with the expressions above against the NULL call. */
+int muxgl_fmx_unknown(muxgl_handle* h, const double* gp0 /* NULL or [S][3] */,
+                      double* ll_ju /* NULL or [C][K] */, double* ll_u /* NULL or [C] */,
+                      double* ll_uu /* NULL or [C] */, float* kernel_ms /* NULL or one float */);
+
 /* Near-tie calls of the EM iterations since muxgl_fmx_set_clusters.  The kernels' log-likelihoods equal the reference's to
  * ~1e-12, not to the last bit; a cell where a comparison of cmd_cram_freemux2.cpp:469-497,521-584 has a margin within
  * 1e-9 x max(1, |LL|) is therefore not decided by them but listed, and its contested hypotheses are recomputed in the

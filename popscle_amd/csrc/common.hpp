@@ -689,6 +689,9 @@ int fmx_stream_call_launch(muxgl_handle* h, int64_t c0, int64_t c1, double lsp, 
 int fmx_stream_rows(muxgl_handle* h, const std::vector<int32_t>& cells, double* rows);  // deep-tie rows, host
 const char* fmx_singlets_refusal(const muxgl_handle* h);  // fmx_singlets.hip: why muxgl_fmx_singlets cannot run now, or NULL
 const char* fmx_inclusion_refusal(const muxgl_handle* h);  // fmx_incl.hip: the same for muxgl_fmx_inclusion
+const char* fmx_unknown_refusal(const muxgl_handle* h);    // fmx_unknown.hip: the same for muxgl_fmx_unknown
+// fmx_unknown.hip: the first row of gp0[S][3] that is no probability triple (muxgl_fmx_unknown's rule), or -1
+int64_t fmx_unknown_bad_prior(const double* gp0, int64_t S);
 void fmx_wave_streams_release(muxgl_handle* h);  // the linear/general entry streams and their rank table
 int demux_ensure_ll(muxgl_handle* h, const muxgl_demux_params* p);  // standard LL tensor allocated and zeroed
 int demux_call_wave_launch(muxgl_handle* h, const muxgl_demux_params* p);
@@ -750,6 +753,7 @@ int group_fmx_iterate(muxgl_handle* h, const muxgl_fmx_params* p, muxgl_fmx_cell
 int group_fmx_get_cluster_pileup(muxgl_handle* h, double* gls, int32_t* counts);
 int group_fmx_singlets(muxgl_handle* h, double* sng);
 int group_fmx_inclusion(muxgl_handle* h, const muxgl_fmx_params* p, double* incl, double* tot, double* dbl, int32_t* partner);
+int group_fmx_unknown(muxgl_handle* h, const double* gp0, double* ll_ju, double* ll_u, double* ll_uu, float* kernel_ms);
 void group_fmx_exact_stats(const muxgl_handle* h, int64_t* cells, int64_t* changed, int64_t* unresolved);
 void group_peer_stats(const muxgl_handle* h, int32_t* out);
 int group_get_timing(const muxgl_handle* h, float* ms);

@@ -624,6 +624,32 @@ int group_fmx_singlets(muxgl_handle* h, double* sng) {
   return 0;
 }
 
+// every member sweeps its own cells and writes their rows of the caller's tables; kernel_ms: the slowest member's
+int group_fmx_unknown(muxgl_handle* h, const double* gp0, double* ll_ju, double* ll_u, double* ll_uu, float* kernel_ms) {
+  muxgl_group* g = h->group;
+  if (!g->have_pileup) MUXGL_FAIL(h, "muxgl_fmx_unknown: no pileup set (muxgl_set_pileup)");
+  if (!g->prepared) MUXGL_FAIL(h, "muxgl_fmx_unknown: call muxgl_fmx_prepare first");
+  for (const muxgl_handle* m : g->m)
+    if (const char* why = fmx_unknown_refusal(m)) MUXGL_FAIL(h, "%s", why);
+  if (!ll_ju && !ll_u && !ll_uu) MUXGL_FAIL(h, "muxgl_fmx_unknown: all three outputs are NULL");
+  if (gp0) {  // (once here, so that the group's handle carries the message; the members find nothing)
+    const int64_t bad = fmx_unknown_bad_prior(gp0, g->S);
+    if (bad >= 0)
+      MUXGL_FAIL(h, "muxgl_fmx_unknown: gp0 row of marker %lld (%g, %g, %g) is not a probability triple (entries in [0, 1], "
+                    "sum within 1e-6 of 1)",
+                 (long long)bad, gp0[3 * bad], gp0[3 * bad + 1], gp0[3 * bad + 2]);
+  }
+  std::vector<float> ms((size_t)g->n, 0.f);
+  if (for_members(h, [&](int r) {
+        const size_t c = (size_t)g->cb[(size_t)r];
+        return muxgl_fmx_unknown(g->m[(size_t)r], gp0, ll_ju ? ll_ju + c * (size_t)g->K : nullptr, ll_u ? ll_u + c : nullptr,
+                                 ll_uu ? ll_uu + c : nullptr, kernel_ms ? &ms[(size_t)r] : nullptr);
+      }))
+    return 1;
+  if (kernel_ms) *kernel_ms = *std::max_element(ms.begin(), ms.end());
+  return 0;
+}
+
 // every member folds its own cells and writes their rows of the caller's tables
 int group_fmx_inclusion(muxgl_handle* h, const muxgl_fmx_params* p, double* incl, double* tot, double* dbl, int32_t* partner) {
   muxgl_group* g = h->group;

@@ -1,7 +1,7 @@
-// table_plan.hpp -- the host side of the three per-droplet tables (demux_singlets.hip, fmx_singlets.hip,
-// demux_unknown.hip): how the cells of a call are cut into work items and swept in batches.  Plain C++ (no HIP), in the
-// manner of pairs_plan.hpp, so tests/test_table_plan.py compiles it on its own (tests/csrc/table_plan_probe.cpp) and holds
-// it to the loops it replaced.
+// table_plan.hpp -- the host side of the four per-droplet tables (demux_singlets.hip, fmx_singlets.hip,
+// demux_unknown.hip, fmx_unknown.hip): how the cells of a call are cut into work items and swept in batches.  Plain C++
+// (no HIP), in the manner of pairs_plan.hpp, so tests/test_table_plan.py compiles it on its own
+// (tests/csrc/table_plan_probe.cpp) and holds it to the loops it replaced.
 //
 // A cell of more than PART entries is cut into ceil(len / PART) parts, every other cell (an empty one too) is one part.
 // A part is one work item with a slab row of its own: the first part of a cell writes the cell's row (rows [0, cells of
@@ -48,7 +48,7 @@ struct batches {
   int64_t over = -1;         // the first cell whose cost alone exceeds the budget (it is a batch of its own), or none
 };
 
-// cost(len, parts) of a cell, in the unit of the budget: rows for the singlet tables, bytes for the unknown-donor call
+// cost(len, parts) of a cell, in the unit of the budget: rows for the singlet tables, bytes for the unknown-donor calls
 template <class Cost>
 batches plan(const int64_t* cell_ptr, int64_t C, size_t budget, Cost cost) {
   batches b;
@@ -79,6 +79,14 @@ batches plan(const int64_t* cell_ptr, int64_t C, size_t budget, Cost cost) {
 inline size_t unknown_bytes(int64_t len, int64_t np, int A, int VC) {
   const size_t row_bytes = sizeof(double) * (size_t)A * 2 * VC;
   return (size_t)len * A * 6 * sizeof(double) + (size_t)np * (row_bytes + sizeof(item)) + row_bytes + sizeof(cell);
+}
+
+// device bytes of a cell in a batch of freemuxlet's unknown-donor call at K clusters: its entries' weights (three and two
+// scalars, 40 bytes an entry), its slab rows of K + 2 doubles (one per part) with their items, and its rows of the three
+// tables (K + 2 doubles)
+inline size_t fmx_unknown_bytes(int64_t len, int64_t np, int K) {
+  const size_t row_bytes = sizeof(double) * ((size_t)K + 2);
+  return (size_t)len * 5 * sizeof(double) + (size_t)np * (row_bytes + sizeof(item)) + row_bytes;
 }
 
 // the items of the batch [c0, c1), and per cell of several parts its cut and/or per cell its record (NULL: not wanted)

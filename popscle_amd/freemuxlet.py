@@ -169,7 +169,7 @@ def settle_near_ties(engs, gather, doublet_prior, geno_error):
 
 def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early_stop=True, exchange=None,
            exchange_tensor=engine_exchange_tensor, log=None, per=None, timings=None, sync=None, stream_ctx=None,
-           want_singlets=False, want_inclusion=False):
+           want_singlets=False, want_inclusion=False, *, want_unknown=False):
     """EM loop of cmd_cram_freemux2.cpp:373-605 on a prepared engine.  One rank: a plain engine holding the whole
     pileup.  Several ranks: an engine holding the rank's slabs (load_rank), `exchange` a TorchExchange and
     per = (cells per rank, SNPs per rank) of the equal-slice plan the slabs were cut by.  clust0 spans the whole job.
@@ -179,7 +179,9 @@ def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early
     like the records, in the original cell order): (records, stats, sng) -- the counterpart of
     demuxlet.run_sharded(want_singlets=True).  want_inclusion: also the dict of job-wide per-droplet, per-cluster inclusion
     tables of the last iteration (Engine.fmx_inclusion, gathered the same way) as the last element:
-    (records, stats, [sng,] inclusion)."""
+    (records, stats, [sng,] inclusion).  want_unknown (keyword only): also the dict of the three job-wide tables of
+    Engine.fmx_unknown (Hardy-Weinberg prior) of the last iteration, gathered the same way, as the last element;
+    unknown_summary() turns them into per-droplet calls."""
     ex = exchange or NoExchange()
     t_start = time.perf_counter()
     eng.fmx_set_clusters(K, np.ascontiguousarray(clust0, dtype=np.int32))  # :277-288, own SNP range
@@ -276,7 +278,7 @@ def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early
     out = np.zeros(eng.C_total, dtype=cells.dtype)
     for b, e, raw in parts:
         out[b:e] = np.frombuffer(raw, dtype=cells.dtype)
-    if not want_singlets and not want_inclusion:
+    if not want_singlets and not want_inclusion and not want_unknown:
         return out, history
     res = [out, history]
     if want_singlets:
@@ -291,7 +293,38 @@ def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early
             for n, raw in raws.items():
                 incl[n][b:e] = np.frombuffer(raw, dtype=incl[n].dtype).reshape((e - b,) + incl[n].shape[1:])
         res.append(incl)
+    if want_unknown:
+        mine = {n: a for n, a in eng.fmx_unknown().items() if n != "kernel_ms"}
+        unk = {n: np.zeros((eng.C_total,) + a.shape[1:], dtype=a.dtype) for n, a in mine.items()}
+        for b, e, raws in ex.gather_objects((c0, c0 + len(cells), {n: a.tobytes() for n, a in mine.items()})):
+            for n, raw in raws.items():
+                unk[n][b:e] = np.frombuffer(raw, dtype=np.float64).reshape((e - b,) + unk[n].shape[1:])
+        res.append(unk)
     return tuple(res)
+
+
+def unknown_summary(tables, best_llk):
+    """Per droplet, how well a donor that no cluster holds explains it, from the tables of Engine.fmx_unknown (dict with
+    ll_ju [C][K], ll_u [C], ll_uu [C]) and the records' bestLLK [C].  Pure numpy.  Returns a dict: half_clust int32 and
+    half_llk float64 [C], the largest ll_ju of the droplet and its cluster (ties to the lowest cluster; a NaN counts as
+    -inf); unk_llk [C], the largest of ll_u, ll_uu and half_llk; diff [C] = best_llk - unk_llk (-inf - -inf counts as 0:
+    neither explains the droplet); n_better int, the droplets with diff < -2, the margin the reference's own calls use
+    (cmd_cram_freemux2.cpp:521-584)."""
+    ju = np.asarray(tables["ll_ju"], dtype=np.float64)
+    lu = np.asarray(tables["ll_u"], dtype=np.float64)
+    uu = np.asarray(tables["ll_uu"], dtype=np.float64)
+    best = np.asarray(best_llk, dtype=np.float64)
+    if ju.ndim != 2 or ju.shape[1] < 1 or lu.shape != ju.shape[:1] or uu.shape != lu.shape or best.shape != lu.shape:
+        raise ValueError("tables must be ll_ju [C][K], ll_u [C], ll_uu [C] and best_llk [C]")
+    Cn = ju.shape[0]
+    cand = np.where(np.isnan(ju), -np.inf, ju)
+    half_clust = np.argmax(cand, axis=1).astype(np.int32)  # (argmax: the first, i.e. the lowest cluster, on ties)
+    half_llk = cand[np.arange(Cn), half_clust]
+    unk_llk = np.maximum(np.maximum(np.where(np.isnan(lu), -np.inf, lu), np.where(np.isnan(uu), -np.inf, uu)), half_llk)
+    with np.errstate(invalid="ignore"):
+        diff = best - unk_llk
+    diff = np.where(np.isnan(diff), 0.0, diff)
+    return dict(half_clust=half_clust, half_llk=half_llk, unk_llk=unk_llk, diff=diff, n_better=int((diff < -2.0).sum()))
 
 
 def match_table(ll, ll0, nsnps=None):

@@ -33,6 +33,13 @@
 //       doublet, cmd_cram_freemux2.cpp:469-513).  Columns BARCODE, CLUST, NUM.SNPS, NUM.READS, LLK.INCL (%.4lf),
 //       POSTPRB.INCL (%.3lg, exp(incl - tot)), DBL.PARTNER (cluster), DBL.LLK (%.4lf); the last two are NA where no
 //       doublet hypothesis holds the cluster (one cluster)
+//       --write-unknown: also <O>.clust1.unk.gz (BGZF), one row per droplet of .clust1.samples.gz: how well a donor that NO
+//       cluster holds explains it, from the last EM iteration -- a donor spread over other clusters because --nsample is
+//       too small, or one the greedy start gave no cluster (muxgl_fmx_unknown with the Hardy-Weinberg triple of
+//       cmd_cram_freemux2.cpp:388-390 as the unknown donor's genotype prior: the reference's own numbers for a cluster
+//       without cells).  Columns BARCODE, NUM.SNPS, NUM.READS, BEST.LLK (of .clust1.samples.gz), UNK.SNG.LLK (one unknown
+//       donor), UNK.DBL.LLK (two unknown donors), HALF.CLUST and HALF.LLK (the cluster that pairs best with an unknown
+//       donor; ties to the lowest cluster), DIFF.LLK.CLUST.UNK (BEST.LLK minus the largest of the three); LLKs %.4lf
 //       --write-cluster-pairs: did the run split one donor over two clusters.  After the EM every pair of final cluster
 //       pileups is scored as one donor against two unrelated donors on the device (muxgl_fmx_cluster_pairs).  Writes
 //       <O>.clust1.ldist.gz (BGZF), one row per pair a > b in ascending (a, b) order: ID1, ID2, NSNP (markers both have
@@ -520,6 +527,7 @@ int cmd_freemuxlet(int argc, char** argv) {
   bool auxFiles = false, keepInitMissing = false, randomizeSingletScore = false, noEarlyStop = false;
   bool writeSinglets = false;  // (ours) <out>.clust1.sing2.gz: every droplet against every cluster
   bool writeInclusion = false;  // (ours) <out>.clust1.incl.gz: per-cluster marginals of the last E-step's pair triangle
+  bool writeUnknown = false;    // (ours) <out>.clust1.unk.gz: every droplet against a donor no cluster holds
   bool writeClusterPairs = false;  // (ours) <out>.clust1.ldist.gz: every pair of final clusters as one donor or two
   VcfReader vr;  // (ours) --match-vcf: genotypes of pooled donors the final clusters are scored against
   std::vector<std::string> smIDs;
@@ -544,6 +552,7 @@ int cmd_freemuxlet(int argc, char** argv) {
   a.add_bool("aux-files", &auxFiles);
   a.add_bool("write-singlets", &writeSinglets);
   a.add_bool("write-inclusion", &writeInclusion);
+  a.add_bool("write-unknown", &writeUnknown);
   a.add_bool("write-cluster-pairs", &writeClusterPairs);
   a.add_int("verbose", &verbose);
   a.add_double("doublet-prior", &doublet_prior);
@@ -797,6 +806,46 @@ int cmd_freemuxlet(int argc, char** argv) {
     });
     wi.close();
     tmr.lap("freemuxlet: write .clust1.incl.gz");
+  }
+  if (writeUnknown) {
+    // .clust1.unk.gz: one row per droplet (the order of .clust1.samples.gz), from the posteriors of the last E-step, like
+    // .clust1.sing2.gz.  The cluster that pairs best with the unknown donor: the largest ll_ju, ties to the lowest cluster
+    const size_t Kz = (size_t)K;
+    BigVec<double> ju((size_t)C * Kz);
+    std::vector<double> lu((size_t)C), uu((size_t)C);
+    check(h, muxgl_fmx_unknown(h, nullptr, ju.data(), lu.data(), uu.data(), nullptr), "muxgl_fmx_unknown");
+    tmr.lap("freemuxlet: muxgl_fmx_unknown");
+    std::vector<int32_t> hclust((size_t)C);
+    std::vector<double> hllk((size_t)C), diff((size_t)C);
+    parallel_for(C, plp_threads(), [&](int64_t i) {
+      const double* row = ju.data() + (size_t)i * Kz;
+      auto val = [](double v) { return std::isnan(v) ? -INFINITY : v; };
+      size_t b = 0;
+      for (size_t j = 1; j < Kz; ++j)
+        if (val(row[j]) > val(row[b])) b = j;
+      hclust[(size_t)i] = (int32_t)b;
+      hllk[(size_t)i] = val(row[b]);
+      const double top = std::max(std::max(val(lu[(size_t)i]), val(uu[(size_t)i])), val(row[b]));
+      const double d = cells[(size_t)i].bestLLK - top;
+      diff[(size_t)i] = std::isnan(d) ? 0.0 : d;  // (-inf against -inf: neither explains the droplet)
+    });
+    int64_t nbetter = 0;
+    for (int64_t i = 0; i < C; ++i) nbetter += diff[(size_t)i] < -2.0;
+    OutFile wu(cf.outPrefix + ".clust1.unk.gz", true);
+    wu.printf("BARCODE\tNUM.SNPS\tNUM.READS\tBEST.LLK\tUNK.SNG.LLK\tUNK.DBL.LLK\tHALF.CLUST\tHALF.LLK\tDIFF.LLK.CLUST.UNK\n");
+    write_rows_parallel(wu, C, [&](int64_t i, std::string& o) {
+      char num[320];
+      const int n = snprintf(num, sizeof(num), "\t%d\t%d\t%.4lf\t%.4lf\t%.4lf\t%d\t%.4lf\t%.4lf\n", nSNPs[(size_t)i],
+                             nReads[(size_t)i], cells[(size_t)i].bestLLK, lu[(size_t)i], uu[(size_t)i], (int)hclust[(size_t)i],
+                             hllk[(size_t)i], diff[(size_t)i]);
+      o.append(p.bcs[(size_t)i]);
+      o.append(num, (size_t)std::min<int>(n, (int)sizeof(num) - 1));
+    });
+    wu.close();
+    notice("%lld of %lld droplets are explained better by more than 2 by a donor that no cluster holds (DIFF.LLK.CLUST.UNK < "
+           "-2 in .clust1.unk.gz): a larger --nsample may be meant",
+           (long long)nbetter, (long long)C);
+    tmr.lap("freemuxlet: write .clust1.unk.gz");
   }
   if (wantMatch) {
     // .clust1.match.gz / .clust1.match.best.gz: the final cluster pileups (what .clust1.vcf.gz printed) against the donors
@@ -1295,7 +1344,10 @@ int main(int argc, char** argv) {
                     "    against two unrelated donors (ID1 ID2 NSNP LLK0 LLK2 LDIFF DIFF.SNP; one device)\n"
                     "  freemuxlet --write-inclusion: also <out>.clust1.incl.gz, per droplet and cluster the evidence that the\n"
                     "    cluster is in the droplet and the cluster it pairs best with, in the last iteration (BARCODE CLUST\n"
-                    "    NUM.SNPS NUM.READS LLK.INCL POSTPRB.INCL DBL.PARTNER DBL.LLK)\n");
+                    "    NUM.SNPS NUM.READS LLK.INCL POSTPRB.INCL DBL.PARTNER DBL.LLK)\n"
+                    "  freemuxlet --write-unknown: also <out>.clust1.unk.gz, per droplet how well a donor that no cluster holds\n"
+                    "    explains it in the last iteration (BARCODE NUM.SNPS NUM.READS BEST.LLK UNK.SNG.LLK UNK.DBL.LLK HALF.CLUST\n"
+                    "    HALF.LLK DIFF.LLK.CLUST.UNK); a notice counts the droplets it explains better by more than 2\n");
     return 1;
   }
   try {

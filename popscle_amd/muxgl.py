@@ -110,6 +110,7 @@ SYMBOLS = {
     "muxgl_fmx_iterate": (C.c_int, [_VP, C.POINTER(_FmxParams), _VP, _VP, _VP, _VP, _VP]),
     "muxgl_fmx_singlets": (C.c_int, [_VP, _VP]),
     "muxgl_fmx_inclusion": (C.c_int, [_VP, C.POINTER(_FmxParams), _VP, _VP, _VP, _VP]),
+    "muxgl_fmx_unknown": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP]),
     "muxgl_fmx_get_cluster_pileup": (C.c_int, [_VP, _VP, _VP]),
     "muxgl_fmx_match_donors": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
     "muxgl_fmx_cluster_pairs": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
@@ -163,6 +164,7 @@ class MuxglError(RuntimeError):
     pass
 
 
+FMX_UNKNOWN_FIELDS = ("ll_ju", "ll_u", "ll_uu")  # the outputs of muxgl_fmx_unknown, in the order of its arguments
 EXACT_STATS = ("cells", "mirror_turned", "mirror_exact_ties", "near_ties", "deep", "changed")
 
 
@@ -549,6 +551,32 @@ class Engine:
                 shape = (self.C,) if name == "tot" else (self.C, self.K)
                 out[name] = np.zeros(shape, dtype=np.int32 if name == "partner" else np.float64)
         self._check(self.lib.muxgl_fmx_inclusion(self.h, C.byref(p), *[_ptr(out.get(n)) for n in self.FMX_INCLUSION_FIELDS]))
+        return out
+
+    FMX_UNKNOWN_FIELDS = FMX_UNKNOWN_FIELDS
+
+    def fmx_unknown(self, gp0=None, want=FMX_UNKNOWN_FIELDS):
+        """muxgl_fmx_unknown: every droplet (of the handle's own cells) against a donor that no cluster holds, from the
+        posteriors the last E-step read (include/muxgl.h).  dict of ll_ju float64 [C][K], cluster j plus the unknown
+        donor; ll_u float64 [C], the unknown donor alone; ll_uu float64 [C], two unknown donors; and kernel_ms, the event
+        time of the call's kernels.  gp0: the unknown donor's genotype prior [S][3] (rows must be probability triples), or
+        None for the Hardy-Weinberg triple of fmx_prepare's af.  want: the subset of the three to fetch (the others are
+        passed as NULL).  At any K, on every E-step path; freemuxlet.unknown_summary() turns the tables into calls."""
+        unknown = set(want) - set(FMX_UNKNOWN_FIELDS)
+        if unknown:
+            raise ValueError(f"unknown fields {sorted(unknown)}")
+        if gp0 is not None:
+            gp0 = _arr(gp0, np.float64, "gp0")
+            if gp0.shape != (self.S, 3):
+                raise ValueError("gp0 must be [S][3]")
+        out = {}
+        for name in FMX_UNKNOWN_FIELDS:
+            if name in want:
+                out[name] = np.zeros((self.C, self.K) if name == "ll_ju" else (self.C,), dtype=np.float64)
+        ms = C.c_float(0.0)
+        self._check(self.lib.muxgl_fmx_unknown(self.h, _ptr(gp0), *[_ptr(out.get(n)) for n in FMX_UNKNOWN_FIELDS],
+                                                C.byref(ms)))
+        out["kernel_ms"] = float(ms.value)
         return out
 
     # ---- freemuxlet-old: pairwise distance matrix and voting passes (cmd_cram_freemuxlet.cpp:176-343)
