@@ -377,6 +377,33 @@ int muxgl_fmx_greedy_stats(const muxgl_handle* h, int64_t* near_ties, int64_t* o
  * (cmd_cram_freemux2.cpp:277-288) and resets types/jBest/kBest (:263-265,349-350).  clust[C], -1 = unassigned. */
 int muxgl_fmx_set_clusters(muxgl_handle* h, int32_t K, const int32_t* clust);
 
+/* Anchored clusters: a pool of which only some donors are genotyped.  Clusters 0 .. n_anchor-1 take their genotype
+ * posteriors from the panel of muxgl_demux_set_gp instead of from their cluster pileups: cluster i reads column donor[i].
+ * n_anchor = 0 (donor may be NULL) removes the anchors.  The other clusters are learned from the droplets as ever, in the
+ * same EM; with K = n_anchor the run is a genotype-driven assignment in freemuxlet's arithmetic.
+ *
+ * From the next posterior phase on (muxgl_fmx_iterate, muxgl_fmx_iter_gp) the row [s][i] of an anchored cluster that every
+ * E-step path, the exact near-tie path and the three tables muxgl_fmx_singlets / _inclusion / _unknown read is
+ *   - at a marker with genotypes (has_gp[s]): the panel row gp[s][donor[i]] as given -- the loader has applied its error
+ *     model; geno_error is not mixed in again;
+ *   - at a marker without: the row of a cluster without cells (HWE at af[s], mixed with itself by geno_error), so an
+ *     anchored donor without any genotype behaves bit for bit like an empty cluster.
+ * Clusters >= n_anchor are untouched and the priors of a singlet and a doublet use the whole K.  donor may name a column
+ * twice: such clusters tie exactly and the scan order decides, as it does for clusters without cells.
+ *
+ * The M-step is unchanged: singlets still merge into an anchored cluster's pileup.  muxgl_fmx_get_cluster_pileup,
+ * muxgl_fmx_match_donors, muxgl_fmx_cluster_pairs and a written cluster VCF therefore keep describing the DROPLETS assigned
+ * to a cluster; for an anchored cluster that is a check on the panel's genotypes, not what the next E-step reads.
+ *
+ * The anchors belong to the cluster state: muxgl_fmx_set_clusters, muxgl_fmx_prepare, muxgl_set_pileup and
+ * muxgl_demux_set_gp (the panel they index goes) drop them, as do muxgl_fmx_set_column_slab and a muxgl_fmx_set_shard
+ * range that is not the whole job.  This call -- also the removal -- makes the three tables
+ * unavailable until the next E-step and has the near-tie cells settled again.  Call it after muxgl_fmx_set_clusters.
+ * Refused, with the handle left as it was: no clusters set; n_anchor outside [0, K]; n_anchor > 0 without a panel, with
+ * donor == NULL or with a donor outside [0, V); a handle with a caller's own slabs (muxgl_fmx_set_column_slab) or shard
+ * (muxgl_fmx_set_shard with less than the whole job).  Device groups are supported. */
+int muxgl_fmx_set_anchors(muxgl_handle* h, int32_t n_anchor, const int32_t* donor /* [n_anchor], each in [0, V) */);
+
 /* one EM iteration, cmd_cram_freemux2.cpp:375-597: E-step, scans, re-assignment, ordered M-step.
  * out: NULL or [C].  full_ll: NULL or [C][K(K+1)/2].
  * The streamed E-step (K > 255, MUXGL_FLAG_FORCE_STREAMED_ESTEP at K > 32, or a K <= 255 job whose [C][K(K+1)/2] table

@@ -215,6 +215,10 @@ struct muxgl_handle {
   double* d_fll = nullptr;        // [C][K(K+1)/2]; not allocated when the E-step is streamed (fmx_stream.hip)
   bool fmx_streamed = false;      // muxgl_fmx_set_clusters chose the streamed E-step (path_choice.hpp)
   int fmx_sng_state = 0;          // FMX_SNG_*: is d_cgp what the last E-step read? (muxgl_fmx_singlets, fmx_singlets.hip)
+  // anchored clusters (fmx_anchor.hip): clusters 0 .. n_anchor-1 read column d_anchor[i] of the panel d_gp instead of
+  // their pileups.  Part of the cluster state; they go with the clusters and with the panel (fmx_anchors_drop)
+  int32_t n_anchor = 0;
+  int32_t* d_anchor = nullptr;    // [n_anchor] donor of every anchored cluster, each in [0, V)
   // the streamed E-step's buffers (fmx_stream.hip), kept between iterations: block list, slab, per-cell states
   int32_t* d_fblocks = nullptr;
   int fblocks_k = -1;
@@ -269,6 +273,17 @@ struct muxgl_handle {
 };
 
 extern thread_local std::string g_muxgl_create_error;
+
+// The anchors of muxgl_fmx_set_anchors go: with the clusters (muxgl_fmx_set_clusters, muxgl_fmx_prepare, a new pileup or
+// slab) and with the panel they index (demux_panel_release).  Where there were some, d_cgp is no longer what the next
+// E-step reads: as muxgl_fmx_set_anchors itself, no table of the last E-step and no settled near-tie cell survives.
+static inline void fmx_anchors_drop(muxgl_handle* h) {
+  if (h->n_anchor == 0) return;
+  h->n_anchor = 0;
+  h->fmx_sng_state = FMX_SNG_NONE;
+  h->xs_keep = false;
+  ++h->xs_epoch;
+}
 
 // MUXGL_TIMING=1: host-side stage times of the hand-over calls on stderr
 struct host_timer {
@@ -721,6 +736,8 @@ int fmx_cluster_counts_device(muxgl_handle* m);  // m->d_ccnt := read counts of 
 int fmx_snp_major_full(muxgl_handle* h);  // d_segls / d_secnt on first use (freemuxlet-old)
 int fmx_phase_gp(muxgl_handle* h, const muxgl_fmx_params* p);
 int fmx_phase_estep(muxgl_handle* h, const muxgl_fmx_params* p);
+int fmx_anchor_launch(muxgl_handle* h, const muxgl_fmx_params* p);  // fmx_anchor.hip: the anchored columns of d_cgp
+int fmx_set_anchors_on(muxgl_handle* h, int32_t n_anchor, const int32_t* donor, bool member);
 int fmx_phase_mstep(muxgl_handle* h);
 int fmx_mstep_stream_launch(muxgl_handle* h);  // K <= 64 (fmx_mstep.hip)
 // fmx_exact.hip: near-tie calls settled in the reference's arithmetic (steps A, B, C; all three on one handle)
@@ -748,6 +765,7 @@ int group_fmx_prepare(muxgl_handle* h, const double* af, double* cell_llk0, doub
                       int32_t* cell_nreads);
 int group_fmx_get_entry_gls(muxgl_handle* h, double* gls, int32_t* counts);
 int group_fmx_set_clusters(muxgl_handle* h, int32_t K, const int32_t* clust);
+int group_fmx_set_anchors(muxgl_handle* h, int32_t n_anchor, const int32_t* donor);
 int group_fmx_iterate(muxgl_handle* h, const muxgl_fmx_params* p, muxgl_fmx_cell* out, int32_t* nsingle, int32_t* namb,
                       int32_t* nchanged, double* full_ll);
 int group_fmx_get_cluster_pileup(muxgl_handle* h, double* gls, int32_t* counts);

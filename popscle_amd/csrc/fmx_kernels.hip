@@ -661,6 +661,7 @@ static int fmx_prepare_cols(muxgl_handle* h, const double* af) {
   dev_free(&h->d_egls);  // (both M-step kernels read the SNP-major six-value copy on a column slab)
   h->fmx_prepared = true;
   h->K = 0;
+  fmx_anchors_drop(h);
   h->fc0 = 0;
   h->fc1 = h->C;
   h->fs0 = h->slab_s0;
@@ -748,6 +749,7 @@ int muxgl_fmx_prepare(muxgl_handle* h, const double* af, double* cell_llk0, doub
   }
   h->fmx_prepared = true;
   h->K = 0;
+  fmx_anchors_drop(h);  // (they name clusters of the state that goes here)
   h->fc0 = 0;
   h->fc1 = C;
   h->fs0 = h->col ? h->col->slab_s0 : 0;
@@ -813,6 +815,7 @@ int fmx_attach_column_slab(muxgl_handle* h, int64_t C_total, int64_t c0, int64_t
   h->cell_base = c0;
   h->fmx_prepared = false;
   h->K = 0;
+  fmx_anchors_drop(h);
   return 0;
 }
 
@@ -851,6 +854,7 @@ int muxgl_fmx_set_clusters(muxgl_handle* h, int32_t K, const int32_t* clust) {
   for (int64_t i = 0; i < CT; ++i)
     if (clust[i] >= K) MUXGL_FAIL(h, "muxgl_fmx_set_clusters: cell %lld has cluster %d >= K", (long long)i, clust[i]);
   h->K = K;
+  fmx_anchors_drop(h);  // new clusters start without anchors (muxgl_fmx_set_anchors comes after this call)
   muxgl_handle* m = h->col ? h->col : h;  // who holds the cluster pileups and runs the ordered merge
   m->K = K;
   if (dev_alloc(h, &m->d_cgls, (size_t)K * S * 9)) return 1;
@@ -925,6 +929,8 @@ int fmx_phase_gp(muxgl_handle* h, const muxgl_fmx_params* p) {
   if (n > 0)
     hipLaunchKernelGGL(fmx_cgp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->S, m->fs0, m->fs1,
                        h->K, h->d_af, m->d_cgls, p->geno_error, h->d_cgp);
+  // anchored clusters: their columns again, from the panel (fmx_anchor.hip)
+  if (h->n_anchor > 0 && fmx_anchor_launch(h, p)) return 1;
   toc(h, MUXGL_T_FMX_GP);
   HIPCHK(h, hipGetLastError());
   if (h->fmx_sng_state == FMX_SNG_READY) h->fmx_sng_state = FMX_SNG_STALE;  // d_cgp is no longer what the last E-step read
@@ -1193,6 +1199,7 @@ int muxgl_fmx_set_shard(muxgl_handle* h, int64_t c0, int64_t c1, int64_t s0, int
   h->fc1 = c1;
   h->fs0 = s0;
   h->fs1 = s1;
+  if (c0 != 0 || c1 != h->C || s0 != 0 || s1 != h->S) fmx_anchors_drop(h);  // (anchors: whole-job handles and groups only)
   demux_row_release(&h->frow);
   demux_row_release(&h->fqrow);
   if (c0 != 0 || c1 != h->C) {  // chunk tables of the cell shard for the row / quad E-step

@@ -280,6 +280,7 @@ void demux_panel_release(muxgl_handle* h) {
     dev_free(&h->qrow->d_quad_order);
   }
   h->V = 0;
+  fmx_anchors_drop(h);  // (they index the panel that goes here)
   h->gp_min_sum = 1.0;
   h->gp_unit_sums = false;
   h->have_dp = false;
@@ -356,6 +357,7 @@ int muxgl_set_pileup_role(muxgl_handle* h, int role, int64_t C, int64_t S, int64
   }
   h->fmx_prepared = false;
   h->K = 0;
+  fmx_anchors_drop(h);
   dev_free(&h->d_sgn);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   tm.lap("set_pileup: final sync");
@@ -432,6 +434,7 @@ void muxgl_destroy(muxgl_handle* h) {
   dev_free(&h->d_cgls);
   dev_free(&h->d_ccnt);
   dev_free(&h->d_cgp);
+  dev_free(&h->d_anchor);
   dev_free(&h->d_clust);
   dev_free(&h->d_clust8);
   h->clust8_n = -1;

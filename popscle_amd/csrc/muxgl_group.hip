@@ -433,6 +433,24 @@ int group_fmx_set_clusters(muxgl_handle* h, int32_t K, const int32_t* clust) {
   return 0;
 }
 
+// every member holds the whole panel and writes the anchored columns of its own SNP range (fmx_anchor.hip); the
+// all-gather of the posterior rows in group_fmx_iterate carries them with the rest
+int group_fmx_set_anchors(muxgl_handle* h, int32_t n_anchor, const int32_t* donor) {
+  muxgl_group* g = h->group;
+  if (!g->prepared || g->K < 1) MUXGL_FAIL(h, "muxgl_fmx_set_anchors: no clusters set (call muxgl_fmx_set_clusters first)");
+  // (checked here once, so that the group's handle carries the plain message and no member is left with other anchors
+  //  than the rest)
+  if (n_anchor < 0 || n_anchor > g->K) MUXGL_FAIL(h, "muxgl_fmx_set_anchors: n_anchor=%d outside [0, K=%d]", n_anchor, g->K);
+  if (n_anchor > 0) {
+    if (g->V < 1) MUXGL_FAIL(h, "muxgl_fmx_set_anchors: no genotype panel set (muxgl_demux_set_gp)");
+    if (!donor) MUXGL_FAIL(h, "muxgl_fmx_set_anchors: donor is NULL with n_anchor=%d", n_anchor);
+    for (int32_t i = 0; i < n_anchor; ++i)
+      if (donor[i] < 0 || donor[i] >= g->V)
+        MUXGL_FAIL(h, "muxgl_fmx_set_anchors: donor[%d]=%d outside [0, V=%d)", i, donor[i], g->V);
+  }
+  return for_members(h, [&](int r) { return fmx_set_anchors_on(g->m[(size_t)r], n_anchor, donor, true); });
+}
+
 // One EM iteration (cmd_cram_freemux2.cpp:375-597) on the group.  Everything is enqueued from this thread; the devices
 // wait for each other through events only.  Buffer hazards: a member's posterior rows are rewritten by its next
 // posterior phase, which sits behind its M-step, which sits behind its assignment pulls, which wait for every member's

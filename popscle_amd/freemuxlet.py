@@ -169,7 +169,7 @@ def settle_near_ties(engs, gather, doublet_prior, geno_error):
 
 def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early_stop=True, exchange=None,
            exchange_tensor=engine_exchange_tensor, log=None, per=None, timings=None, sync=None, stream_ctx=None,
-           want_singlets=False, want_inclusion=False, *, want_unknown=False):
+           want_singlets=False, want_inclusion=False, *, want_unknown=False, anchors=None):
     """EM loop of cmd_cram_freemux2.cpp:373-605 on a prepared engine.  One rank: a plain engine holding the whole
     pileup.  Several ranks: an engine holding the rank's slabs (load_rank), `exchange` a TorchExchange and
     per = (cells per rank, SNPs per rank) of the equal-slice plan the slabs were cut by.  clust0 spans the whole job.
@@ -181,11 +181,18 @@ def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early
     tables of the last iteration (Engine.fmx_inclusion, gathered the same way) as the last element:
     (records, stats, [sng,] inclusion).  want_unknown (keyword only): also the dict of the three job-wide tables of
     Engine.fmx_unknown (Hardy-Weinberg prior) of the last iteration, gathered the same way, as the last element;
-    unknown_summary() turns them into per-droplet calls."""
+    unknown_summary() turns them into per-droplet calls.  anchors (keyword only): a list of columns of the panel the
+    engine holds (demux_set_gp); clusters 0 .. len(anchors)-1 are held to those donors' genotypes and the others are
+    learned (Engine.fmx_set_anchors, after fmx_set_clusters; anchor_start() makes a clust0 for it).  One engine with the
+    whole pileup or a device group only: refused with more than one rank or always=True."""
     ex = exchange or NoExchange()
+    multi = ex.world > 1 or getattr(ex, "always", False)  # (always: the exchange path with a single rank, for tests)
+    if anchors is not None and multi:
+        raise ValueError("run_em: anchors need one engine with the whole job (or a device group), not ranks with slabs")
     t_start = time.perf_counter()
     eng.fmx_set_clusters(K, np.ascontiguousarray(clust0, dtype=np.int32))  # :277-288, own SNP range
-    multi = ex.world > 1 or getattr(ex, "always", False)  # (always: the exchange path with a single rank, for tests)
+    if anchors is not None:
+        eng.fmx_set_anchors(anchors)
     if multi:
         per_c, per_s = per
         t_cgp, t_clust = exchange_tensor(eng, UNIT_CGP), exchange_tensor(eng, UNIT_CLUST)
@@ -301,6 +308,48 @@ def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early
                 unk[n][b:e] = np.frombuffer(raw, dtype=np.float64).reshape((e - b,) + unk[n].shape[1:])
         res.append(unk)
     return tuple(res)
+
+
+def anchor_start(llr, nsnps, ncells, donor, K):
+    """Where an anchored run starts: the relabelling of K greedy clusters (csrc/anchor_plan.hpp is the same function in
+    C++; pure numpy).  llr [K][V] = ll - ll0 of Engine.fmx_match_donors on the greedy clusters, nsnps [K] its markers,
+    ncells [K] the cells of every greedy cluster, donor [n] the anchored donors (cluster i of the run is donor[i]).
+    Candidates (greedy cluster k, anchor i) in order of llr[k][donor[i]] descending, then k, then i ascending, are accepted
+    one to one while llr > 0 (a NaN counts as -inf; a cluster with nsnps == 0 never matches): cluster k becomes cluster i.
+    An anchor without a match starts empty.  The unmatched clusters fill the free ids n .. K-1 in order of cell count
+    descending, then id ascending; those that do not fit leave their cells unassigned.  Returns a dict: new_id int32 [K]
+    (the run's cluster of every greedy cluster, or -1), match int32 [n] (the greedy cluster an anchor starts from, or -1)
+    and match_llr float64 [n] (its llr, or NaN).  clust0 of the run is np.where(c >= 0, new_id[c], -1) of the greedy c."""
+    llr = np.asarray(llr, dtype=np.float64)
+    nsnps = np.asarray(nsnps)
+    ncells = np.asarray(ncells, dtype=np.int64)
+    donor = np.asarray(donor, dtype=np.int64).reshape(-1)
+    K = int(K)
+    n = donor.size
+    if llr.ndim != 2 or llr.shape[0] != K or nsnps.shape != (K,) or ncells.shape != (K,) or n > K:
+        raise ValueError("llr must be [K][V], nsnps and ncells [K], and at most K donors")
+    if n and (donor.min() < 0 or donor.max() >= llr.shape[1]):
+        raise ValueError("donor outside [0, V)")
+    new_id = np.full(K, -1, dtype=np.int32)
+    match = np.full(n, -1, dtype=np.int32)
+    match_llr = np.full(n, np.nan)
+    if n:
+        v = llr[:, donor]  # [K][n]
+        v = np.where(np.isnan(v) | (nsnps == 0)[:, None], -np.inf, v)
+        kk, ii = np.meshgrid(np.arange(K), np.arange(n), indexing="ij")
+        order = np.lexsort((ii.ravel(), kk.ravel(), -v.ravel()))  # (last key first: value descending, then k, then i)
+        for c in order:
+            k, i = int(kk.ravel()[c]), int(ii.ravel()[c])
+            if not v[k, i] > 0.0:
+                break
+            if new_id[k] >= 0 or match[i] >= 0:
+                continue
+            new_id[k], match[i], match_llr[i] = i, k, v[k, i]
+    left = [k for k in range(K) if new_id[k] < 0]
+    left.sort(key=lambda k: (-int(ncells[k]), k))
+    for j, k in enumerate(left[:K - n]):
+        new_id[k] = n + j
+    return dict(new_id=new_id, match=match, match_llr=match_llr)
 
 
 def unknown_summary(tables, best_llk):

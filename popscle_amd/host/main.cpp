@@ -54,6 +54,15 @@
 //       (%.4lf), POSTPRB (%.3lg, equal priors over the donors); and <O>.clust1.match.best.gz, one row per cluster: CLUST,
 //       NUM.SNPS, BEST.SM_ID, BEST.LLR, NEXT.SM_ID, NEXT.LLR, DIFF.LLR, RECIPROCAL (1: the cluster is also the best
 //       cluster of its best donor), NA where there is none.  One device only: refused with --devices naming several
+//       --anchor-vcf FILE: a pool of which only some donors are genotyped.  FILE is read as --match-vcf's (the same flags);
+//       its n donors, in the VCF's sample order, become clusters 0 .. n-1, held to their genotypes for the whole EM
+//       (muxgl_fmx_set_anchors), and the clusters n .. K-1 are learned from the droplets; --nsample K is the total, K >= n.
+//       Start: the greedy clusters are matched to the donors (muxgl_fmx_match_donors, csrc/anchor_plan.hpp) and relabelled;
+//       with --init-cluster the file's ids are taken as they are (required with --devices naming several).  Writes
+//       <O>.clust1.anchors.gz (BGZF), one row per cluster: CLUST, SM_ID, START.CLUST and START.LLR (the greedy cluster the
+//       donor started from and the log Bayes factor of that match), N.SNG (droplets called singlets of the cluster); NA for
+//       a free cluster or where there was no start match; and, on one device, the two match tables above against the
+//       anchor panel.  --match-vcf next to it is an error
 //   popscle-amd freemuxlet-old --plp P --nsample K --out O [...]               mirrors cmdCramFreemuxlet (cmd_cram_freemuxlet.cpp)
 //   popscle-amd dump-plp   --plp P [--vcf V --field F] --out FILE              loader only: packed pileup to a binary file
 //   popscle-amd synth-plp  --cells C --snps S --samples V --out P              a synthetic data set in the real file formats
@@ -63,6 +72,7 @@
 // behind muxgl_* calls; there is no CPU implementation of it in this program.
 #include <cmath>
 
+#include "../csrc/anchor_plan.hpp"
 #include "plp.hpp"
 #include "synthplp.hpp"
 
@@ -534,10 +544,13 @@ int cmd_freemuxlet(int argc, char** argv) {
   std::string smList;
   Args a;
   cf.add(a);
+  std::string anchorVcf;  // (ours) --anchor-vcf: genotypes of SOME pooled donors; clusters 0 .. n-1 are held to them
   a.add_string("match-vcf", &vr.path);
-  bool wantMatch = false;
+  a.add_string("anchor-vcf", &anchorVcf);
+  bool wantMatch = false, wantAnchor = false;
   for (int i = 0; i < argc; ++i) wantMatch = wantMatch || !strcmp(argv[i], "--match-vcf");
-  if (wantMatch) {  // demuxlet's genotype flags, with their meanings; unknown to freemuxlet otherwise, as in the reference
+  for (int i = 0; i < argc; ++i) wantAnchor = wantAnchor || !strcmp(argv[i], "--anchor-vcf");
+  if (wantMatch || wantAnchor) {  // demuxlet's genotype flags, with their meanings; unknown to freemuxlet otherwise, as in the reference
     a.add_string("field", &cf.lo.field);
     a.add_double("geno-error-offset", &cf.lo.genoErrorOffset);
     a.add_double("geno-error-coeff", &cf.lo.genoErrorCoeffR2);
@@ -570,7 +583,16 @@ int cmd_freemuxlet(int argc, char** argv) {
   if (nSamples < 0 || nSamples > MUXGL_MAX_CLUSTERS)
     fatal("freemuxlet: --nsample %d outside [1, %d], the clusters the library supports (MUXGL_MAX_CLUSTERS)", nSamples,
           MUXGL_MAX_CLUSTERS);
+  if (wantMatch && wantAnchor)
+    fatal("freemuxlet: --match-vcf cannot be combined with --anchor-vcf: an anchored run's match tables (.clust1.match.gz, "
+          ".clust1.match.best.gz) are written against the anchor panel");
   if (wantMatch && vr.path.empty()) fatal("freemuxlet: --match-vcf needs a file name");
+  if (wantAnchor && anchorVcf.empty()) fatal("freemuxlet: --anchor-vcf needs a file name");
+  if (wantAnchor && cf.grouped() && initClusterFile.empty())
+    fatal("freemuxlet: --anchor-vcf with --devices naming more than one device needs --init-cluster: the default start of an "
+          "anchored run matches the greedy clusters to the donors (muxgl_fmx_match_donors), which is not available on a "
+          "device group");
+  if (wantAnchor) vr.path = anchorVcf;
   if (wantMatch && cf.grouped())
     fatal("freemuxlet: --match-vcf is not available with --devices naming more than one device: a group's cluster pileups "
           "are cut by SNP range (muxgl_fmx_match_donors scores the whole pileup on one device); run it on one device");
@@ -580,7 +602,7 @@ int cmd_freemuxlet(int argc, char** argv) {
 
   Pileup p;
   StageTimer tmr;
-  if (wantMatch) {  // the demuxlet loader: its merge-join with the markers and its GP construction (the pileup is the same)
+  if (wantMatch || wantAnchor) {  // the demuxlet loader: its merge-join with the markers and its GP construction (the pileup is the same)
     vr.wanted = smIDs;
     if (!smList.empty()) {
       TsvReader t(smList);
@@ -594,6 +616,10 @@ int cmd_freemuxlet(int argc, char** argv) {
   tmr.lap("freemuxlet: load");
   const int64_t C = p.C(), S = p.S();
   const int K = nSamples;
+  const int nAnchor = wantAnchor ? p.nv : 0;  // donors are anchored in the VCF's sample order: cluster i is sample i
+  if (wantAnchor && (nAnchor < 1 || nAnchor > K))
+    fatal("freemuxlet: --anchor-vcf holds %d donors; --nsample %d is the total number of clusters and must be at least that",
+          nAnchor, K);
 
   std::map<std::string, int32_t> initCluster;  // :90-104
   if (!initClusterFile.empty()) {
@@ -677,6 +703,32 @@ int cmd_freemuxlet(int argc, char** argv) {
     check(h, muxgl_fmx_prepare(h, af.data(), nullptr, nullptr, nullptr, nullptr), "muxgl_fmx_prepare");
     tmr.lap("freemuxlet: device group init+hand-over");
   }
+  // Where an anchored run starts (csrc/anchor_plan.hpp): the greedy clusters matched to the donors, one to one while the
+  // Bayes factor favours the donor, take the donors' ids; the others fill the free ids, the largest first
+  std::vector<int32_t> anchorStart((size_t)nAnchor, -1);
+  std::vector<double> anchorStartLlr((size_t)nAnchor, NAN);
+  if (wantAnchor && initClusterFile.empty()) {
+    const size_t V = (size_t)p.nv, Kz = (size_t)K;
+    check(h, muxgl_fmx_set_clusters(h, K, clusts.data()), "muxgl_fmx_set_clusters");
+    check(h, muxgl_demux_set_gp(h, p.nv, p.gp.data(), p.has_gp.data()), "muxgl_demux_set_gp");
+    std::vector<double> mll(Kz * V), mll0(Kz);
+    std::vector<int32_t> mns(Kz), donor((size_t)nAnchor);
+    check(h, muxgl_fmx_match_donors(h, mll.data(), mll0.data(), mns.data(), nullptr), "muxgl_fmx_match_donors");
+    for (size_t k = 0; k < Kz; ++k)
+      for (size_t v = 0; v < V; ++v) mll[k * V + v] -= mll0[k];
+    std::vector<int64_t> ncells(Kz, 0);
+    for (int64_t i = 0; i < C; ++i)
+      if (clusts[(size_t)i] >= 0) ++ncells[(size_t)clusts[(size_t)i]];
+    for (int i = 0; i < nAnchor; ++i) donor[(size_t)i] = i;
+    const anchor_plan::start st = anchor_plan::plan(K, p.nv, mll.data(), mns.data(), ncells.data(), nAnchor, donor.data());
+    for (int64_t i = 0; i < C; ++i)
+      if (clusts[(size_t)i] >= 0) clusts[(size_t)i] = st.new_id[(size_t)clusts[(size_t)i]];
+    anchorStart = st.match;
+    anchorStartLlr = st.match_llr;
+    int matched = 0;
+    for (int i = 0; i < nAnchor; ++i) matched += st.match[(size_t)i] >= 0;
+    notice("Anchored start: %d of %d donors matched to a greedy cluster", matched, nAnchor);
+  }
   tmr.lap("freemuxlet: .lmix + initial clusters");
   notice("Finished assigning initial identity of the cluster..");
   if (auxFiles) {  // :265-274
@@ -687,6 +739,13 @@ int cmd_freemuxlet(int argc, char** argv) {
   std::vector<uint8_t> snps_observed((size_t)S, 0);  // :279-288
   mark_observed_snps(p, snps_observed);
   check(h, muxgl_fmx_set_clusters(h, K, clusts.data()), "muxgl_fmx_set_clusters");
+  if (wantAnchor) {  // clusters 0 .. nAnchor-1 read the donors' genotypes from here on; the others are learned
+    std::vector<int32_t> donor((size_t)nAnchor);
+    for (int i = 0; i < nAnchor; ++i) donor[(size_t)i] = i;
+    if (!initClusterFile.empty())  // (the default start has handed the panel over already)
+      check(h, muxgl_demux_set_gp(h, p.nv, p.gp.data(), p.has_gp.data()), "muxgl_demux_set_gp");
+    check(h, muxgl_fmx_set_anchors(h, nAnchor, donor.data()), "muxgl_fmx_set_anchors");
+  }
   time_t now = std::time(nullptr);
   tm* ltm = localtime(&now);
   BigVec<double> cgls((size_t)K * S * 9);  // (not zero-filled: 2.3 GB at configs[4]; muxgl_fmx_get_cluster_pileup writes all of it)
@@ -847,10 +906,29 @@ int cmd_freemuxlet(int argc, char** argv) {
            (long long)nbetter, (long long)C);
     tmr.lap("freemuxlet: write .clust1.unk.gz");
   }
-  if (wantMatch) {
+  if (wantAnchor) {
+    // .clust1.anchors.gz: one row per cluster -- the donor it is held to, the greedy cluster it started from with the log
+    // Bayes factor of that match, and the droplets called singlets of it
+    std::vector<int64_t> nsng((size_t)K, 0);
+    for (int64_t i = 0; i < C; ++i)
+      if (cells[(size_t)i].clust >= 0 && cells[(size_t)i].clust < K) ++nsng[(size_t)cells[(size_t)i].clust];
+    OutFile wa(cf.outPrefix + ".clust1.anchors.gz", true);
+    wa.printf("CLUST\tSM_ID\tSTART.CLUST\tSTART.LLR\tN.SNG\n");
+    for (int k = 0; k < K; ++k) {
+      wa.printf("%d\t%s\t", k, k < nAnchor ? sid(p, k) : "NA");
+      if (k < nAnchor && anchorStart[(size_t)k] >= 0) wa.printf("%d\t%.4lf\t", (int)anchorStart[(size_t)k], anchorStartLlr[(size_t)k]);
+      else wa.printf("NA\tNA\t");
+      wa.printf("%lld\n", (long long)nsng[(size_t)k]);
+    }
+    wa.close();
+    tmr.lap("freemuxlet: write .clust1.anchors.gz");
+  }
+  if (wantMatch || (wantAnchor && !cf.grouped())) {
     // .clust1.match.gz / .clust1.match.best.gz: the final cluster pileups (what .clust1.vcf.gz printed) against the donors
+    // (an anchored run: against the anchor panel, which the handle holds already -- a check of the droplets assigned to an
+    // anchored cluster against the genotypes the cluster was held to)
     const size_t V = (size_t)p.nv, Kz = (size_t)K;
-    check(h, muxgl_demux_set_gp(h, p.nv, p.gp.data(), p.has_gp.data()), "muxgl_demux_set_gp");
+    if (!wantAnchor) check(h, muxgl_demux_set_gp(h, p.nv, p.gp.data(), p.has_gp.data()), "muxgl_demux_set_gp");
     std::vector<double> mll(Kz * V), mll0(Kz);
     std::vector<int32_t> mns(Kz);
     float kms = 0.f;
@@ -1340,6 +1418,10 @@ int main(int argc, char** argv) {
                     "    against every cluster in the last iteration (BARCODE CLUST NUM.SNPS NUM.READS LLK1 POSTPRB)\n"
                     "  freemuxlet --match-vcf FILE [demuxlet's genotype flags]: also <out>.clust1.match.gz and .clust1.match.best.gz,\n"
                     "      the final clusters scored against the donors' genotypes in FILE (one device)\n"
+                    "  freemuxlet --anchor-vcf FILE [demuxlet's genotype flags]: clusters 0 .. n-1 are held to the n donors of FILE\n"
+                    "      (sample order), the others up to --nsample are learned; also <out>.clust1.anchors.gz (CLUST SM_ID\n"
+                    "      START.CLUST START.LLR N.SNG) and, on one device, the match tables against FILE; several devices need\n"
+                    "      --init-cluster; not together with --match-vcf\n"
                     "  freemuxlet --write-cluster-pairs: also <out>.clust1.ldist.gz, every pair of final clusters as one donor\n"
                     "    against two unrelated donors (ID1 ID2 NSNP LLK0 LLK2 LDIFF DIFF.SNP; one device)\n"
                     "  freemuxlet --write-inclusion: also <out>.clust1.incl.gz, per droplet and cluster the evidence that the\n"

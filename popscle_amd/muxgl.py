@@ -107,6 +107,7 @@ SYMBOLS = {
     "muxgl_fmx_greedy_stats": (C.c_int, [_VP, _VP, _VP]),
     "muxgl_fmx_score_stats": (C.c_int, [_VP, _VP]),
     "muxgl_fmx_set_clusters": (C.c_int, [_VP, C.c_int32, _VP]),
+    "muxgl_fmx_set_anchors": (C.c_int, [_VP, C.c_int32, _VP]),
     "muxgl_fmx_iterate": (C.c_int, [_VP, C.POINTER(_FmxParams), _VP, _VP, _VP, _VP, _VP]),
     "muxgl_fmx_singlets": (C.c_int, [_VP, _VP]),
     "muxgl_fmx_inclusion": (C.c_int, [_VP, C.POINTER(_FmxParams), _VP, _VP, _VP, _VP]),
@@ -286,6 +287,7 @@ class Engine:
         self.cell_base = 0
         self.V = 0
         self.K = 0
+        self.n_anchor = 0  # clusters 0 .. n_anchor-1 are held to donors of the panel (fmx_set_anchors)
         self.n_alpha = 0
 
     def close(self):
@@ -325,6 +327,7 @@ class Engine:
         self.C, self.S, self.nnz, self.R = C_, int(S), nnz, R
         self.C_total, self.cell_base = C_, 0
         self.V = self.K = self.n_alpha = 0   # the library drops the panel, the last grid and the clusters with the pileup
+        self.n_anchor = 0
 
     def fmx_set_column_slab(self, C_total, c0, s0, s1, cell_ptr, entry_snp, entry_rptr, reads):
         """attach the column slab (all C_total cells, entries with s0 <= SNP < s1) to a handle holding a row slab"""
@@ -338,6 +341,7 @@ class Engine:
                                                         reads.size, _ptr(cell_ptr), _ptr(entry_snp), _ptr(entry_rptr),
                                                         _ptr(reads)))
         self.C_total, self.cell_base = int(C_total), int(c0)
+        self.n_anchor = 0
 
     def stream(self):
         """the hipStream_t (as an integer) the handle's kernels are enqueued on"""
@@ -352,6 +356,7 @@ class Engine:
         self._check(self.lib.muxgl_demux_set_gp(self.h, gp.shape[1], _ptr(gp), _ptr(has_gp)))
         self.V = gp.shape[1]
         self.n_alpha = 0   # (demux_entry_pg wants a run on this panel)
+        self.n_anchor = 0  # (the anchors indexed the panel that went)
 
     def demux_run(self, alphas=(0.0, 0.5), doublet_prior=0.5, want_cells=True, want_full_ll=False):
         key = (tuple(alphas), float(doublet_prior))
@@ -476,6 +481,7 @@ class Engine:
         nsnps = np.zeros(self.C, dtype=np.int32)
         nreads = np.zeros(self.C, dtype=np.int32)
         self._check(self.lib.muxgl_fmx_prepare(self.h, _ptr(af), _ptr(llk0), _ptr(llk2), _ptr(nsnps), _ptr(nreads)))
+        self.n_anchor = 0
         return llk0, llk2, nsnps, nreads
 
     def fmx_entry_gls(self):
@@ -511,6 +517,18 @@ class Engine:
             raise ValueError("clust must be [C] (the whole job's cells for a slabbed handle)")
         self._check(self.lib.muxgl_fmx_set_clusters(self.h, int(K), _ptr(clust)))
         self.K = int(K)
+        self.n_anchor = 0
+
+    def fmx_set_anchors(self, donors):
+        """muxgl_fmx_set_anchors: clusters 0 .. len(donors)-1 take their genotype posteriors from the panel of
+        demux_set_gp, cluster i from column donors[i], instead of from their droplets; the other clusters are learned as
+        ever (include/muxgl.h).  An empty list (or None) removes the anchors.  After fmx_set_clusters; dropped again by
+        fmx_set_clusters, fmx_prepare, set_pileup and demux_set_gp.  n_anchor mirrors the library's count."""
+        d = _arr([] if donors is None else donors, np.int32, "donors")
+        if d.ndim != 1:
+            raise ValueError("donors must be a list of panel columns")
+        self._check(self.lib.muxgl_fmx_set_anchors(self.h, int(d.size), _ptr(d) if d.size else None))
+        self.n_anchor = int(d.size)
 
     def fmx_iterate(self, doublet_prior=0.5, geno_error=0.1, want_cells=True, want_full_ll=False):
         p = _FmxParams(float(doublet_prior), float(geno_error))
@@ -612,6 +630,8 @@ class Engine:
     # ---- sharded EM phases (multi-GPU); the collectives between them belong to the caller (popscle_amd/freemuxlet.py)
     def fmx_set_shard(self, c0, c1, s0, s1):
         self._check(self.lib.muxgl_fmx_set_shard(self.h, int(c0), int(c1), int(s0), int(s1)))
+        if (int(c0), int(c1), int(s0), int(s1)) != (0, self.C, 0, self.S):
+            self.n_anchor = 0  # (anchors live on whole-job handles and device groups only)
 
     def fmx_iter_gp(self, doublet_prior=0.5, geno_error=0.1):
         p = _FmxParams(float(doublet_prior), float(geno_error))
