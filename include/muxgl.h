@@ -404,6 +404,34 @@ int muxgl_fmx_set_clusters(muxgl_handle* h, int32_t K, const int32_t* clust);
  * (muxgl_fmx_set_shard with less than the whole job).  Device groups are supported. */
 int muxgl_fmx_set_anchors(muxgl_handle* h, int32_t n_anchor, const int32_t* donor /* [n_anchor], each in [0, V) */);
 
+/* Anchors with a mode each: muxgl_fmx_set_anchors is this call with mode == NULL (all HELD), and after it every anchored
+ * cluster is HELD again.  The same refusals and the same state effects; a mode other than the two below is refused too,
+ * with the handle -- its anchors and their modes included -- left as it was.
+ *
+ * MUXGL_ANCHOR_HELD   the panel row IS the posterior row, as described above.
+ * MUXGL_ANCHOR_PRIOR  the panel row is the PRIOR of the posterior the droplets form ("learn the genotypes with the donor
+ *   VCF as prior"): for low-pass or imputed panels, RNA-derived calls, flat GP / PL rows.  Cluster i with v = donor[i] is a
+ *   free cluster whose Hardy-Weinberg triple inside the product of cmd_cram_freemux2.cpp:402-415 is the panel row:
+ *     - at a marker with genotypes, with w = gp[s][v][0..2] and d = (gls[0], gls[4], gls[8]) of the cluster's own pileup:
+ *       q_g = w_g d_g / sum_g w_g d_g, then, if geno_error > 0, q_g <- (1 - e) q_g + e p_g with p the Hardy-Weinberg triple
+ *       at af[s].  A zero in w is a zero in q before the mix.  d is positive, so the sum vanishes only for a row w without
+ *       a positive entry; such a row (or one holding a NaN) is used as given, as for a HELD cluster;
+ *     - at a marker without, the row of the free cluster with this pileup, bit for bit.
+ *   A PRIOR cluster whose panel rows equal the Hardy-Weinberg triples bit for bit, or without genotypes anywhere, is a free
+ *   cluster bit for bit, on every E-step path and on the exact near-tie path.  The M-step, the priors of a singlet and a
+ *   doublet and the state rules are those of a HELD cluster; HELD and PRIOR clusters mix freely. */
+#define MUXGL_ANCHOR_HELD 0
+#define MUXGL_ANCHOR_PRIOR 1
+int muxgl_fmx_set_anchors_mode(muxgl_handle* h, int32_t n_anchor, const int32_t* donor /* [n_anchor] */,
+                               const uint8_t* mode /* [n_anchor] MUXGL_ANCHOR_*, or NULL = all HELD */);
+
+/* The posterior rows [s][k][0..2] of clusters k0 <= k < k1 that the last posterior phase (muxgl_fmx_iterate,
+ * muxgl_fmx_iter_gp) wrote and its E-step read -- free, HELD and PRIOR clusters alike; for a PRIOR cluster the genotypes
+ * as the droplets refined them.  out: [S][k1 - k0][3].  Reads state and changes none.  Refused: no clusters set; before
+ * the first posterior phase after muxgl_fmx_set_clusters; a range outside [0, K].  On a sharded handle the rows outside its
+ * own SNP range are what the caller's exchange put there.  Device groups are supported. */
+int muxgl_fmx_get_cluster_gp(muxgl_handle* h, int32_t k0, int32_t k1, double* out /* [S][k1-k0][3] */);
+
 /* one EM iteration, cmd_cram_freemux2.cpp:375-597: E-step, scans, re-assignment, ordered M-step.
  * out: NULL or [C].  full_ll: NULL or [C][K(K+1)/2].
  * The streamed E-step (K > 255, MUXGL_FLAG_FORCE_STREAMED_ESTEP at K > 32, or a K <= 255 job whose [C][K(K+1)/2] table

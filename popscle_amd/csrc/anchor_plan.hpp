@@ -71,3 +71,33 @@ inline start plan(int K, int V, const double* llr /*[K][V]*/, const int32_t* nsn
 }
 
 }  // namespace anchor_plan
+
+// ---- `freemuxlet --anchor-refine-list FILE`: which anchored donors are MUXGL_ANCHOR_PRIOR (freemuxlet.refine_modes is the
+// same function in Python).  ids: the anchored donors in cluster order; listed: the text of FILE, one sample ID per line --
+// the first white-space separated word; empty lines and lines starting with '#' do not count.  A listed donor is PRIOR (1),
+// the others HELD (0); naming one twice is allowed.  An ID that is no anchored donor: false, with the ID in *unknown.
+#include <sstream>
+#include <string>
+
+namespace anchor_plan {
+
+inline bool refine_modes(const std::vector<std::string>& ids, const std::string& listed, std::vector<uint8_t>* mode,
+                         std::string* unknown) {
+  mode->assign(ids.size(), 0);
+  std::istringstream in(listed);
+  std::string line, word;
+  while (std::getline(in, line)) {
+    std::istringstream ls(line);
+    if (!(ls >> word) || word[0] == '#') continue;
+    bool found = false;
+    for (size_t i = 0; i < ids.size(); ++i)
+      if (ids[i] == word) (*mode)[i] = 1, found = true;
+    if (!found) {
+      *unknown = word;
+      return false;
+    }
+  }
+  return true;
+}
+
+}  // namespace anchor_plan

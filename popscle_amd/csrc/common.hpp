@@ -219,6 +219,12 @@ struct muxgl_handle {
   // their pileups.  Part of the cluster state; they go with the clusters and with the panel (fmx_anchors_drop)
   int32_t n_anchor = 0;
   int32_t* d_anchor = nullptr;    // [n_anchor] donor of every anchored cluster, each in [0, V)
+  // their modes (muxgl_fmx_set_anchors_mode): a MUXGL_ANCHOR_PRIOR cluster is a free cluster whose Hardy-Weinberg triple in
+  // the posterior's product is the panel row (fmx_prior_kernel, behind fmx_anchor_kernel, and its twin in rows_kernel)
+  int32_t n_prior = 0;
+  uint8_t* d_anchor_mode = nullptr;  // [n_anchor] MUXGL_ANCHOR_*
+  int32_t* d_prior = nullptr;        // [n_prior] the PRIOR clusters, ascending
+  bool cgp_valid = false;            // a posterior phase has written d_cgp for these clusters (muxgl_fmx_get_cluster_gp)
   // the streamed E-step's buffers (fmx_stream.hip), kept between iterations: block list, slab, per-cell states
   int32_t* d_fblocks = nullptr;
   int fblocks_k = -1;
@@ -280,6 +286,7 @@ extern thread_local std::string g_muxgl_create_error;
 static inline void fmx_anchors_drop(muxgl_handle* h) {
   if (h->n_anchor == 0) return;
   h->n_anchor = 0;
+  h->n_prior = 0;
   h->fmx_sng_state = FMX_SNG_NONE;
   h->xs_keep = false;
   ++h->xs_epoch;
@@ -737,7 +744,8 @@ int fmx_snp_major_full(muxgl_handle* h);  // d_segls / d_secnt on first use (fre
 int fmx_phase_gp(muxgl_handle* h, const muxgl_fmx_params* p);
 int fmx_phase_estep(muxgl_handle* h, const muxgl_fmx_params* p);
 int fmx_anchor_launch(muxgl_handle* h, const muxgl_fmx_params* p);  // fmx_anchor.hip: the anchored columns of d_cgp
-int fmx_set_anchors_on(muxgl_handle* h, int32_t n_anchor, const int32_t* donor, bool member);
+int fmx_set_anchors_on(muxgl_handle* h, int32_t n_anchor, const int32_t* donor, const uint8_t* mode, bool member);
+int fmx_get_cluster_gp_on(muxgl_handle* h, int32_t k0, int32_t k1, double* out);
 int fmx_phase_mstep(muxgl_handle* h);
 int fmx_mstep_stream_launch(muxgl_handle* h);  // K <= 64 (fmx_mstep.hip)
 // fmx_exact.hip: near-tie calls settled in the reference's arithmetic (steps A, B, C; all three on one handle)
@@ -765,7 +773,8 @@ int group_fmx_prepare(muxgl_handle* h, const double* af, double* cell_llk0, doub
                       int32_t* cell_nreads);
 int group_fmx_get_entry_gls(muxgl_handle* h, double* gls, int32_t* counts);
 int group_fmx_set_clusters(muxgl_handle* h, int32_t K, const int32_t* clust);
-int group_fmx_set_anchors(muxgl_handle* h, int32_t n_anchor, const int32_t* donor);
+int group_fmx_set_anchors(muxgl_handle* h, int32_t n_anchor, const int32_t* donor, const uint8_t* mode);
+int group_fmx_get_cluster_gp(muxgl_handle* h, int32_t k0, int32_t k1, double* out);
 int group_fmx_iterate(muxgl_handle* h, const muxgl_fmx_params* p, muxgl_fmx_cell* out, int32_t* nsingle, int32_t* namb,
                       int32_t* nchanged, double* full_ll);
 int group_fmx_get_cluster_pileup(muxgl_handle* h, double* gls, int32_t* counts);

@@ -48,14 +48,17 @@ using exact_arith::entry_pileup;
 using exact_arith::merge;
 
 // rows[(i * K + c) * 3 ..] = gp1s of cluster c at SNP snps[i] (:402-415), for the SNPs inside [s0, s1); owned[i] = 1 there.
-// Clusters below n_anchor are anchored (fmx_anchor.hip): their row is fmx_anchor_row's, not their chain's.
+// Clusters below n_anchor are anchored (fmx_anchor.hip).  HELD (amode NULL or 0): the row is fmx_anchor_row's, not the
+// chain's.  PRIOR: the chain is walked as a free cluster's and the panel row takes the place of the Hardy-Weinberg triple in
+// the product (fmx_prior_row).
 __global__ void __launch_bounds__(256)
     rows_kernel(int64_t n, int K, const int32_t* __restrict__ snps, int64_t s0, int64_t s1,
                 const int64_t* __restrict__ entry_rptr, const uint8_t* __restrict__ reads, const double* __restrict__ lut,
                 const double* __restrict__ af, const int64_t* __restrict__ snp_ptr, const int64_t* __restrict__ snp_entry,
                 const int32_t* __restrict__ snp_cell, const int32_t* __restrict__ prev_clust, double geno_error,
-                int n_anchor, int V, const int32_t* __restrict__ anchor, const double* __restrict__ gp,
-                const uint8_t* __restrict__ has_gp, double* __restrict__ rows, uint8_t* __restrict__ owned) {
+                int n_anchor, int V, const int32_t* __restrict__ anchor, const uint8_t* __restrict__ amode,
+                const double* __restrict__ gp, const uint8_t* __restrict__ has_gp, double* __restrict__ rows,
+                uint8_t* __restrict__ owned) {
 #pragma clang fp contract(off)
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (tid >= n * K) return;
@@ -70,9 +73,10 @@ __global__ void __launch_bounds__(256)
   // divisions -- once per member with a sixteenth of the lanes active.  So every lane first moves its own cursor to its
   // NEXT member (a cheap scan, eight members' dependent loads in flight at a time), then all lanes merge together: the
   // heavy part runs as often as the longest chain of the wave has members, not as often as the list is long.
-  const bool anchored = c < n_anchor;
+  const bool prior = c < n_anchor && amode && amode[c] == MUXGL_ANCHOR_PRIOR;
+  const bool anchored = c < n_anchor && !prior;  // (HELD)
   const int64_t p1 = snp_ptr[snp + 1];
-  // (an anchored lane has no chain to walk: its cursor starts exhausted, and it stays in the loop for the wave's vote)
+  // (a HELD lane has no chain to walk: its cursor starts exhausted, and it stays in the loop for the wave's vote)
   int64_t p = anchored ? p1 : snp_ptr[snp];
   for (;;) {
     int64_t hit = -1;
@@ -119,6 +123,8 @@ __global__ void __launch_bounds__(256)
     gp1s[2] = (1 - geno_error) * gp1s[2] + geno_error * gp0s[2];
   }
   if (anchored) fmx_anchor_row<true>(has_gp[snp] != 0, gp + ((size_t)snp * V + anchor[c]) * 3, a, geno_error, gp1s);
+  if (prior)
+    fmx_prior_row<true>(has_gp[snp] != 0, gp + ((size_t)snp * V + anchor[c]) * 3, g[0], g[4], g[8], a, geno_error, gp1s);
   double* o = rows + (size_t)tid * 3;
   o[0] = gp1s[0], o[1] = gp1s[1], o[2] = gp1s[2];
   if (c == 0) owned[i] = 1;
@@ -338,7 +344,8 @@ int fmx_exact_rows(muxgl_handle* h, const muxgl_fmx_params* p, const int32_t* sn
     if (e == hipSuccess) {
       hipLaunchKernelGGL(rows_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, n, K, d_snps, m->fs0, m->fs1,
                          m->d_entry_rptr, m->d_reads, h->d_lut, h->d_af, m->d_snp_ptr, m->d_snp_entry, m->d_snp_cell,
-                         m->d_prev_clust, p->geno_error, h->n_anchor, h->V, h->d_anchor, h->d_gp, h->d_has_gp, d_rows,
+                         m->d_prev_clust, p->geno_error, h->n_anchor, h->V, h->d_anchor,
+                         h->n_prior > 0 ? h->d_anchor_mode : nullptr, h->d_gp, h->d_has_gp, d_rows,
                          d_owned);
       e = hipGetLastError();
     }

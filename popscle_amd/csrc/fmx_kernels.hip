@@ -661,6 +661,7 @@ static int fmx_prepare_cols(muxgl_handle* h, const double* af) {
   dev_free(&h->d_egls);  // (both M-step kernels read the SNP-major six-value copy on a column slab)
   h->fmx_prepared = true;
   h->K = 0;
+  h->cgp_valid = false;
   fmx_anchors_drop(h);
   h->fc0 = 0;
   h->fc1 = h->C;
@@ -749,6 +750,7 @@ int muxgl_fmx_prepare(muxgl_handle* h, const double* af, double* cell_llk0, doub
   }
   h->fmx_prepared = true;
   h->K = 0;
+  h->cgp_valid = false;
   fmx_anchors_drop(h);  // (they name clusters of the state that goes here)
   h->fc0 = 0;
   h->fc1 = C;
@@ -815,6 +817,7 @@ int fmx_attach_column_slab(muxgl_handle* h, int64_t C_total, int64_t c0, int64_t
   h->cell_base = c0;
   h->fmx_prepared = false;
   h->K = 0;
+  h->cgp_valid = false;
   fmx_anchors_drop(h);
   return 0;
 }
@@ -854,6 +857,7 @@ int muxgl_fmx_set_clusters(muxgl_handle* h, int32_t K, const int32_t* clust) {
   for (int64_t i = 0; i < CT; ++i)
     if (clust[i] >= K) MUXGL_FAIL(h, "muxgl_fmx_set_clusters: cell %lld has cluster %d >= K", (long long)i, clust[i]);
   h->K = K;
+  h->cgp_valid = false;  // (muxgl_fmx_get_cluster_gp: no posterior phase for these clusters yet)
   fmx_anchors_drop(h);  // new clusters start without anchors (muxgl_fmx_set_anchors comes after this call)
   muxgl_handle* m = h->col ? h->col : h;  // who holds the cluster pileups and runs the ordered merge
   m->K = K;
@@ -929,8 +933,9 @@ int fmx_phase_gp(muxgl_handle* h, const muxgl_fmx_params* p) {
   if (n > 0)
     hipLaunchKernelGGL(fmx_cgp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->S, m->fs0, m->fs1,
                        h->K, h->d_af, m->d_cgls, p->geno_error, h->d_cgp);
-  // anchored clusters: their columns again, from the panel (fmx_anchor.hip)
+  // anchored clusters: their columns again, from the panel -- and, in PRIOR mode, from the pileups too (fmx_anchor.hip)
   if (h->n_anchor > 0 && fmx_anchor_launch(h, p)) return 1;
+  h->cgp_valid = true;
   toc(h, MUXGL_T_FMX_GP);
   HIPCHK(h, hipGetLastError());
   if (h->fmx_sng_state == FMX_SNG_READY) h->fmx_sng_state = FMX_SNG_STALE;  // d_cgp is no longer what the last E-step read

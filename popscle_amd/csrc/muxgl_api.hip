@@ -357,6 +357,7 @@ int muxgl_set_pileup_role(muxgl_handle* h, int role, int64_t C, int64_t S, int64
   }
   h->fmx_prepared = false;
   h->K = 0;
+  h->cgp_valid = false;
   fmx_anchors_drop(h);
   dev_free(&h->d_sgn);
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -435,6 +436,8 @@ void muxgl_destroy(muxgl_handle* h) {
   dev_free(&h->d_ccnt);
   dev_free(&h->d_cgp);
   dev_free(&h->d_anchor);
+  dev_free(&h->d_anchor_mode);
+  dev_free(&h->d_prior);
   dev_free(&h->d_clust);
   dev_free(&h->d_clust8);
   h->clust8_n = -1;

@@ -435,7 +435,7 @@ int group_fmx_set_clusters(muxgl_handle* h, int32_t K, const int32_t* clust) {
 
 // every member holds the whole panel and writes the anchored columns of its own SNP range (fmx_anchor.hip); the
 // all-gather of the posterior rows in group_fmx_iterate carries them with the rest
-int group_fmx_set_anchors(muxgl_handle* h, int32_t n_anchor, const int32_t* donor) {
+int group_fmx_set_anchors(muxgl_handle* h, int32_t n_anchor, const int32_t* donor, const uint8_t* mode) {
   muxgl_group* g = h->group;
   if (!g->prepared || g->K < 1) MUXGL_FAIL(h, "muxgl_fmx_set_anchors: no clusters set (call muxgl_fmx_set_clusters first)");
   // (checked here once, so that the group's handle carries the plain message and no member is left with other anchors
@@ -447,8 +447,24 @@ int group_fmx_set_anchors(muxgl_handle* h, int32_t n_anchor, const int32_t* dono
     for (int32_t i = 0; i < n_anchor; ++i)
       if (donor[i] < 0 || donor[i] >= g->V)
         MUXGL_FAIL(h, "muxgl_fmx_set_anchors: donor[%d]=%d outside [0, V=%d)", i, donor[i], g->V);
+    for (int32_t i = 0; mode && i < n_anchor; ++i)
+      if (mode[i] != MUXGL_ANCHOR_HELD && mode[i] != MUXGL_ANCHOR_PRIOR)
+        MUXGL_FAIL(h, "muxgl_fmx_set_anchors: mode[%d]=%d is neither MUXGL_ANCHOR_HELD (0) nor MUXGL_ANCHOR_PRIOR (1)", i,
+                   (int)mode[i]);
   }
-  return for_members(h, [&](int r) { return fmx_set_anchors_on(g->m[(size_t)r], n_anchor, donor, true); });
+  return for_members(h, [&](int r) { return fmx_set_anchors_on(g->m[(size_t)r], n_anchor, donor, mode, true); });
+}
+
+// after muxgl_fmx_iterate every member holds all the posterior rows (its own and the pulled ones): the first member's
+int group_fmx_get_cluster_gp(muxgl_handle* h, int32_t k0, int32_t k1, double* out) {
+  muxgl_group* g = h->group;
+  if (!g->prepared || g->K < 1) MUXGL_FAIL(h, "muxgl_fmx_get_cluster_gp: no clusters set (call muxgl_fmx_set_clusters first)");
+  muxgl_handle* m = g->m[0];
+  if (fmx_get_cluster_gp_on(m, k0, k1, out)) {
+    h->err = m->err;
+    return 1;
+  }
+  return 0;
 }
 
 // One EM iteration (cmd_cram_freemux2.cpp:375-597) on the group.  Everything is enqueued from this thread; the devices

@@ -169,7 +169,7 @@ def settle_near_ties(engs, gather, doublet_prior, geno_error):
 
 def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early_stop=True, exchange=None,
            exchange_tensor=engine_exchange_tensor, log=None, per=None, timings=None, sync=None, stream_ctx=None,
-           want_singlets=False, want_inclusion=False, *, want_unknown=False, anchors=None):
+           want_singlets=False, want_inclusion=False, *, want_unknown=False, anchors=None, anchor_modes=None):
     """EM loop of cmd_cram_freemux2.cpp:373-605 on a prepared engine.  One rank: a plain engine holding the whole
     pileup.  Several ranks: an engine holding the rank's slabs (load_rank), `exchange` a TorchExchange and
     per = (cells per rank, SNPs per rank) of the equal-slice plan the slabs were cut by.  clust0 spans the whole job.
@@ -184,15 +184,19 @@ def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early
     unknown_summary() turns them into per-droplet calls.  anchors (keyword only): a list of columns of the panel the
     engine holds (demux_set_gp); clusters 0 .. len(anchors)-1 are held to those donors' genotypes and the others are
     learned (Engine.fmx_set_anchors, after fmx_set_clusters; anchor_start() makes a clust0 for it).  One engine with the
-    whole pileup or a device group only: refused with more than one rank or always=True."""
+    whole pileup or a device group only: refused with more than one rank or always=True.  anchor_modes (keyword only,
+    with anchors): one of muxgl.ANCHOR_HELD / ANCHOR_PRIOR per anchor; a PRIOR donor's genotypes are the prior of the
+    posterior the droplets form (Engine.fmx_cluster_gp has the refined rows afterwards, refine_summary() sums them up)."""
     ex = exchange or NoExchange()
     multi = ex.world > 1 or getattr(ex, "always", False)  # (always: the exchange path with a single rank, for tests)
     if anchors is not None and multi:
         raise ValueError("run_em: anchors need one engine with the whole job (or a device group), not ranks with slabs")
+    if anchor_modes is not None and (anchors is None or len(anchor_modes) != len(anchors)):
+        raise ValueError("run_em: anchor_modes needs anchors, one mode each")
     t_start = time.perf_counter()
     eng.fmx_set_clusters(K, np.ascontiguousarray(clust0, dtype=np.int32))  # :277-288, own SNP range
     if anchors is not None:
-        eng.fmx_set_anchors(anchors)
+        eng.fmx_set_anchors(anchors, anchor_modes)
     if multi:
         per_c, per_s = per
         t_cgp, t_clust = exchange_tensor(eng, UNIT_CGP), exchange_tensor(eng, UNIT_CLUST)
@@ -350,6 +354,46 @@ def anchor_start(llr, nsnps, ncells, donor, K):
     for j, k in enumerate(left[:K - n]):
         new_id[k] = n + j
     return dict(new_id=new_id, match=match, match_llr=match_llr)
+
+
+def refine_modes(sample_ids, listed):
+    """The modes of `freemuxlet --anchor-refine-list FILE` (csrc/anchor_plan.hpp refine_modes is the same function in C++):
+    sample_ids the anchored donors in cluster order, listed the text of FILE -- one sample ID per line, the first
+    white-space separated word; empty lines and lines starting with '#' do not count.  A listed donor is ANCHOR_PRIOR, the
+    others ANCHOR_HELD; naming one twice is allowed, an ID that is no anchored donor is a ValueError."""
+    ids = list(sample_ids)
+    modes = [0] * len(ids)
+    for line in listed.splitlines():
+        words = line.split()
+        if not words or words[0].startswith("#"):
+            continue
+        if words[0] not in ids:
+            raise ValueError(f"--anchor-refine-list: '{words[0]}' is not a sample of the anchor VCF")
+        for i, s in enumerate(ids):
+            if s == words[0]:
+                modes[i] = 1
+    return modes
+
+
+def refine_summary(panel, has_gp, rows):
+    """What the droplets made of the PRIOR donors' genotypes.  panel [S][n][3]: the donors' panel rows as demux_set_gp took
+    them; has_gp [S]; rows [S][n][3]: the posterior rows of their clusters (Engine.fmx_cluster_gp).  Pure numpy.  Returns a
+    dict of arrays [n], over the markers with genotypes: n_geno int64 their number, n_changed int64 the markers whose
+    arg-max genotype moved (first maximum on both sides), mean_max_prior and mean_max_post float64 the means of the
+    largest panel and of the largest posterior probability (NaN without a marker)."""
+    panel = np.asarray(panel, dtype=np.float64)
+    rows = np.asarray(rows, dtype=np.float64)
+    has = np.asarray(has_gp).astype(bool).reshape(-1)
+    if panel.ndim != 3 or panel.shape[2] != 3 or rows.shape != panel.shape or has.shape != (panel.shape[0],):
+        raise ValueError("panel and rows must be [S][n][3] and has_gp [S]")
+    n = panel.shape[1]
+    pw, pr = panel[has], rows[has]
+    n_geno = np.full(n, pw.shape[0], dtype=np.int64)
+    if pw.shape[0] == 0:
+        nan = np.full(n, np.nan)
+        return dict(n_geno=n_geno, n_changed=np.zeros(n, dtype=np.int64), mean_max_prior=nan, mean_max_post=nan.copy())
+    return dict(n_geno=n_geno, n_changed=(pw.argmax(axis=2) != pr.argmax(axis=2)).sum(axis=0).astype(np.int64),
+                mean_max_prior=pw.max(axis=2).mean(axis=0), mean_max_post=pr.max(axis=2).mean(axis=0))
 
 
 def unknown_summary(tables, best_llk):

@@ -63,6 +63,14 @@
 //       donor started from and the log Bayes factor of that match), N.SNG (droplets called singlets of the cluster); NA for
 //       a free cluster or where there was no start match; and, on one device, the two match tables above against the
 //       anchor panel.  --match-vcf next to it is an error
+//       --anchor-refine (with --anchor-vcf): every anchored donor's genotypes are the PRIOR of the posterior the droplets
+//       form (MUXGL_ANCHOR_PRIOR, muxgl_fmx_set_anchors_mode), not the posterior itself: for low-pass or imputed panels,
+//       RNA-derived calls, flat GP / PL rows.  --anchor-refine-list FILE: only the donors whose sample IDs FILE lists, one
+//       per line; an ID that is no sample of the anchor VCF is an error.  Either flag adds a MODE column (HELD / PRIOR, NA
+//       for a free cluster) to <O>.clust1.anchors.gz and writes <O>.clust1.refined.gz (BGZF), one row per PRIOR cluster:
+//       CLUST, SM_ID, N.GENO (markers with genotypes), N.CHANGED (those whose most likely genotype moved), MEAN.MAXGP.PRIOR
+//       and MEAN.MAXGP.POST (%.4lf: the means of the largest panel and of the largest posterior probability over them).
+//       Without the two flags every output is what it is without them, byte for byte
 //   popscle-amd freemuxlet-old --plp P --nsample K --out O [...]               mirrors cmdCramFreemuxlet (cmd_cram_freemuxlet.cpp)
 //   popscle-amd dump-plp   --plp P [--vcf V --field F] --out FILE              loader only: packed pileup to a binary file
 //   popscle-amd synth-plp  --cells C --snps S --samples V --out P              a synthetic data set in the real file formats
@@ -71,6 +79,8 @@
 // the reference commands, and the text writers with the reference's printf formats.  All arithmetic of the path is
 // behind muxgl_* calls; there is no CPU implementation of it in this program.
 #include <cmath>
+#include <fstream>
+#include <sstream>
 
 #include "../csrc/anchor_plan.hpp"
 #include "plp.hpp"
@@ -547,6 +557,10 @@ int cmd_freemuxlet(int argc, char** argv) {
   std::string anchorVcf;  // (ours) --anchor-vcf: genotypes of SOME pooled donors; clusters 0 .. n-1 are held to them
   a.add_string("match-vcf", &vr.path);
   a.add_string("anchor-vcf", &anchorVcf);
+  bool anchorRefine = false;      // (ours) --anchor-refine: every anchored donor in PRIOR mode
+  std::string anchorRefineList;   // (ours) --anchor-refine-list: the listed sample IDs in PRIOR mode
+  a.add_bool("anchor-refine", &anchorRefine);
+  a.add_string("anchor-refine-list", &anchorRefineList);
   bool wantMatch = false, wantAnchor = false;
   for (int i = 0; i < argc; ++i) wantMatch = wantMatch || !strcmp(argv[i], "--match-vcf");
   for (int i = 0; i < argc; ++i) wantAnchor = wantAnchor || !strcmp(argv[i], "--anchor-vcf");
@@ -588,6 +602,8 @@ int cmd_freemuxlet(int argc, char** argv) {
           ".clust1.match.best.gz) are written against the anchor panel");
   if (wantMatch && vr.path.empty()) fatal("freemuxlet: --match-vcf needs a file name");
   if (wantAnchor && anchorVcf.empty()) fatal("freemuxlet: --anchor-vcf needs a file name");
+  const bool wantRefine = anchorRefine || !anchorRefineList.empty();
+  if (wantRefine && !wantAnchor) fatal("freemuxlet: --anchor-refine and --anchor-refine-list need --anchor-vcf");
   if (wantAnchor && cf.grouped() && initClusterFile.empty())
     fatal("freemuxlet: --anchor-vcf with --devices naming more than one device needs --init-cluster: the default start of an "
           "anchored run matches the greedy clusters to the donors (muxgl_fmx_match_donors), which is not available on a "
@@ -620,6 +636,20 @@ int cmd_freemuxlet(int argc, char** argv) {
   if (wantAnchor && (nAnchor < 1 || nAnchor > K))
     fatal("freemuxlet: --anchor-vcf holds %d donors; --nsample %d is the total number of clusters and must be at least that",
           nAnchor, K);
+  std::vector<uint8_t> anchorMode((size_t)nAnchor, anchorRefine ? MUXGL_ANCHOR_PRIOR : MUXGL_ANCHOR_HELD);
+  if (!anchorRefineList.empty()) {  // (with --anchor-refine next to it all donors are PRIOR; the list is still checked)
+    std::ifstream lf(anchorRefineList);
+    if (!lf) fatal("freemuxlet: cannot open --anchor-refine-list %s", anchorRefineList.c_str());
+    std::stringstream text;
+    text << lf.rdbuf();
+    std::vector<std::string> ids;
+    for (int i = 0; i < nAnchor; ++i) ids.push_back(sid(p, i));
+    std::vector<uint8_t> listed;
+    std::string unknown;
+    if (!anchor_plan::refine_modes(ids, text.str(), &listed, &unknown))
+      fatal("freemuxlet: --anchor-refine-list: '%s' is not a sample of the anchor VCF", unknown.c_str());
+    if (!anchorRefine) anchorMode = listed;
+  }
 
   std::map<std::string, int32_t> initCluster;  // :90-104
   if (!initClusterFile.empty()) {
@@ -744,7 +774,8 @@ int cmd_freemuxlet(int argc, char** argv) {
     for (int i = 0; i < nAnchor; ++i) donor[(size_t)i] = i;
     if (!initClusterFile.empty())  // (the default start has handed the panel over already)
       check(h, muxgl_demux_set_gp(h, p.nv, p.gp.data(), p.has_gp.data()), "muxgl_demux_set_gp");
-    check(h, muxgl_fmx_set_anchors(h, nAnchor, donor.data()), "muxgl_fmx_set_anchors");
+    if (wantRefine) check(h, muxgl_fmx_set_anchors_mode(h, nAnchor, donor.data(), anchorMode.data()), "muxgl_fmx_set_anchors_mode");
+    else check(h, muxgl_fmx_set_anchors(h, nAnchor, donor.data()), "muxgl_fmx_set_anchors");
   }
   time_t now = std::time(nullptr);
   tm* ltm = localtime(&now);
@@ -913,15 +944,45 @@ int cmd_freemuxlet(int argc, char** argv) {
     for (int64_t i = 0; i < C; ++i)
       if (cells[(size_t)i].clust >= 0 && cells[(size_t)i].clust < K) ++nsng[(size_t)cells[(size_t)i].clust];
     OutFile wa(cf.outPrefix + ".clust1.anchors.gz", true);
-    wa.printf("CLUST\tSM_ID\tSTART.CLUST\tSTART.LLR\tN.SNG\n");
+    wa.printf("CLUST\tSM_ID\tSTART.CLUST\tSTART.LLR\tN.SNG%s\n", wantRefine ? "\tMODE" : "");
     for (int k = 0; k < K; ++k) {
       wa.printf("%d\t%s\t", k, k < nAnchor ? sid(p, k) : "NA");
       if (k < nAnchor && anchorStart[(size_t)k] >= 0) wa.printf("%d\t%.4lf\t", (int)anchorStart[(size_t)k], anchorStartLlr[(size_t)k]);
       else wa.printf("NA\tNA\t");
-      wa.printf("%lld\n", (long long)nsng[(size_t)k]);
+      wa.printf("%lld", (long long)nsng[(size_t)k]);
+      if (wantRefine) wa.printf("\t%s", k >= nAnchor ? "NA" : anchorMode[(size_t)k] == MUXGL_ANCHOR_PRIOR ? "PRIOR" : "HELD");
+      wa.printf("\n");
     }
     wa.close();
     tmr.lap("freemuxlet: write .clust1.anchors.gz");
+  }
+  if (wantRefine) {
+    // .clust1.refined.gz: what the droplets made of the PRIOR donors' genotypes (freemuxlet.refine_summary is the same
+    // summary in numpy) -- the posterior rows the last E-step read against the panel rows, over the markers with genotypes
+    const size_t V = (size_t)p.nv, n = (size_t)nAnchor;
+    std::vector<double> rows((size_t)S * n * 3);
+    check(h, muxgl_fmx_get_cluster_gp(h, 0, nAnchor, rows.data()), "muxgl_fmx_get_cluster_gp");
+    auto argmax3 = [](const double* r) { return r[1] > r[0] ? (r[2] > r[1] ? 2 : 1) : (r[2] > r[0] ? 2 : 0); };  // (the first maximum)
+    OutFile wr(cf.outPrefix + ".clust1.refined.gz", true);
+    wr.printf("CLUST\tSM_ID\tN.GENO\tN.CHANGED\tMEAN.MAXGP.PRIOR\tMEAN.MAXGP.POST\n");
+    for (size_t k = 0; k < n; ++k) {
+      if (anchorMode[k] != MUXGL_ANCHOR_PRIOR) continue;
+      int64_t ng = 0, nc = 0;
+      double sw = 0, sq = 0;
+      for (int64_t s = 0; s < S; ++s) {
+        if (!p.has_gp[(size_t)s]) continue;
+        const double* w = &p.gp[((size_t)s * V + k) * 3];
+        const double* q = &rows[((size_t)s * n + k) * 3];
+        ++ng;
+        nc += argmax3(w) != argmax3(q);
+        sw += std::max(w[0], std::max(w[1], w[2]));
+        sq += std::max(q[0], std::max(q[1], q[2]));
+      }
+      if (ng) wr.printf("%d\t%s\t%lld\t%lld\t%.4lf\t%.4lf\n", (int)k, sid(p, (int)k), (long long)ng, (long long)nc, sw / ng, sq / ng);
+      else wr.printf("%d\t%s\t0\t0\tNA\tNA\n", (int)k, sid(p, (int)k));
+    }
+    wr.close();
+    tmr.lap("freemuxlet: write .clust1.refined.gz");
   }
   if (wantMatch || (wantAnchor && !cf.grouped())) {
     // .clust1.match.gz / .clust1.match.best.gz: the final cluster pileups (what .clust1.vcf.gz printed) against the donors
@@ -1422,6 +1483,10 @@ int main(int argc, char** argv) {
                     "      (sample order), the others up to --nsample are learned; also <out>.clust1.anchors.gz (CLUST SM_ID\n"
                     "      START.CLUST START.LLR N.SNG) and, on one device, the match tables against FILE; several devices need\n"
                     "      --init-cluster; not together with --match-vcf\n"
+                    "  freemuxlet --anchor-vcf FILE --anchor-refine: the donors' genotypes are the prior of the genotypes the\n"
+                    "      droplets form, not held (--anchor-refine-list FILE: only the sample IDs listed there); adds a MODE\n"
+                    "      column to <out>.clust1.anchors.gz and writes <out>.clust1.refined.gz (CLUST SM_ID N.GENO N.CHANGED\n"
+                    "      MEAN.MAXGP.PRIOR MEAN.MAXGP.POST)\n"
                     "  freemuxlet --write-cluster-pairs: also <out>.clust1.ldist.gz, every pair of final clusters as one donor\n"
                     "    against two unrelated donors (ID1 ID2 NSNP LLK0 LLK2 LDIFF DIFF.SNP; one device)\n"
                     "  freemuxlet --write-inclusion: also <out>.clust1.incl.gz, per droplet and cluster the evidence that the\n"

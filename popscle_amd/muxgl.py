@@ -33,6 +33,7 @@ FLAG_SPLIT_GENERAL_SWEEP = 512
 FLAG_GROUP_PROBE_SELF = 1024
 FLAG_FORCE_STREAMED_CALL = 2048
 FLAG_FORCE_STREAMED_ESTEP = 4096
+ANCHOR_HELD, ANCHOR_PRIOR = 0, 1  # modes of an anchored cluster (MUXGL_ANCHOR_*)
 MAX_CLUSTERS = 1024  # freemuxlet: largest K (MUXGL_MAX_CLUSTERS)
 MAX_DEVICES = 16
 XCHG_PAD = 64
@@ -108,6 +109,8 @@ SYMBOLS = {
     "muxgl_fmx_score_stats": (C.c_int, [_VP, _VP]),
     "muxgl_fmx_set_clusters": (C.c_int, [_VP, C.c_int32, _VP]),
     "muxgl_fmx_set_anchors": (C.c_int, [_VP, C.c_int32, _VP]),
+    "muxgl_fmx_set_anchors_mode": (C.c_int, [_VP, C.c_int32, _VP, _VP]),
+    "muxgl_fmx_get_cluster_gp": (C.c_int, [_VP, C.c_int32, C.c_int32, _VP]),
     "muxgl_fmx_iterate": (C.c_int, [_VP, C.POINTER(_FmxParams), _VP, _VP, _VP, _VP, _VP]),
     "muxgl_fmx_singlets": (C.c_int, [_VP, _VP]),
     "muxgl_fmx_inclusion": (C.c_int, [_VP, C.POINTER(_FmxParams), _VP, _VP, _VP, _VP]),
@@ -288,6 +291,7 @@ class Engine:
         self.V = 0
         self.K = 0
         self.n_anchor = 0  # clusters 0 .. n_anchor-1 are held to donors of the panel (fmx_set_anchors)
+        self._anchor_modes = ()  # their modes (anchor_modes)
         self.n_alpha = 0
 
     def close(self):
@@ -519,16 +523,41 @@ class Engine:
         self.K = int(K)
         self.n_anchor = 0
 
-    def fmx_set_anchors(self, donors):
-        """muxgl_fmx_set_anchors: clusters 0 .. len(donors)-1 take their genotype posteriors from the panel of
+    @property
+    def anchor_modes(self):
+        """the modes of the anchored clusters, a tuple of ANCHOR_HELD / ANCHOR_PRIOR of length n_anchor (mirrors the
+        library: whatever drops the anchors empties it)"""
+        return self._anchor_modes if len(self._anchor_modes) == self.n_anchor else (ANCHOR_HELD,) * self.n_anchor
+
+    def fmx_set_anchors(self, donors, modes=None):
+        """muxgl_fmx_set_anchors[_mode]: clusters 0 .. len(donors)-1 take their genotype posteriors from the panel of
         demux_set_gp, cluster i from column donors[i], instead of from their droplets; the other clusters are learned as
-        ever (include/muxgl.h).  An empty list (or None) removes the anchors.  After fmx_set_clusters; dropped again by
-        fmx_set_clusters, fmx_prepare, set_pileup and demux_set_gp.  n_anchor mirrors the library's count."""
+        ever (include/muxgl.h).  modes: None (all ANCHOR_HELD: the panel row is the posterior) or one of ANCHOR_HELD /
+        ANCHOR_PRIOR per donor (PRIOR: the panel row is the prior of the posterior the droplets form).  An empty list (or
+        None) removes the anchors.  After fmx_set_clusters; dropped again by fmx_set_clusters, fmx_prepare, set_pileup and
+        demux_set_gp.  n_anchor and anchor_modes mirror the library."""
         d = _arr([] if donors is None else donors, np.int32, "donors")
         if d.ndim != 1:
             raise ValueError("donors must be a list of panel columns")
-        self._check(self.lib.muxgl_fmx_set_anchors(self.h, int(d.size), _ptr(d) if d.size else None))
+        if modes is None:
+            self._check(self.lib.muxgl_fmx_set_anchors(self.h, int(d.size), _ptr(d) if d.size else None))
+            md = np.zeros(d.size, dtype=np.uint8)
+        else:
+            md = _arr(modes, np.uint8, "modes")
+            if md.shape != d.shape:
+                raise ValueError("modes must hold one mode per donor")
+            self._check(self.lib.muxgl_fmx_set_anchors_mode(self.h, int(d.size), _ptr(d) if d.size else None,
+                                                            _ptr(md) if md.size else None))
         self.n_anchor = int(d.size)
+        self._anchor_modes = tuple(int(x) for x in md)
+
+    def fmx_cluster_gp(self, k0=0, k1=None):
+        """muxgl_fmx_get_cluster_gp: the posterior rows [S][k1-k0][3] of clusters k0 .. k1-1 that the last posterior phase
+        wrote and its E-step read (k1 None: up to K)"""
+        k1 = self.K if k1 is None else int(k1)
+        out = np.zeros((self.S, max(k1 - int(k0), 0), 3), dtype=np.float64)
+        self._check(self.lib.muxgl_fmx_get_cluster_gp(self.h, int(k0), k1, _ptr(out)))
+        return out
 
     def fmx_iterate(self, doublet_prior=0.5, geno_error=0.1, want_cells=True, want_full_ll=False):
         p = _FmxParams(float(doublet_prior), float(geno_error))

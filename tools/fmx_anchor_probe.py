@@ -1,7 +1,8 @@
 """What anchoring costs an EM iteration (muxgl_fmx_set_anchors, fmx_anchor.hip): the posterior phase and a whole
 iteration, with and without anchors, on the same handle.
 
-    python tools/fmx_anchor_probe.py [--cases a,b] [--repeats N] [--out profiles/fmx_anchor_probe.jsonl]
+    python tools/fmx_anchor_probe.py [--cases a,b] [--repeats N] [--mode held|prior]
+                                     [--out profiles/fmx_anchor_probe.jsonl]
 
 One JSON line per shape.  Every shape runs in a child process of its own under `timeout`, one after the other, and the
 probe stops at the first child that fails: nothing is started on a device another step has just left in doubt.
@@ -15,6 +16,12 @@ muxgl_fmx_iterate without records.  Medians, with min and max of iter_ms.  The E
 three rounds and the anchor kernel moves S x n x 24 bytes once per iteration (anchor_mb), so the expectation is "within the
 spread between the two plain rounds"; the EM moves on between the rounds (other assignments, other cluster pileups), which
 is part of that spread.  Nothing is asserted.
+
+--mode prior (muxgl_fmx_set_anchors_mode): four rounds -- plain, HELD, PRIOR (the same n clusters with the panel as the
+prior of the posterior the droplets form: fmx_prior_kernel behind fmx_anchor_kernel, the cluster pileups' three diagonal
+doubles at a 72-byte stride plus 24 bytes of panel per lane), plain again; the line carries "mode": "prior".  A line
+replaces the line of the same shape and mode; lines carrying "build" (figures of another commit's build, taken with that
+commit's probe and added by hand) are kept.
 """
 import argparse
 import json
@@ -35,7 +42,7 @@ CASES = {
 }
 
 
-def run_case(name, repeats):
+def run_case(name, repeats, mode="held"):
     from popscle_amd import muxgl, synth
 
     cfg, scale, C, S, K, ment, n, _ = CASES[name]
@@ -77,10 +84,15 @@ def run_case(name, repeats):
         plain = round_of(e)
         e.fmx_set_anchors(list(range(n)))
         anchored = round_of(e)
+        if mode == "prior":
+            e.fmx_set_anchors(list(range(n)), [muxgl.ANCHOR_PRIOR] * n)
+            prior = round_of(e)
         e.fmx_set_anchors([])
         again = round_of(e)
     r = dict(case=name, C=int(p.C), S=int(p.S), K=int(K), n_anchor=int(n), nnz=int(p.nnz), repeats=repeats,
              anchor_mb=round(p.S * n * 24 / 1e6, 3), plain=plain, anchored=anchored, plain_again=again)
+    if mode == "prior":
+        r = dict(r, mode="prior", prior=prior)
     print(json.dumps(r), flush=True)
 
 
@@ -89,15 +101,16 @@ def main():
     ap.add_argument("--cases", default=",".join(CASES))
     ap.add_argument("--case", default=None, help="(child) run one shape in this process")
     ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--mode", choices=["held", "prior"], default="held")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fmx_anchor_probe.jsonl"))
     a = ap.parse_args()
     if a.case:
-        run_case(a.case, a.repeats)
+        run_case(a.case, a.repeats, a.mode)
         return 0
     lines = []
     for name in a.cases.split(","):
         r = subprocess.run(["timeout", "-k", "10", str(CASES[name][7]), sys.executable, os.path.abspath(__file__), "--case", name,
-                            "--repeats", str(a.repeats)], capture_output=True, text=True)
+                            "--repeats", str(a.repeats), "--mode", a.mode], capture_output=True, text=True)
         sys.stderr.write(r.stderr[-2000:])
         if r.returncode != 0:
             print(f"{name}: exit status {r.returncode}; stopping", file=sys.stderr)
@@ -105,14 +118,18 @@ def main():
         line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
         print(line, flush=True)
         lines.append(line)
-    if lines:  # the lines of the shapes run now replace those of the same shapes in an existing file
-        done = {json.loads(ln)["case"] for ln in lines}
+    if lines:  # the lines of the shapes run now replace those of the same shapes (and mode) in an existing file
+        def key(ln):
+            j = json.loads(ln)
+            return (j["case"], j.get("mode", "held"), j.get("build"))
+
+        done = {key(ln) for ln in lines}
         kept = []
         if os.path.exists(a.out):
-            kept = [ln for ln in open(a.out).read().splitlines() if ln.strip() and json.loads(ln)["case"] not in done]
+            kept = [ln for ln in open(a.out).read().splitlines() if ln.strip() and key(ln) not in done]
         rank = {name: i for i, name in enumerate(CASES)}
-        with open(a.out, "w") as f:
-            f.write("\n".join(sorted(kept + lines, key=lambda ln: rank.get(json.loads(ln)["case"], 99))) + "\n")
+        with open(a.out, "w") as f:   # (stable: by mode and build first, then by shape)
+            f.write("\n".join(sorted(kept + lines, key=lambda ln: (key(ln)[1], key(ln)[2] or "", rank.get(key(ln)[0], 99)))) + "\n")
     return 0 if len(lines) == len(a.cases.split(",")) else 1
 
 
