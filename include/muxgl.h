@@ -290,6 +290,52 @@ int muxgl_demux_unknown(muxgl_handle* h, const muxgl_demux_params* p, const doub
                         double* ll_ju /* NULL or [C][V][n_alpha] */, double* ll_uj /* NULL or [C][V][n_alpha] */,
                         double* ll_uu /* NULL or [C][n_alpha] */, float* kernel_ms /* NULL or one float */);
 
+/* The usable reads (every read byte but MUXGL_READ_OTHER) of the pileup by marker and allele, over the droplets whose
+ * byte of cell_mask is not 0 (cell_mask == NULL: over all of them): n_ref[s] / n_alt[s] = reads of marker s with bit 7
+ * clear / set.  A device kernel over the entries with integer adds: exact, and the same whatever the order.  Needs only
+ * muxgl_set_pileup; one device or a device group (every member counts its own droplets, the counts are added on the
+ * host).  It reads the pileup and changes no state.  What it is for: the ALT fraction of the pool's free-floating RNA,
+ * amb_af of muxgl_demux_ambient, from all droplets or from the nearly empty ones. */
+int muxgl_pileup_allele_counts(muxgl_handle* h, const uint8_t* cell_mask /* NULL = all, or [C] */,
+                               int64_t* n_ref /* [S] */, int64_t* n_alt /* [S] */);
+
+/* Every droplet as ONE cell of sample j plus a share rho of ambient RNA: the hypothesis the reference lacks (its only
+ * reading of a singlet from a high-soup prep is "j plus one other donor", a doublet with a partner picked nearly at
+ * random).  The ambient RNA is no donor: its ALT fraction at marker s is the pool's, amb_af[s], any number in [0, 1],
+ * where a second donor's genotype m of cmd_cram_demuxlet.cpp:655-725 stands, as 2 * amb_af[s]:
+ *   p(l, f, rho)    = 0.5 * l + (2 * f - l) * 0.5 * rho
+ *   a_e[r][l]       = product over the usable reads of entry e of (pR * (1 - p) + pA * p),  p = p(l, amb_af[s_e], rho[r])
+ *   w_e[r][l]       = (a_e[r][l] / q_max_e + 1e-10) / (1 + 1e-10)
+ *   ll_amb[c][j][r] = sum over the entries e of droplet c whose marker has genotypes of
+ *                     log( sum_l gp[s_e][j][l] * w_e[r][l] )
+ * q_max_e is the entry's scale under the alpha grid of p: the number that scales pG_e in muxgl_demux_run,
+ * muxgl_demux_singlets and muxgl_demux_unknown with that grid (doublet_prior is not read).  The ambient products take
+ * part in no maximum, they are only divided by the grid's; a / q_max may exceed 1 by a modest factor where the best p
+ * of an entry is not on the grid.  ll_amb is therefore on the scale of the log-likelihoods of the records and of the
+ * singlet table, and may be subtracted from dblBestLLK or from a row of muxgl_demux_singlets.  Three identities:
+ *   amb_af in {0, 0.5, 1} and rho[r] == alpha[n]: w_e[r][l] = pG_e[n][l][2 f], and ll_amb[c][j][r] is the reference's
+ *     llksAB[(j, V, n)] on the panel with one donor appended whose row at marker s is one-hot at genotype 2 * amb_af[s];
+ *   rho[r] == 0: the column is the table of muxgl_demux_singlets with the same grid;
+ *   rho[r] == 1: p is amb_af, the column is the same for every sample ("nothing but soup").
+ * The rho reported for a droplet by a caller is the maximum over the grid rho[], not an estimate with an error bar.
+ * A marker without genotypes contributes a factor of exactly 1 (:733), a droplet without entries gets zeros.  Needs
+ * muxgl_set_pileup and muxgl_demux_set_gp, not a previous muxgl_demux_run; any V up to MUXGL_MAX_SAMPLES; 1 <= n_rho <=
+ * MUXGL_MAX_ALPHA; every rho and every amb_af[s] of a marker with genotypes finite and in [0, 1] (the values of markers
+ * without genotypes do not matter); one device or a device group (every member fills the rows of its own cells).  It
+ * fails, naming the reason and leaving the handle usable, without a pileup or a GP tensor, with ll_amb == NULL, with
+ * n_rho or n_alpha out of range, with a rho or an amb_af out of range or not finite, and when one cell alone exceeds
+ * the budget.  kernel_ms (NULL allowed) receives the hipEvent time of the call's kernels, from a pair of events the call
+ * makes for itself (a group: the slowest member's): the records, full_ll, plans, timing slots and cached grid of
+ * muxgl_demux_run and every freemuxlet state stay as they are.
+ * Device memory: nothing proportional to nnz x n_rho is held for the whole pileup.  The cells are swept in batches of
+ * whole cells whose 3 n_rho weights per entry, slab rows and table rows fit the streamed call's budget (4 GiB or a third
+ * of the device, MUXGL_DEMUX_SLAB_MB); each batch is copied out before the next.  The table is bit-identical from call
+ * to call, for any budget, for any split of rho[] over several calls, on one device, on a group and through the
+ * sharded driver. */
+int muxgl_demux_ambient(muxgl_handle* h, const muxgl_demux_params* p, const double* amb_af /* [S] */, int32_t n_rho,
+                        const double* rho /* [n_rho] */, double* ll_amb /* [C][V][n_rho] */,
+                        float* kernel_ms /* NULL or one float */);
+
 /* The calls rounding noise could decide, settled in the reference's own arithmetic -- HOST pass, no device work, no
  * handle (popscle_amd/host/exact_calls.hpp).  The kernels' log-likelihoods equal the reference's to ~1e-12, not to the last
  * bit, and every decision of cmd_cram_demuxlet.cpp:827-837,883-906,925-988 compares two of them.  For the cells of

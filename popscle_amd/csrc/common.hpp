@@ -676,6 +676,14 @@ int demux_singlets_run(muxgl_handle* h, const muxgl_demux_params* p, double* sng
 // demux_unknown.hip: the three tables of muxgl_demux_unknown to the host (any may be NULL), rows of the handle's own cells
 int demux_unknown_run(muxgl_handle* h, const muxgl_demux_params* p, const double* gp0, double* ll_ju, double* ll_uj,
                       double* ll_uu, float* kernel_ms);
+// demux_ambient.hip: the table of muxgl_demux_ambient to the host, rows of the handle's own cells.  n_rho and rho are
+// checked by the caller (demux_ambient_bad_rho), amb_af here, against the handle's has_gp
+int demux_ambient_run(muxgl_handle* h, const muxgl_demux_params* p, const double* amb_af, int n_rho, const double* rho,
+                      double* ll_amb, float* kernel_ms);
+int demux_ambient_bad_rho(int n_rho, const double* rho);  // the first rho that is not a finite number in [0, 1], or -1
+// demux_ambient.hip: usable reads by marker and allele of the handle's own cells whose mask byte is set (cell_mask: host
+// [C] or NULL), to n_ref / n_alt (host [S])
+int pileup_allele_counts_run(muxgl_handle* h, const uint8_t* cell_mask, int64_t* n_ref, int64_t* n_alt);
 struct demux_incl_out {  // muxgl_demux_inclusion's outputs (host; any may be NULL), rows of the handle's own cells
   double *incl, *tot, *dbl;
   int32_t *partner, *alpha_idx, *first;
@@ -767,6 +775,9 @@ int group_demux_singlets(muxgl_handle* h, const muxgl_demux_params* p, double* s
 int group_demux_inclusion(muxgl_handle* h, const muxgl_demux_params* p, const demux_incl_out& out);
 int group_demux_unknown(muxgl_handle* h, const muxgl_demux_params* p, const double* gp0, double* ll_ju, double* ll_uj,
                         double* ll_uu, float* kernel_ms);
+int group_demux_ambient(muxgl_handle* h, const muxgl_demux_params* p, const double* amb_af, int32_t n_rho, const double* rho,
+                        double* ll_amb, float* kernel_ms);
+int group_pileup_allele_counts(muxgl_handle* h, const uint8_t* cell_mask, int64_t* n_ref, int64_t* n_alt);
 const muxgl_demux_cell* group_demux_results(const muxgl_handle* h);
 int group_demux_get_entry_pg(muxgl_handle* h, double* pg);
 int group_fmx_prepare(muxgl_handle* h, const double* af, double* cell_llk0, double* cell_llk2, int32_t* cell_nsnps,

@@ -658,6 +658,32 @@ int muxgl_demux_unknown(muxgl_handle* h, const muxgl_demux_params* p, const doub
   return demux_unknown_run(h, p, gp0, ll_ju, ll_uj, ll_uu, kernel_ms);
 }
 
+int muxgl_pileup_allele_counts(muxgl_handle* h, const uint8_t* cell_mask, int64_t* n_ref, int64_t* n_alt) {
+  if (!h) return 1;
+  if (h->group) return group_pileup_allele_counts(h, cell_mask, n_ref, n_alt);
+  HIPCHK(h, hipSetDevice(h->device));
+  if (!h->d_cell_ptr) MUXGL_FAIL(h, "muxgl_pileup_allele_counts: no pileup set (muxgl_set_pileup)");
+  if (!n_ref || !n_alt) MUXGL_FAIL(h, "muxgl_pileup_allele_counts: NULL output");
+  return pileup_allele_counts_run(h, cell_mask, n_ref, n_alt);
+}
+
+int muxgl_demux_ambient(muxgl_handle* h, const muxgl_demux_params* p, const double* amb_af, int32_t n_rho, const double* rho,
+                        double* ll_amb, float* kernel_ms) {
+  if (!h) return 1;
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (h->group) return group_demux_ambient(h, p, amb_af, n_rho, rho, ll_amb, kernel_ms);
+  HIPCHK(h, hipSetDevice(h->device));
+  if (check_demux_params(h, p)) return 1;
+  if (!ll_amb) MUXGL_FAIL(h, "muxgl_demux_ambient: NULL output");
+  if (n_rho < 1 || n_rho > MUXGL_MAX_ALPHA) MUXGL_FAIL(h, "muxgl_demux_ambient: n_rho=%d outside [1,%d]", n_rho, MUXGL_MAX_ALPHA);
+  if (!rho || !amb_af) MUXGL_FAIL(h, "muxgl_demux_ambient: %s is NULL", rho ? "amb_af" : "rho");
+  if (const int r = demux_ambient_bad_rho(n_rho, rho); r >= 0)
+    MUXGL_FAIL(h, "muxgl_demux_ambient: rho[%d] (%g) is not a finite number in [0, 1]", r, rho[r]);
+  // (no clear_timing, no timing slot: records, timings and state of the last muxgl_demux_run keep their values; with no
+  // cell there is no table, but the profile is still checked)
+  return demux_ambient_run(h, p, amb_af, n_rho, rho, ll_amb, kernel_ms);
+}
+
 int muxgl_demux_oct_split(const muxgl_handle* h, int64_t* info) {
   if (!h || !info) return 1;
   if (h->group) {

@@ -343,6 +343,52 @@ int group_demux_unknown(muxgl_handle* h, const muxgl_demux_params* p, const doub
   return 0;
 }
 
+// every member sweeps its own cells and writes their rows of the caller's table; kernel_ms: the slowest member's
+int group_demux_ambient(muxgl_handle* h, const muxgl_demux_params* p, const double* amb_af, int32_t n_rho, const double* rho,
+                        double* ll_amb, float* kernel_ms) {
+  muxgl_group* g = h->group;
+  if (!p) MUXGL_FAIL(h, "demux params NULL");
+  if (p->n_alpha < 1 || p->n_alpha > MUXGL_MAX_ALPHA) MUXGL_FAIL(h, "n_alpha=%d outside [1,%d]", p->n_alpha, MUXGL_MAX_ALPHA);
+  if (!g->have_pileup) MUXGL_FAIL(h, "no pileup set (muxgl_set_pileup)");
+  if (g->V < 1) MUXGL_FAIL(h, "no GP tensor set (muxgl_demux_set_gp)");
+  if (!ll_amb) MUXGL_FAIL(h, "muxgl_demux_ambient: NULL output");
+  if (n_rho < 1 || n_rho > MUXGL_MAX_ALPHA) MUXGL_FAIL(h, "muxgl_demux_ambient: n_rho=%d outside [1,%d]", n_rho, MUXGL_MAX_ALPHA);
+  if (!rho || !amb_af) MUXGL_FAIL(h, "muxgl_demux_ambient: %s is NULL", rho ? "amb_af" : "rho");
+  if (const int r = demux_ambient_bad_rho(n_rho, rho); r >= 0)
+    MUXGL_FAIL(h, "muxgl_demux_ambient: rho[%d] (%g) is not a finite number in [0, 1]", r, rho[r]);
+  std::vector<float> ms((size_t)g->n, 0.f);
+  if (for_members(h, [&](int r) {  // (every member checks amb_af against its copy of has_gp)
+        const size_t o = (size_t)g->cb[(size_t)r] * (size_t)g->V * (size_t)n_rho;
+        return muxgl_demux_ambient(g->m[(size_t)r], p, amb_af, n_rho, rho, ll_amb + o, kernel_ms ? &ms[(size_t)r] : nullptr);
+      }))
+    return 1;
+  if (kernel_ms) *kernel_ms = *std::max_element(ms.begin(), ms.end());
+  return 0;
+}
+
+// every member counts the reads of its own cells; the counts are added here (integers: exact in any order)
+int group_pileup_allele_counts(muxgl_handle* h, const uint8_t* cell_mask, int64_t* n_ref, int64_t* n_alt) {
+  muxgl_group* g = h->group;
+  if (!g->have_pileup) MUXGL_FAIL(h, "muxgl_pileup_allele_counts: no pileup set (muxgl_set_pileup)");
+  if (!n_ref || !n_alt) MUXGL_FAIL(h, "muxgl_pileup_allele_counts: NULL output");
+  const size_t S = (size_t)g->S;
+  std::vector<int64_t> part((size_t)g->n * 2 * S);
+  if (for_members(h, [&](int r) {
+        int64_t* q = part.data() + (size_t)r * 2 * S;
+        return muxgl_pileup_allele_counts(g->m[(size_t)r], cell_mask ? cell_mask + g->cb[(size_t)r] : nullptr, q, q + S);
+      }))
+    return 1;
+  for (size_t s = 0; s < S; ++s) n_ref[s] = n_alt[s] = 0;
+  for (int r = 0; r < g->n; ++r) {
+    const int64_t* q = part.data() + (size_t)r * 2 * S;
+    for (size_t s = 0; s < S; ++s) {
+      n_ref[s] += q[s];
+      n_alt[s] += q[S + s];
+    }
+  }
+  return 0;
+}
+
 const muxgl_demux_cell* group_demux_results(const muxgl_handle* h) { return h->group->h_dcells; }
 
 int group_demux_get_entry_pg(muxgl_handle* h, double* pg) {

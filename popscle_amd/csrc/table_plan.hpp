@@ -81,6 +81,13 @@ inline size_t unknown_bytes(int64_t len, int64_t np, int A, int VC) {
   return (size_t)len * A * 6 * sizeof(double) + (size_t)np * (row_bytes + sizeof(item)) + row_bytes + sizeof(cell);
 }
 
+// device bytes of a cell in a batch of the ambient call at NR rhos and V samples: its entries' weights (three per rho),
+// its slab rows (one per part) with their items, and its row of the table with its record
+inline size_t ambient_bytes(int64_t len, int64_t np, int NR, int V) {
+  const size_t row_bytes = sizeof(double) * (size_t)NR * V;
+  return (size_t)len * NR * 3 * sizeof(double) + (size_t)np * (row_bytes + sizeof(item)) + row_bytes + sizeof(cell);
+}
+
 // device bytes of a cell in a batch of freemuxlet's unknown-donor call at K clusters: its entries' weights (three and two
 // scalars, 40 bytes an entry), its slab rows of K + 2 doubles (one per part) with their items, and its rows of the three
 // tables (K + 2 doubles)

@@ -11,12 +11,13 @@ from .freemuxlet import NoExchange
 
 
 def run_sharded(engine_factory, p, alphas=(0.0, 0.5), doublet_prior=0.5, exchange=None, want_singlets=False,
-                want_inclusion=False, *, want_unknown=False):
+                want_inclusion=False, *, want_unknown=False, want_ambient=None):
     """engine_factory() -> object with set_pileup / demux_set_gp / demux_run (muxgl.Engine).  Returns the [C] records of
     the whole pileup on every rank, in the original cell order; with want_singlets also the [C][V] table of singlet
     log-likelihoods (Engine.demux_singlets), gathered the same way: (records, sng); with want_inclusion also the dict of
     per-droplet, per-sample inclusion tables (Engine.demux_inclusion): (records, [sng,] inclusion); with want_unknown
-    (keyword only) also the dict of the three tables of Engine.demux_unknown (panel mean) as the last element.
+    (keyword only) also the dict of the three tables of Engine.demux_unknown (panel mean); with want_ambient = (amb_af,
+    rhos) (keyword only) also the [C][V][n_rho] table of Engine.demux_ambient, as the last element.
     Cells are independent, so every rank fills the rows of its own cells."""
     ex = exchange or NoExchange()
     ranges = shard.cell_shards(p.cell_ptr, ex.world)
@@ -30,7 +31,7 @@ def run_sharded(engine_factory, p, alphas=(0.0, 0.5), doublet_prior=0.5, exchang
     out = np.zeros(p.C, dtype=cells.dtype)
     for b, e, raw in parts:
         out[b:e] = np.frombuffer(raw, dtype=cells.dtype)
-    if not want_singlets and not want_inclusion and not want_unknown:
+    if not want_singlets and not want_inclusion and not want_unknown and want_ambient is None:
         return out
     ret = [out]
     V = p.gp.shape[1]
@@ -53,4 +54,10 @@ def run_sharded(engine_factory, p, alphas=(0.0, 0.5), doublet_prior=0.5, exchang
             for k, v in unk.items():
                 v[b:e] = np.frombuffer(raw[k], dtype=v.dtype).reshape((e - b,) + v.shape[1:])
         ret.append(unk)
+    if want_ambient is not None:
+        amb_af, rhos = want_ambient
+        amb = np.zeros((p.C, V, len(rhos)), dtype=np.float64)
+        for b, e, raw in ex.gather_objects((c0, c1, eng.demux_ambient(alphas, amb_af, rhos)["ll"].tobytes())):
+            amb[b:e] = np.frombuffer(raw, dtype=np.float64).reshape(e - b, V, len(rhos))
+        ret.append(amb)
     return tuple(ret)

@@ -21,6 +21,17 @@
 //       (one unknown donor), UNK.DBL.ALPHA (%.2lf), UNK.DBL.LLK (two unknown donors, the best alpha), HALF.GUESS (SM,*,alpha:
 //       the known donor has share 1 - alpha; *,SM,alpha: share alpha), HALF.LLK, DIFF.LLK.PANEL.UNK (BEST.LLK minus the
 //       largest of the three); LLKs %.4lf; NA where a column has no hypothesis (a grid of one alpha)
+//       --write-ambient: also <O>.amb.gz (BGZF), one row per printed droplet: the droplet as ONE cell of a sample plus a
+//       share rho of ambient RNA (muxgl_demux_ambient) -- the reading the reference lacks, which calls a clean singlet
+//       from a high-soup prep a doublet with a partner picked nearly at random.  --ambient-rho x (repeatable; default 0
+//       0.05 0.1 0.15 0.2 0.3 0.4 0.5) is the grid of shares; the ALT fraction of the ambient RNA per marker is read from
+//       --ambient-af FILE (one number per line, in .var.gz order) or else made from the pileup itself: the usable reads
+//       of the loaded droplets by marker and allele (muxgl_pileup_allele_counts; --ambient-max-reads N: of the droplets
+//       with at most N reads only, 0 = all) with one pseudo-read at the AF column of .var.gz, (n_alt + AF) / (n_ref + n_alt
+//       + 1).  Columns BARCODE, NUM.SNPS, NUM.READS, DROPLET.TYPE, BEST.LLK, SNG.BEST.GUESS, SNG.BEST.LLK (those of .best,
+//       LLKs %.4lf), AMB.GUESS (the sample), AMB.RHO (%.2lf: the best share ON THE GRID, no estimate with an error bar),
+//       AMB.LLK (ties: the lower sample, then the lower rho index), DIFF.LLK.AMB.BEST = AMB.LLK - BEST.LLK.  The calls of
+//       .best and every other file are unchanged
 //   popscle-amd freemuxlet --plp P --nsample K --out O [...]                   mirrors cmdCramFreemux2 (cmd_cram_freemux2.cpp)
 //       --write-singlets: also <O>.clust1.sing2.gz (BGZF), the singlet log-likelihood of every droplet against every
 //       cluster as the last EM iteration formed it (llks[j(j+1)/2 + j], cmd_cram_freemux2.cpp:448-455; the reference
@@ -176,9 +187,17 @@ int cmd_demuxlet(int argc, char** argv) {
   bool writeSinglets = false;  // (ours) <out>.sing2.gz: the reference's disabled .sing2 writer (:580,839-848)
   bool writeInclusion = false;  // (ours) <out>.incl.gz: per-sample marginals of the disabled .pair writer (:852-877)
   bool writeUnknown = false;  // (ours) <out>.unk.gz: the droplet against a donor missing from the VCF (llksA0 / llks00, :749-773)
+  bool writeAmbient = false;  // (ours) <out>.amb.gz: the droplet as one cell plus a share of ambient RNA (muxgl_demux_ambient)
+  std::vector<double> ambRho;
+  std::string ambAfFile;
+  int32_t ambMaxReads = 0;
   Args a;
   cf.add(a);
   a.add_bool("write-unknown", &writeUnknown);
+  a.add_bool("write-ambient", &writeAmbient);
+  a.add_multi_double("ambient-rho", &ambRho);
+  a.add_string("ambient-af", &ambAfFile);
+  a.add_int("ambient-max-reads", &ambMaxReads);
   a.add_bool("device-calls", &deviceCalls);
   a.add_bool("write-singlets", &writeSinglets);
   a.add_bool("write-inclusion", &writeInclusion);
@@ -209,6 +228,9 @@ int cmd_demuxlet(int argc, char** argv) {
     gridAlpha.push_back(0.5);
   }
   if ((int)gridAlpha.size() > MUXGL_MAX_ALPHA) fatal("at most %d --alpha values are supported", MUXGL_MAX_ALPHA);
+  if (ambRho.empty()) ambRho = {0.0, 0.05, 0.1, 0.15, 0.2, 0.3, 0.4, 0.5};
+  if ((int)ambRho.size() > MUXGL_MAX_ALPHA) fatal("at most %d --ambient-rho values are supported", MUXGL_MAX_ALPHA);
+  if (ambMaxReads < 0) fatal("--ambient-max-reads must not be negative");
   vr.wanted = smIDs;
   if (!smList.empty()) {
     TsvReader t(smList);
@@ -379,6 +401,59 @@ int cmd_demuxlet(int argc, char** argv) {
     }
     wu.close();
     tm.lap("demuxlet: write .unk.gz");
+  }
+  if (writeAmbient) {
+    // .amb.gz: one row per printed droplet (the order and the filters of .best).  The ambient profile: the caller's file,
+    // or the pileup's own reads with one pseudo-read at the population frequency
+    const size_t V = (size_t)p.nv, NR = ambRho.size(), S = (size_t)p.S();
+    std::vector<double> f(S);
+    if (!ambAfFile.empty()) {
+      TsvReader t(ambAfFile);
+      size_t n = 0;
+      for (; t.read_line() > 0; ++n)
+        if (n < S) f[n] = t.double_field_at(0);
+      if (n != S) fatal("--ambient-af: %s holds %zu lines, the pileup has %zu markers", ambAfFile.c_str(), n, S);
+    } else {
+      std::vector<uint8_t> mask;
+      if (ambMaxReads > 0) {
+        mask.resize((size_t)p.C());
+        int64_t kept = 0;
+        for (int64_t i = 0; i < p.C(); ++i) kept += mask[(size_t)i] = p.cell_uniq_reads[(size_t)i] <= ambMaxReads;
+        notice("Ambient profile from the %lld of %lld droplets with at most %d reads", (long long)kept, (long long)p.C(), ambMaxReads);
+      }
+      std::vector<int64_t> n_ref(S), n_alt(S);
+      check(h, muxgl_pileup_allele_counts(h, mask.empty() ? nullptr : mask.data(), n_ref.data(), n_alt.data()),
+            "muxgl_pileup_allele_counts");
+      for (size_t s = 0; s < S; ++s)
+        f[s] = ((double)n_alt[s] + p.snps[s].af) / ((double)n_ref[s] + (double)n_alt[s] + 1.0);
+      tm.lap("demuxlet: muxgl_pileup_allele_counts");
+    }
+    std::vector<double> amb((size_t)p.C() * V * NR);
+    check(h, muxgl_demux_ambient(h, &dp, f.data(), (int32_t)NR, ambRho.data(), amb.data(), nullptr), "muxgl_demux_ambient");
+    tm.lap("demuxlet: muxgl_demux_ambient");
+    OutFile wa(cf.outPrefix + ".amb.gz", true);
+    wa.printf("BARCODE\tNUM.SNPS\tNUM.READS\tDROPLET.TYPE\tBEST.LLK\tSNG.BEST.GUESS\tSNG.BEST.LLK\tAMB.GUESS\tAMB.RHO\tAMB.LLK\t"
+              "DIFF.LLK.AMB.BEST\n");
+    int64_t rescued = 0;
+    for (auto it = bc_map.begin(); it != bc_map.end(); ++it) {
+      const int32_t i = it->second;
+      const muxgl_demux_cell& c = cells[(size_t)i];
+      if (p.cell_totl_reads[(size_t)i] < cf.lo.minRead || p.cell_uniq_reads[(size_t)i] < cf.lo.minUMI ||
+          c.nsnps < cf.lo.minSNP || !c.valid)
+        continue;
+      const double* row = amb.data() + (size_t)i * V * NR;
+      size_t at = 0;  // the best (sample, rho): by value, then (sample, rho index) ascending
+      for (size_t x = 1; x < V * NR; ++x)
+        if (row[x] > row[at]) at = x;
+      if (c.type == 1 && row[at] > c.dblBestLLK + 2.0) ++rescued;
+      wa.printf("%s\t%u\t%d\t%s\t%.4lf\t%s\t%.4lf\t%s\t%.2lf\t%.4lf\t%.4lf\n", it->first.c_str(), (unsigned)c.nsnps,
+                p.cell_uniq_reads[(size_t)i], tname[c.type], c.bestLLK, sid(p, c.sBest), c.sngBestLLK, sid(p, (int)(at / NR)),
+                ambRho[at % NR], row[at], row[at] - c.bestLLK);
+    }
+    wa.close();
+    notice("Ambient RNA: %lld droplets called DBL are explained better, by more than 2 in log-likelihood, as one cell plus "
+           "ambient RNA than as their best doublet", (long long)rescued);
+    tm.lap("demuxlet: write .amb.gz");
   }
   notice("Finished writing output files");
   muxgl_destroy(h);
@@ -1472,6 +1547,8 @@ int main(int argc, char** argv) {
                     "  demuxlet --write-inclusion: also <out>.incl.gz, per printed droplet and sample the evidence that the sample\n"
                     "    is in the droplet and the doublet it pairs best in (BARCODE SM_ID NUM.SNPS NUM.READS LLK.INCL\n"
                     "    POSTPRB.INCL DBL.PARTNER DBL.ALPHA DBL.LLK)\n"
+                    "  demuxlet --write-ambient [--ambient-rho x ...] [--ambient-af FILE] [--ambient-max-reads N]: also <out>.amb.gz,\n"
+                    "      per printed droplet the best reading as one cell of a sample plus a share rho of ambient RNA\n"
                     "  demuxlet --write-unknown: also <out>.unk.gz, per printed droplet how well a donor missing from the VCF\n"
                     "    explains it (BARCODE NUM.SNPS NUM.READS BEST.LLK UNK.SNG.LLK UNK.DBL.ALPHA UNK.DBL.LLK HALF.GUESS\n"
                     "    HALF.LLK DIFF.LLK.PANEL.UNK)\n"

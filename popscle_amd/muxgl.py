@@ -97,6 +97,8 @@ SYMBOLS = {
     "muxgl_demux_singlets": (C.c_int, [_VP, C.POINTER(_DemuxParams), _VP]),
     "muxgl_demux_inclusion": (C.c_int, [_VP, C.POINTER(_DemuxParams), _VP, _VP, _VP, _VP, _VP, _VP]),
     "muxgl_demux_unknown": (C.c_int, [_VP, C.POINTER(_DemuxParams), _VP, _VP, _VP, _VP, _VP]),
+    "muxgl_demux_ambient": (C.c_int, [_VP, C.POINTER(_DemuxParams), _VP, C.c_int32, _VP, _VP, _VP]),
+    "muxgl_pileup_allele_counts": (C.c_int, [_VP, _VP, _VP, _VP]),
     "muxgl_demux_results": (_VP, [_VP]),
     "muxgl_demux_oct_split": (C.c_int, [_VP, _VP]),
     "muxgl_demux_exact_calls": (C.c_int, [C.c_int64, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP,
@@ -251,6 +253,41 @@ def unknown_summary(tables, alphas):
         out["half_alpha_idx"][some] = ((b // 2) % (A - 1) + 1)[some]
         out["half_known_major"][some] = (1 - b % 2)[some]
     return out
+
+
+def ambient_profile(n_ref, n_alt, af):
+    """The ALT fraction of the pool's free-floating RNA per marker, from the read counts of Engine.pileup_allele_counts and
+    the population ALT frequency af: (n_alt + af) / (n_ref + n_alt + 1), i.e. one pseudo-read at the population
+    frequency, so a marker nobody covered falls back to af.  float64 [S], in [0, 1] wherever af is."""
+    n_ref = np.asarray(n_ref, dtype=np.float64)
+    n_alt = np.asarray(n_alt, dtype=np.float64)
+    af = np.asarray(af, dtype=np.float64)
+    if n_ref.shape != n_alt.shape or af.shape != n_ref.shape or n_ref.ndim != 1:
+        raise ValueError("n_ref, n_alt and af must be [S]")
+    return (n_alt + af) / (n_ref + n_alt + 1.0)
+
+
+def ambient_summary(ll, rhos):
+    """Per droplet, the best "one cell of sample j plus a share rho of ambient RNA" hypothesis of the table of
+    Engine.demux_ambient (ll float64 [C][V][n_rho]).  Pure numpy.  Returns a dict of [C] arrays: amb_llk, amb_sample,
+    amb_rho_idx, amb_rho: the maximum over (sample, rho index), ties decided by value descending, then (sample, rho index)
+    ascending; base_llk, base_sample: the maximum at the smallest rho (the first of them on ties) alone, for comparison --
+    the singlet call where that rho is 0.  The rho of a droplet is the best point of the grid `rhos`, not an estimate
+    with an error bar."""
+    ll = np.asarray(ll, dtype=np.float64)
+    rh = np.asarray(rhos, dtype=np.float64)
+    if ll.ndim != 3 or rh.ndim != 1 or ll.shape[2] != rh.size or rh.size < 1 or ll.shape[1] < 1:
+        raise ValueError("ll must be [C][V][n_rho] with V >= 1 and n_rho = len(rhos) >= 1")
+    Cn, V, NR = ll.shape
+    flat = ll.reshape(Cn, V * NR)
+    flat = np.where(np.isnan(flat), -np.inf, flat)
+    b = np.argmax(flat, axis=1)  # (first maximum in (sample, rho index) order)
+    ar = np.arange(Cn)
+    r0 = int(np.argmin(rh))  # (first smallest)
+    base = flat.reshape(Cn, V, NR)[:, :, r0]
+    bs = np.argmax(base, axis=1)
+    return {"amb_llk": flat[ar, b], "amb_sample": (b // NR).astype(np.int32), "amb_rho_idx": (b % NR).astype(np.int32),
+            "amb_rho": rh[b % NR] if Cn else np.zeros(0), "base_llk": base[ar, bs], "base_sample": bs.astype(np.int32)}
 
 
 def _ptr(a):
@@ -457,6 +494,41 @@ class Engine:
                                                   C.byref(ms)))
         out["kernel_ms"] = float(ms.value)
         return out
+
+    def demux_ambient(self, alphas, amb_af, rhos):
+        """muxgl_demux_ambient: every droplet as one cell of sample j plus a share rho of ambient RNA whose ALT fraction
+        at marker s is amb_af[s] (include/muxgl.h).  dict of ll float64 [C][V][n_rho], on the scale of the records'
+        log-likelihoods under the grid `alphas`, and kernel_ms, the event time of the call's kernels.  At any V, without
+        a previous demux_run; ambient_profile() makes amb_af from pileup_allele_counts(), ambient_summary() turns the
+        table into per-droplet calls."""
+        if len(alphas) > MAX_ALPHA:
+            raise ValueError("too many alphas")
+        p = _DemuxParams()
+        p.n_alpha = len(alphas)
+        for i, a in enumerate(alphas):
+            p.alpha[i] = float(a)
+        p.doublet_prior = 0.5  # (not read by the call)
+        amb_af = _arr(amb_af, np.float64, "amb_af")
+        if amb_af.shape != (self.S,):
+            raise ValueError("amb_af must be [S]")
+        rhos = _arr(rhos, np.float64, "rhos").reshape(-1)
+        out = np.zeros((self.C, self.V, rhos.size), dtype=np.float64)
+        ms = C.c_float(0.0)
+        self._check(self.lib.muxgl_demux_ambient(self.h, C.byref(p), _ptr(amb_af), rhos.size, _ptr(rhos), _ptr(out),
+                                                  C.byref(ms)))
+        return {"ll": out, "kernel_ms": float(ms.value)}
+
+    def pileup_allele_counts(self, mask=None):
+        """muxgl_pileup_allele_counts: (n_ref, n_alt), int64 [S] each, the usable reads of the droplets whose mask entry is
+        true (None: all of them) by marker and allele; exact integer counts from the device."""
+        if mask is not None:
+            mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+            if mask.shape != (self.C,):
+                raise ValueError("mask must be [C]")
+        n_ref = np.zeros(self.S, dtype=np.int64)
+        n_alt = np.zeros(self.S, dtype=np.int64)
+        self._check(self.lib.muxgl_pileup_allele_counts(self.h, _ptr(mask), _ptr(n_ref), _ptr(n_alt)))
+        return n_ref, n_alt
 
     def demux_results_view(self):
         """zero-copy view of the pinned [C] record buffer of the last run"""
