@@ -593,6 +593,48 @@ int muxgl_fmx_unknown(muxgl_handle* h, const double* gp0 /* NULL or [S][3] */,
                       double* ll_ju /* NULL or [C][K] */, double* ll_u /* NULL or [C] */,
                       double* ll_uu /* NULL or [C] */, float* kernel_ms /* NULL or one float */);
 
+/* Every droplet as ONE cell of cluster j plus a share rho of ambient RNA: the reading freemuxlet lacks (a clean singlet
+ * from a high-soup prep comes out as a doublet of its own cluster with a partner picked nearly at random), the counterpart
+ * of muxgl_demux_ambient.  The ambient RNA is no donor: its ALT fraction at marker s is the pool's, amb_af[s], any number
+ * in [0, 1], and its share any rho in [0, 1].  This is calculate_snp_droplet_pileup (sc_drop_seq.cpp:452-509, alpha =
+ * 0.5) with three ambient elements per rho carried along the entry's nine:
+ *   p(l, f, rho) = 0.5 * l + (2 * f - l) * 0.5 * rho                                (f = amb_af[s_e])
+ *   per usable read of entry e, in read order (a byte of MUXGL_READ_OTHER is skipped, :468):
+ *       nine[i] *= mat * frac_i + e4                                               (:483-491)
+ *       a[r][l] *= mat * (ALT read ? p : 1 - p) + e4,   p = p(l, f, rho[r])
+ *       t = nine[0] + ... + nine[8]; nine and a are all divided by t               (:493-494)
+ *   after the reads every element of nine and of a below 1e-6 becomes 1e-6 (:498-501, sc_drop_seq.h:14),
+ *       T = sum of the floored nine, w_e[r][l] = a[r][l] / T                       (:502-504)
+ *   ll_amb[c][j][r] = sum over the entries e of droplet c, in entry order, of
+ *                     log( q[s_e][j][0] * w_e[r][0] + q[s_e][j][1] * w_e[r][1] + q[s_e][j][2] * w_e[r][2] )
+ * q[s][j][.] are the cluster posteriors the last E-step read (MUXGL_BUF_CGP, geno_error mixed in).  The ambient elements
+ * take part in none of the sums t and T: those are the numbers behind the entry likelihoods of muxgl_fmx_prepare, so
+ * ll_amb is on the scale of the log-likelihoods of .clust1.samples.gz and of muxgl_fmx_singlets, and may be subtracted
+ * from bestLLK or dblBestLLK.  Every marker contributes (freemuxlet has no has_gp).  Three identities:
+ *   amb_af in {0, 0.5, 1} and rho[r] == 0.5: p = (l + 2 f) / 4 exactly, w_e[r][l] is the entry likelihood gls[3 l + 2 f],
+ *     and ll_amb[c][j][r] is the reference's doublet slot (j, X) for a cluster X whose posterior row at marker s is one-hot
+ *     at genotype 2 * amb_af[s];
+ *   rho[r] == 0: w_e[r][l] = gls[4 l], the column is the table of muxgl_fmx_singlets;
+ *   rho[r] == 1: p is amb_af, the column is the same for every cluster (up to the rounding of q's row sums).
+ * The rho reported for a droplet by a caller is the maximum over the grid rho[], not an estimate with an error bar.
+ * State rules and refusals are muxgl_fmx_unknown's under this call's name: call it after muxgl_fmx_iterate, or after
+ * muxgl_fmx_iter_estep and before the next muxgl_fmx_iter_gp.  It also fails, naming the reason and leaving the handle
+ * usable, with ll_amb, amb_af or rho NULL, with n_rho outside [1, 16], naming the first rho and then the first marker
+ * whose value is not a finite number in [0, 1], and when one cell alone exceeds the budget (naming MUXGL_FMX_SLAB_MB).
+ * It reads state and changes none: records, counters, assignments, cluster pileups, MUXGL_BUF_CGP and whether the other
+ * table calls may run stay as they are; it caches nothing on the handle.  kernel_ms (NULL allowed) receives the hipEvent
+ * time of the call's kernels, from a pair of events the call makes for itself (a group: the slowest member's): no timing
+ * slot of muxgl_get_timing is touched.  With C == 0 the call succeeds and writes nothing; a droplet without entries gets
+ * zeros.  1 <= K <= MUXGL_MAX_CLUSTERS whichever E-step path ran; one device, a device group (every member fills the rows
+ * of its own cells) and a slabbed or sharded handle (the output covers the handle's own cells).
+ * Device memory: nothing proportional to nnz x n_rho is held for the whole pileup.  The cells are swept in batches of
+ * whole cells whose 24 bytes of weights per entry and rho, slab rows and table rows fit the streamed E-step's budget
+ * (4 GiB or a third of the device, MUXGL_FMX_SLAB_MB); each batch is copied out before the next.  The table is
+ * bit-identical from call to call, for any budget, for any split of rho[] over several calls, on one device, on a group
+ * and through the sharded driver. */
+int muxgl_fmx_ambient(muxgl_handle* h, const double* amb_af /* [S] */, int32_t n_rho, const double* rho /* [n_rho] */,
+                      double* ll_amb /* [C][K][n_rho] */, float* kernel_ms /* NULL or one float */);
+
 /* Near-tie calls of the EM iterations since muxgl_fmx_set_clusters.  The kernels' log-likelihoods equal the reference's to
  * ~1e-12, not to the last bit; a cell where a comparison of cmd_cram_freemux2.cpp:469-497,521-584 has a margin within
  * 1e-9 x max(1, |LL|) is therefore not decided by them but listed, and its contested hypotheses are recomputed in the

@@ -722,6 +722,10 @@ const char* fmx_inclusion_refusal(const muxgl_handle* h);  // fmx_incl.hip: the 
 const char* fmx_unknown_refusal(const muxgl_handle* h);    // fmx_unknown.hip: the same for muxgl_fmx_unknown
 // fmx_unknown.hip: the first row of gp0[S][3] that is no probability triple (muxgl_fmx_unknown's rule), or -1
 int64_t fmx_unknown_bad_prior(const double* gp0, int64_t S);
+const char* fmx_ambient_refusal(const muxgl_handle* h);    // fmx_ambient.hip: the same for muxgl_fmx_ambient
+// fmx_ambient.hip: muxgl_fmx_ambient's checks of its arguments, on the host: 0, or 1 with the reason written to `why`
+int fmx_ambient_bad_args(const double* amb_af, int64_t S, int32_t n_rho, const double* rho, double* ll_amb, char* why,
+                         size_t why_len);
 void fmx_wave_streams_release(muxgl_handle* h);  // the linear/general entry streams and their rank table
 int demux_ensure_ll(muxgl_handle* h, const muxgl_demux_params* p);  // standard LL tensor allocated and zeroed
 int demux_call_wave_launch(muxgl_handle* h, const muxgl_demux_params* p);
@@ -792,6 +796,7 @@ int group_fmx_get_cluster_pileup(muxgl_handle* h, double* gls, int32_t* counts);
 int group_fmx_singlets(muxgl_handle* h, double* sng);
 int group_fmx_inclusion(muxgl_handle* h, const muxgl_fmx_params* p, double* incl, double* tot, double* dbl, int32_t* partner);
 int group_fmx_unknown(muxgl_handle* h, const double* gp0, double* ll_ju, double* ll_u, double* ll_uu, float* kernel_ms);
+int group_fmx_ambient(muxgl_handle* h, const double* amb_af, int32_t n_rho, const double* rho, double* ll_amb, float* kernel_ms);
 void group_fmx_exact_stats(const muxgl_handle* h, int64_t* cells, int64_t* changed, int64_t* unresolved);
 void group_peer_stats(const muxgl_handle* h, int32_t* out);
 int group_get_timing(const muxgl_handle* h, float* ms);

@@ -730,6 +730,25 @@ int group_fmx_unknown(muxgl_handle* h, const double* gp0, double* ll_ju, double*
   return 0;
 }
 
+// every member sweeps its own cells and writes their rows of the caller's table; kernel_ms: the slowest member's
+int group_fmx_ambient(muxgl_handle* h, const double* amb_af, int32_t n_rho, const double* rho, double* ll_amb, float* kernel_ms) {
+  muxgl_group* g = h->group;
+  if (!g->have_pileup) MUXGL_FAIL(h, "muxgl_fmx_ambient: no pileup set (muxgl_set_pileup)");
+  if (!g->prepared) MUXGL_FAIL(h, "muxgl_fmx_ambient: call muxgl_fmx_prepare first");
+  for (const muxgl_handle* m : g->m)
+    if (const char* why = fmx_ambient_refusal(m)) MUXGL_FAIL(h, "%s", why);
+  char why[256];  // (once here, so that the group's handle carries the message; the members find nothing)
+  if (fmx_ambient_bad_args(amb_af, g->S, n_rho, rho, ll_amb, why, sizeof(why))) MUXGL_FAIL(h, "%s", why);
+  std::vector<float> ms((size_t)g->n, 0.f);
+  if (for_members(h, [&](int r) {
+        const size_t o = (size_t)g->cb[(size_t)r] * (size_t)g->K * (size_t)n_rho;
+        return muxgl_fmx_ambient(g->m[(size_t)r], amb_af, n_rho, rho, ll_amb + o, kernel_ms ? &ms[(size_t)r] : nullptr);
+      }))
+    return 1;
+  if (kernel_ms) *kernel_ms = *std::max_element(ms.begin(), ms.end());
+  return 0;
+}
+
 // every member folds its own cells and writes their rows of the caller's tables
 int group_fmx_inclusion(muxgl_handle* h, const muxgl_fmx_params* p, double* incl, double* tot, double* dbl, int32_t* partner) {
   muxgl_group* g = h->group;

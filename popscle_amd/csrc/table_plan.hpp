@@ -96,6 +96,14 @@ inline size_t fmx_unknown_bytes(int64_t len, int64_t np, int K) {
   return (size_t)len * 5 * sizeof(double) + (size_t)np * (row_bytes + sizeof(item)) + row_bytes;
 }
 
+// device bytes of a cell in a batch of freemuxlet's ambient call at NR rhos and K clusters: its entries' weights (three per
+// rho, 24 bytes per entry and rho), its slab rows of NR x K doubles (one per part) with their items, and its row of the
+// table with its record
+inline size_t fmx_ambient_bytes(int64_t len, int64_t np, int NR, int K) {
+  const size_t row_bytes = sizeof(double) * (size_t)NR * (size_t)K;
+  return (size_t)len * NR * 3 * sizeof(double) + (size_t)np * (row_bytes + sizeof(item)) + row_bytes + sizeof(cell);
+}
+
 // the items of the batch [c0, c1), and per cell of several parts its cut and/or per cell its record (NULL: not wanted)
 inline void fill(const int64_t* cell_ptr, int64_t c0, int64_t c1, begin_fn begin, std::vector<item>& items,
                  std::vector<cut>* cuts, std::vector<cell>* cells) {

@@ -25,6 +25,7 @@ import time
 import numpy as np
 
 from . import shard
+from .muxgl import ambient_summary as muxgl_ambient_summary
 
 UNIT_CGP, UNIT_CLUST, UNIT_STAT = 0, 1, 2
 
@@ -169,7 +170,8 @@ def settle_near_ties(engs, gather, doublet_prior, geno_error):
 
 def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early_stop=True, exchange=None,
            exchange_tensor=engine_exchange_tensor, log=None, per=None, timings=None, sync=None, stream_ctx=None,
-           want_singlets=False, want_inclusion=False, *, want_unknown=False, anchors=None, anchor_modes=None):
+           want_singlets=False, want_inclusion=False, *, want_unknown=False, anchors=None, anchor_modes=None,
+           want_ambient=None):
     """EM loop of cmd_cram_freemux2.cpp:373-605 on a prepared engine.  One rank: a plain engine holding the whole
     pileup.  Several ranks: an engine holding the rank's slabs (load_rank), `exchange` a TorchExchange and
     per = (cells per rank, SNPs per rank) of the equal-slice plan the slabs were cut by.  clust0 spans the whole job.
@@ -181,7 +183,9 @@ def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early
     tables of the last iteration (Engine.fmx_inclusion, gathered the same way) as the last element:
     (records, stats, [sng,] inclusion).  want_unknown (keyword only): also the dict of the three job-wide tables of
     Engine.fmx_unknown (Hardy-Weinberg prior) of the last iteration, gathered the same way, as the last element;
-    unknown_summary() turns them into per-droplet calls.  anchors (keyword only): a list of columns of the panel the
+    unknown_summary() turns them into per-droplet calls.  want_ambient = (amb_af, rhos) (keyword only): also the job-wide
+    [C][K][n_rho] table of Engine.fmx_ambient of the last iteration, gathered the same way, as the last element;
+    ambient_summary() turns it into per-droplet calls.  anchors (keyword only): a list of columns of the panel the
     engine holds (demux_set_gp); clusters 0 .. len(anchors)-1 are held to those donors' genotypes and the others are
     learned (Engine.fmx_set_anchors, after fmx_set_clusters; anchor_start() makes a clust0 for it).  One engine with the
     whole pileup or a device group only: refused with more than one rank or always=True.  anchor_modes (keyword only,
@@ -289,7 +293,7 @@ def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early
     out = np.zeros(eng.C_total, dtype=cells.dtype)
     for b, e, raw in parts:
         out[b:e] = np.frombuffer(raw, dtype=cells.dtype)
-    if not want_singlets and not want_inclusion and not want_unknown:
+    if not want_singlets and not want_inclusion and not want_unknown and want_ambient is None:
         return out, history
     res = [out, history]
     if want_singlets:
@@ -311,6 +315,12 @@ def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early
             for n, raw in raws.items():
                 unk[n][b:e] = np.frombuffer(raw, dtype=np.float64).reshape((e - b,) + unk[n].shape[1:])
         res.append(unk)
+    if want_ambient is not None:
+        amb_af, rhos = want_ambient
+        amb = np.zeros((eng.C_total, K, len(rhos)), dtype=np.float64)
+        for b, e, raw in ex.gather_objects((c0, c0 + len(cells), eng.fmx_ambient(amb_af, rhos)["ll"].tobytes())):
+            amb[b:e] = np.frombuffer(raw, dtype=np.float64).reshape(e - b, K, len(rhos))
+        res.append(amb)
     return tuple(res)
 
 
@@ -394,6 +404,17 @@ def refine_summary(panel, has_gp, rows):
         return dict(n_geno=n_geno, n_changed=np.zeros(n, dtype=np.int64), mean_max_prior=nan, mean_max_post=nan.copy())
     return dict(n_geno=n_geno, n_changed=(pw.argmax(axis=2) != pr.argmax(axis=2)).sum(axis=0).astype(np.int64),
                 mean_max_prior=pw.max(axis=2).mean(axis=0), mean_max_post=pr.max(axis=2).mean(axis=0))
+
+
+def ambient_summary(ll_amb, rhos):
+    """Per droplet, the best "one cell of cluster j plus a share rho of ambient RNA" reading of the table of
+    Engine.fmx_ambient (ll_amb float64 [C][K][n_rho]): muxgl.ambient_summary as it is, its tie rule included (value first,
+    then (cluster, rho index) ascending), with the cluster fields also under freemuxlet's names: amb_clust = amb_sample,
+    base_clust = base_sample."""
+    out = muxgl_ambient_summary(ll_amb, rhos)
+    out["amb_clust"] = out["amb_sample"]
+    out["base_clust"] = out["base_sample"]
+    return out
 
 
 def unknown_summary(tables, best_llk):

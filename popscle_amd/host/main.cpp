@@ -51,6 +51,14 @@
 //       without cells).  Columns BARCODE, NUM.SNPS, NUM.READS, BEST.LLK (of .clust1.samples.gz), UNK.SNG.LLK (one unknown
 //       donor), UNK.DBL.LLK (two unknown donors), HALF.CLUST and HALF.LLK (the cluster that pairs best with an unknown
 //       donor; ties to the lowest cluster), DIFF.LLK.CLUST.UNK (BEST.LLK minus the largest of the three); LLKs %.4lf
+//       --write-ambient: also <O>.clust1.amb.gz (BGZF), one row per droplet of .clust1.samples.gz: the droplet as ONE cell of
+//       a cluster plus a share rho of ambient RNA, from the last EM iteration (muxgl_fmx_ambient) -- the reading the
+//       reference lacks, which calls a clean singlet from a high-soup prep a doublet of its own cluster with a partner
+//       picked nearly at random.  --ambient-rho, --ambient-af and --ambient-max-reads mean what they mean for demuxlet
+//       (the default grid too; the droplets of --ambient-max-reads are counted by NUM.READS).  Columns BARCODE, NUM.SNPS,
+//       NUM.READS, DROPLET.TYPE, BEST.LLK, SNG.BEST.GUESS, SNG.BEST.LLK (those of .clust1.samples.gz, LLKs %.4lf), AMB.GUESS
+//       (the cluster), AMB.RHO (%.2lf: the best share ON THE GRID), AMB.LLK (ties: the lower cluster, then the lower rho
+//       index), DIFF.LLK.AMB.BEST = AMB.LLK - BEST.LLK.  The calls and every other file are unchanged
 //       --write-cluster-pairs: did the run split one donor over two clusters.  After the EM every pair of final cluster
 //       pileups is scored as one donor against two unrelated donors on the device (muxgl_fmx_cluster_pairs).  Writes
 //       <O>.clust1.ldist.gz (BGZF), one row per pair a > b in ascending (a, b) order: ID1, ID2, NSNP (markers both have
@@ -623,6 +631,10 @@ int cmd_freemuxlet(int argc, char** argv) {
   bool writeSinglets = false;  // (ours) <out>.clust1.sing2.gz: every droplet against every cluster
   bool writeInclusion = false;  // (ours) <out>.clust1.incl.gz: per-cluster marginals of the last E-step's pair triangle
   bool writeUnknown = false;    // (ours) <out>.clust1.unk.gz: every droplet against a donor no cluster holds
+  bool writeAmbient = false;    // (ours) <out>.clust1.amb.gz: every droplet as one cell plus a share of ambient RNA
+  std::vector<double> ambRho;
+  std::string ambAfFile;
+  int32_t ambMaxReads = 0;
   bool writeClusterPairs = false;  // (ours) <out>.clust1.ldist.gz: every pair of final clusters as one donor or two
   VcfReader vr;  // (ours) --match-vcf: genotypes of pooled donors the final clusters are scored against
   std::vector<std::string> smIDs;
@@ -655,6 +667,10 @@ int cmd_freemuxlet(int argc, char** argv) {
   a.add_bool("write-singlets", &writeSinglets);
   a.add_bool("write-inclusion", &writeInclusion);
   a.add_bool("write-unknown", &writeUnknown);
+  a.add_bool("write-ambient", &writeAmbient);
+  a.add_multi_double("ambient-rho", &ambRho);
+  a.add_string("ambient-af", &ambAfFile);
+  a.add_int("ambient-max-reads", &ambMaxReads);
   a.add_bool("write-cluster-pairs", &writeClusterPairs);
   a.add_int("verbose", &verbose);
   a.add_double("doublet-prior", &doublet_prior);
@@ -672,6 +688,9 @@ int cmd_freemuxlet(int argc, char** argv) {
   if (nSamples < 0 || nSamples > MUXGL_MAX_CLUSTERS)
     fatal("freemuxlet: --nsample %d outside [1, %d], the clusters the library supports (MUXGL_MAX_CLUSTERS)", nSamples,
           MUXGL_MAX_CLUSTERS);
+  if (ambRho.empty()) ambRho = {0.0, 0.05, 0.1, 0.15, 0.2, 0.3, 0.4, 0.5};
+  if ((int)ambRho.size() > MUXGL_MAX_ALPHA) fatal("at most %d --ambient-rho values are supported", MUXGL_MAX_ALPHA);
+  if (ambMaxReads < 0) fatal("--ambient-max-reads must not be negative");
   if (wantMatch && wantAnchor)
     fatal("freemuxlet: --match-vcf cannot be combined with --anchor-vcf: an anchored run's match tables (.clust1.match.gz, "
           ".clust1.match.best.gz) are written against the anchor panel");
@@ -1011,6 +1030,68 @@ int cmd_freemuxlet(int argc, char** argv) {
            "-2 in .clust1.unk.gz): a larger --nsample may be meant",
            (long long)nbetter, (long long)C);
     tmr.lap("freemuxlet: write .clust1.unk.gz");
+  }
+  if (writeAmbient) {
+    // .clust1.amb.gz: one row per droplet (the order of .clust1.samples.gz), from the posteriors of the last E-step, like
+    // .clust1.sing2.gz.  The ambient profile: the caller's file, or the pileup's own reads with one pseudo-read at the
+    // population frequency
+    const size_t Kz = (size_t)K, NR = ambRho.size();
+    std::vector<double> f((size_t)S);
+    if (!ambAfFile.empty()) {
+      TsvReader t(ambAfFile);
+      size_t n = 0;
+      for (; t.read_line() > 0; ++n)
+        if (n < (size_t)S) f[n] = t.double_field_at(0);
+      if (n != (size_t)S) fatal("--ambient-af: %s holds %zu lines, the pileup has %zu markers", ambAfFile.c_str(), n, (size_t)S);
+    } else {
+      std::vector<uint8_t> mask;
+      if (ambMaxReads > 0) {
+        mask.resize((size_t)C);
+        int64_t kept = 0;
+        for (int64_t i = 0; i < C; ++i) kept += mask[(size_t)i] = nReads[(size_t)i] <= ambMaxReads;
+        notice("Ambient profile from the %lld of %lld droplets with at most %d reads", (long long)kept, (long long)C, ambMaxReads);
+      }
+      std::vector<int64_t> n_ref((size_t)S), n_alt((size_t)S);
+      check(h, muxgl_pileup_allele_counts(h, mask.empty() ? nullptr : mask.data(), n_ref.data(), n_alt.data()),
+            "muxgl_pileup_allele_counts");
+      for (size_t s = 0; s < (size_t)S; ++s) f[s] = ((double)n_alt[s] + af[s]) / ((double)n_ref[s] + (double)n_alt[s] + 1.0);
+      tmr.lap("freemuxlet: muxgl_pileup_allele_counts");
+    }
+    BigVec<double> amb((size_t)C * Kz * NR);
+    check(h, muxgl_fmx_ambient(h, f.data(), (int32_t)NR, ambRho.data(), amb.data(), nullptr), "muxgl_fmx_ambient");
+    tmr.lap("freemuxlet: muxgl_fmx_ambient");
+    std::vector<size_t> best((size_t)C);
+    parallel_for(C, plp_threads(), [&](int64_t i) {
+      const double* row = amb.data() + (size_t)i * Kz * NR;
+      auto val = [](double v) { return std::isnan(v) ? -INFINITY : v; };
+      size_t at = 0;  // the best (cluster, rho): by value, then (cluster, rho index) ascending
+      for (size_t x = 1; x < Kz * NR; ++x)
+        if (val(row[x]) > val(row[at])) at = x;
+      best[(size_t)i] = at;
+    });
+    int64_t rescued = 0;
+    for (int64_t i = 0; i < C; ++i) {
+      const double v = amb.data()[(size_t)i * Kz * NR + best[(size_t)i]];
+      rescued += cells[(size_t)i].type == 1 && v > cells[(size_t)i].dblBestLLK + 2.0;
+    }
+    OutFile wa(cf.outPrefix + ".clust1.amb.gz", true);
+    wa.printf("BARCODE\tNUM.SNPS\tNUM.READS\tDROPLET.TYPE\tBEST.LLK\tSNG.BEST.GUESS\tSNG.BEST.LLK\tAMB.GUESS\tAMB.RHO\tAMB.LLK\t"
+              "DIFF.LLK.AMB.BEST\n");
+    write_rows_parallel(wa, C, [&](int64_t i, std::string& o) {
+      const muxgl_fmx_cell& c = cells[(size_t)i];
+      const size_t at = best[(size_t)i];
+      const double v = amb.data()[(size_t)i * Kz * NR + at];
+      char num[320];
+      const int n = snprintf(num, sizeof(num), "\t%d\t%d\t%s\t%.4lf\t%d\t%.4lf\t%d\t%.2lf\t%.4lf\t%.4lf\n", nSNPs[(size_t)i],
+                             nReads[(size_t)i], (c.type == 2) ? "AMB" : ((c.type == 0) ? "SNG" : "DBL"), c.bestLLK, c.sBest,
+                             c.sngBestLLK, (int)(at / NR), ambRho[at % NR], v, v - c.bestLLK);
+      o.append(p.bcs[(size_t)i]);
+      o.append(num, (size_t)std::min<int>(n, (int)sizeof(num) - 1));
+    });
+    wa.close();
+    notice("Ambient RNA: %lld droplets called DBL are explained better, by more than 2 in log-likelihood, as one cell plus "
+           "ambient RNA than as their best doublet", (long long)rescued);
+    tmr.lap("freemuxlet: write .clust1.amb.gz");
   }
   if (wantAnchor) {
     // .clust1.anchors.gz: one row per cluster -- the donor it is held to, the greedy cluster it started from with the log
@@ -1569,6 +1650,8 @@ int main(int argc, char** argv) {
                     "  freemuxlet --write-inclusion: also <out>.clust1.incl.gz, per droplet and cluster the evidence that the\n"
                     "    cluster is in the droplet and the cluster it pairs best with, in the last iteration (BARCODE CLUST\n"
                     "    NUM.SNPS NUM.READS LLK.INCL POSTPRB.INCL DBL.PARTNER DBL.LLK)\n"
+                    "  freemuxlet --write-ambient [--ambient-rho x ...] [--ambient-af FILE] [--ambient-max-reads N]: also\n"
+                    "    <out>.clust1.amb.gz, per droplet the best reading as one cell of a cluster plus a share rho of ambient RNA\n"
                     "  freemuxlet --write-unknown: also <out>.clust1.unk.gz, per droplet how well a donor that no cluster holds\n"
                     "    explains it in the last iteration (BARCODE NUM.SNPS NUM.READS BEST.LLK UNK.SNG.LLK UNK.DBL.LLK HALF.CLUST\n"
                     "    HALF.LLK DIFF.LLK.CLUST.UNK); a notice counts the droplets it explains better by more than 2\n");

@@ -117,6 +117,7 @@ SYMBOLS = {
     "muxgl_fmx_singlets": (C.c_int, [_VP, _VP]),
     "muxgl_fmx_inclusion": (C.c_int, [_VP, C.POINTER(_FmxParams), _VP, _VP, _VP, _VP]),
     "muxgl_fmx_unknown": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP]),
+    "muxgl_fmx_ambient": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, _VP]),
     "muxgl_fmx_get_cluster_pileup": (C.c_int, [_VP, _VP, _VP]),
     "muxgl_fmx_match_donors": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
     "muxgl_fmx_cluster_pairs": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
@@ -697,6 +698,21 @@ class Engine:
                                                 C.byref(ms)))
         out["kernel_ms"] = float(ms.value)
         return out
+
+    def fmx_ambient(self, amb_af, rhos):
+        """muxgl_fmx_ambient: every droplet (of the handle's own cells) as one cell of cluster j plus a share rho of
+        ambient RNA whose ALT fraction at marker s is amb_af[s], from the posteriors the last E-step read
+        (include/muxgl.h).  dict of ll float64 [C][K][n_rho], on the scale of the records' log-likelihoods, and
+        kernel_ms, the event time of the call's kernels.  At any K, on every E-step path; ambient_profile() makes amb_af
+        from pileup_allele_counts(), freemuxlet.ambient_summary() turns the table into per-droplet calls."""
+        amb_af = _arr(amb_af, np.float64, "amb_af")
+        if amb_af.shape != (self.S,):
+            raise ValueError("amb_af must be [S]")
+        rhos = _arr(rhos, np.float64, "rhos").reshape(-1)
+        out = np.zeros((self.C, self.K, rhos.size), dtype=np.float64)
+        ms = C.c_float(0.0)
+        self._check(self.lib.muxgl_fmx_ambient(self.h, _ptr(amb_af), rhos.size, _ptr(rhos), _ptr(out), C.byref(ms)))
+        return {"ll": out, "kernel_ms": float(ms.value)}
 
     # ---- freemuxlet-old: pairwise distance matrix and voting passes (cmd_cram_freemuxlet.cpp:176-343)
     def fmxold_pair_dist(self, bf_thres=5.41, want_full=False):
