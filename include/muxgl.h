@@ -317,7 +317,8 @@ int muxgl_pileup_allele_counts(muxgl_handle* h, const uint8_t* cell_mask /* NULL
  *     llksAB[(j, V, n)] on the panel with one donor appended whose row at marker s is one-hot at genotype 2 * amb_af[s];
  *   rho[r] == 0: the column is the table of muxgl_demux_singlets with the same grid;
  *   rho[r] == 1: p is amb_af, the column is the same for every sample ("nothing but soup").
- * The rho reported for a droplet by a caller is the maximum over the grid rho[], not an estimate with an error bar.
+ * The rho reported for a droplet by a caller is the maximum over the grid rho[]; muxgl_demux_ambient_fit (below) gives
+ * the continuous estimate with its observed information.
  * A marker without genotypes contributes a factor of exactly 1 (:733), a droplet without entries gets zeros.  Needs
  * muxgl_set_pileup and muxgl_demux_set_gp, not a previous muxgl_demux_run; any V up to MUXGL_MAX_SAMPLES; 1 <= n_rho <=
  * MUXGL_MAX_ALPHA; every rho and every amb_af[s] of a marker with genotypes finite and in [0, 1] (the values of markers
@@ -335,6 +336,45 @@ int muxgl_pileup_allele_counts(muxgl_handle* h, const uint8_t* cell_mask /* NULL
 int muxgl_demux_ambient(muxgl_handle* h, const muxgl_demux_params* p, const double* amb_af /* [S] */, int32_t n_rho,
                         const double* rho /* [n_rho] */, double* ll_amb /* [C][V][n_rho] */,
                         float* kernel_ms /* NULL or one float */);
+
+/* The ambient share of muxgl_demux_ambient as a per-droplet maximum-likelihood estimate, for n_cand candidate samples per
+ * droplet (cand[c][k] = a sample, or -1 to skip the slot).  With w_e[l](rho) exactly as above (the reference's per-read
+ * term of cmd_cram_demuxlet.cpp:655-725 with p = 0.5 * l + (2 * f - l) * 0.5 * rho of :673, divided by q_max_e of the alpha
+ * grid of p, + 1e-10, / (1 + 1e-10)):
+ *   LL(rho) = sum over the entries e of droplet c whose marker has genotypes of log( sum_l gp[s_e][j][l] * w_e[l](rho) )
+ * Every read's factor is linear in rho, so an entry's product is a polynomial in rho and LL', LL'' are analytic: the
+ * product rule along the reads, no division, no finite difference.  Per (c, k), each array [C][n_cand]:
+ *   rho_hat  the maximiser of LL on [0, rho_max]: LL is taken at the nine points i * rho_max / 8, the best of them (ties
+ *            to the lowest index) with its two neighbours, clipped to [0, rho_max], is the bracket, and rho_hat is the
+ *            maximiser of LL inside the bracket, found by a safeguarded Newton iteration on LL' (the Newton step where
+ *            LL'' < 0 and the step stays strictly inside the bracket, bisection otherwise; the bracket shrinks by the sign
+ *            of LL' at every step; it stops after a Newton step <= 1e-9, or when the bracket or a bisection step is <= 1e-9 -- after
+ *            one last Newton step from there where one is possible -- or after 48 steps);
+ *   ll_hat   LL(rho_hat);   ll_zero  LL(0), the candidate's entry of muxgl_demux_singlets;   info  -LL''(rho_hat);
+ *   status   0 interior and converged; 1 at the lower bound (rho_hat == 0.0 exactly and LL'(0) <= 0); 2 at the upper
+ *            bound (rho_hat == rho_max exactly and LL'(rho_max) >= 0); 3 step cap reached (the values are those of the
+ *            best point evaluated, by LL); 4 slot skipped (cand < 0: all outputs 0); 5 droplet without a scored entry (all outputs 0);
+ *   n_steps  the evaluations of (LL, LL', LL'') after the one at the best coarse point (0 at a bound).
+ * The caller's standard error of rho_hat is info^(-1/2) where status is 0 and info > 0; at status 1 or 2 the estimate
+ * sits on a bound and has NO standard error (info is still -LL'' there, for what it is worth).  The likelihood ratio
+ * against rho = 0 is 2 * (ll_hat - ll_zero).
+ * Needs muxgl_set_pileup and muxgl_demux_set_gp, not a previous muxgl_demux_run; any V up to MUXGL_MAX_SAMPLES; 1 <= n_cand
+ * <= MUXGL_MAX_FIT_CAND; 0 < rho_max <= 1, finite; every cand in [-1, V); amb_af as for muxgl_demux_ambient; any of the six outputs may
+ * be NULL, not all; one device or a device group (every member fits its own cells).  It fails, naming the reason and
+ * leaving the handle usable, without a pileup or a GP tensor, with every output NULL, with cand == NULL, and with n_cand,
+ * n_alpha, rho_max, a candidate or an amb_af out of range or not finite.  kernel_ms (NULL allowed) receives the hipEvent
+ * time of the call's one kernel, from a pair of events the call makes for itself (a group: the slowest member's).  The
+ * call reads state and changes none: records, full_ll, plans, timing slots and the cached grid stay as they are.
+ * Device memory: the inputs, cand and the outputs.  Nothing proportional to nnz is allocated, so no slab budget applies
+ * and MUXGL_DEMUX_SLAB_MB is not read.  The whole fit of a (droplet, candidate) runs in one wave of one launch with every
+ * reduction tree fixed by the droplet alone: the outputs are bit-identical from call to call, for any order, grouping or
+ * repetition of candidates, for any subset of outputs, on one device, on a group and through the sharded driver. */
+#define MUXGL_MAX_FIT_CAND 16 /* candidates per droplet of muxgl_demux_ambient_fit */
+int muxgl_demux_ambient_fit(muxgl_handle* h, const muxgl_demux_params* p, const double* amb_af /* [S] */,
+                            int32_t n_cand, const int32_t* cand /* [C][n_cand], sample or -1 */, double rho_max,
+                            double* rho_hat, double* ll_hat, double* ll_zero, double* info,   /* each [C][n_cand] or NULL */
+                            int32_t* status, int32_t* n_steps,                                /* [C][n_cand] or NULL */
+                            float* kernel_ms);
 
 /* The calls rounding noise could decide, settled in the reference's own arithmetic -- HOST pass, no device work, no
  * handle (popscle_amd/host/exact_calls.hpp).  The kernels' log-likelihoods equal the reference's to ~1e-12, not to the last

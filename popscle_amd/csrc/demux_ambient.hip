@@ -327,18 +327,23 @@ int demux_ambient_bad_rho(int n_rho, const double* rho) {
   return -1;
 }
 
+// the ambient profile: a fraction wherever a marker has genotypes
+int demux_ambient_check_af(muxgl_handle* h, const double* amb_af, const char* who) {
+  const int64_t S = h->S;
+  std::vector<uint8_t> has_gp((size_t)S);
+  if (S > 0) HIPCHK(h, hipMemcpyAsync(has_gp.data(), h->d_has_gp, (size_t)S, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (int64_t s = 0; s < S; ++s)
+    if (has_gp[(size_t)s] && !(std::isfinite(amb_af[s]) && amb_af[s] >= 0.0 && amb_af[s] <= 1.0))
+      MUXGL_FAIL(h, "%s: amb_af of marker %lld (%g) is not a finite number in [0, 1]", who, (long long)s, amb_af[s]);
+  return 0;
+}
+
 int demux_ambient_run(muxgl_handle* h, const muxgl_demux_params* p, const double* amb_af, int NR, const double* rho,
                       double* ll_amb, float* kernel_ms) {
   const int V = h->V, A = p->n_alpha;
   const int64_t C = h->C, S = h->S;
-  {  // the ambient profile: a fraction wherever a marker has genotypes
-    std::vector<uint8_t> has_gp((size_t)S);
-    if (S > 0) HIPCHK(h, hipMemcpyAsync(has_gp.data(), h->d_has_gp, (size_t)S, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (int64_t s = 0; s < S; ++s)
-      if (has_gp[(size_t)s] && !(std::isfinite(amb_af[s]) && amb_af[s] >= 0.0 && amb_af[s] <= 1.0))
-        MUXGL_FAIL(h, "muxgl_demux_ambient: amb_af of marker %lld (%g) is not a finite number in [0, 1]", (long long)s, amb_af[s]);
-  }
+  if (demux_ambient_check_af(h, amb_af, "muxgl_demux_ambient")) return 1;
   std::vector<int64_t> cell_ptr((size_t)C + 1);
   HIPCHK(h, hipMemcpyAsync(cell_ptr.data(), h->d_cell_ptr, sizeof(int64_t) * (size_t)(C + 1), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));

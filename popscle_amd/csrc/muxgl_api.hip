@@ -684,6 +684,24 @@ int muxgl_demux_ambient(muxgl_handle* h, const muxgl_demux_params* p, const doub
   return demux_ambient_run(h, p, amb_af, n_rho, rho, ll_amb, kernel_ms);
 }
 
+int muxgl_demux_ambient_fit(muxgl_handle* h, const muxgl_demux_params* p, const double* amb_af, int32_t n_cand,
+                            const int32_t* cand, double rho_max, double* rho_hat, double* ll_hat, double* ll_zero, double* info,
+                            int32_t* status, int32_t* n_steps, float* kernel_ms) {
+  if (!h) return 1;
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (h->group)
+    return group_demux_ambient_fit(h, p, amb_af, n_cand, cand, rho_max, rho_hat, ll_hat, ll_zero, info, status, n_steps, kernel_ms);
+  HIPCHK(h, hipSetDevice(h->device));
+  if (check_demux_params(h, p)) return 1;
+  char why[256];
+  if (demux_ambient_fit_bad_args(amb_af, n_cand, cand, h->C, h->V, rho_max,
+                                 rho_hat || ll_hat || ll_zero || info || status || n_steps, why, sizeof(why)))
+    MUXGL_FAIL(h, "%s", why);
+  // (no clear_timing, no timing slot: the call reads state and changes none; with no cell there is nothing to fit, but the
+  // profile is still checked)
+  return demux_ambient_fit_run(h, p, amb_af, n_cand, cand, rho_max, rho_hat, ll_hat, ll_zero, info, status, n_steps, kernel_ms);
+}
+
 int muxgl_demux_oct_split(const muxgl_handle* h, int64_t* info) {
   if (!h || !info) return 1;
   if (h->group) {

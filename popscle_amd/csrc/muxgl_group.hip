@@ -366,6 +366,32 @@ int group_demux_ambient(muxgl_handle* h, const muxgl_demux_params* p, const doub
   return 0;
 }
 
+// every member fits its own cells and writes their rows of the caller's arrays; kernel_ms: the slowest member's
+int group_demux_ambient_fit(muxgl_handle* h, const muxgl_demux_params* p, const double* amb_af, int32_t n_cand,
+                            const int32_t* cand, double rho_max, double* rho_hat, double* ll_hat, double* ll_zero, double* info,
+                            int32_t* status, int32_t* n_steps, float* kernel_ms) {
+  muxgl_group* g = h->group;
+  if (!p) MUXGL_FAIL(h, "demux params NULL");
+  if (p->n_alpha < 1 || p->n_alpha > MUXGL_MAX_ALPHA) MUXGL_FAIL(h, "n_alpha=%d outside [1,%d]", p->n_alpha, MUXGL_MAX_ALPHA);
+  if (!g->have_pileup) MUXGL_FAIL(h, "no pileup set (muxgl_set_pileup)");
+  if (g->V < 1) MUXGL_FAIL(h, "no GP tensor set (muxgl_demux_set_gp)");
+  char why[256];
+  if (demux_ambient_fit_bad_args(amb_af, n_cand, cand, g->C, g->V, rho_max,
+                                 rho_hat || ll_hat || ll_zero || info || status || n_steps, why, sizeof(why)))
+    MUXGL_FAIL(h, "%s", why);
+  std::vector<float> ms((size_t)g->n, 0.f);
+  if (for_members(h, [&](int r) {  // (every member checks amb_af against its copy of has_gp)
+        const size_t o = (size_t)g->cb[(size_t)r] * (size_t)n_cand;
+        return muxgl_demux_ambient_fit(g->m[(size_t)r], p, amb_af, n_cand, cand + o, rho_max, rho_hat ? rho_hat + o : nullptr,
+                                       ll_hat ? ll_hat + o : nullptr, ll_zero ? ll_zero + o : nullptr, info ? info + o : nullptr,
+                                       status ? status + o : nullptr, n_steps ? n_steps + o : nullptr,
+                                       kernel_ms ? &ms[(size_t)r] : nullptr);
+      }))
+    return 1;
+  if (kernel_ms) *kernel_ms = *std::max_element(ms.begin(), ms.end());
+  return 0;
+}
+
 // every member counts the reads of its own cells; the counts are added here (integers: exact in any order)
 int group_pileup_allele_counts(muxgl_handle* h, const uint8_t* cell_mask, int64_t* n_ref, int64_t* n_alt) {
   muxgl_group* g = h->group;

@@ -10,14 +10,24 @@ from . import shard
 from .freemuxlet import NoExchange
 
 
+def top_samples(sng, n_top):
+    """int32 [C][n_top]: the n_top best samples of every row of a singlet table [C][V], best first, ties to the lower
+    index"""
+    sng = np.asarray(sng, dtype=np.float64)
+    order = np.argsort(-np.where(np.isnan(sng), -np.inf, sng), axis=1, kind="stable")
+    return np.ascontiguousarray(order[:, :n_top], dtype=np.int32)
+
+
 def run_sharded(engine_factory, p, alphas=(0.0, 0.5), doublet_prior=0.5, exchange=None, want_singlets=False,
-                want_inclusion=False, *, want_unknown=False, want_ambient=None):
+                want_inclusion=False, *, want_unknown=False, want_ambient=None, want_ambient_fit=None):
     """engine_factory() -> object with set_pileup / demux_set_gp / demux_run (muxgl.Engine).  Returns the [C] records of
     the whole pileup on every rank, in the original cell order; with want_singlets also the [C][V] table of singlet
     log-likelihoods (Engine.demux_singlets), gathered the same way: (records, sng); with want_inclusion also the dict of
     per-droplet, per-sample inclusion tables (Engine.demux_inclusion): (records, [sng,] inclusion); with want_unknown
     (keyword only) also the dict of the three tables of Engine.demux_unknown (panel mean); with want_ambient = (amb_af,
-    rhos) (keyword only) also the [C][V][n_rho] table of Engine.demux_ambient, as the last element.
+    rhos) (keyword only) also the [C][V][n_rho] table of Engine.demux_ambient; with want_ambient_fit = (amb_af, rho_max,
+    n_top) (keyword only) also the dict of Engine.demux_ambient_fit for the n_top best samples of every droplet's row of the
+    singlet table (ties to the lower index) with those candidates under "cand" ([C][n_top]), as the last element.
     Cells are independent, so every rank fills the rows of its own cells."""
     ex = exchange or NoExchange()
     ranges = shard.cell_shards(p.cell_ptr, ex.world)
@@ -31,7 +41,7 @@ def run_sharded(engine_factory, p, alphas=(0.0, 0.5), doublet_prior=0.5, exchang
     out = np.zeros(p.C, dtype=cells.dtype)
     for b, e, raw in parts:
         out[b:e] = np.frombuffer(raw, dtype=cells.dtype)
-    if not want_singlets and not want_inclusion and not want_unknown and want_ambient is None:
+    if not want_singlets and not want_inclusion and not want_unknown and want_ambient is None and want_ambient_fit is None:
         return out
     ret = [out]
     V = p.gp.shape[1]
@@ -60,4 +70,15 @@ def run_sharded(engine_factory, p, alphas=(0.0, 0.5), doublet_prior=0.5, exchang
         for b, e, raw in ex.gather_objects((c0, c1, eng.demux_ambient(alphas, amb_af, rhos)["ll"].tobytes())):
             amb[b:e] = np.frombuffer(raw, dtype=np.float64).reshape(e - b, V, len(rhos))
         ret.append(amb)
+    if want_ambient_fit is not None:
+        amb_af, rho_max, n_top = want_ambient_fit
+        n_top = min(int(n_top), V)
+        cand = top_samples(eng.demux_singlets(alphas), n_top)
+        mine = {k: v for k, v in eng.demux_ambient_fit(alphas, amb_af, cand, rho_max).items() if k != "kernel_ms"}
+        mine["cand"] = cand
+        fit = {k: np.zeros((p.C, n_top), dtype=v.dtype) for k, v in mine.items()}
+        for b, e, raw in ex.gather_objects((c0, c1, {k: v.tobytes() for k, v in mine.items()})):
+            for k, v in fit.items():
+                v[b:e] = np.frombuffer(raw[k], dtype=v.dtype).reshape(e - b, n_top)
+        ret.append(fit)
     return tuple(ret)

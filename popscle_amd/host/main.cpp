@@ -29,9 +29,15 @@
 //       of the loaded droplets by marker and allele (muxgl_pileup_allele_counts; --ambient-max-reads N: of the droplets
 //       with at most N reads only, 0 = all) with one pseudo-read at the AF column of .var.gz, (n_alt + AF) / (n_ref + n_alt
 //       + 1).  Columns BARCODE, NUM.SNPS, NUM.READS, DROPLET.TYPE, BEST.LLK, SNG.BEST.GUESS, SNG.BEST.LLK (those of .best,
-//       LLKs %.4lf), AMB.GUESS (the sample), AMB.RHO (%.2lf: the best share ON THE GRID, no estimate with an error bar),
+//       LLKs %.4lf), AMB.GUESS (the sample), AMB.RHO (%.2lf: the best share ON THE GRID; --fit-ambient estimates it),
 //       AMB.LLK (ties: the lower sample, then the lower rho index), DIFF.LLK.AMB.BEST = AMB.LLK - BEST.LLK.  The calls of
 //       .best and every other file are unchanged
+//       --fit-ambient: also <O>.ambfit.gz (BGZF), per printed droplet one row for SNG.BEST.GUESS and one for SNG.NEXT.GUESS
+//       of .best: the maximum-likelihood share of ambient RNA on [0, --ambient-fit-max x] (default 0.5) under the model of
+//       --write-ambient, with the profile of --ambient-af / --ambient-max-reads (muxgl_demux_ambient_fit).  Columns BARCODE,
+//       NUM.SNPS, NUM.READS, SM_ID, SNG.LLK (the sample's singlet LLK), AMB.RHO.MLE, AMB.RHO.SE (the standard error from the
+//       observed information; NA on a bound or where the information is not positive), AMB.LLK.MLE, AMB.LRT = 2 (AMB.LLK.MLE -
+//       SNG.LLK), STATUS (0 interior, 1 lower bound, 2 upper bound, 3 step cap, 5 no scored marker); all %.4lf
 //   popscle-amd freemuxlet --plp P --nsample K --out O [...]                   mirrors cmdCramFreemux2 (cmd_cram_freemux2.cpp)
 //       --write-singlets: also <O>.clust1.sing2.gz (BGZF), the singlet log-likelihood of every droplet against every
 //       cluster as the last EM iteration formed it (llks[j(j+1)/2 + j], cmd_cram_freemux2.cpp:448-455; the reference
@@ -196,6 +202,8 @@ int cmd_demuxlet(int argc, char** argv) {
   bool writeInclusion = false;  // (ours) <out>.incl.gz: per-sample marginals of the disabled .pair writer (:852-877)
   bool writeUnknown = false;  // (ours) <out>.unk.gz: the droplet against a donor missing from the VCF (llksA0 / llks00, :749-773)
   bool writeAmbient = false;  // (ours) <out>.amb.gz: the droplet as one cell plus a share of ambient RNA (muxgl_demux_ambient)
+  bool fitAmbient = false;  // (ours) <out>.ambfit.gz: the maximum-likelihood ambient share with its standard error (muxgl_demux_ambient_fit)
+  double ambFitMax = 0.5;
   std::vector<double> ambRho;
   std::string ambAfFile;
   int32_t ambMaxReads = 0;
@@ -203,6 +211,8 @@ int cmd_demuxlet(int argc, char** argv) {
   cf.add(a);
   a.add_bool("write-unknown", &writeUnknown);
   a.add_bool("write-ambient", &writeAmbient);
+  a.add_bool("fit-ambient", &fitAmbient);
+  a.add_double("ambient-fit-max", &ambFitMax);
   a.add_multi_double("ambient-rho", &ambRho);
   a.add_string("ambient-af", &ambAfFile);
   a.add_int("ambient-max-reads", &ambMaxReads);
@@ -239,6 +249,7 @@ int cmd_demuxlet(int argc, char** argv) {
   if (ambRho.empty()) ambRho = {0.0, 0.05, 0.1, 0.15, 0.2, 0.3, 0.4, 0.5};
   if ((int)ambRho.size() > MUXGL_MAX_ALPHA) fatal("at most %d --ambient-rho values are supported", MUXGL_MAX_ALPHA);
   if (ambMaxReads < 0) fatal("--ambient-max-reads must not be negative");
+  if (!(std::isfinite(ambFitMax) && ambFitMax > 0.0 && ambFitMax <= 1.0)) fatal("--ambient-fit-max must lie in (0, 1]");
   vr.wanted = smIDs;
   if (!smList.empty()) {
     TsvReader t(smList);
@@ -410,11 +421,14 @@ int cmd_demuxlet(int argc, char** argv) {
     wu.close();
     tm.lap("demuxlet: write .unk.gz");
   }
-  if (writeAmbient) {
-    // .amb.gz: one row per printed droplet (the order and the filters of .best).  The ambient profile: the caller's file,
-    // or the pileup's own reads with one pseudo-read at the population frequency
-    const size_t V = (size_t)p.nv, NR = ambRho.size(), S = (size_t)p.S();
-    std::vector<double> f(S);
+  // The ambient profile of --write-ambient and --fit-ambient: the caller's file, or the pileup's own reads with one
+  // pseudo-read at the population frequency; made once
+  std::vector<double> ambProfile;
+  auto ambient_profile = [&]() -> const std::vector<double>& {
+    const size_t S = (size_t)p.S();
+    std::vector<double>& f = ambProfile;
+    if (!f.empty() || S == 0) return f;
+    f.resize(S);
     if (!ambAfFile.empty()) {
       TsvReader t(ambAfFile);
       size_t n = 0;
@@ -436,6 +450,12 @@ int cmd_demuxlet(int argc, char** argv) {
         f[s] = ((double)n_alt[s] + p.snps[s].af) / ((double)n_ref[s] + (double)n_alt[s] + 1.0);
       tm.lap("demuxlet: muxgl_pileup_allele_counts");
     }
+    return f;
+  };
+  if (writeAmbient) {
+    // .amb.gz: one row per printed droplet (the order and the filters of .best)
+    const size_t V = (size_t)p.nv, NR = ambRho.size();
+    const std::vector<double>& f = ambient_profile();
     std::vector<double> amb((size_t)p.C() * V * NR);
     check(h, muxgl_demux_ambient(h, &dp, f.data(), (int32_t)NR, ambRho.data(), amb.data(), nullptr), "muxgl_demux_ambient");
     tm.lap("demuxlet: muxgl_demux_ambient");
@@ -462,6 +482,43 @@ int cmd_demuxlet(int argc, char** argv) {
     notice("Ambient RNA: %lld droplets called DBL are explained better, by more than 2 in log-likelihood, as one cell plus "
            "ambient RNA than as their best doublet", (long long)rescued);
     tm.lap("demuxlet: write .amb.gz");
+  }
+  if (fitAmbient) {
+    // .ambfit.gz: per printed droplet (the order and the filters of .best) one row for SNG.BEST.GUESS and one for
+    // SNG.NEXT.GUESS (none where .best has NA there)
+    const std::vector<double>& f = ambient_profile();
+    const size_t n = (size_t)p.C() * 2;
+    std::vector<int32_t> cand(n), status(n);
+    for (int64_t i = 0; i < p.C(); ++i) {
+      const muxgl_demux_cell& c = cells[(size_t)i];
+      cand[(size_t)i * 2] = (c.valid && c.sBest >= 0 && c.sBest < p.nv) ? c.sBest : -1;
+      cand[(size_t)i * 2 + 1] = (c.valid && c.sNext >= 0 && c.sNext < p.nv) ? c.sNext : -1;
+    }
+    std::vector<double> rho(n), llh(n), ll0(n), info(n);
+    check(h, muxgl_demux_ambient_fit(h, &dp, f.data(), 2, cand.data(), ambFitMax, rho.data(), llh.data(), ll0.data(), info.data(),
+                                     status.data(), nullptr, nullptr),
+          "muxgl_demux_ambient_fit");
+    tm.lap("demuxlet: muxgl_demux_ambient_fit");
+    OutFile wf(cf.outPrefix + ".ambfit.gz", true);
+    wf.printf("BARCODE\tNUM.SNPS\tNUM.READS\tSM_ID\tSNG.LLK\tAMB.RHO.MLE\tAMB.RHO.SE\tAMB.LLK.MLE\tAMB.LRT\tSTATUS\n");
+    for (auto it = bc_map.begin(); it != bc_map.end(); ++it) {
+      const int32_t i = it->second;
+      const muxgl_demux_cell& c = cells[(size_t)i];
+      if (p.cell_totl_reads[(size_t)i] < cf.lo.minRead || p.cell_uniq_reads[(size_t)i] < cf.lo.minUMI ||
+          c.nsnps < cf.lo.minSNP || !c.valid)
+        continue;
+      for (size_t k = 0; k < 2; ++k) {
+        const size_t x = (size_t)i * 2 + k;
+        if (cand[x] < 0) continue;
+        wf.printf("%s\t%u\t%d\t%s\t%.4lf\t%.4lf\t", it->first.c_str(), (unsigned)c.nsnps, p.cell_uniq_reads[(size_t)i],
+                  sid(p, cand[x]), ll0[x], rho[x]);
+        if (status[x] == 0 && info[x] > 0.0) wf.printf("%.4lf", 1.0 / sqrt(info[x]));  // (on a bound: no standard error)
+        else wf.printf("NA");
+        wf.printf("\t%.4lf\t%.4lf\t%d\n", llh[x], 2.0 * (llh[x] - ll0[x]), (int)status[x]);
+      }
+    }
+    wf.close();
+    tm.lap("demuxlet: write .ambfit.gz");
   }
   notice("Finished writing output files");
   muxgl_destroy(h);
@@ -1650,6 +1707,9 @@ int main(int argc, char** argv) {
                     "  freemuxlet --write-inclusion: also <out>.clust1.incl.gz, per droplet and cluster the evidence that the\n"
                     "    cluster is in the droplet and the cluster it pairs best with, in the last iteration (BARCODE CLUST\n"
                     "    NUM.SNPS NUM.READS LLK.INCL POSTPRB.INCL DBL.PARTNER DBL.LLK)\n"
+                    "  demuxlet --fit-ambient [--ambient-fit-max x] [--ambient-af FILE] [--ambient-max-reads N]: also <out>.ambfit.gz,\n"
+                    "      per printed droplet and for its best and next singlet sample the maximum-likelihood ambient share on\n"
+                    "      [0, x] (default 0.5) with its standard error and the likelihood ratio against no ambient RNA\n"
                     "  freemuxlet --write-ambient [--ambient-rho x ...] [--ambient-af FILE] [--ambient-max-reads N]: also\n"
                     "    <out>.clust1.amb.gz, per droplet the best reading as one cell of a cluster plus a share rho of ambient RNA\n"
                     "  freemuxlet --write-unknown: also <out>.clust1.unk.gz, per droplet how well a donor that no cluster holds\n"

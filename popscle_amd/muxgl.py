@@ -99,6 +99,8 @@ SYMBOLS = {
     "muxgl_demux_unknown": (C.c_int, [_VP, C.POINTER(_DemuxParams), _VP, _VP, _VP, _VP, _VP]),
     "muxgl_demux_ambient": (C.c_int, [_VP, C.POINTER(_DemuxParams), _VP, C.c_int32, _VP, _VP, _VP]),
     "muxgl_pileup_allele_counts": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "muxgl_demux_ambient_fit": (C.c_int, [_VP, C.POINTER(_DemuxParams), _VP, C.c_int32, _VP, C.c_double,
+                                          _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "muxgl_demux_results": (_VP, [_VP]),
     "muxgl_demux_oct_split": (C.c_int, [_VP, _VP]),
     "muxgl_demux_exact_calls": (C.c_int, [C.c_int64, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP,
@@ -273,8 +275,8 @@ def ambient_summary(ll, rhos):
     Engine.demux_ambient (ll float64 [C][V][n_rho]).  Pure numpy.  Returns a dict of [C] arrays: amb_llk, amb_sample,
     amb_rho_idx, amb_rho: the maximum over (sample, rho index), ties decided by value descending, then (sample, rho index)
     ascending; base_llk, base_sample: the maximum at the smallest rho (the first of them on ties) alone, for comparison --
-    the singlet call where that rho is 0.  The rho of a droplet is the best point of the grid `rhos`, not an estimate
-    with an error bar."""
+    the singlet call where that rho is 0.  The rho of a droplet is the best point of the grid `rhos`;
+    Engine.demux_ambient_fit estimates it."""
     ll = np.asarray(ll, dtype=np.float64)
     rh = np.asarray(rhos, dtype=np.float64)
     if ll.ndim != 3 or rh.ndim != 1 or ll.shape[2] != rh.size or rh.size < 1 or ll.shape[1] < 1:
@@ -289,6 +291,20 @@ def ambient_summary(ll, rhos):
     bs = np.argmax(base, axis=1)
     return {"amb_llk": flat[ar, b], "amb_sample": (b // NR).astype(np.int32), "amb_rho_idx": (b % NR).astype(np.int32),
             "amb_rho": rh[b % NR] if Cn else np.zeros(0), "base_llk": base[ar, bs], "base_sample": bs.astype(np.int32)}
+
+
+def ambient_fit_summary(fit):
+    """What a caller reads off the dict of Engine.demux_ambient_fit.  Pure numpy.  Returns a dict of arrays of the shape of
+    fit["rho_hat"]: se, the standard error info ** -0.5 of rho_hat where status is 0 and info > 0 and NaN elsewhere (an
+    estimate on a bound, status 1 or 2, has no standard error), and lrt, the likelihood ratio 2 * (ll_hat - ll_zero)
+    against rho = 0 (0 where the slot was skipped or the droplet has no scored entry)."""
+    info = np.asarray(fit["info"], dtype=np.float64)
+    status = np.asarray(fit["status"])
+    ok = (status == 0) & (info > 0.0)
+    se = np.full(info.shape, np.nan)
+    se[ok] = 1.0 / np.sqrt(info[ok])
+    lrt = 2.0 * (np.asarray(fit["ll_hat"], dtype=np.float64) - np.asarray(fit["ll_zero"], dtype=np.float64))
+    return {"se": se, "lrt": lrt}
 
 
 def _ptr(a):
@@ -518,6 +534,44 @@ class Engine:
         self._check(self.lib.muxgl_demux_ambient(self.h, C.byref(p), _ptr(amb_af), rhos.size, _ptr(rhos), _ptr(out),
                                                   C.byref(ms)))
         return {"ll": out, "kernel_ms": float(ms.value)}
+
+    AMBIENT_FIT_FIELDS = ("rho_hat", "ll_hat", "ll_zero", "info", "status", "n_steps")
+
+    def demux_ambient_fit(self, params, amb_af, cand, rho_max=0.5, want=AMBIENT_FIT_FIELDS):
+        """muxgl_demux_ambient_fit: per droplet and candidate sample, the maximum-likelihood ambient share on [0, rho_max]
+        under the model of demux_ambient, with its observed information (include/muxgl.h).  params: the alpha grid (a
+        sequence of alphas); cand: int32 [C][n_cand] (or [C]), a sample or -1 per slot.  dict of rho_hat, ll_hat, ll_zero,
+        info float64 [C][n_cand], status, n_steps int32 [C][n_cand], and kernel_ms.  want: the subset of the six to fetch
+        (the others are passed as NULL).  ambient_fit_summary() gives the standard error and the likelihood ratio."""
+        alphas = params
+        if len(alphas) > MAX_ALPHA:
+            raise ValueError("too many alphas")
+        unknown = set(want) - set(self.AMBIENT_FIT_FIELDS)
+        if unknown:
+            raise ValueError(f"unknown fields {sorted(unknown)}")
+        p = _DemuxParams()
+        p.n_alpha = len(alphas)
+        for i, a in enumerate(alphas):
+            p.alpha[i] = float(a)
+        p.doublet_prior = 0.5  # (not read by the call)
+        amb_af = _arr(amb_af, np.float64, "amb_af")
+        if amb_af.shape != (self.S,):
+            raise ValueError("amb_af must be [S]")
+        cand = _arr(cand, np.int32, "cand")
+        if cand.ndim == 1:
+            cand = cand.reshape(-1, 1)
+        if cand.ndim != 2 or cand.shape[0] != self.C:
+            raise ValueError("cand must be [C][n_cand]")
+        out = {}
+        for name in self.AMBIENT_FIT_FIELDS:
+            if name in want:
+                out[name] = np.zeros(cand.shape, dtype=np.int32 if name in ("status", "n_steps") else np.float64)
+        ms = C.c_float(0.0)
+        self._check(self.lib.muxgl_demux_ambient_fit(self.h, C.byref(p), _ptr(amb_af), cand.shape[1], _ptr(cand),
+                                                      float(rho_max), *[_ptr(out.get(n)) for n in self.AMBIENT_FIT_FIELDS],
+                                                      C.byref(ms)))
+        out["kernel_ms"] = float(ms.value)
+        return out
 
     def pileup_allele_counts(self, mask=None):
         """muxgl_pileup_allele_counts: (n_ref, n_alt), int64 [S] each, the usable reads of the droplets whose mask entry is

@@ -1,0 +1,83 @@
+"""`popscle-amd demuxlet --fit-ambient` on a small synthetic pileup: <out>.ambfit.gz has, per row of .best and in its order,
+one row for SNG.BEST.GUESS and one for SNG.NEXT.GUESS; the rows are Engine.demux_ambient_fit with the same profile and
+candidates through the format strings; --ambient-fit-max sets the upper bound; and the flag changes nothing else: .best and
+.amb.gz are the same bytes with and without it, and there is no .ambfit.gz without it."""
+import gzip
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from popscle_amd import muxgl, plpio, synth
+from test_cli_gpu import BIN, as_pileup
+
+pytestmark = pytest.mark.gpu
+
+HEADER = "BARCODE\tNUM.SNPS\tNUM.READS\tSM_ID\tSNG.LLK\tAMB.RHO.MLE\tAMB.RHO.SE\tAMB.LLK.MLE\tAMB.LRT\tSTATUS"
+
+
+def run(cmd):
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr
+    return r.stderr
+
+
+def expected_rows(best_rows, index, ids, fit, cand):
+    sm = muxgl.ambient_fit_summary(fit)
+    rows = []
+    for brow in best_rows:
+        i = index[brow[1]]
+        assert [ids[int(c)] for c in cand[i]] == [brow[12], brow[14]]          # SNG.BEST.GUESS, SNG.NEXT.GUESS of .best
+        for k in range(2):
+            se = "NA" if np.isnan(sm["se"][i, k]) else "%.4f" % sm["se"][i, k]
+            rows.append("\t".join(brow[1:4] + [ids[int(cand[i, k])], "%.4f" % fit["ll_zero"][i, k], "%.4f" % fit["rho_hat"][i, k], se,
+                                               "%.4f" % fit["ll_hat"][i, k], "%.4f" % sm["lrt"][i, k], "%d" % fit["status"][i, k]]))
+    return rows
+
+
+@pytest.mark.parametrize("devices", [None, "0,0"])
+def test_demuxlet_cli_fit_ambient(tmp_path, devices):
+    import pyplp
+
+    V, S = 8, 1200
+    p = synth.make_pileup(60, S, V, seed=5, mean_entries=150, min_entries=20, doublet_frac=0.3, reads_lambda=1.0)
+    prefix = str(tmp_path / "plp")
+    plpio.write_plp(prefix, p, seed=5, extra_cells=1)
+    vcf = str(tmp_path / "g.vcf.gz")
+    plpio.write_vcf(vcf, p, p.truth["G"].astype(np.int64), field="GT", missing_frac=0.02, drop_snps=range(0, S, 37))
+    alphas = (0.0, 0.25, 0.5)
+    base = ([BIN, "demuxlet", "--plp", prefix, "--vcf", vcf, "--field", "GT"] + [x for a in alphas for x in ("--alpha", str(a))]
+            + (["--devices", devices] if devices else []))
+    plain, out, both, capped = (str(tmp_path / n) for n in ("plain", "out", "both", "capped"))
+    run(base + ["--out", plain, "--write-ambient"])
+    run(base + ["--out", out, "--fit-ambient"])
+    run(base + ["--out", both, "--write-ambient", "--fit-ambient"])
+    run(base + ["--out", capped, "--fit-ambient", "--ambient-fit-max", "0.0625"])
+    best = open(plain + ".best", "rb").read()
+    assert not os.path.exists(plain + ".ambfit.gz") and not os.path.exists(out + ".amb.gz")
+    assert best == open(out + ".best", "rb").read() == open(both + ".best", "rb").read() == open(capped + ".best", "rb").read()
+    assert gzip.open(plain + ".amb.gz", "rb").read() == gzip.open(both + ".amb.gz", "rb").read()
+    assert open(plain + ".amb.gz", "rb").read() == open(both + ".amb.gz", "rb").read()
+    got = gzip.open(out + ".ambfit.gz", "rt").read().splitlines()
+    assert got == gzip.open(both + ".ambfit.gz", "rt").read().splitlines()
+
+    d = pyplp.load(prefix, vcf=vcf, field="GT")
+    q = as_pileup(d)
+    ids = [f"S{v}" for v in range(V)]
+    best_rows = [ln.split("\t") for ln in best.decode().splitlines()[1:]]
+    index = {bc: i for i, bc in enumerate(d["bcs"])}
+    with muxgl.Engine(0) as e:
+        e.set_pileup(q.S, q.cell_ptr, q.entry_snp, q.entry_rptr, q.reads)
+        e.demux_set_gp(q.gp, q.has_gp)
+        rec = e.demux_run(alphas, 0.5)
+        cand = np.stack([rec["sBest"], rec["sNext"]], axis=1).astype(np.int32)
+        cand[(rec["valid"] == 0)[:, None] | (cand < 0) | (cand >= V)] = -1      # (no row is printed for those)
+        f = muxgl.ambient_profile(*e.pileup_allele_counts(), q.af)
+        fit = e.demux_ambient_fit(alphas, f, cand, 0.5)
+        fit_capped = e.demux_ambient_fit(alphas, f, cand, 0.0625)
+    assert got[0] == HEADER and len(best_rows) > 0
+    assert got[1:] == expected_rows(best_rows, index, ids, fit, cand)
+    capped_rows = gzip.open(capped + ".ambfit.gz", "rt").read().splitlines()
+    assert capped_rows[1:] == expected_rows(best_rows, index, ids, fit_capped, cand)
+    assert (fit_capped["rho_hat"] <= 0.0625).all() and (fit_capped["status"] == 2).any() and "NA" in {r.split("\t")[6] for r in capped_rows[1:]}
