@@ -656,7 +656,8 @@ int muxgl_fmx_unknown(muxgl_handle* h, const double* gp0 /* NULL or [S][3] */,
  *     at genotype 2 * amb_af[s];
  *   rho[r] == 0: w_e[r][l] = gls[4 l], the column is the table of muxgl_fmx_singlets;
  *   rho[r] == 1: p is amb_af, the column is the same for every cluster (up to the rounding of q's row sums).
- * The rho reported for a droplet by a caller is the maximum over the grid rho[], not an estimate with an error bar.
+ * The rho reported for a droplet by a caller is the maximum over the grid rho[]; muxgl_fmx_ambient_fit (below) gives the
+ * continuous estimate with its observed information.
  * State rules and refusals are muxgl_fmx_unknown's under this call's name: call it after muxgl_fmx_iterate, or after
  * muxgl_fmx_iter_estep and before the next muxgl_fmx_iter_gp.  It also fails, naming the reason and leaving the handle
  * usable, with ll_amb, amb_af or rho NULL, with n_rho outside [1, 16], naming the first rho and then the first marker
@@ -674,6 +675,48 @@ int muxgl_fmx_unknown(muxgl_handle* h, const double* gp0 /* NULL or [S][3] */,
  * and through the sharded driver. */
 int muxgl_fmx_ambient(muxgl_handle* h, const double* amb_af /* [S] */, int32_t n_rho, const double* rho /* [n_rho] */,
                       double* ll_amb /* [C][K][n_rho] */, float* kernel_ms /* NULL or one float */);
+
+/* The ambient share of muxgl_fmx_ambient as a per-droplet maximum-likelihood estimate, for n_cand candidate clusters per
+ * droplet (cand[c][k] = a cluster, or -1 to skip the slot): the counterpart of muxgl_demux_ambient_fit.  The model is
+ * muxgl_fmx_ambient's, unchanged; with a[l](rho), T and q exactly as above,
+ *   LL(rho) = sum over ALL entries e of droplet c of log( q[s_e][j][0] * w_e[0] + q[s_e][j][1] * w_e[1] + q[s_e][j][2] * w_e[2] ),
+ *   w_e[l] = max(a[l](rho), 1e-6) / T.
+ * Every read's ambient factor is linear in rho with slope v = +-mat * (2 * f - l) * 0.5 (+ for an ALT read), so a[l] is a
+ * polynomial in rho and its derivatives follow from the product rule along the reads (a'' = a'' * fac + 2 * a' * v; a' =
+ * a' * fac + a * v; a = a * fac; all three divided by the read's t).  The 1e-6 floor makes LL piecewise: where a[l] < 1e-6
+ * the element is the constant 1e-6 and its derivatives are 0 -- the derivative of the floored function on that piece.  LL
+ * is continuous; where an element crosses the floor LL' jumps, always upward (max(a, 1e-6) is convex in a), so a maximum of
+ * LL never sits on such a kink and the search, which narrows its bracket by the sign of LL' alone, closes on a smooth zero
+ * of LL'.  An upward jump can also start a second rise of LL inside the bracket of the coarse points; therefore, where an
+ * element is below the floor at one of the bracket's three coarse points and not at another, LL is first taken on the 65
+ * points lo + (hi - lo) * i / 64 of that bracket and the best of them (ties to the lowest index) with its two neighbours
+ * becomes the bracket; status 1 / 2 then need that point to be 0 / rho_max.  Per (c, k), each array [C][n_cand]: rho_hat, ll_hat, ll_zero (the candidate's entry of muxgl_fmx_singlets),
+ * info, status and n_steps mean what they mean for muxgl_demux_ambient_fit, found by the same search (the nine coarse
+ * points i * rho_max / 8, the bracket around the best, the bound tests, the safeguarded Newton iteration on LL' with the
+ * stops 1e-9, one last Newton step, 48 steps), with the statuses
+ *   0 interior and converged; 1 at the lower bound; 2 at the upper bound; 3 step cap reached; 4 slot skipped (cand < 0: all
+ *   outputs 0); 5 droplet without entries (all outputs 0); 6 LL at a coarse point is not finite -- a posterior row of
+ *   exactly 0 at one of the droplet's markers makes a factor 0: rho_hat = 0, ll_hat = ll_zero = -inf, info = 0, n_steps = 0;
+ *   no NaN is written.
+ * The standard error of rho_hat is info^(-1/2) where status is 0 and info > 0; on a bound there is none.  The likelihood
+ * ratio against rho = 0 is 2 * (ll_hat - ll_zero).
+ * State rules are muxgl_fmx_ambient's under this call's name: call it after muxgl_fmx_iterate, or after
+ * muxgl_fmx_iter_estep and before the next muxgl_fmx_iter_gp.  1 <= n_cand <= MUXGL_MAX_FIT_CAND; 0 < rho_max <= 1, finite;
+ * every cand in [-1, K); every amb_af[s] a finite number in [0, 1]; any of the six outputs may be NULL, not all.  Every
+ * refusal names its reason and leaves the handle usable.  Any K up to MUXGL_MAX_CLUSTERS on every E-step path, with
+ * anchors held or as priors; one device, a device group (every member fits its own cells) and a slabbed or sharded handle
+ * (the outputs cover the handle's own cells).  With C == 0 the call succeeds and writes nothing.  It reads state and
+ * changes none and touches no timing slot; kernel_ms (NULL allowed) receives the hipEvent time of the call's one kernel
+ * from events of its own (a group: the slowest member's).
+ * Device memory: the inputs, cand and the outputs.  The entry likelihoods are recomputed on every pass; nothing
+ * proportional to nnz is allocated, so no slab budget applies and MUXGL_FMX_SLAB_MB is not read.  The whole fit of a
+ * (droplet, candidate) runs in one wave of one launch with every reduction tree fixed by the droplet alone: the outputs
+ * are bit-identical from call to call, for any order, grouping or repetition of candidates, for any subset of outputs, on
+ * one device, on a group and through the sharded driver. */
+int muxgl_fmx_ambient_fit(muxgl_handle* h, const double* amb_af /* [S] */, int32_t n_cand,
+                          const int32_t* cand /* [C][n_cand], cluster or -1 */, double rho_max,
+                          double* rho_hat, double* ll_hat, double* ll_zero, double* info, /* [C][n_cand] or NULL */
+                          int32_t* status, int32_t* n_steps, float* kernel_ms);
 
 /* Near-tie calls of the EM iterations since muxgl_fmx_set_clusters.  The kernels' log-likelihoods equal the reference's to
  * ~1e-12, not to the last bit; a cell where a comparison of cmd_cram_freemux2.cpp:469-497,521-584 has a margin within

@@ -1,0 +1,290 @@
+// ambient_fit_search.hpp -- the search of the two ambient fits, muxgl_demux_ambient_fit (demux_ambient_fit.hip)
+// and muxgl_fmx_ambient_fit (fmx_ambient_fit.hip): one wave maximises LL(rho) on [0, rho_max] for one
+// (droplet, candidate).  The model is the caller's: two callables that return, in every lane the same bits,
+//   coarse(x[3], o[3])   o[k] = LL(x[k]) for k < NC
+//   deriv(x, L, d1, d2)  (LL, LL', LL'') at x
+// so every decision below is wave-uniform.  The rules:
+//   * LL on the nine coarse points i rho_max / 8, NC per pass; the best point, ties to the lowest index; the bracket is its
+//     two neighbours, clipped to [0, rho_max];
+//   * (LL, LL', LL'') at the best point x.  LL'(x) <= 0 at x = 0 is the lower bound (status 1), LL'(x) >= 0 at x = rho_max the
+//     upper (status 2); otherwise the sign of LL'(x) keeps the half of the bracket that holds the maximum;
+//   * safeguarded Newton on LL': x - LL' / LL'' when LL'' < 0 and the point lies strictly inside the bracket, the
+//     bracket's midpoint otherwise; the bracket shrinks by the sign of LL' after every evaluation.  It stops (status 0)
+//     when LL' is 0 or so small that the Newton step no longer moves x, after a Newton step <= 1e-9, or when the bracket or
+//     a bisection step is <= 1e-9 and no Newton step is possible from there: where one is, it is taken first (it stays
+//     inside the bracket, so it is <= 1e-9 too), which leaves LL' at rounding level, not at up to 1e-9 info.  After 48
+//     steps it gives up (status 3) and returns the best point evaluated, by LL.  n_steps counts the evaluations after the
+//     one at the coarse best point.
+// Only the sign of LL' narrows the bracket, so an LL' that jumps upward inside it (a floored element of the freemuxlet
+// model) cannot trap the search: from LL'(a) > 0 > LL'(b) it closes on a zero that LL' crosses downward.
+#pragma once
+#include <cmath>
+
+#include "common.hpp"
+
+namespace ambient_fit {
+
+constexpr int MAX_STEPS = 48;
+constexpr double STOP = 1e-9;
+
+enum : int32_t {
+  INTERIOR = 0,
+  LOWER = 1,
+  UPPER = 2,
+  STEP_CAP = 3,
+  SKIPPED = 4,    // cand == -1
+  NO_ENTRY = 5,   // no scored entry
+  NOT_FINITE = 6  // LL at a coarse point is not finite (freemuxlet: a posterior row of exactly 0)
+};
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// v, of which every lane holds the same bits, as a value the compiler knows to be wave-uniform: it may then live in scalar
+// registers across a pass instead of taking two vector registers of every lane.  Changes no bit.
+__device__ __forceinline__ double uniform(double v) {
+  const uint64_t u = (uint64_t)__double_as_longlong(v);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
+  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+
+struct result {
+  double rho_hat = 0.0, ll_hat = 0.0, ll_zero = 0.0, info = 0.0;
+  int32_t status = SKIPPED, steps = 0;
+};
+
+// NC: coarse points per pass (1 or 3).  FINITE: end with NOT_FINITE when LL at a coarse point is not finite (rho_hat = 0,
+// ll_hat = ll_zero = -inf, info = 0, no step).  empty(): after the first derivative pass, whether the droplet has no scored
+// entry (NO_ENTRY: all outputs 0).  UNIFORM_STATE (newton): the doubles the search carries across a derivative pass go
+// through uniform() before it (fam_fit_kernel needs the sixteen vector registers to stay within 128; amb_fit_kernel keeps
+// the code it had).
+__device__ __forceinline__ result not_finite() {
+  result res;
+  res.ll_hat = -__builtin_huge_val();
+  res.ll_zero = -__builtin_huge_val();
+  res.status = NOT_FINITE;
+  return res;
+}
+
+// The second half of the search: from the bracket [a, b] around the best point x (at_lo: x is 0 and the best point is the
+// bracket's lower end; at_hi likewise with rho_max), the bound tests and the safeguarded Newton iteration.
+template <bool UNIFORM_STATE, class Deriv, class Empty>
+__device__ __forceinline__ result newton(double a, double x, double b, bool at_lo, bool at_hi, double ll_zero, Deriv&& deriv,
+                                         Empty&& empty) {
+  result res;
+  int32_t status, steps = 0;
+  double L = 0.0, d1 = 0.0, d2 = 0.0;
+  // the best point evaluated, by LL: what a fit that runs into the step cap returns
+  double xb = x, Lb = 0.0, d2b = 0.0;
+  double step = 1.0;
+  bool newton = false;  // the last move was a Newton step
+  status = STEP_CAP;
+  for (bool first = true;; first = false) {  // (one evaluation site: the pass is inlined once)
+    if (UNIFORM_STATE) {  // what the search carries across the pass
+      a = uniform(a), b = uniform(b), x = uniform(x), xb = uniform(xb), Lb = uniform(Lb), d2b = uniform(d2b);
+      step = uniform(step), ll_zero = uniform(ll_zero);
+    }
+    deriv(x, L, d1, d2);
+    if (first || L > Lb) xb = x, Lb = L, d2b = d2;
+    if (first) {
+      if (empty()) status = NO_ENTRY;
+      else if (at_lo && d1 <= 0.0) status = LOWER;
+      else if (at_hi && d1 >= 0.0) status = UPPER;
+      if (status != STEP_CAP) break;
+    } else {
+      ++steps;
+    }
+    if (d1 > 0.0) a = x; else if (d1 < 0.0) b = x;
+    if (d1 == 0.0 || (newton && step <= STOP)) {  // a Newton step within the stop: x is converged quadratically
+      status = INTERIOR;
+      break;
+    }
+    if (steps == MAX_STEPS) break;
+    double xn = x - d1 / d2;
+    if (d2 < 0.0 && xn == x) {  // LL' is at rounding level: the Newton step no longer moves x
+      status = INTERIOR;
+      break;
+    }
+    newton = d2 < 0.0 && xn > a && xn < b;
+    if (!newton) {
+      // the bracket, or the bisection step that led here, is within the stop.  (Where a Newton step is possible it was
+      // taken above: it lies inside the bracket, so it is within the stop too, and the fit ends after it with LL' at
+      // rounding level instead of up to 1e-9 info.)
+      if (b - a <= STOP || (!first && step <= STOP)) {
+        status = INTERIOR;
+        break;
+      }
+      xn = 0.5 * (a + b);
+    }
+    step = fabs(xn - x);
+    x = xn;
+  }
+  if (status == STEP_CAP) x = xb, L = Lb, d2 = d2b;
+  if (status == NO_ENTRY) ll_zero = 0.0;
+  if (status != NO_ENTRY) res.rho_hat = x, res.ll_hat = L, res.info = -d2;
+  res.ll_zero = ll_zero;
+  res.status = status, res.steps = steps;
+  return res;
+}
+
+template <int NC, bool FINITE, class Coarse, class Deriv, class Empty>
+__device__ __forceinline__ result search(double rho_max, Coarse&& coarse, Deriv&& deriv, Empty&& empty) {
+  double ll_zero = 0.0;
+  // the nine coarse points i * rho_max / 8 (the division by 8 is exact: point 8 is rho_max bit for bit)
+  double best_ll = 0.0;
+  int best = 0;
+  bool finite = true;
+  for (int i0 = 0; i0 < 9; i0 += NC) {
+    const double xs[3] = {(double)i0 * rho_max / 8.0, (double)(i0 + 1) * rho_max / 8.0, (double)(i0 + 2) * rho_max / 8.0};
+    double o[3];
+    coarse(xs, o);
+    if (i0 == 0) ll_zero = o[0];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+      if (FINITE) finite = finite && (o[k] - o[k] == 0.0);
+      if ((i0 == 0 && k == 0) || o[k] > best_ll) best_ll = o[k], best = i0 + k;  // (ties to the lowest index)
+    }
+  }
+  if (FINITE && !finite) return not_finite();
+  double a = (double)(best > 0 ? best - 1 : 0) * rho_max / 8.0;
+  double b = (double)(best < 8 ? best + 1 : 8) * rho_max / 8.0;
+  double x = (double)best * rho_max / 8.0;
+  return newton<false>(a, x, b, best == 0, best == 8, ll_zero, deriv, empty);
+}
+
+// The search for a model whose LL is piecewise: freemuxlet's 1e-6 floor.  LL' jumps upward where an element
+// leaves or reaches the floor, so LL can rise a second time inside the bracket and the rules above would then end on the
+// local maximum next to the best coarse point.  coarse(x[3], o[3], crosses) also says whether any element is below the
+// floor at one of its three points and not at another.  After the nine coarse points one more pass takes the bracket's
+// three points (lo, best, hi): where no element crosses the floor between them LL is smooth there and the search goes
+// on as above.  Where one does, LL is taken on the 65 points lo + (hi - lo) i / 64; the best of them (ties to the lowest
+// index) with its two neighbours is the bracket, and the bound tests and the Newton iteration run from there.  An element
+// is a product of positive linear factors, so it is above the floor on an interval: one that is above it at lo and at hi
+// is above it in between.  Every pass goes through one call site (the pass is inlined once); every decision is
+// wave-uniform.
+template <class Coarse, class Deriv, class Empty>
+__device__ __forceinline__ result search_piecewise(double rho_max, Coarse&& coarse, Deriv&& deriv, Empty&& empty) {
+  constexpr int FINE = 64, T_BRACKET = 3, T_FINE = 4, T_END = T_FINE + (FINE + 3) / 3;
+  double ll_zero = 0.0, best_ll = 0.0, lo = 0.0, hi = 0.0, mid = 0.0;
+  int best = 0;
+  bool finite = true, fine = false;
+  for (int t = 0; t < T_END; ++t) {
+    ll_zero = uniform(ll_zero), best_ll = uniform(best_ll), lo = uniform(lo), hi = uniform(hi), mid = uniform(mid);
+    best = __builtin_amdgcn_readfirstlane(best);
+    finite = __builtin_amdgcn_readfirstlane((int)finite) != 0;
+    if (t == T_BRACKET) {
+      if (!finite) return not_finite();
+      lo = (double)(best > 0 ? best - 1 : 0) * rho_max / 8.0;
+      hi = (double)(best < 8 ? best + 1 : 8) * rho_max / 8.0;
+      mid = (double)best * rho_max / 8.0;
+    }
+    double xs[3], o[3];
+    int idx[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      idx[k] = (t < T_BRACKET ? t : t - T_FINE) * 3 + k;
+      if (t < T_BRACKET) xs[k] = (double)idx[k] * rho_max / 8.0;  // (the division by 8 is exact: point 8 is rho_max bit for bit)
+      else if (t == T_BRACKET) xs[k] = k == 0 ? lo : k == 1 ? mid : hi;
+      else xs[k] = idx[k] >= FINE ? hi : lo + (hi - lo) * (double)idx[k] / (double)FINE;
+    }
+    bool crosses = false;
+    coarse(xs, o, crosses);
+    if (t == T_BRACKET) {
+      if (!crosses) break;
+      fine = true;
+      continue;
+    }
+    if (t == 0) ll_zero = o[0];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      if (t < T_BRACKET) finite = finite && (o[k] - o[k] == 0.0);
+      if (idx[k] > FINE) continue;  // (the last fine pass repeats hi)
+      if (idx[k] == 0 || o[k] > best_ll) best_ll = o[k], best = idx[k];  // (ties to the lowest index)
+    }
+  }
+  if (!fine) return newton<true>(lo, mid, hi, best == 0, best == 8, ll_zero, deriv, empty);
+  auto pt = [&](int i) { return i >= FINE ? hi : lo + (hi - lo) * (double)i / (double)FINE; };
+  const double x = pt(best);
+  return newton<true>(pt(best > 0 ? best - 1 : 0), x, pt(best < FINE ? best + 1 : FINE), best == 0 && x == 0.0,
+                      best == FINE && x == rho_max, ll_zero, deriv, empty);
+}
+
+// lane 0 of the wave of `unit` writes its row: dout [4][n_units] rho_hat, ll_hat, ll_zero, info; iout [2][n_units] status,
+// n_steps
+__device__ __forceinline__ void store(const result& r, int lane, int64_t unit, int64_t n_units, double* __restrict__ dout,
+                                      int32_t* __restrict__ iout) {
+  if (lane == 0) {
+    dout[unit] = r.rho_hat;
+    dout[n_units + unit] = r.ll_hat;
+    dout[2 * n_units + unit] = r.ll_zero;
+    dout[3 * n_units + unit] = r.info;
+    iout[unit] = r.status;
+    iout[n_units + unit] = r.steps;
+  }
+}
+
+// ---- the host side of a fit call ----
+struct outputs {  // each host [C][n_cand] or NULL
+  double *rho_hat, *ll_hat, *ll_zero, *info;
+  int32_t *status, *n_steps;
+  bool any() const { return rho_hat || ll_hat || ll_zero || info || status || n_steps; }
+};
+
+// the arguments both calls check alike, on the host: 0, or 1 with the reason in `why`.  what: "sample" or "cluster", n_what
+// of them
+inline int bad_args(const char* who, const char* what, const double* amb_af, int32_t n_cand, const int32_t* cand, int64_t C,
+                    int n_what, double rho_max, bool any_out, char* why, size_t n) {
+  if (!any_out) return snprintf(why, n, "%s: every output is NULL", who), 1;
+  if (n_cand < 1 || n_cand > MUXGL_MAX_FIT_CAND)
+    return snprintf(why, n, "%s: n_cand=%d outside [1,%d]", who, n_cand, MUXGL_MAX_FIT_CAND), 1;
+  if (!cand || !amb_af) return snprintf(why, n, "%s: %s is NULL", who, cand ? "amb_af" : "cand"), 1;
+  if (!(std::isfinite(rho_max) && rho_max > 0.0 && rho_max <= 1.0))
+    return snprintf(why, n, "%s: rho_max (%g) is not a finite number in (0, 1]", who, rho_max), 1;
+  for (int64_t i = 0; i < C * n_cand; ++i)
+    if (cand[i] < -1 || cand[i] >= n_what)
+      return snprintf(why, n, "%s: cand[%lld][%d] (%d) is neither -1 nor a %s in [0,%d)", who, (long long)(i / n_cand),
+                      (int)(i % n_cand), cand[i], what, n_what), 1;
+  return 0;
+}
+
+// amb_af and cand to the device, launch(n_units, d_af, d_cand, d_dout, d_iout) between the call's own events, the wanted
+// outputs to the host.  Nothing proportional to nnz is allocated; the handle's timing slots keep their values.
+template <class Launch>
+int host_run(muxgl_handle* h, const char* who, const double* amb_af, int n_cand, const int32_t* cand, const outputs& o,
+             float* kernel_ms, Launch&& launch) {
+  const int64_t C = h->C, S = h->S, n_units = C * n_cand;
+  if (n_units == 0) return 0;
+  if ((n_units + 3) / 4 > 0x7fffffffLL)
+    MUXGL_FAIL(h, "%s: %lld droplets x %d candidates exceed one launch", who, (long long)C, n_cand);
+  dev_tmp<double> d_af, d_dout;
+  dev_tmp<int32_t> d_cand, d_iout;
+  if (dev_alloc(h, &d_af.p, (size_t)S)) return 1;
+  if (dev_alloc(h, &d_cand.p, (size_t)n_units)) return 1;
+  if (dev_alloc(h, &d_dout.p, (size_t)n_units * 4)) return 1;
+  if (dev_alloc(h, &d_iout.p, (size_t)n_units * 2)) return 1;
+  call_events ev;  // (the handle's timing slots keep their values)
+  if (ev.create(h, kernel_ms, who)) return 1;
+  if (S > 0) HIPCHK(h, hipMemcpyAsync(d_af.p, amb_af, sizeof(double) * (size_t)S, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_cand.p, cand, sizeof(int32_t) * (size_t)n_units, hipMemcpyHostToDevice, h->stream));
+  if (ev.start(h)) return 1;
+  if (launch(n_units, d_af.p, d_cand.p, d_dout.p, d_iout.p)) return 1;
+  if (ev.stop(h)) return 1;
+  double* const dst[4] = {o.rho_hat, o.ll_hat, o.ll_zero, o.info};
+  for (int k = 0; k < 4; ++k)
+    if (dst[k])
+      HIPCHK(h, hipMemcpyAsync(dst[k], d_dout.p + (size_t)k * n_units, sizeof(double) * (size_t)n_units, hipMemcpyDeviceToHost,
+                               h->stream));
+  int32_t* const idst[2] = {o.status, o.n_steps};
+  for (int k = 0; k < 2; ++k)
+    if (idst[k])
+      HIPCHK(h, hipMemcpyAsync(idst[k], d_iout.p + (size_t)k * n_units, sizeof(int32_t) * (size_t)n_units, hipMemcpyDeviceToHost,
+                               h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  ev.add();
+  return 0;
+}
+
+}  // namespace ambient_fit

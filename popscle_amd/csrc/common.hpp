@@ -736,6 +736,10 @@ const char* fmx_ambient_refusal(const muxgl_handle* h);    // fmx_ambient.hip: t
 // fmx_ambient.hip: muxgl_fmx_ambient's checks of its arguments, on the host: 0, or 1 with the reason written to `why`
 int fmx_ambient_bad_args(const double* amb_af, int64_t S, int32_t n_rho, const double* rho, double* ll_amb, char* why,
                          size_t why_len);
+// fmx_ambient_fit.hip: the same two for muxgl_fmx_ambient_fit
+const char* fmx_ambient_fit_refusal(const muxgl_handle* h);
+int fmx_ambient_fit_bad_args(const double* amb_af, int64_t S, int32_t n_cand, const int32_t* cand, int64_t C, int K,
+                             double rho_max, bool any_out, char* why, size_t n);
 void fmx_wave_streams_release(muxgl_handle* h);  // the linear/general entry streams and their rank table
 int demux_ensure_ll(muxgl_handle* h, const muxgl_demux_params* p);  // standard LL tensor allocated and zeroed
 int demux_call_wave_launch(muxgl_handle* h, const muxgl_demux_params* p);
@@ -810,6 +814,9 @@ int group_fmx_singlets(muxgl_handle* h, double* sng);
 int group_fmx_inclusion(muxgl_handle* h, const muxgl_fmx_params* p, double* incl, double* tot, double* dbl, int32_t* partner);
 int group_fmx_unknown(muxgl_handle* h, const double* gp0, double* ll_ju, double* ll_u, double* ll_uu, float* kernel_ms);
 int group_fmx_ambient(muxgl_handle* h, const double* amb_af, int32_t n_rho, const double* rho, double* ll_amb, float* kernel_ms);
+int group_fmx_ambient_fit(muxgl_handle* h, const double* amb_af, int32_t n_cand, const int32_t* cand, double rho_max,
+                          double* rho_hat, double* ll_hat, double* ll_zero, double* info, int32_t* status, int32_t* n_steps,
+                          float* kernel_ms);
 void group_fmx_exact_stats(const muxgl_handle* h, int64_t* cells, int64_t* changed, int64_t* unresolved);
 void group_peer_stats(const muxgl_handle* h, int32_t* out);
 int group_get_timing(const muxgl_handle* h, float* ms);

@@ -19,16 +19,8 @@
 // bytes through the Phred table in LDS, dots the three triples with the candidate's gp row and adds its share of
 // (LL, LL', LL'') in entry order; a fixed xor butterfly adds the 64 shares (a + b commutes, so every lane holds the same
 // bits and every decision below is wave-uniform).  The whole fit runs in this one launch:
-//   * LL on the nine coarse points i rho_max / 8, three per pass (nine products per lane, as in a derivative pass); the best
-//     point, ties to the lowest index; the bracket is its two neighbours, clipped to [0, rho_max];
-//   * (LL, LL', LL'') at the best point x.  LL'(x) <= 0 at x = 0 is the lower bound (status 1), LL'(x) >= 0 at x = rho_max the
-//     upper (status 2); otherwise the sign of LL'(x) keeps the half of the bracket that holds the maximum;
-//   * safeguarded Newton on LL': x - LL' / LL'' when LL'' < 0 and the point lies strictly inside the bracket, the
-//     bracket's midpoint otherwise; the bracket shrinks by the sign of LL' after every evaluation.  It stops (status 0)
-//     when LL' is 0 or so small that the Newton step no longer moves x, after a Newton step <= 1e-9, or when the bracket or a bisection step is <= 1e-9 and no Newton step
-//     is possible from there: where one is, it is taken first (it stays inside the bracket, so it is <= 1e-9 too), which
-//     leaves LL' at rounding level, not at up to 1e-9 info.  After 48 steps it gives up (status 3) and returns the best
-//     point evaluated, by LL.  n_steps counts the evaluations after the one at the coarse best point.
+// the search of ambient_fit_search.hpp, shared with muxgl_fmx_ambient_fit, three coarse points per pass (nine products per
+// lane, as in a derivative pass).
 // Every reduction tree is fixed by the cell alone (lane = entry index modulo 64, then the butterfly), there is no atomic
 // and nothing depends on the batch, the device or the other candidates: the outputs are bit-identical from call to call,
 // for any budget, any order or grouping of the candidates, on one device, on a group and through the sharded driver.
@@ -37,6 +29,7 @@
 #include <cmath>
 #include <vector>
 
+#include "ambient_fit_search.hpp"
 #include "demux_entry.hpp"
 
 namespace {
@@ -44,15 +37,6 @@ namespace {
 struct fit_grid {
   double a[MUXGL_MAX_ALPHA];
 };
-
-constexpr int FIT_MAX_STEPS = 48;
-constexpr double FIT_STOP = 1e-9;
-
-__device__ __forceinline__ double fit_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // One pass of a wave over the entries [e0, e1) of a cell for candidate column j.
 //   DERIV = false: out[k] = LL(x[k]) for the NC <= 3 shares x[0..NC-1]
@@ -169,9 +153,9 @@ __device__ __forceinline__ void fit_pass(int64_t e0, int64_t e1, int lane, const
       if (NC > 2) s2 += pos_log(fma(g2, fma(am[8], sc, t10), fma(g1, fma(am[7], sc, t10), g0 * fma(am[6], sc, t10))), 0.0);
     }
   }
-  out[0] = fit_wave_sum(s0);
-  out[1] = (DERIV || NC > 1) ? fit_wave_sum(s1) : 0.0;
-  out[2] = (DERIV || NC > 2) ? fit_wave_sum(s2) : 0.0;
+  out[0] = ambient_fit::wave_sum(s0);
+  out[1] = (DERIV || NC > 1) ? ambient_fit::wave_sum(s1) : 0.0;
+  out[2] = (DERIV || NC > 2) ? ambient_fit::wave_sum(s2) : 0.0;
   if (n_scored) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) ns += __shfl_xor(ns, off, 64);
@@ -198,8 +182,7 @@ __global__ void __launch_bounds__(256)
   const int lane = threadIdx.x & 63;
   const int64_t c = unit / n_cand;
   const int32_t j = cand[unit];
-  double rho_hat = 0.0, ll_hat = 0.0, ll_zero = 0.0, info = 0.0;
-  int32_t status = 4, steps = 0;
+  ambient_fit::result res;  // (cand == -1: status 4, all outputs 0)
   if (j >= 0) {
     const int64_t e0 = cell_ptr[c], e1 = cell_ptr[c + 1];
     const size_t V3 = (size_t)V * 3;
@@ -211,81 +194,15 @@ __global__ void __launch_bounds__(256)
       fit_pass<NA, false, NC>(e0, e1, lane, entry_snp, entry_rptr, reads, lut, al, af, has_gp, gpj, V3, x, o, nullptr);
     };
     int n_scored = 0;
-    double L = 0.0, d1 = 0.0, d2 = 0.0;
-    auto deriv = [&](double x) {
+    auto deriv = [&](double x, double& L, double& d1, double& d2) {
       const double xs[3] = {x, 0.0, 0.0};
       double o[3];
       fit_pass<NA, true, 1>(e0, e1, lane, entry_snp, entry_rptr, reads, lut, al, af, has_gp, gpj, V3, xs, o, &n_scored);
       L = o[0], d1 = o[1], d2 = o[2];
     };
-    // the nine coarse points i * rho_max / 8 (the division by 8 is exact: point 8 is rho_max bit for bit)
-    double best_ll = 0.0;
-    int best = 0;
-    for (int i0 = 0; i0 < 9; i0 += NC) {
-      const double xs[3] = {(double)i0 * rho_max / 8.0, (double)(i0 + 1) * rho_max / 8.0, (double)(i0 + 2) * rho_max / 8.0};
-      double o[3];
-      coarse(xs, o);
-      if (i0 == 0) ll_zero = o[0];
-#pragma unroll
-      for (int k = 0; k < NC; ++k)
-        if ((i0 == 0 && k == 0) || o[k] > best_ll) best_ll = o[k], best = i0 + k;  // (ties to the lowest index)
-    }
-    double a = (double)(best > 0 ? best - 1 : 0) * rho_max / 8.0;
-    double b = (double)(best < 8 ? best + 1 : 8) * rho_max / 8.0;
-    double x = (double)best * rho_max / 8.0;
-    // the best point evaluated, by LL: what a fit that runs into the step cap returns
-    double xb = x, Lb = 0.0, d2b = 0.0;
-    double step = 1.0;
-    bool newton = false;  // the last move was a Newton step
-    status = 3;
-    for (bool first = true;; first = false) {  // (one evaluation site: the pass is inlined once)
-      deriv(x);
-      if (first || L > Lb) xb = x, Lb = L, d2b = d2;
-      if (first) {
-        if (n_scored == 0) status = 5;
-        else if (best == 0 && d1 <= 0.0) status = 1;
-        else if (best == 8 && d1 >= 0.0) status = 2;
-        if (status != 3) break;
-      } else {
-        ++steps;
-      }
-      if (d1 > 0.0) a = x; else if (d1 < 0.0) b = x;
-      if (d1 == 0.0 || (newton && step <= FIT_STOP)) {  // a Newton step within the stop: x is converged quadratically
-        status = 0;
-        break;
-      }
-      if (steps == FIT_MAX_STEPS) break;
-      double xn = x - d1 / d2;
-      if (d2 < 0.0 && xn == x) {  // LL' is at rounding level: the Newton step no longer moves x
-        status = 0;
-        break;
-      }
-      newton = d2 < 0.0 && xn > a && xn < b;
-      if (!newton) {
-        // the bracket, or the bisection step that led here, is within the stop.  (Where a Newton step is possible it was
-        // taken above: it lies inside the bracket, so it is within the stop too, and the fit ends after it with LL' at
-        // rounding level instead of up to 1e-9 info.)
-        if (b - a <= FIT_STOP || (!first && step <= FIT_STOP)) {
-          status = 0;
-          break;
-        }
-        xn = 0.5 * (a + b);
-      }
-      step = fabs(xn - x);
-      x = xn;
-    }
-    if (status == 3) x = xb, L = Lb, d2 = d2b;
-    if (status == 5) ll_zero = 0.0;
-    if (status != 5) rho_hat = x, ll_hat = L, info = -d2;
+    res = ambient_fit::search<NC, false>(rho_max, coarse, deriv, [&] { return n_scored == 0; });
   }
-  if (lane == 0) {
-    dout[unit] = rho_hat;
-    dout[n_units + unit] = ll_hat;
-    dout[2 * n_units + unit] = ll_zero;
-    dout[3 * n_units + unit] = info;
-    iout[unit] = status;
-    iout[n_units + unit] = steps;
-  }
+  ambient_fit::store(res, lane, unit, n_units, dout, iout);
 }
 
 template <int NA>
@@ -309,56 +226,19 @@ int fit_dispatch(muxgl_handle* h, int A, int64_t n_units, int n_cand, const int3
 
 int demux_ambient_fit_bad_args(const double* amb_af, int32_t n_cand, const int32_t* cand,
                                int64_t C, int V, double rho_max, bool any_out, char* why, size_t n) {
-  const char* who = "muxgl_demux_ambient_fit";
-  if (!any_out) return snprintf(why, n, "%s: every output is NULL", who), 1;
-  if (n_cand < 1 || n_cand > MUXGL_MAX_FIT_CAND)
-    return snprintf(why, n, "%s: n_cand=%d outside [1,%d]", who, n_cand, MUXGL_MAX_FIT_CAND), 1;
-  if (!cand || !amb_af) return snprintf(why, n, "%s: %s is NULL", who, cand ? "amb_af" : "cand"), 1;
-  if (!(std::isfinite(rho_max) && rho_max > 0.0 && rho_max <= 1.0))
-    return snprintf(why, n, "%s: rho_max (%g) is not a finite number in (0, 1]", who, rho_max), 1;
-  for (int64_t i = 0; i < C * n_cand; ++i)
-    if (cand[i] < -1 || cand[i] >= V)
-      return snprintf(why, n, "%s: cand[%lld][%d] (%d) is neither -1 nor a sample in [0,%d)", who, (long long)(i / n_cand),
-                      (int)(i % n_cand), cand[i], V), 1;
-  return 0;
+  return ambient_fit::bad_args("muxgl_demux_ambient_fit", "sample", amb_af, n_cand, cand, C, V, rho_max, any_out, why, n);
 }
 
 int demux_ambient_fit_run(muxgl_handle* h, const muxgl_demux_params* p, const double* amb_af, int n_cand,
                           const int32_t* cand, double rho_max, double* rho_hat, double* ll_hat, double* ll_zero,
                           double* info, int32_t* status, int32_t* n_steps, float* kernel_ms) {
   if (demux_ambient_check_af(h, amb_af, "muxgl_demux_ambient_fit")) return 1;
-  const int64_t C = h->C, S = h->S, n_units = C * n_cand;
-  if (n_units == 0) return 0;
-  if ((n_units + 3) / 4 > 0x7fffffffLL)
-    MUXGL_FAIL(h, "muxgl_demux_ambient_fit: %lld droplets x %d candidates exceed one launch", (long long)C, n_cand);
   const int A = p->n_alpha;
   fit_grid al;
   for (int i = 0; i < MUXGL_MAX_ALPHA; ++i) al.a[i] = i < A ? p->alpha[i] : p->alpha[0];  // (repeats of alpha[0] change no maximum)
-
-  dev_tmp<double> d_af, d_dout;
-  dev_tmp<int32_t> d_cand, d_iout;
-  if (dev_alloc(h, &d_af.p, (size_t)S)) return 1;
-  if (dev_alloc(h, &d_cand.p, (size_t)n_units)) return 1;
-  if (dev_alloc(h, &d_dout.p, (size_t)n_units * 4)) return 1;
-  if (dev_alloc(h, &d_iout.p, (size_t)n_units * 2)) return 1;
-  call_events ev;  // (the handle's timing slots keep their values)
-  if (ev.create(h, kernel_ms, "muxgl_demux_ambient_fit")) return 1;
-  if (S > 0) HIPCHK(h, hipMemcpyAsync(d_af.p, amb_af, sizeof(double) * (size_t)S, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(d_cand.p, cand, sizeof(int32_t) * (size_t)n_units, hipMemcpyHostToDevice, h->stream));
-  if (ev.start(h)) return 1;
-  if (fit_dispatch(h, A, n_units, n_cand, d_cand.p, rho_max, al, d_af.p, d_dout.p, d_iout.p)) return 1;
-  if (ev.stop(h)) return 1;
-  double* const dst[4] = {rho_hat, ll_hat, ll_zero, info};
-  for (int k = 0; k < 4; ++k)
-    if (dst[k])
-      HIPCHK(h, hipMemcpyAsync(dst[k], d_dout.p + (size_t)k * n_units, sizeof(double) * (size_t)n_units, hipMemcpyDeviceToHost,
-                               h->stream));
-  int32_t* const idst[2] = {status, n_steps};
-  for (int k = 0; k < 2; ++k)
-    if (idst[k])
-      HIPCHK(h, hipMemcpyAsync(idst[k], d_iout.p + (size_t)k * n_units, sizeof(int32_t) * (size_t)n_units, hipMemcpyDeviceToHost,
-                               h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  ev.add();
-  return 0;
+  const ambient_fit::outputs out = {rho_hat, ll_hat, ll_zero, info, status, n_steps};
+  return ambient_fit::host_run(h, "muxgl_demux_ambient_fit", amb_af, n_cand, cand, out, kernel_ms,
+                               [&](int64_t n_units, const double* d_af, const int32_t* d_cand, double* d_dout, int32_t* d_iout) {
+                                 return fit_dispatch(h, A, n_units, n_cand, d_cand, rho_max, al, d_af, d_dout, d_iout);
+                               });
 }

@@ -775,6 +775,32 @@ int group_fmx_ambient(muxgl_handle* h, const double* amb_af, int32_t n_rho, cons
   return 0;
 }
 
+// every member fits its own cells and writes their rows of the caller's arrays; kernel_ms: the slowest member's
+int group_fmx_ambient_fit(muxgl_handle* h, const double* amb_af, int32_t n_cand, const int32_t* cand, double rho_max,
+                          double* rho_hat, double* ll_hat, double* ll_zero, double* info, int32_t* status, int32_t* n_steps,
+                          float* kernel_ms) {
+  muxgl_group* g = h->group;
+  if (!g->have_pileup) MUXGL_FAIL(h, "muxgl_fmx_ambient_fit: no pileup set (muxgl_set_pileup)");
+  if (!g->prepared) MUXGL_FAIL(h, "muxgl_fmx_ambient_fit: call muxgl_fmx_prepare first");
+  for (const muxgl_handle* m : g->m)
+    if (const char* why = fmx_ambient_fit_refusal(m)) MUXGL_FAIL(h, "%s", why);
+  char why[256];  // (once here, so that the group's handle carries the message; the members find nothing)
+  if (fmx_ambient_fit_bad_args(amb_af, g->S, n_cand, cand, g->C, g->K, rho_max,
+                               rho_hat || ll_hat || ll_zero || info || status || n_steps, why, sizeof(why)))
+    MUXGL_FAIL(h, "%s", why);
+  std::vector<float> ms((size_t)g->n, 0.f);
+  if (for_members(h, [&](int r) {
+        const size_t o = (size_t)g->cb[(size_t)r] * (size_t)n_cand;
+        return muxgl_fmx_ambient_fit(g->m[(size_t)r], amb_af, n_cand, cand + o, rho_max, rho_hat ? rho_hat + o : nullptr,
+                                     ll_hat ? ll_hat + o : nullptr, ll_zero ? ll_zero + o : nullptr, info ? info + o : nullptr,
+                                     status ? status + o : nullptr, n_steps ? n_steps + o : nullptr,
+                                     kernel_ms ? &ms[(size_t)r] : nullptr);
+      }))
+    return 1;
+  if (kernel_ms) *kernel_ms = *std::max_element(ms.begin(), ms.end());
+  return 0;
+}
+
 // every member folds its own cells and writes their rows of the caller's tables
 int group_fmx_inclusion(muxgl_handle* h, const muxgl_fmx_params* p, double* incl, double* tot, double* dbl, int32_t* partner) {
   muxgl_group* g = h->group;

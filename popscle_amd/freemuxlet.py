@@ -25,6 +25,7 @@ import time
 import numpy as np
 
 from . import shard
+from .muxgl import ambient_fit_summary as muxgl_ambient_fit_summary
 from .muxgl import ambient_summary as muxgl_ambient_summary
 
 UNIT_CGP, UNIT_CLUST, UNIT_STAT = 0, 1, 2
@@ -171,7 +172,7 @@ def settle_near_ties(engs, gather, doublet_prior, geno_error):
 def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early_stop=True, exchange=None,
            exchange_tensor=engine_exchange_tensor, log=None, per=None, timings=None, sync=None, stream_ctx=None,
            want_singlets=False, want_inclusion=False, *, want_unknown=False, anchors=None, anchor_modes=None,
-           want_ambient=None):
+           want_ambient=None, want_ambient_fit=None):
     """EM loop of cmd_cram_freemux2.cpp:373-605 on a prepared engine.  One rank: a plain engine holding the whole
     pileup.  Several ranks: an engine holding the rank's slabs (load_rank), `exchange` a TorchExchange and
     per = (cells per rank, SNPs per rank) of the equal-slice plan the slabs were cut by.  clust0 spans the whole job.
@@ -185,7 +186,10 @@ def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early
     Engine.fmx_unknown (Hardy-Weinberg prior) of the last iteration, gathered the same way, as the last element;
     unknown_summary() turns them into per-droplet calls.  want_ambient = (amb_af, rhos) (keyword only): also the job-wide
     [C][K][n_rho] table of Engine.fmx_ambient of the last iteration, gathered the same way, as the last element;
-    ambient_summary() turns it into per-droplet calls.  anchors (keyword only): a list of columns of the panel the
+    ambient_summary() turns it into per-droplet calls.  want_ambient_fit = (amb_af, rho_max, n_top) (keyword only): also
+    the job-wide dict of Engine.fmx_ambient_fit of the last iteration for the n_top best clusters of every droplet's row of
+    the singlet table (ties to the lower index), with those candidates under "cand" ([C][n_top]), gathered the same way,
+    as the last element; ambient_fit_summary() gives the standard errors.  anchors (keyword only): a list of columns of the panel the
     engine holds (demux_set_gp); clusters 0 .. len(anchors)-1 are held to those donors' genotypes and the others are
     learned (Engine.fmx_set_anchors, after fmx_set_clusters; anchor_start() makes a clust0 for it).  One engine with the
     whole pileup or a device group only: refused with more than one rank or always=True.  anchor_modes (keyword only,
@@ -293,7 +297,7 @@ def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early
     out = np.zeros(eng.C_total, dtype=cells.dtype)
     for b, e, raw in parts:
         out[b:e] = np.frombuffer(raw, dtype=cells.dtype)
-    if not want_singlets and not want_inclusion and not want_unknown and want_ambient is None:
+    if not want_singlets and not want_inclusion and not want_unknown and want_ambient is None and want_ambient_fit is None:
         return out, history
     res = [out, history]
     if want_singlets:
@@ -321,6 +325,17 @@ def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early
         for b, e, raw in ex.gather_objects((c0, c0 + len(cells), eng.fmx_ambient(amb_af, rhos)["ll"].tobytes())):
             amb[b:e] = np.frombuffer(raw, dtype=np.float64).reshape(e - b, K, len(rhos))
         res.append(amb)
+    if want_ambient_fit is not None:
+        amb_af, rho_max, n_top = want_ambient_fit
+        n_top = min(int(n_top), K)
+        cand = top_clusters(eng.fmx_singlets(), n_top)
+        mine = {k: v for k, v in eng.fmx_ambient_fit(amb_af, cand, rho_max).items() if k != "kernel_ms"}
+        mine["cand"] = cand
+        fit = {k: np.zeros((eng.C_total, n_top), dtype=v.dtype) for k, v in mine.items()}
+        for b, e, raw in ex.gather_objects((c0, c0 + len(cells), {k: v.tobytes() for k, v in mine.items()})):
+            for k, v in fit.items():
+                v[b:e] = np.frombuffer(raw[k], dtype=v.dtype).reshape(e - b, n_top)
+        res.append(fit)
     return tuple(res)
 
 
@@ -415,6 +430,23 @@ def ambient_summary(ll_amb, rhos):
     out["amb_clust"] = out["amb_sample"]
     out["base_clust"] = out["base_sample"]
     return out
+
+
+def top_clusters(sng, n_top):
+    """int32 [C][n_top]: the n_top best clusters of every row of a singlet table [C][K], best first, ties to the lower
+    index"""
+    sng = np.asarray(sng, dtype=np.float64)
+    order = np.argsort(-np.where(np.isnan(sng), -np.inf, sng), axis=1, kind="stable")
+    return np.ascontiguousarray(order[:, :n_top], dtype=np.int32)
+
+
+def ambient_fit_summary(fit):
+    """What a caller reads off the dict of Engine.fmx_ambient_fit: muxgl.ambient_fit_summary as it is, with clusters for
+    samples -- se, the standard error of rho_hat where status is 0 and info > 0 and NaN elsewhere (an estimate on a bound
+    has none), and lrt, the likelihood ratio 2 * (ll_hat - ll_zero) against rho = 0 (NaN at status 6, where both are
+    -inf)."""
+    with np.errstate(invalid="ignore"):
+        return muxgl_ambient_fit_summary(fit)
 
 
 def unknown_summary(tables, best_llk):

@@ -65,6 +65,13 @@
 //       NUM.READS, DROPLET.TYPE, BEST.LLK, SNG.BEST.GUESS, SNG.BEST.LLK (those of .clust1.samples.gz, LLKs %.4lf), AMB.GUESS
 //       (the cluster), AMB.RHO (%.2lf: the best share ON THE GRID), AMB.LLK (ties: the lower cluster, then the lower rho
 //       index), DIFF.LLK.AMB.BEST = AMB.LLK - BEST.LLK.  The calls and every other file are unchanged
+//       --fit-ambient: also <O>.clust1.ambfit.gz (BGZF), per droplet of .clust1.samples.gz one row for SNG.BEST.GUESS and one
+//       for SNG.NEXT.GUESS: the maximum-likelihood share of ambient RNA on [0, --ambient-fit-max x] (default 0.5) under the
+//       model of --write-ambient, from the last EM iteration, with the profile of --ambient-af / --ambient-max-reads
+//       (muxgl_fmx_ambient_fit).  The columns of demuxlet's .ambfit.gz with CLUST in place of SM_ID: BARCODE, NUM.SNPS,
+//       NUM.READS, CLUST, SNG.LLK (the cluster's singlet LLK), AMB.RHO.MLE, AMB.RHO.SE (NA on a bound or where the
+//       information is not positive), AMB.LLK.MLE, AMB.LRT = 2 (AMB.LLK.MLE - SNG.LLK) (NA at status 6), STATUS (0 interior,
+//       1 lower bound, 2 upper bound, 3 step cap, 5 no entries, 6 a posterior row of exactly 0); all %.4lf
 //       --write-cluster-pairs: did the run split one donor over two clusters.  After the EM every pair of final cluster
 //       pileups is scored as one donor against two unrelated donors on the device (muxgl_fmx_cluster_pairs).  Writes
 //       <O>.clust1.ldist.gz (BGZF), one row per pair a > b in ascending (a, b) order: ID1, ID2, NSNP (markers both have
@@ -689,6 +696,8 @@ int cmd_freemuxlet(int argc, char** argv) {
   bool writeInclusion = false;  // (ours) <out>.clust1.incl.gz: per-cluster marginals of the last E-step's pair triangle
   bool writeUnknown = false;    // (ours) <out>.clust1.unk.gz: every droplet against a donor no cluster holds
   bool writeAmbient = false;    // (ours) <out>.clust1.amb.gz: every droplet as one cell plus a share of ambient RNA
+  bool fitAmbient = false;      // (ours) <out>.clust1.ambfit.gz: the maximum-likelihood ambient share with its standard error
+  double ambFitMax = 0.5;
   std::vector<double> ambRho;
   std::string ambAfFile;
   int32_t ambMaxReads = 0;
@@ -725,6 +734,8 @@ int cmd_freemuxlet(int argc, char** argv) {
   a.add_bool("write-inclusion", &writeInclusion);
   a.add_bool("write-unknown", &writeUnknown);
   a.add_bool("write-ambient", &writeAmbient);
+  a.add_bool("fit-ambient", &fitAmbient);
+  a.add_double("ambient-fit-max", &ambFitMax);
   a.add_multi_double("ambient-rho", &ambRho);
   a.add_string("ambient-af", &ambAfFile);
   a.add_int("ambient-max-reads", &ambMaxReads);
@@ -748,6 +759,7 @@ int cmd_freemuxlet(int argc, char** argv) {
   if (ambRho.empty()) ambRho = {0.0, 0.05, 0.1, 0.15, 0.2, 0.3, 0.4, 0.5};
   if ((int)ambRho.size() > MUXGL_MAX_ALPHA) fatal("at most %d --ambient-rho values are supported", MUXGL_MAX_ALPHA);
   if (ambMaxReads < 0) fatal("--ambient-max-reads must not be negative");
+  if (!(std::isfinite(ambFitMax) && ambFitMax > 0.0 && ambFitMax <= 1.0)) fatal("--ambient-fit-max must lie in (0, 1]");
   if (wantMatch && wantAnchor)
     fatal("freemuxlet: --match-vcf cannot be combined with --anchor-vcf: an anchored run's match tables (.clust1.match.gz, "
           ".clust1.match.best.gz) are written against the anchor panel");
@@ -1088,12 +1100,13 @@ int cmd_freemuxlet(int argc, char** argv) {
            (long long)nbetter, (long long)C);
     tmr.lap("freemuxlet: write .clust1.unk.gz");
   }
-  if (writeAmbient) {
-    // .clust1.amb.gz: one row per droplet (the order of .clust1.samples.gz), from the posteriors of the last E-step, like
-    // .clust1.sing2.gz.  The ambient profile: the caller's file, or the pileup's own reads with one pseudo-read at the
-    // population frequency
-    const size_t Kz = (size_t)K, NR = ambRho.size();
-    std::vector<double> f((size_t)S);
+  // The ambient profile of --write-ambient and --fit-ambient: the caller's file, or the pileup's own reads with one
+  // pseudo-read at the population frequency; made once
+  std::vector<double> ambProfile;
+  auto ambient_profile = [&]() -> const std::vector<double>& {
+    std::vector<double>& f = ambProfile;
+    if (!f.empty() || S == 0) return f;
+    f.resize((size_t)S);
     if (!ambAfFile.empty()) {
       TsvReader t(ambAfFile);
       size_t n = 0;
@@ -1114,6 +1127,13 @@ int cmd_freemuxlet(int argc, char** argv) {
       for (size_t s = 0; s < (size_t)S; ++s) f[s] = ((double)n_alt[s] + af[s]) / ((double)n_ref[s] + (double)n_alt[s] + 1.0);
       tmr.lap("freemuxlet: muxgl_pileup_allele_counts");
     }
+    return f;
+  };
+  if (writeAmbient) {
+    // .clust1.amb.gz: one row per droplet (the order of .clust1.samples.gz), from the posteriors of the last E-step, like
+    // .clust1.sing2.gz
+    const size_t Kz = (size_t)K, NR = ambRho.size();
+    const std::vector<double>& f = ambient_profile();
     BigVec<double> amb((size_t)C * Kz * NR);
     check(h, muxgl_fmx_ambient(h, f.data(), (int32_t)NR, ambRho.data(), amb.data(), nullptr), "muxgl_fmx_ambient");
     tmr.lap("freemuxlet: muxgl_fmx_ambient");
@@ -1149,6 +1169,43 @@ int cmd_freemuxlet(int argc, char** argv) {
     notice("Ambient RNA: %lld droplets called DBL are explained better, by more than 2 in log-likelihood, as one cell plus "
            "ambient RNA than as their best doublet", (long long)rescued);
     tmr.lap("freemuxlet: write .clust1.amb.gz");
+  }
+  if (fitAmbient) {
+    // .clust1.ambfit.gz: per droplet (the order of .clust1.samples.gz) one row for SNG.BEST.GUESS and one for SNG.NEXT.GUESS
+    // (none where the record has no such cluster), from the posteriors of the last E-step
+    const std::vector<double>& f = ambient_profile();
+    const size_t n = (size_t)C * 2;
+    std::vector<int32_t> cand(n), status(n);
+    for (int64_t i = 0; i < C; ++i) {
+      const muxgl_fmx_cell& c = cells[(size_t)i];
+      cand[(size_t)i * 2] = (c.sBest >= 0 && c.sBest < K) ? c.sBest : -1;
+      cand[(size_t)i * 2 + 1] = (c.sNext >= 0 && c.sNext < K) ? c.sNext : -1;
+    }
+    std::vector<double> rho(n), llh(n), ll0(n), info(n);
+    check(h, muxgl_fmx_ambient_fit(h, f.data(), 2, cand.data(), ambFitMax, rho.data(), llh.data(), ll0.data(), info.data(),
+                                   status.data(), nullptr, nullptr),
+          "muxgl_fmx_ambient_fit");
+    tmr.lap("freemuxlet: muxgl_fmx_ambient_fit");
+    OutFile wf(cf.outPrefix + ".clust1.ambfit.gz", true);
+    wf.printf("BARCODE\tNUM.SNPS\tNUM.READS\tCLUST\tSNG.LLK\tAMB.RHO.MLE\tAMB.RHO.SE\tAMB.LLK.MLE\tAMB.LRT\tSTATUS\n");
+    write_rows_parallel(wf, C, [&](int64_t i, std::string& o) {
+      for (size_t k = 0; k < 2; ++k) {
+        const size_t x = (size_t)i * 2 + k;
+        if (cand[x] < 0) continue;
+        char num[320], se[32], lrt[32];
+        if (status[x] == 0 && info[x] > 0.0) snprintf(se, sizeof(se), "%.4lf", 1.0 / sqrt(info[x]));  // (on a bound: no standard error)
+        else snprintf(se, sizeof(se), "NA");
+        const double r = 2.0 * (llh[x] - ll0[x]);
+        if (std::isfinite(r)) snprintf(lrt, sizeof(lrt), "%.4lf", r);
+        else snprintf(lrt, sizeof(lrt), "NA");
+        const int m = snprintf(num, sizeof(num), "\t%d\t%d\t%d\t%.4lf\t%.4lf\t%s\t%.4lf\t%s\t%d\n", nSNPs[(size_t)i],
+                               nReads[(size_t)i], cand[x], ll0[x], rho[x], se, llh[x], lrt, (int)status[x]);
+        o.append(p.bcs[(size_t)i]);
+        o.append(num, (size_t)std::min<int>(m, (int)sizeof(num) - 1));
+      }
+    });
+    wf.close();
+    tmr.lap("freemuxlet: write .clust1.ambfit.gz");
   }
   if (wantAnchor) {
     // .clust1.anchors.gz: one row per cluster -- the donor it is held to, the greedy cluster it started from with the log
@@ -1712,6 +1769,9 @@ int main(int argc, char** argv) {
                     "      [0, x] (default 0.5) with its standard error and the likelihood ratio against no ambient RNA\n"
                     "  freemuxlet --write-ambient [--ambient-rho x ...] [--ambient-af FILE] [--ambient-max-reads N]: also\n"
                     "    <out>.clust1.amb.gz, per droplet the best reading as one cell of a cluster plus a share rho of ambient RNA\n"
+                    "  freemuxlet --fit-ambient [--ambient-fit-max x] [--ambient-af FILE] [--ambient-max-reads N]: also\n"
+                    "    <out>.clust1.ambfit.gz, per droplet and for its best and next singlet cluster the maximum-likelihood ambient\n"
+                    "    share on [0, x] (default 0.5) with its standard error and the likelihood ratio against no ambient RNA\n"
                     "  freemuxlet --write-unknown: also <out>.clust1.unk.gz, per droplet how well a donor that no cluster holds\n"
                     "    explains it in the last iteration (BARCODE NUM.SNPS NUM.READS BEST.LLK UNK.SNG.LLK UNK.DBL.LLK HALF.CLUST\n"
                     "    HALF.LLK DIFF.LLK.CLUST.UNK); a notice counts the droplets it explains better by more than 2\n");

@@ -120,6 +120,7 @@ SYMBOLS = {
     "muxgl_fmx_inclusion": (C.c_int, [_VP, C.POINTER(_FmxParams), _VP, _VP, _VP, _VP]),
     "muxgl_fmx_unknown": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP]),
     "muxgl_fmx_ambient": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, _VP]),
+    "muxgl_fmx_ambient_fit": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "muxgl_fmx_get_cluster_pileup": (C.c_int, [_VP, _VP, _VP]),
     "muxgl_fmx_match_donors": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
     "muxgl_fmx_cluster_pairs": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
@@ -767,6 +768,34 @@ class Engine:
         ms = C.c_float(0.0)
         self._check(self.lib.muxgl_fmx_ambient(self.h, _ptr(amb_af), rhos.size, _ptr(rhos), _ptr(out), C.byref(ms)))
         return {"ll": out, "kernel_ms": float(ms.value)}
+
+    def fmx_ambient_fit(self, amb_af, cand, rho_max=0.5, want=AMBIENT_FIT_FIELDS):
+        """muxgl_fmx_ambient_fit: per droplet (of the handle's own cells) and candidate cluster, the maximum-likelihood
+        ambient share on [0, rho_max] under the model of fmx_ambient, with its observed information, from the posteriors
+        the last E-step read (include/muxgl.h).  cand: int32 [C][n_cand] (or [C]), a cluster or -1 per slot.  dict of
+        rho_hat, ll_hat, ll_zero, info float64 [C][n_cand], status, n_steps int32 [C][n_cand], and kernel_ms.  want: the
+        subset of the six to fetch (the others are passed as NULL).  freemuxlet.ambient_fit_summary() gives the standard
+        error and the likelihood ratio."""
+        unknown = set(want) - set(self.AMBIENT_FIT_FIELDS)
+        if unknown:
+            raise ValueError(f"unknown fields {sorted(unknown)}")
+        amb_af = _arr(amb_af, np.float64, "amb_af")
+        if amb_af.shape != (self.S,):
+            raise ValueError("amb_af must be [S]")
+        cand = _arr(cand, np.int32, "cand")
+        if cand.ndim == 1:
+            cand = cand.reshape(-1, 1)
+        if cand.ndim != 2 or cand.shape[0] != self.C:
+            raise ValueError("cand must be [C][n_cand]")
+        out = {}
+        for name in self.AMBIENT_FIT_FIELDS:
+            if name in want:
+                out[name] = np.zeros(cand.shape, dtype=np.int32 if name in ("status", "n_steps") else np.float64)
+        ms = C.c_float(0.0)
+        self._check(self.lib.muxgl_fmx_ambient_fit(self.h, _ptr(amb_af), cand.shape[1], _ptr(cand), float(rho_max),
+                                                    *[_ptr(out.get(n)) for n in self.AMBIENT_FIT_FIELDS], C.byref(ms)))
+        out["kernel_ms"] = float(ms.value)
+        return out
 
     # ---- freemuxlet-old: pairwise distance matrix and voting passes (cmd_cram_freemuxlet.cpp:176-343)
     def fmxold_pair_dist(self, bf_thres=5.41, want_full=False):

@@ -1,0 +1,534 @@
+"""GPU tests of muxgl_fmx_ambient_fit (fmx_ambient_fit.hip): the per-droplet maximum-likelihood ambient share of a candidate
+cluster with its observed information.  Against the restatement (tests/fmx_ambient_fit_ref.py) evaluated at the device's own
+rho_hat, against the restatement's Newton-free maximiser, against the existing calls (singlet table, ambient table), the
+bounds and the statuses, bit identity across calls, budgets, device groups, slabbed ranks, the sharded driver, orders and
+groupings of candidates and subsets of outputs, the state the call must leave alone, and the refusals.
+
+The posteriors of the shape tests are handed in: the clusters are set from the truth (muxgl_fmx_set_clusters), held to the
+panel's genotypes (muxgl_fmx_set_anchors), and one E-step runs; the restatement reads the posteriors that E-step read
+(muxgl_fmx_get_cluster_gp).
+
+Bars (check_fit): ll_hat, ll_zero within parity.LL_TOL; info and the implied LL' (0 at an interior estimate) within 1000 x
+the float64-to-longdouble disagreement of the restatement on the case, floored at 1e-9 x the sum of absolute per-entry
+terms (over absolute summands where that is exactly 0); the restated LL at the device's estimate within 1e-9 of the LL at
+the restatement's; where the restated info is >= 1 the two estimates within 1e-6 and the statuses equal.  A pair with an
+element within 1e-6 relative of the 1e-6 floor at the device's rho_hat sits on a kink of LL' in one precision and beside it
+in the other: it skips the two derivative bars only, and such pairs may be at most 1 % of the fitted ones."""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+
+import ambient_ref as ar
+import fmx_ambient_fit_ref as ffr
+import fmx_ambient_ref as fr
+import parity
+from popscle_amd import freemuxlet, muxgl, synth
+from test_fmx_ambient_fit import check_soup_fits
+from test_fmx_singlets_gpu import _clust_buffer, _local_allgather, prepared, spread_init
+
+pytestmark = pytest.mark.gpu
+
+XE = muxgl.FLAG_FORCE_STREAMED_ESTEP
+DEFAULT_RHOS = fr.DEFAULT_RHOS
+FIELDS = muxgl.Engine.AMBIENT_FIT_FIELDS
+WORST = {}   # what -> worst figure seen, printed by every check
+
+
+def same(a, b, fields=FIELDS):
+    return all(a[k].tobytes() == b[k].tobytes() for k in fields)
+
+
+def note(what, v):
+    WORST[what] = max(WORST.get(what, 0.0), float(v))
+
+
+def check_fit(p, q, f, cand, rho_max, got, what, pairs=None, ll_tol=parity.LL_TOL):
+    """every bar of the module's docstring on the (droplet, slot) pairs of `pairs` (None: all); returns the number of
+    interior fits and of those with restated info >= 1"""
+    ld = np.longdouble
+    cand = np.asarray(cand).reshape(p.C, -1)
+    assert all(got[k].shape == cand.shape for k in FIELDS)
+    assert (got["n_steps"] <= 48).all() and (got["n_steps"] >= 0).all() and not (got["status"] == 3).any()
+    assert not any(np.isnan(got[k]).any() for k in FIELDS)
+    fitted = strong = checked = on_kink = 0
+    seen = {}
+    for c, k in (pairs if pairs is not None else [(c, k) for c in range(p.C) for k in range(cand.shape[1])]):
+        j = int(cand[c, k])
+        g = {n: got[n][c, k] for n in FIELDS}
+        if j < 0:
+            assert g["status"] == 4 and all(g[n] == 0 for n in FIELDS if n != "status"), (c, k, g)
+            continue
+        if (c, j) not in seen:
+            seen[(c, j)] = ffr.fit(p, q, f, c, j, rho_max)
+        r = seen[(c, j)]
+        cell = r["cell"]
+        if cell.n == 0:
+            assert g["status"] == 5 and all(g[n] == 0 for n in FIELDS if n != "status"), (c, k, g)
+            continue
+        if r["status"] == 6:
+            assert g["status"] == 6 and g["rho_hat"] == 0 and g["ll_hat"] == g["ll_zero"] == -np.inf and g["info"] == 0 \
+                and g["n_steps"] == 0, (c, k, g)
+            continue
+        x = float(g["rho_hat"])
+        assert g["status"] in (0, 1, 2) and 0.0 <= x <= rho_max, (c, k, g)
+        L, d1, d2, aL, a1, a2, s1, s2, near = [float(v[0]) for v in cell.eval([x], ld)]
+        L64, d164, d264 = [float(v[0]) for v in cell.eval([x], np.float64)[:3]]
+        tol1 = max(1000.0 * abs(d164 - d1), 1e-9 * a1)
+        tol2 = max(1000.0 * abs(d264 - d2), 1e-9 * a2)
+        if tol1 == 0.0 or tol2 == 0.0:   # every term exactly 0 in both precisions: the floor over absolute summands
+            tol1, tol2 = max(tol1, 1e-9 * s1), max(tol2, 1e-9 * s2)
+        kink = near < 1e-6               # an element on the floor's edge: the derivative bars do not apply
+        checked += 1
+        on_kink += kink
+        note(f"{what}: |ll_hat - ref|", abs(g["ll_hat"] - L))
+        note(f"{what}: |ll_zero - ref|", abs(g["ll_zero"] - r["ll_zero"]))
+        assert abs(g["ll_hat"] - L) <= ll_tol and abs(g["ll_zero"] - r["ll_zero"]) <= ll_tol, (c, k, g, L)
+        if not kink:
+            note(f"{what}: |info - ref| / tol", abs(g["info"] + d2) / tol2)
+            assert abs(g["info"] + d2) <= tol2, (c, k, g, d2, tol2)
+        if g["status"] == 1:
+            assert x == 0.0 and (kink or d1 <= tol1), (c, k, g, d1)
+        elif g["status"] == 2:
+            assert x == rho_max and (kink or d1 >= -tol1), (c, k, g, d1)
+        else:
+            if not kink:
+                note(f"{what}: |LL'(rho_hat)| / tol", abs(d1) / tol1)
+                assert abs(d1) <= tol1, (c, k, g, d1, tol1)
+            fitted += 1
+        note(f"{what}: LL(ref rho) - LL(device rho)", r["ll_hat"] - L)
+        assert L >= r["ll_hat"] - 1e-9, (c, k, g, r["rho_hat"], r["ll_hat"], L)
+        if r["info"] >= 1.0:
+            strong += g["status"] == 0
+            note(f"{what}: |rho_hat - ref|", abs(x - r["rho_hat"]))
+            assert abs(x - r["rho_hat"]) <= 1e-6, (c, k, g, r["rho_hat"], r["info"])
+            assert g["status"] == r["status"], (c, k, g, r["status"])
+    assert on_kink <= 0.01 * checked, (on_kink, checked)
+    for key in sorted(WORST):
+        if key.startswith(what + ":"):
+            print(f"fmx ambient fit {key} {WORST[key]:.3e}")
+    print(f"fmx ambient fit {what}: {fitted} interior fits, {strong} with info >= 1, {on_kink} on a kink, mean n_steps "
+          f"{float(got['n_steps'][got['status'] == 0].mean()) if (got['status'] == 0).any() else 0.0:.2f}")
+    return fitted, strong
+
+
+def ready(p, K, init, devs=0, flags=0, anchors=None, modes=None, ge=0.1):
+    """an engine after one E-step on the clusters `init`; anchors: the donors clusters 0 .. are held to"""
+    e = prepared(p, devs, flags)
+    if anchors is not None:
+        e.demux_set_gp(p.gp, p.has_gp)
+    e.fmx_set_clusters(K, init)
+    if anchors is not None:
+        e.fmx_set_anchors(anchors, modes)
+    e.fmx_iterate(0.5, ge)
+    return e
+
+
+# ---- 1. parity and optimality over the shapes ----------------------------------------------------------------------------
+
+@pytest.mark.parametrize("K,V,seed", [(1, 6, 7), (6, 6, 46), (17, 17, 57), (70, 70, 110), (300, 300, 340)])
+def test_shapes_vs_restatement(K, V, seed):
+    """droplets of 0, 1, 2, 63, 64, 65, 2048, 2049 and 5003 entries; K = 17, 70 and 300 run the wave, the oct and the streamed
+    E-step.  K > 1: cluster j is held to donor j and the candidates are the droplet's own cluster and the next one.  K = 1:
+    one cluster learned from all droplets of six donors"""
+    p, who, pool = ffr.shaped(V, seed)
+    if K == 1:
+        init, anchors, cand = np.zeros(p.C, np.int32), None, np.zeros((p.C, 1), np.int32)
+    else:
+        init, anchors = who.astype(np.int32), list(range(K))
+        cand = np.stack([who, (who + 1) % K], axis=1).astype(np.int32)
+    with ready(p, K, init, anchors=anchors) as e:
+        q = e.fmx_cluster_gp()
+        got = e.fmx_ambient_fit(pool, cand, 0.5)
+    assert got["kernel_ms"] > 0.0
+    fitted, strong = check_fit(p, q, pool, cand, 0.5, got, f"shapes K={K}")
+    assert got["status"][0].tolist() == [5] * cand.shape[1]                              # the droplet without entries
+    assert K == 1 or (fitted >= 5 and strong >= 0.8 * fitted), (fitted, strong)
+
+
+def small_case(K=17, seed=77, entries=(0, 1, 65, 300, 2, 130), S=900):
+    p, who, pool = ffr.shaped_pileup(list(entries), S, K, seed, missing_gp_frac=0.0)
+    return p, who.astype(np.int32), pool
+
+
+def test_sixteen_candidates_with_skips_and_repeats():
+    K = 17
+    p, who, pool = small_case(K)
+    rng = np.random.default_rng(5)
+    cand = rng.integers(-1, K, size=(p.C, 16)).astype(np.int32)
+    cand[:, 0] = who
+    cand[:, 3] = who                                                                     # a repeated candidate
+    cand[:, 7] = -1
+    with ready(p, K, who, anchors=list(range(K))) as e:
+        q = e.fmx_cluster_gp()
+        got = e.fmx_ambient_fit(pool, cand, 0.4)
+    check_fit(p, q, pool, cand, 0.4, got, "16 candidates")
+    assert all(got[k][:, 3].tobytes() == got[k][:, 0].tobytes() for k in FIELDS)
+    assert (got["status"][:, 7] == 4).all() and (got["status"][0] >= 4).all()           # skipped slots; the empty droplet
+
+
+def test_a_zeroed_posterior_row_gives_status_6_and_no_nan():
+    import torch
+
+    K = 5
+    p, who, pool = small_case(K, seed=78)
+    cand = np.stack([who, (who + 1) % K, (who + 2) % K], axis=1).astype(np.int32)
+    with ready(p, K, who) as e:
+        clean = e.fmx_ambient_fit(pool, cand, 0.5)
+        c = 3                                                                            # the droplet of 300 entries
+        s, j = int(p.entry_snp[int(p.cell_ptr[c]) + 17]), int(cand[c, 1])
+        t = freemuxlet.engine_exchange_tensor(e, freemuxlet.UNIT_CGP)
+        t[s, j * 3:j * 3 + 3] = 0.0                                                      # cluster j at one of the droplet's markers
+        torch.cuda.synchronize()
+        q = e.fmx_cluster_gp()
+        assert not q[s, j].any()
+        got = e.fmx_ambient_fit(pool, cand, 0.5)
+    hit = np.array([[s in p.entry_snp[p.cell_ptr[d]:p.cell_ptr[d + 1]] and cand[d, k] == j for k in range(3)] for d in range(p.C)])
+    assert hit[c, 1] and (got["status"][hit] == 6).all() and not (got["status"][~hit] == 6).any()
+    assert (got["rho_hat"][hit] == 0).all() and (got["ll_hat"][hit] == -np.inf).all() and (got["ll_zero"][hit] == -np.inf).all()
+    assert (got["info"][hit] == 0).all() and (got["n_steps"][hit] == 0).all()
+    assert not any(np.isnan(got[k]).any() for k in FIELDS)
+    assert all(got[k][~hit].tobytes() == clean[k][~hit].tobytes() for k in FIELDS)       # every other pair as before
+    check_fit(p, q, pool, cand, 0.5, got, "zeroed row")
+    sm = freemuxlet.ambient_fit_summary(got)
+    assert np.isnan(sm["se"][hit]).all() and np.isnan(sm["lrt"][hit]).all()
+
+
+def test_droplets_without_entries():
+    K = 4
+    p, who, pool = small_case(K, seed=9, entries=(3, 0, 70, 0))
+    with ready(p, K, who) as e:
+        got = e.fmx_ambient_fit(pool, np.array([[0, -1], [1, 2], [3, 3], [-1, 0]], dtype=np.int32))
+    assert got["status"][[1, 3]].tolist() == [[5, 5], [4, 5]] and got["status"][0, 1] == 4
+    assert all(not got[k][[1, 3]].any() for k in FIELDS if k != "status")
+
+
+def test_zero_cells():
+    """C == 0: the call succeeds and writes nothing"""
+    K = 4
+    p, who, pool = small_case(K, seed=9, entries=(3, 0, 70, 0))
+    with muxgl.Engine(0) as e:
+        e.set_pileup(p.S, np.zeros(1, np.int64), np.zeros(0, np.int32), np.zeros(1, np.int64), np.zeros(0, np.uint8))
+        e.fmx_prepare(p.af)
+        e.fmx_set_clusters(K, np.zeros(0, np.int32))
+        e.fmx_iterate(0.5, 0.1)
+        got = e.fmx_ambient_fit(pool, np.zeros((0, 2), np.int32))
+        assert got["rho_hat"].shape == (0, 2) and got["kernel_ms"] == 0.0
+        VP = ctypes.c_void_p
+        canary = np.full(4, 7.0)
+        assert e.lib.muxgl_fmx_ambient_fit(e.h, pool.ctypes.data_as(VP), 2, np.zeros(2, np.int32).ctypes.data_as(VP),
+                                           ctypes.c_double(0.5), canary.ctypes.data_as(VP), *[None] * 6) == 0
+        assert (canary == 7.0).all()
+
+
+# ---- 2. consistency with the existing calls ------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("K,flags", [(6, 0), (40, 0), (40, XE)])
+def test_consistent_with_the_singlet_and_the_ambient_tables(K, flags):
+    p, who, pool = small_case(K, seed=300 + K, entries=(0, 5, 64, 200, 700, 2100, 90, 33), S=2500)
+    with ready(p, K, who, flags=flags, anchors=list(range(K))) as e:
+        sng = e.fmx_singlets()
+        cand = freemuxlet.top_clusters(sng, 2)
+        got = e.fmx_ambient_fit(pool, cand, 0.5)
+        table = e.fmx_ambient(pool, DEFAULT_RHOS)["ll"]
+        at_hat = np.zeros(cand.shape)
+        for c in range(p.C):                       # the table at the droplet's own estimates: one rho per call and slot
+            for k in range(2):
+                at_hat[c, k] = e.fmx_ambient(pool, [got["rho_hat"][c, k]])["ll"][c, cand[c, k], 0]
+        coarse = e.fmx_ambient(pool, ffr.coarse_points(0.5))["ll"]
+    rows = np.arange(p.C)[:, None]
+    d0 = np.abs(got["ll_zero"] - sng[rows, cand]).max()
+    d1 = np.abs(got["ll_hat"] - at_hat).max()
+    print(f"fmx ambient fit K={K} flags={flags}: |ll_zero - singlet table| {d0:.3e}, |ll_hat - ambient table at rho_hat| {d1:.3e}")
+    assert d0 <= parity.LL_TOL and d1 <= parity.LL_TOL
+    assert (got["status"][1:] <= 2).all() and (got["status"] == 0).any()
+    xs = ffr.coarse_points(0.5)
+    for c in range(1, p.C):                        # no point of the default grid inside the bracket is better
+        for k in range(2):
+            i = int(np.argmax(coarse[c, cand[c, k]]))
+            lo, hi = xs[max(i - 1, 0)], xs[min(i + 1, 8)]
+            assert lo <= got["rho_hat"][c, k] <= hi, (c, k, lo, hi, got["rho_hat"][c, k])
+            inside = [r for r, rho in enumerate(DEFAULT_RHOS) if lo <= rho <= hi]
+            assert inside and (got["ll_hat"][c, k] >= table[c, cand[c, k], inside] - 1e-9).all(), (c, k)
+
+
+# ---- 3. bounds, and what the feature is for ---------------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def soup_fit(soup, rho_max):
+    """the SOUP pileup of fmx_ambient_ref.py with the clusters handed in from the truth, one E-step, every droplet's own
+    cluster as the candidate"""
+    p, who, _pool = ar.soup_pileup(soup=soup, **fr.SOUP)
+    who = who.astype(np.int32)
+    with ready(p, fr.SOUP["V"], who) as e:
+        f = muxgl.ambient_profile(*e.pileup_allele_counts(), p.af)
+        q = e.fmx_cluster_gp()
+        got = e.fmx_ambient_fit(f, who, rho_max)
+        table = e.fmx_ambient(f, DEFAULT_RHOS)["ll"]
+    return p, who, f, q, got, table
+
+
+def test_no_soup_sits_on_the_lower_bound_and_a_small_cap_on_the_upper():
+    p, who, f, q, got, table = soup_fit(0.0, 0.5)
+    at0 = got["status"][:, 0] == 1
+    print(f"soup = 0: {int(at0.sum())} of {p.C} droplets at the lower bound")
+    assert at0.sum() > p.C / 2 and (got["rho_hat"][at0] == 0.0).all() and (got["n_steps"][at0] == 0).all()
+    assert np.abs(got["ll_hat"][at0] - got["ll_zero"][at0]).max() <= 1e-9      # (both are LL(0))
+    p, who, f, q, got, table = soup_fit(0.2, 0.05)
+    at_cap = got["status"][:, 0] == 2
+    print(f"soup = 0.2, rho_max = 0.05: {int(at_cap.sum())} of {p.C} droplets at the upper bound")
+    assert at_cap.sum() > p.C / 2 and got["rho_hat"][at_cap].tobytes() == np.full(int(at_cap.sum()), 0.05).tobytes()
+    assert (got["n_steps"][at_cap] == 0).all()
+    check_fit(p, q, f, who, 0.05, got, "upper bound", pairs=[(c, 0) for c in range(0, p.C, 96)])
+
+
+@pytest.mark.parametrize("soup", [0.2, 0.0])
+def test_the_device_meets_the_soup_sanity_check(soup):
+    """tests/test_fmx_ambient_fit.py holds the restatement to the same check on every eighth droplet of the same pileup"""
+    p, who, f, q, got, table = soup_fit(soup, 0.5)
+    check_soup_fits(got["rho_hat"][:, 0], got["status"][:, 0], table, who, soup)
+    check_fit(p, q, f, who, 0.5, got, f"soup {soup}", pairs=[(c, 0) for c in range(0, p.C, 96)])
+
+
+# ---- 4. bit identity ---------------------------------------------------------------------------------------------------
+
+def _long_cells_pileup(seed, C=30):
+    p = synth.make_pileup(C, 9000, 8, seed=seed, mean_entries=700, sigma=1.0, min_entries=1, max_entries=6000, with_gp=False)
+    assert np.diff(p.cell_ptr).max() > 2048
+    return p
+
+
+@functools.lru_cache(maxsize=None)
+def identity_case(K, C=30):
+    p = _long_cells_pileup(11000 + K, C)
+    f = ar.draw_af(p.S, seed=K)
+    cand = np.random.default_rng(K).integers(-1, K, size=(p.C, 16)).astype(np.int32)
+    init = spread_init(p.C, K)
+    with prepared(p) as e:
+        e.fmx_set_clusters(K, init)
+        for _ in range(2):
+            cells, st = e.fmx_iterate(0.5, 0.1)
+        want = e.fmx_ambient_fit(f, cand, 0.37)
+    return p, f, cand, init, want, cells
+
+
+def test_call_to_call_budget_permutation_split_and_null_outputs(monkeypatch):
+    K = 24
+    p, f, cand, init, want, _cells = identity_case(K)
+    assert (want["status"] == 0).any() and (want["status"] == 4).any()
+    monkeypatch.delenv("MUXGL_FMX_SLAB_MB", raising=False)
+    with prepared(p) as e:
+        e.fmx_set_clusters(K, init)
+        for _ in range(2):
+            e.fmx_iterate(0.5, 0.1)
+        assert same(e.fmx_ambient_fit(f, cand, 0.37), want) and same(e.fmx_ambient_fit(f, cand, 0.37), want)
+        perm = np.random.default_rng(1).permutation(16)
+        got = e.fmx_ambient_fit(f, np.ascontiguousarray(cand[:, perm]), 0.37)
+        assert same(got, {k: np.ascontiguousarray(want[k][:, perm]) for k in FIELDS})
+        lo = e.fmx_ambient_fit(f, np.ascontiguousarray(cand[:, :8]), 0.37)
+        hi = e.fmx_ambient_fit(f, np.ascontiguousarray(cand[:, 8:]), 0.37)
+        assert same({k: np.concatenate([lo[k], hi[k]], axis=1) for k in FIELDS}, want)
+        twice = e.fmx_ambient_fit(f, np.ascontiguousarray(np.repeat(cand[:, :8], 2, axis=1)), 0.37)   # every candidate twice
+        assert same({k: np.ascontiguousarray(twice[k][:, ::2]) for k in FIELDS}, lo)
+        assert same({k: np.ascontiguousarray(twice[k][:, 1::2]) for k in FIELDS}, lo)
+        for sub in (("rho_hat",), ("status", "n_steps"), ("info", "ll_zero"), ("ll_hat", "n_steps", "rho_hat")):
+            got = e.fmx_ambient_fit(f, cand, 0.37, want=sub)
+            assert set(got) == set(sub) | {"kernel_ms"} and same(got, want, sub)
+        for mb in ("1", "64"):
+            monkeypatch.setenv("MUXGL_FMX_SLAB_MB", mb)                                   # (not read by the call)
+            assert same(e.fmx_ambient_fit(f, cand, 0.37), want)
+        monkeypatch.delenv("MUXGL_FMX_SLAB_MB")
+
+
+@pytest.mark.parametrize("K", [24, 300])
+def test_device_groups(K):
+    p, f, cand, init, want, cells = identity_case(K)
+    for devs in ([0, 0], [0, 0, 0]):
+        with prepared(p, devs) as e:
+            e.fmx_set_clusters(K, init)
+            for _ in range(2):
+                gcells, _st = e.fmx_iterate(0.5, 0.1)
+            got = e.fmx_ambient_fit(f, cand, 0.37)
+        parity.same_records(gcells, cells)
+        assert same(got, want) and got["kernel_ms"] > 0.0, devs
+
+
+@pytest.mark.parametrize("K,world,flags", [(20, 2, 0), (300, 3, 0)])
+def test_slabbed_ranks_and_the_sharded_driver(K, world, flags):
+    """every rank holds its two slabs (freemuxlet.load_rank) and fits its own cells; the exchanges of the driver are device
+    copies between the handles here (as in test_fmx_ambient_gpu.py).  The ranks' outputs, concatenated, are the one-handle
+    outputs bit for bit; and run_em(want_ambient_fit=...) returns them for the best clusters of the singlet table."""
+    import torch
+
+    p, f, cand, init, want, cells = identity_case(K, C=36)
+    (c_ranges, per_c), (s_ranges, per_s) = freemuxlet.plan_ranges(p.C, p.S, world)
+    engs = [muxgl.Engine(0, flags) for _ in range(world)]
+    for r, e in enumerate(engs):
+        freemuxlet.load_rank(e, p, c_ranges[r], s_ranges[r])
+        e.fmx_set_clusters(K, init)
+    for it in range(2):
+        for e in engs:
+            e.fmx_iter_gp(0.5, 0.1)
+        torch.cuda.synchronize()
+        _local_allgather(engs, muxgl.BUF_CGP, per_s, p.S, K * 3 * 8)
+        torch.cuda.synchronize()
+        for e in engs:
+            e.fmx_iter_estep(0.5, 0.1)
+        for e in engs:
+            e.fmx_iter_fetch()
+        if sum(e.fmx_exact_pending() for e in engs) > 0:
+            freemuxlet.settle_near_ties(engs, lambda obj: [obj], 0.5, 0.1)
+        torch.cuda.synchronize()
+        _local_allgather(engs, muxgl.BUF_CLUST, per_c, p.C, 4)
+        torch.cuda.synchronize()
+        for e in engs:
+            e.fmx_iter_mstep()
+    parts = [e.fmx_ambient_fit(f, np.ascontiguousarray(cand[c_ranges[r][0]:c_ranges[r][1]]), 0.37) for r, e in enumerate(engs)]
+    for e in engs:
+        e.close()
+    assert same({k: np.concatenate([x[k] for x in parts]) for k in FIELDS}, want)
+    with prepared(p) as e:
+        e.fmx_set_clusters(K, init)
+        for _ in range(2):
+            e.fmx_iterate(0.5, 0.1)
+        top = freemuxlet.top_clusters(e.fmx_singlets(), 3)
+        direct = e.fmx_ambient_fit(f, top, 0.37)
+    with prepared(p) as e:
+        out, hist, got = freemuxlet.run_em(e, K, init, max_iter=2, early_stop=False, want_ambient_fit=(f, 0.37, 3))
+    assert out.tobytes() == cells.tobytes() and np.array_equal(got["cand"], top) and same(got, direct)
+
+
+# ---- 5. state ------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("anchored", [None, "held", "prior"])
+def test_records_tables_pileups_and_timing_slots_stay(anchored):
+    K = 6
+    p, who, pool = small_case(K, seed=10200, entries=(40, 0, 90, 300, 7, 130, 64, 33, 2100, 12), S=2500)
+    cand = np.random.default_rng(3).integers(-1, K, size=(p.C, 3)).astype(np.int32)
+    with prepared(p) as e:
+        if anchored:
+            e.demux_set_gp(p.gp, p.has_gp)
+        e.fmx_set_clusters(K, who)
+        if anchored:
+            e.fmx_set_anchors([0, 1, 2], None if anchored == "held" else [muxgl.ANCHOR_PRIOR, muxgl.ANCHOR_HELD, muxgl.ANCHOR_PRIOR])
+        e.fmx_iterate(0.5, 0.1)
+        e.fmx_iter_gp(0.5, 0.1)
+        e.fmx_iter_estep(0.5, 0.1)
+
+        def state():
+            cells, st, full = e.fmx_iter_fetch(want_full_ll=True)
+            unk = e.fmx_unknown()
+            return (cells.tobytes(), tuple(st), full.tobytes(), e.fmx_singlets().tobytes(), e.fmx_ambient(pool, DEFAULT_RHOS)["ll"].tobytes(),
+                    tuple(unk[n].tobytes() for n in muxgl.FMX_UNKNOWN_FIELDS), tuple(x.tobytes() for x in e.fmx_cluster_pileup()),
+                    e.fmx_cluster_gp().tobytes(), _clust_buffer(e).tobytes())
+
+        s0 = state()
+        t0, (sum0, calls0) = e.timing().copy(), e.timing_sum()
+        a = e.fmx_ambient_fit(pool, cand, 0.5)
+        e.fmx_ambient_fit(pool, cand[:, :1], 0.25)
+        sum1, calls1 = e.timing_sum()
+        assert np.array_equal(e.timing(), t0) and np.array_equal(sum1, sum0) and calls1 == calls0   # every timing slot
+        assert state() == s0
+        e.fmx_iter_mstep()
+        assert same(e.fmx_ambient_fit(pool, cand, 0.5), a)                # behind the M-step: the same posteriors
+        assert (a["status"] == 0).any()
+
+
+@pytest.mark.parametrize("K,devs,flags", [(6, 0, 0), (40, 0, XE), (300, 0, 0), (24, [0, 0], 0)])
+def test_the_call_leaves_the_em_alone(K, devs, flags):
+    p = synth.make_pileup(300, 500, 4, seed=10300 + K, mean_entries=10, min_entries=2, reads_lambda=0.3, with_gp=False)
+    init = (np.arange(p.C) % 3).astype(np.int32)
+    f = ar.draw_af(p.S, seed=K)
+    cand = np.random.default_rng(K).integers(-1, K, size=(p.C, 2)).astype(np.int32)
+
+    def run(with_call):
+        out = []
+        with prepared(p, devs, flags) as e:
+            e.fmx_set_clusters(K, init)
+            for _ in range(4):
+                cells, st = e.fmx_iterate(0.5, 0.1)   # the twin handle never makes the call
+                if with_call:
+                    sng, t0 = e.fmx_singlets(), e.timing().copy()
+                    e.fmx_ambient_fit(f, cand, 0.5)
+                    assert np.array_equal(e.timing(), t0)
+                    assert e.fmx_singlets().tobytes() == sng.tobytes()   # the other table calls, before and after
+                    e.fmx_unknown()
+                    e.fmx_inclusion(0.5)
+                out.append((cells.tobytes(), tuple(st), tuple(x.tobytes() for x in e.fmx_cluster_pileup()), e.fmx_exact_stats()))
+        return out
+
+    assert run(False) == run(True)
+
+
+# ---- 6. refusals ---------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("devs", [0, [0, 0]])
+def test_refusals_leave_the_handle_usable(devs):
+    K = 5
+    p, who, pool = small_case(K, seed=612, entries=(5, 0, 130, 64), S=400)
+    f = pool
+    cand = np.stack([who, (who + 3) % K], axis=1).astype(np.int32)
+    with ready(p, K, who, devs) as e:
+        fresh = e.fmx_ambient_fit(f, cand, 0.5)
+    VP = ctypes.c_void_p
+
+    def raw(e, n_cand=2, cnd=cand, rho_max=0.5, outs=True, af=f):
+        bufs = [np.zeros(cand.shape), np.zeros(cand.shape), np.zeros(cand.shape), np.zeros(cand.shape),
+                np.zeros(cand.shape, np.int32), np.zeros(cand.shape, np.int32)]
+        rc = e.lib.muxgl_fmx_ambient_fit(e.h, None if af is None else af.ctypes.data_as(VP), n_cand,
+                                         None if cnd is None else cnd.ctypes.data_as(VP), ctypes.c_double(rho_max),
+                                         *[b.ctypes.data_as(VP) if outs else None for b in bufs], None)
+        return rc, e.lib.muxgl_last_error(e.h)
+
+    def refused(e, word, **kw):
+        rc, why = raw(e, **kw)
+        assert rc != 0 and why.startswith(b"muxgl_fmx_ambient_fit: ") and word in why, (kw, why)
+
+    with muxgl.Engine(devs) as e:
+        def still_good():
+            assert same(e.fmx_ambient_fit(f, cand, 0.5), fresh)
+
+        refused(e, b"no pileup")
+        e.set_pileup(p.S, p.cell_ptr, p.entry_snp, p.entry_rptr, p.reads)
+        refused(e, b"muxgl_fmx_prepare")
+        e.fmx_prepare(p.af)
+        refused(e, b"E-step")
+        e.fmx_set_clusters(K, who)
+        refused(e, b"no E-step since muxgl_fmx_set_clusters")
+        e.fmx_iterate(0.5, 0.1)
+        still_good()
+        refused(e, b"every output is NULL", outs=False)
+        still_good()
+        refused(e, b"cand is NULL", cnd=None)
+        refused(e, b"amb_af is NULL", af=None)
+        still_good()
+        for n_cand in (0, 17, -1):
+            refused(e, b"n_cand", n_cand=n_cand)
+        still_good()
+        for bad in (0.0, -0.1, 1.5, float("nan"), float("inf")):
+            refused(e, b"rho_max", rho_max=bad)
+        still_good()
+        for bad in (-2, K, 1 << 20):
+            c2 = cand.copy()
+            c2[2, 1] = bad
+            refused(e, b"cand[2][1]", cnd=c2)
+            still_good()
+        for bad in (-0.01, 1.5, float("nan"), float("inf")):
+            for s in (0, 17, p.S - 1):
+                g = f.copy()
+                g[s] = bad
+                g[min(s + 3, p.S - 1)] = bad                                             # (the first offending marker is named)
+                refused(e, f"amb_af of marker {s} ".encode(), af=g)
+            still_good()
+        with pytest.raises(ValueError):
+            e.fmx_ambient_fit(f[:-1], cand)
+        with pytest.raises(ValueError):
+            e.fmx_ambient_fit(f, cand[:-1])
+        if devs == 0:                    # (the phases run on a one-device handle)
+            e.fmx_iter_gp(0.5, 0.1)      # the posteriors of the NEXT iteration
+            refused(e, b"the cluster posteriors were rewritten")
+        e.fmx_set_clusters(K, who)       # fresh clusters: the fit of the old ones is gone
+        refused(e, b"no E-step since muxgl_fmx_set_clusters")
+        e.fmx_iterate(0.5, 0.1)
+        still_good()
