@@ -376,6 +376,49 @@ int muxgl_demux_ambient_fit(muxgl_handle* h, const muxgl_demux_params* p, const 
                             int32_t* status, int32_t* n_steps,                                /* [C][n_cand] or NULL */
                             float* kernel_ms);
 
+/* The mixing share of a doublet as a per-droplet maximum-likelihood estimate, for n_cand pairs of samples per droplet
+ * (pair[c][slot] = (j, k), or (-1, -1) to skip the slot).  muxgl_demux_run scores a pair only at the alphas of its grid,
+ * one V x V sweep per point; this call fits alpha for the pairs a caller names.  With j the first sample and alpha the
+ * share of k, the reference's own doublet term (cmd_cram_demuxlet.cpp:655-746):
+ *   p(l, m, alpha) = 0.5 * l + (m - l) * 0.5 * alpha                                                        (:673)
+ *   a_e[l][m]      = product over the usable reads of entry e of (pR * (1 - p) + pA * p)
+ *   w_e[l][m]      = (a_e[l][m] / q_max_e + 1e-10) / (1 + 1e-10), q_max_e the entry's scale under the alpha grid of p
+ *   LL(alpha)      = sum over the entries e of droplet c whose marker has genotypes of
+ *                    log( sum_l sum_m (gp[s_e][j][l] * gp[s_e][k][m]) * w_e[l][m] )                         (:738-746)
+ * Every read's factor is linear in alpha (dt/dalpha = (pA - pR) (m - l) 0.5, exactly 0 on the diagonal l == m), so an
+ * entry's product is a polynomial in alpha and LL', LL'' are analytic: the product rule along the reads, no division, no
+ * finite difference.  At every alpha[n] of the grid LL is the reference's llksAB[j][k][n]; alpha = 0 is sample j alone and
+ * alpha = 1 sample k alone, so both singlets nest in the model.  Per (c, slot), each array [C][n_cand]:
+ *   alpha_hat, ll_hat, info, status, n_steps   by the rules of muxgl_demux_ambient_fit above, with alpha in the place of
+ *            rho: the nine points i * alpha_max / 8, the best of them (ties to the lowest index) with its two neighbours
+ *            as the bracket, safeguarded Newton on LL', the same stops, 48 steps; status 0 interior, 1 at the lower bound
+ *            (alpha_hat == 0.0 exactly), 2 at the upper (alpha_hat == alpha_max exactly), 3 step cap, 4 slot skipped (an
+ *            index < 0: all outputs 0), 5 droplet without a scored entry (all outputs 0);
+ *   ll_zero  LL(0): sample j alone, the reference's llksAB[j][k][n] for alpha[n] == 0, within rounding of j's entry of
+ *            muxgl_demux_singlets;
+ *   ll_top   LL(alpha_max), coarse point 8: with alpha_max == 1 sample k alone, with alpha_max == alpha[n] the reference's
+ *            llksAB[j][k][n].  At status 2 ll_hat == ll_top bit for bit, at status 1 ll_hat == ll_zero.
+ * The caller's standard error of alpha_hat is info^(-1/2) where status is 0 and info > 0; on a bound there is
+ * NO standard error.  With alpha_max == 1 the likelihood ratio against "one cell" is 2 * (ll_hat - max(ll_zero, ll_top)).
+ * Needs muxgl_set_pileup and muxgl_demux_set_gp, not a previous muxgl_demux_run; any V up to MUXGL_MAX_SAMPLES (no full_ll
+ * tensor, no 255-sample limit); 1 <= n_cand <= MUXGL_MAX_FIT_CAND; 0 < alpha_max <= 1, finite; every index in [-1, V);
+ * j == k is allowed (the reference's slot (j, j, n)); any of the seven outputs may be NULL, not all; one device or a
+ * device group (every member fits its own cells).  It fails, naming the reason and leaving the handle usable, without a
+ * pileup or a GP tensor, with every output NULL, with pair == NULL, with n_cand, n_alpha, alpha_max or an index out of
+ * range, and with a slot of exactly one negative index.  kernel_ms (NULL allowed) receives the hipEvent time of the
+ * call's one kernel, from a pair of events the call makes for itself (a group: the slowest member's).  The call reads
+ * state and changes none: records, full_ll, plans, timing slots and the cached grid stay as they are.
+ * Device memory: pair and the outputs.  Nothing proportional to nnz is allocated, so no slab budget applies and
+ * MUXGL_DEMUX_SLAB_MB is not read.  The whole fit of a (droplet, slot) runs in one wave of one launch with every
+ * reduction tree fixed by the droplet alone: the outputs are bit-identical from call to call, for any order, grouping or
+ * repetition of slots, for any subset of outputs, on one device, on a group and through the sharded driver. */
+int muxgl_demux_alpha_fit(muxgl_handle* h, const muxgl_demux_params* p,
+                          int32_t n_cand, const int32_t* pair /* [C][n_cand][2]: (j, k), or (-1, -1) to skip */,
+                          double alpha_max,
+                          double* alpha_hat, double* ll_hat, double* ll_zero, double* ll_top, double* info, /* each [C][n_cand] or NULL */
+                          int32_t* status, int32_t* n_steps,                                                /* [C][n_cand] or NULL */
+                          float* kernel_ms);
+
 /* The calls rounding noise could decide, settled in the reference's own arithmetic -- HOST pass, no device work, no
  * handle (popscle_amd/host/exact_calls.hpp).  The kernels' log-likelihoods equal the reference's to ~1e-12, not to the last
  * bit, and every decision of cmd_cram_demuxlet.cpp:827-837,883-906,925-988 compares two of them.  For the cells of

@@ -691,6 +691,13 @@ int demux_ambient_fit_run(muxgl_handle* h, const muxgl_demux_params* p, const do
                           int32_t* n_steps, float* kernel_ms);
 int demux_ambient_fit_bad_args(const double* amb_af, int32_t n_cand, const int32_t* cand, int64_t C,
                                int V, double rho_max, bool any_out, char* why, size_t n);
+// demux_alpha_fit.hip: the fit of muxgl_demux_alpha_fit to the host, rows of the handle's own cells; the arguments are
+// checked by the caller (demux_alpha_fit_bad_args: 0, or 1 with the reason written to `why`)
+int demux_alpha_fit_run(muxgl_handle* h, const muxgl_demux_params* p, int n_cand, const int32_t* pair, double alpha_max,
+                        double* alpha_hat, double* ll_hat, double* ll_zero, double* ll_top, double* info, int32_t* status,
+                        int32_t* n_steps, float* kernel_ms);
+int demux_alpha_fit_bad_args(int32_t n_cand, const int32_t* pair, int64_t C, int V, double alpha_max, bool any_out, char* why,
+                             size_t n);
 // demux_ambient.hip: usable reads by marker and allele of the handle's own cells whose mask byte is set (cell_mask: host
 // [C] or NULL), to n_ref / n_alt (host [S])
 int pileup_allele_counts_run(muxgl_handle* h, const uint8_t* cell_mask, int64_t* n_ref, int64_t* n_alt);
@@ -799,6 +806,9 @@ int group_pileup_allele_counts(muxgl_handle* h, const uint8_t* cell_mask, int64_
 int group_demux_ambient_fit(muxgl_handle* h, const muxgl_demux_params* p, const double* amb_af, int32_t n_cand,
                             const int32_t* cand, double rho_max, double* rho_hat, double* ll_hat, double* ll_zero, double* info,
                             int32_t* status, int32_t* n_steps, float* kernel_ms);
+int group_demux_alpha_fit(muxgl_handle* h, const muxgl_demux_params* p, int32_t n_cand, const int32_t* pair, double alpha_max,
+                          double* alpha_hat, double* ll_hat, double* ll_zero, double* ll_top, double* info, int32_t* status,
+                          int32_t* n_steps, float* kernel_ms);
 const muxgl_demux_cell* group_demux_results(const muxgl_handle* h);
 int group_demux_get_entry_pg(muxgl_handle* h, double* pg);
 int group_fmx_prepare(muxgl_handle* h, const double* af, double* cell_llk0, double* cell_llk2, int32_t* cell_nsnps,

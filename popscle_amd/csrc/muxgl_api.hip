@@ -702,6 +702,25 @@ int muxgl_demux_ambient_fit(muxgl_handle* h, const muxgl_demux_params* p, const 
   return demux_ambient_fit_run(h, p, amb_af, n_cand, cand, rho_max, rho_hat, ll_hat, ll_zero, info, status, n_steps, kernel_ms);
 }
 
+int muxgl_demux_alpha_fit(muxgl_handle* h, const muxgl_demux_params* p, int32_t n_cand, const int32_t* pair, double alpha_max,
+                          double* alpha_hat, double* ll_hat, double* ll_zero, double* ll_top, double* info, int32_t* status,
+                          int32_t* n_steps, float* kernel_ms) {
+  if (!h) return 1;
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (h->group)
+    return group_demux_alpha_fit(h, p, n_cand, pair, alpha_max, alpha_hat, ll_hat, ll_zero, ll_top, info, status, n_steps,
+                                 kernel_ms);
+  HIPCHK(h, hipSetDevice(h->device));
+  if (check_demux_params(h, p)) return 1;
+  char why[256];
+  if (demux_alpha_fit_bad_args(n_cand, pair, h->C, h->V, alpha_max,
+                               alpha_hat || ll_hat || ll_zero || ll_top || info || status || n_steps, why, sizeof(why)))
+    MUXGL_FAIL(h, "%s", why);
+  // (no clear_timing, no timing slot: the call reads state and changes none)
+  return demux_alpha_fit_run(h, p, n_cand, pair, alpha_max, alpha_hat, ll_hat, ll_zero, ll_top, info, status, n_steps,
+                             kernel_ms);
+}
+
 int muxgl_demux_oct_split(const muxgl_handle* h, int64_t* info) {
   if (!h || !info) return 1;
   if (h->group) {

@@ -392,6 +392,31 @@ int group_demux_ambient_fit(muxgl_handle* h, const muxgl_demux_params* p, const 
   return 0;
 }
 
+// every member fits its own cells and writes their rows of the caller's arrays; kernel_ms: the slowest member's
+int group_demux_alpha_fit(muxgl_handle* h, const muxgl_demux_params* p, int32_t n_cand, const int32_t* pair, double alpha_max,
+                          double* alpha_hat, double* ll_hat, double* ll_zero, double* ll_top, double* info, int32_t* status,
+                          int32_t* n_steps, float* kernel_ms) {
+  muxgl_group* g = h->group;
+  if (!p) MUXGL_FAIL(h, "demux params NULL");
+  if (p->n_alpha < 1 || p->n_alpha > MUXGL_MAX_ALPHA) MUXGL_FAIL(h, "n_alpha=%d outside [1,%d]", p->n_alpha, MUXGL_MAX_ALPHA);
+  if (!g->have_pileup) MUXGL_FAIL(h, "no pileup set (muxgl_set_pileup)");
+  if (g->V < 1) MUXGL_FAIL(h, "no GP tensor set (muxgl_demux_set_gp)");
+  char why[256];
+  if (demux_alpha_fit_bad_args(n_cand, pair, g->C, g->V, alpha_max,
+                               alpha_hat || ll_hat || ll_zero || ll_top || info || status || n_steps, why, sizeof(why)))
+    MUXGL_FAIL(h, "%s", why);
+  std::vector<float> ms((size_t)g->n, 0.f);
+  if (for_members(h, [&](int r) {
+        const size_t o = (size_t)g->cb[(size_t)r] * (size_t)n_cand;
+        auto at = [o](auto* q) { return q ? q + o : nullptr; };
+        return muxgl_demux_alpha_fit(g->m[(size_t)r], p, n_cand, pair + 2 * o, alpha_max, at(alpha_hat), at(ll_hat), at(ll_zero),
+                                     at(ll_top), at(info), at(status), at(n_steps), kernel_ms ? &ms[(size_t)r] : nullptr);
+      }))
+    return 1;
+  if (kernel_ms) *kernel_ms = *std::max_element(ms.begin(), ms.end());
+  return 0;
+}
+
 // every member counts the reads of its own cells; the counts are added here (integers: exact in any order)
 int group_pileup_allele_counts(muxgl_handle* h, const uint8_t* cell_mask, int64_t* n_ref, int64_t* n_alt) {
   muxgl_group* g = h->group;

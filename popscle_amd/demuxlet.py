@@ -18,8 +18,21 @@ def top_samples(sng, n_top):
     return np.ascontiguousarray(order[:, :n_top], dtype=np.int32)
 
 
+def call_pairs(records):
+    """int32 [C][2][2]: per record of Engine.demux_run the pairs (dBest1, dBest2) and (sBest, sNext), each (-1, -1) where the
+    record is not valid or either index is missing (negative): the slots Engine.demux_alpha_fit takes"""
+    rec = np.asarray(records)
+    out = np.full((rec.shape[0], 2, 2), -1, dtype=np.int32)
+    for slot, (a, b) in enumerate((("dBest1", "dBest2"), ("sBest", "sNext"))):
+        ok = (rec["valid"] != 0) & (rec[a] >= 0) & (rec[b] >= 0)
+        out[ok, slot, 0] = rec[a][ok]
+        out[ok, slot, 1] = rec[b][ok]
+    return out
+
+
 def run_sharded(engine_factory, p, alphas=(0.0, 0.5), doublet_prior=0.5, exchange=None, want_singlets=False,
-                want_inclusion=False, *, want_unknown=False, want_ambient=None, want_ambient_fit=None):
+                want_inclusion=False, *, want_unknown=False, want_ambient=None, want_ambient_fit=None,
+                want_alpha_fit=None):
     """engine_factory() -> object with set_pileup / demux_set_gp / demux_run (muxgl.Engine).  Returns the [C] records of
     the whole pileup on every rank, in the original cell order; with want_singlets also the [C][V] table of singlet
     log-likelihoods (Engine.demux_singlets), gathered the same way: (records, sng); with want_inclusion also the dict of
@@ -27,7 +40,9 @@ def run_sharded(engine_factory, p, alphas=(0.0, 0.5), doublet_prior=0.5, exchang
     (keyword only) also the dict of the three tables of Engine.demux_unknown (panel mean); with want_ambient = (amb_af,
     rhos) (keyword only) also the [C][V][n_rho] table of Engine.demux_ambient; with want_ambient_fit = (amb_af, rho_max,
     n_top) (keyword only) also the dict of Engine.demux_ambient_fit for the n_top best samples of every droplet's row of the
-    singlet table (ties to the lower index) with those candidates under "cand" ([C][n_top]), as the last element.
+    singlet table (ties to the lower index) with those candidates under "cand" ([C][n_top]); with want_alpha_fit =
+    (alpha_max,) (keyword only) also the dict of Engine.demux_alpha_fit for the two pairs of call_pairs() of every droplet
+    with those pairs under "pair" ([C][2][2]), as the last element.
     Cells are independent, so every rank fills the rows of its own cells."""
     ex = exchange or NoExchange()
     ranges = shard.cell_shards(p.cell_ptr, ex.world)
@@ -41,7 +56,8 @@ def run_sharded(engine_factory, p, alphas=(0.0, 0.5), doublet_prior=0.5, exchang
     out = np.zeros(p.C, dtype=cells.dtype)
     for b, e, raw in parts:
         out[b:e] = np.frombuffer(raw, dtype=cells.dtype)
-    if not want_singlets and not want_inclusion and not want_unknown and want_ambient is None and want_ambient_fit is None:
+    if not want_singlets and not want_inclusion and not want_unknown and want_ambient is None and want_ambient_fit is None \
+            and want_alpha_fit is None:
         return out
     ret = [out]
     V = p.gp.shape[1]
@@ -80,5 +96,15 @@ def run_sharded(engine_factory, p, alphas=(0.0, 0.5), doublet_prior=0.5, exchang
         for b, e, raw in ex.gather_objects((c0, c1, {k: v.tobytes() for k, v in mine.items()})):
             for k, v in fit.items():
                 v[b:e] = np.frombuffer(raw[k], dtype=v.dtype).reshape(e - b, n_top)
+        ret.append(fit)
+    if want_alpha_fit is not None:
+        (alpha_max,) = want_alpha_fit
+        got = eng.demux_alpha_fit(alphas, call_pairs(cells), alpha_max)
+        mine = {k: got[k] for k in eng.ALPHA_FIT_FIELDS + ("pair",)}
+        fit = {k: np.zeros((p.C,) + v.shape[1:], dtype=v.dtype) for k, v in mine.items()}
+        for b, e, raw in ex.gather_objects((c0, c1, {k: v.tobytes() for k, v in mine.items()})):
+            for k, v in fit.items():
+                v[b:e] = np.frombuffer(raw[k], dtype=v.dtype).reshape((e - b,) + v.shape[1:])
+        fit["alpha_max"] = float(alpha_max)
         ret.append(fit)
     return tuple(ret)

@@ -38,6 +38,14 @@
 //       NUM.SNPS, NUM.READS, SM_ID, SNG.LLK (the sample's singlet LLK), AMB.RHO.MLE, AMB.RHO.SE (the standard error from the
 //       observed information; NA on a bound or where the information is not positive), AMB.LLK.MLE, AMB.LRT = 2 (AMB.LLK.MLE -
 //       SNG.LLK), STATUS (0 interior, 1 lower bound, 2 upper bound, 3 step cap, 5 no scored marker); all %.4lf
+//       --fit-alpha: also <O>.alphafit.gz (BGZF), per printed droplet one row DBL for the two samples of DBL.BEST.GUESS and
+//       one row SNG for (SNG.BEST.GUESS, SNG.NEXT.GUESS) of .best: the maximum-likelihood share alpha of the second sample
+//       on [0, --alpha-fit-max x] (default 1.0) under the reference's doublet model (muxgl_demux_alpha_fit).  Columns
+//       BARCODE, NUM.SNPS, NUM.READS, PAIR, SM1_ID, SM2_ID, SNG1.LLK (the first sample alone), SNG2.LLK (the second alone; NA
+//       when x < 1), ALPHA.MLE, ALPHA.SE (the standard error from the observed information; NA on a bound or where the
+//       information is not positive), MIX.LLK.MLE, MIX.LRT = 2 (MIX.LLK.MLE - the better of SNG1.LLK and SNG2.LLK; SNG1.LLK
+//       alone when x < 1), STATUS (0 interior, 1 lower bound, 2 upper bound, 3 step cap, 5 no scored marker); all %.4lf.
+//       .best and every other file are unchanged
 //   popscle-amd freemuxlet --plp P --nsample K --out O [...]                   mirrors cmdCramFreemux2 (cmd_cram_freemux2.cpp)
 //       --write-singlets: also <O>.clust1.sing2.gz (BGZF), the singlet log-likelihood of every droplet against every
 //       cluster as the last EM iteration formed it (llks[j(j+1)/2 + j], cmd_cram_freemux2.cpp:448-455; the reference
@@ -211,6 +219,8 @@ int cmd_demuxlet(int argc, char** argv) {
   bool writeAmbient = false;  // (ours) <out>.amb.gz: the droplet as one cell plus a share of ambient RNA (muxgl_demux_ambient)
   bool fitAmbient = false;  // (ours) <out>.ambfit.gz: the maximum-likelihood ambient share with its standard error (muxgl_demux_ambient_fit)
   double ambFitMax = 0.5;
+  bool fitAlpha = false;  // (ours) <out>.alphafit.gz: the maximum-likelihood mixing share of the best doublet and of the two best singlets (muxgl_demux_alpha_fit)
+  double alphaFitMax = 1.0;
   std::vector<double> ambRho;
   std::string ambAfFile;
   int32_t ambMaxReads = 0;
@@ -220,6 +230,8 @@ int cmd_demuxlet(int argc, char** argv) {
   a.add_bool("write-ambient", &writeAmbient);
   a.add_bool("fit-ambient", &fitAmbient);
   a.add_double("ambient-fit-max", &ambFitMax);
+  a.add_bool("fit-alpha", &fitAlpha);
+  a.add_double("alpha-fit-max", &alphaFitMax);
   a.add_multi_double("ambient-rho", &ambRho);
   a.add_string("ambient-af", &ambAfFile);
   a.add_int("ambient-max-reads", &ambMaxReads);
@@ -257,6 +269,7 @@ int cmd_demuxlet(int argc, char** argv) {
   if ((int)ambRho.size() > MUXGL_MAX_ALPHA) fatal("at most %d --ambient-rho values are supported", MUXGL_MAX_ALPHA);
   if (ambMaxReads < 0) fatal("--ambient-max-reads must not be negative");
   if (!(std::isfinite(ambFitMax) && ambFitMax > 0.0 && ambFitMax <= 1.0)) fatal("--ambient-fit-max must lie in (0, 1]");
+  if (!(std::isfinite(alphaFitMax) && alphaFitMax > 0.0 && alphaFitMax <= 1.0)) fatal("--alpha-fit-max must lie in (0, 1]");
   vr.wanted = smIDs;
   if (!smList.empty()) {
     TsvReader t(smList);
@@ -526,6 +539,55 @@ int cmd_demuxlet(int argc, char** argv) {
     }
     wf.close();
     tm.lap("demuxlet: write .ambfit.gz");
+  }
+  if (fitAlpha) {
+    // .alphafit.gz: per printed droplet (the order and the filters of .best) one row DBL for the two samples of DBL.BEST
+    // and one row SNG for (SNG.BEST, SNG.NEXT) (none where .best has NA there)
+    const size_t n = (size_t)p.C() * 2;
+    std::vector<int32_t> pair(n * 2), status(n);
+    auto ok = [&](int32_t s) { return s >= 0 && s < p.nv; };
+    for (int64_t i = 0; i < p.C(); ++i) {
+      const muxgl_demux_cell& c = cells[(size_t)i];
+      int32_t* q = &pair[(size_t)i * 4];
+      const bool dbl = c.valid && ok(c.dBest1) && ok(c.dBest2), sng = c.valid && ok(c.sBest) && ok(c.sNext);
+      q[0] = dbl ? c.dBest1 : -1, q[1] = dbl ? c.dBest2 : -1;
+      q[2] = sng ? c.sBest : -1, q[3] = sng ? c.sNext : -1;
+    }
+    std::vector<double> ah(n), llh(n), ll0(n), llt(n), info(n);
+    check(h, muxgl_demux_alpha_fit(h, &dp, 2, pair.data(), alphaFitMax, ah.data(), llh.data(), ll0.data(), llt.data(), info.data(),
+                                   status.data(), nullptr, nullptr),
+          "muxgl_demux_alpha_fit");
+    tm.lap("demuxlet: muxgl_demux_alpha_fit");
+    OutFile wf(cf.outPrefix + ".alphafit.gz", true);
+    wf.printf("BARCODE\tNUM.SNPS\tNUM.READS\tPAIR\tSM1_ID\tSM2_ID\tSNG1.LLK\tSNG2.LLK\tALPHA.MLE\tALPHA.SE\tMIX.LLK.MLE\tMIX.LRT\t"
+              "STATUS\n");
+    const bool whole = alphaFitMax == 1.0;  // (only then is ll_top the second sample alone)
+    int64_t mixed = 0;
+    for (auto it = bc_map.begin(); it != bc_map.end(); ++it) {
+      const int32_t i = it->second;
+      const muxgl_demux_cell& c = cells[(size_t)i];
+      if (p.cell_totl_reads[(size_t)i] < cf.lo.minRead || p.cell_uniq_reads[(size_t)i] < cf.lo.minUMI ||
+          c.nsnps < cf.lo.minSNP || !c.valid)
+        continue;
+      for (size_t k = 0; k < 2; ++k) {
+        const size_t x = (size_t)i * 2 + k;
+        if (pair[x * 2] < 0) continue;
+        const double one = whole ? std::max(ll0[x], llt[x]) : ll0[x];
+        wf.printf("%s\t%u\t%d\t%s\t%s\t%s\t%.4lf\t", it->first.c_str(), (unsigned)c.nsnps, p.cell_uniq_reads[(size_t)i],
+                  k == 0 ? "DBL" : "SNG", sid(p, pair[x * 2]), sid(p, pair[x * 2 + 1]), ll0[x]);
+        if (whole) wf.printf("%.4lf", llt[x]);
+        else wf.printf("NA");
+        wf.printf("\t%.4lf\t", ah[x]);
+        if (status[x] == 0 && info[x] > 0.0) wf.printf("%.4lf", 1.0 / sqrt(info[x]));  // (on a bound: no standard error)
+        else wf.printf("NA");
+        wf.printf("\t%.4lf\t%.4lf\t%d\n", llh[x], 2.0 * (llh[x] - one), (int)status[x]);
+        if (k == 1 && c.type == 0 && llh[x] > one + 2.0) ++mixed;
+      }
+    }
+    wf.close();
+    notice("Mixing share: %lld droplets called SNG are explained better, by more than 2 in log-likelihood, as a mix of their "
+           "best and next singlet at the fitted share than as the better of the two alone", (long long)mixed);
+    tm.lap("demuxlet: write .alphafit.gz");
   }
   notice("Finished writing output files");
   muxgl_destroy(h);
@@ -1767,6 +1829,9 @@ int main(int argc, char** argv) {
                     "  demuxlet --fit-ambient [--ambient-fit-max x] [--ambient-af FILE] [--ambient-max-reads N]: also <out>.ambfit.gz,\n"
                     "      per printed droplet and for its best and next singlet sample the maximum-likelihood ambient share on\n"
                     "      [0, x] (default 0.5) with its standard error and the likelihood ratio against no ambient RNA\n"
+                    "  demuxlet --fit-alpha [--alpha-fit-max x]: also <out>.alphafit.gz, per printed droplet the maximum-likelihood\n"
+                    "      mixing share on [0, x] (default 1.0) of its best doublet's two samples (row DBL) and of its best and next\n"
+                    "      singlet sample (row SNG), with its standard error and the likelihood ratio against the better singlet\n"
                     "  freemuxlet --write-ambient [--ambient-rho x ...] [--ambient-af FILE] [--ambient-max-reads N]: also\n"
                     "    <out>.clust1.amb.gz, per droplet the best reading as one cell of a cluster plus a share rho of ambient RNA\n"
                     "  freemuxlet --fit-ambient [--ambient-fit-max x] [--ambient-af FILE] [--ambient-max-reads N]: also\n"

@@ -101,6 +101,8 @@ SYMBOLS = {
     "muxgl_pileup_allele_counts": (C.c_int, [_VP, _VP, _VP, _VP]),
     "muxgl_demux_ambient_fit": (C.c_int, [_VP, C.POINTER(_DemuxParams), _VP, C.c_int32, _VP, C.c_double,
                                           _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "muxgl_demux_alpha_fit": (C.c_int, [_VP, C.POINTER(_DemuxParams), C.c_int32, _VP, C.c_double,
+                                        _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "muxgl_demux_results": (_VP, [_VP]),
     "muxgl_demux_oct_split": (C.c_int, [_VP, _VP]),
     "muxgl_demux_exact_calls": (C.c_int, [C.c_int64, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP,
@@ -306,6 +308,28 @@ def ambient_fit_summary(fit):
     se[ok] = 1.0 / np.sqrt(info[ok])
     lrt = 2.0 * (np.asarray(fit["ll_hat"], dtype=np.float64) - np.asarray(fit["ll_zero"], dtype=np.float64))
     return {"se": se, "lrt": lrt}
+
+
+def alpha_fit_summary(fit):
+    """What a caller reads off the dict of Engine.demux_alpha_fit (with its "pair" and "alpha_max").  Pure numpy.  Returns a
+    dict of arrays of the shape of fit["alpha_hat"]: se, the standard error info ** -0.5 of alpha_hat where status is 0 and
+    info > 0 and NaN elsewhere (an estimate on a bound has no standard error); lrt, the likelihood ratio
+    2 * (ll_hat - max(ll_zero, ll_top)) against the better of the two samples alone where alpha_max is 1 (ll_top is then
+    the second sample alone) and 2 * (ll_hat - ll_zero) against the first alone where it is smaller; major, int32, the
+    sample of the pair that holds the larger share: the second where alpha_hat > 0.5, else the first (-1 where the slot
+    was skipped)."""
+    info = np.asarray(fit["info"], dtype=np.float64)
+    status = np.asarray(fit["status"])
+    ok = (status == 0) & (info > 0.0)
+    se = np.full(info.shape, np.nan)
+    se[ok] = 1.0 / np.sqrt(info[ok])
+    one = np.asarray(fit["ll_zero"], dtype=np.float64)
+    if float(fit.get("alpha_max", 1.0)) == 1.0:
+        one = np.maximum(one, np.asarray(fit["ll_top"], dtype=np.float64))
+    lrt = 2.0 * (np.asarray(fit["ll_hat"], dtype=np.float64) - one)
+    pair = np.asarray(fit["pair"]).reshape(info.shape + (2,))
+    major = np.where(np.asarray(fit["alpha_hat"]) > 0.5, pair[..., 1], pair[..., 0]).astype(np.int32)
+    return {"se": se, "lrt": lrt, "major": major}
 
 
 def _ptr(a):
@@ -571,6 +595,43 @@ class Engine:
         self._check(self.lib.muxgl_demux_ambient_fit(self.h, C.byref(p), _ptr(amb_af), cand.shape[1], _ptr(cand),
                                                       float(rho_max), *[_ptr(out.get(n)) for n in self.AMBIENT_FIT_FIELDS],
                                                       C.byref(ms)))
+        out["kernel_ms"] = float(ms.value)
+        return out
+
+    ALPHA_FIT_FIELDS = ("alpha_hat", "ll_hat", "ll_zero", "ll_top", "info", "status", "n_steps")
+
+    def demux_alpha_fit(self, params, pairs, alpha_max=1.0, want=ALPHA_FIT_FIELDS):
+        """muxgl_demux_alpha_fit: per droplet and pair of samples (j, k), the maximum-likelihood share alpha of k on
+        [0, alpha_max] under the reference's doublet model, with its observed information (include/muxgl.h).  params: the
+        alpha grid (a sequence of alphas); pairs: int32 [C][n_cand][2] (or [C][2]), (j, k) or (-1, -1) per slot.  dict of
+        alpha_hat, ll_hat, ll_zero, ll_top, info float64 [C][n_cand], status, n_steps int32 [C][n_cand], the pairs under
+        "pair", alpha_max, and kernel_ms.  want: the subset of the seven to fetch (the others are passed as NULL).
+        alpha_fit_summary() gives the standard error, the likelihood ratio and the major sample."""
+        alphas = params
+        if len(alphas) > MAX_ALPHA:
+            raise ValueError("too many alphas")
+        unknown = set(want) - set(self.ALPHA_FIT_FIELDS)
+        if unknown:
+            raise ValueError(f"unknown fields {sorted(unknown)}")
+        p = _DemuxParams()
+        p.n_alpha = len(alphas)
+        for i, a in enumerate(alphas):
+            p.alpha[i] = float(a)
+        p.doublet_prior = 0.5  # (not read by the call)
+        pairs = _arr(pairs, np.int32, "pairs")
+        if pairs.ndim == 2:
+            pairs = pairs.reshape(-1, 1, 2)
+        if pairs.ndim != 3 or pairs.shape[0] != self.C or pairs.shape[2] != 2:
+            raise ValueError("pairs must be [C][n_cand][2]")
+        out = {}
+        for name in self.ALPHA_FIT_FIELDS:
+            if name in want:
+                out[name] = np.zeros(pairs.shape[:2], dtype=np.int32 if name in ("status", "n_steps") else np.float64)
+        ms = C.c_float(0.0)
+        self._check(self.lib.muxgl_demux_alpha_fit(self.h, C.byref(p), pairs.shape[1], _ptr(pairs), float(alpha_max),
+                                                    *[_ptr(out.get(n)) for n in self.ALPHA_FIT_FIELDS], C.byref(ms)))
+        out["pair"] = pairs
+        out["alpha_max"] = float(alpha_max)
         out["kernel_ms"] = float(ms.value)
         return out
 
