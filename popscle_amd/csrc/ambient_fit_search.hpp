@@ -1,6 +1,8 @@
-// ambient_fit_search.hpp -- the search of the two ambient fits, muxgl_demux_ambient_fit (demux_ambient_fit.hip)
-// and muxgl_fmx_ambient_fit (fmx_ambient_fit.hip): one wave maximises LL(rho) on [0, rho_max] for one
-// (droplet, candidate).  The model is the caller's: two callables that return, in every lane the same bits,
+// ambient_fit_search.hpp -- what the per-droplet fits share: muxgl_demux_ambient_fit (demux_ambient_fit.hip),
+// muxgl_fmx_ambient_fit (fmx_ambient_fit.hip) and muxgl_demux_alpha_fit (demux_alpha_fit.hip, DESIGN 4.1h,
+// where rho reads alpha): the search, the pieces of a pass that do not depend on the model, the store of a result and the
+// host side of the call.  The search: one wave maximises LL(rho) on [0, rho_max] for one (droplet, candidate).  The model
+// is the caller's: two callables that return, in every lane the same bits,
 //   coarse(x[3], o[3])   o[k] = LL(x[k]) for k < NC
 //   deriv(x, L, d1, d2)  (LL, LL', LL'') at x
 // so every decision below is wave-uniform.  The rules:
@@ -53,8 +55,47 @@ __device__ __forceinline__ double uniform(double v) {
 
 struct result {
   double rho_hat = 0.0, ll_hat = 0.0, ll_zero = 0.0, info = 0.0;
+  double ll_top = 0.0;  // LL at the upper bound: the caller's, for a call with five double rows (muxgl_demux_alpha_fit)
   int32_t status = SKIPPED, steps = 0;
 };
+
+// ---- what the passes of the fits share ----
+// The product rule along the reads for NE elements, am = (a[NE], a'[NE], a''[NE]): tv(i, t, v) gives element i's factor t
+// of this read and its slope v; a'' = a'' t + 2 a' v; a' = a' t + a v; a = a t, in this order.
+template <int NE, class TV>
+__device__ __forceinline__ void product_rule(double* am, TV&& tv) {
+#pragma unroll
+  for (int i = 0; i < NE; ++i) {
+    double t, v;
+    tv(i, t, v);
+    am[2 * NE + i] = fma(am[2 * NE + i], t, (am[NE + i] + am[NE + i]) * v);
+    am[NE + i] = fma(am[NE + i], t, am[i] * v);
+    am[i] *= t;
+  }
+}
+
+// an entry's (D, D', D'') added to the lane's (LL, LL', LL''): log D, D' / D, D'' / D - (D' / D)^2
+__device__ __forceinline__ void add_entry(double D, double D1, double D2, double& s0, double& s1, double& s2) {
+  const double iD = 1.0 / D;
+  const double q1 = D1 * iD;
+  s0 += pos_log(D, 0.0);
+  s1 += q1;
+  s2 += fma(-q1, q1, D2 * iD);
+}
+
+// the end of a pass: the lanes' sums added over the wave, the N that the pass formed (the others are 0), and the lanes'
+// counts of scored entries where the caller asks for them
+template <int N>
+__device__ __forceinline__ void pass_sums(double s0, double s1, double s2, int ns, double (&out)[3], int* n_scored) {
+  out[0] = wave_sum(s0);
+  out[1] = N > 1 ? wave_sum(s1) : 0.0;
+  out[2] = N > 2 ? wave_sum(s2) : 0.0;
+  if (n_scored) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) ns += __shfl_xor(ns, off, 64);
+    *n_scored = ns;
+  }
+}
 
 // NC: coarse points per pass (1 or 3).  FINITE: end with NOT_FINITE when LL at a coarse point is not finite (rho_hat = 0,
 // ll_hat = ll_zero = -inf, info = 0, no step).  empty(): after the first derivative pass, whether the droplet has no scored
@@ -212,8 +253,9 @@ __device__ __forceinline__ result search_piecewise(double rho_max, Coarse&& coar
                       best == FINE && x == rho_max, ll_zero, deriv, empty);
 }
 
-// lane 0 of the wave of `unit` writes its row: dout [4][n_units] rho_hat, ll_hat, ll_zero, info; iout [2][n_units] status,
-// n_steps
+// lane 0 of the wave of `unit` writes its row: dout [ROWS][n_units] rho_hat, ll_hat, ll_zero, info and, with five rows,
+// ll_top; iout [2][n_units] status, n_steps
+template <int ROWS = 4>
 __device__ __forceinline__ void store(const result& r, int lane, int64_t unit, int64_t n_units, double* __restrict__ dout,
                                       int32_t* __restrict__ iout) {
   if (lane == 0) {
@@ -221,28 +263,37 @@ __device__ __forceinline__ void store(const result& r, int lane, int64_t unit, i
     dout[n_units + unit] = r.ll_hat;
     dout[2 * n_units + unit] = r.ll_zero;
     dout[3 * n_units + unit] = r.info;
+    if (ROWS > 4) dout[4 * n_units + unit] = r.ll_top;
     iout[unit] = r.status;
     iout[n_units + unit] = r.steps;
   }
 }
 
 // ---- the host side of a fit call ----
-struct outputs {  // each host [C][n_cand] or NULL
+struct outputs {  // each host [C][n_cand] or NULL; ll_top: the calls with five double rows only
   double *rho_hat, *ll_hat, *ll_zero, *info;
   int32_t *status, *n_steps;
-  bool any() const { return rho_hat || ll_hat || ll_zero || info || status || n_steps; }
+  double* ll_top = nullptr;
+  bool any() const { return rho_hat || ll_hat || ll_zero || info || ll_top || status || n_steps; }
 };
 
-// the arguments both calls check alike, on the host: 0, or 1 with the reason in `why`.  what: "sample" or "cluster", n_what
-// of them
-inline int bad_args(const char* who, const char* what, const double* amb_af, int32_t n_cand, const int32_t* cand, int64_t C,
-                    int n_what, double rho_max, bool any_out, char* why, size_t n) {
+// the arguments every fit checks alike before its indices, on the host: 0, or 1 with the reason in `why`.  null_arg: the
+// name of a pointer argument that is NULL, or NULL; bound: the name of x_max ("rho_max", "alpha_max")
+inline int bad_head(const char* who, int32_t n_cand, const char* null_arg, const char* bound, double x_max, bool any_out,
+                    char* why, size_t n) {
   if (!any_out) return snprintf(why, n, "%s: every output is NULL", who), 1;
   if (n_cand < 1 || n_cand > MUXGL_MAX_FIT_CAND)
     return snprintf(why, n, "%s: n_cand=%d outside [1,%d]", who, n_cand, MUXGL_MAX_FIT_CAND), 1;
-  if (!cand || !amb_af) return snprintf(why, n, "%s: %s is NULL", who, cand ? "amb_af" : "cand"), 1;
-  if (!(std::isfinite(rho_max) && rho_max > 0.0 && rho_max <= 1.0))
-    return snprintf(why, n, "%s: rho_max (%g) is not a finite number in (0, 1]", who, rho_max), 1;
+  if (null_arg) return snprintf(why, n, "%s: %s is NULL", who, null_arg), 1;
+  if (!(std::isfinite(x_max) && x_max > 0.0 && x_max <= 1.0))
+    return snprintf(why, n, "%s: %s (%g) is not a finite number in (0, 1]", who, bound, x_max), 1;
+  return 0;
+}
+
+// the arguments of the two ambient fits.  what: "sample" or "cluster", n_what of them
+inline int bad_args(const char* who, const char* what, const double* amb_af, int32_t n_cand, const int32_t* cand, int64_t C,
+                    int n_what, double rho_max, bool any_out, char* why, size_t n) {
+  if (bad_head(who, n_cand, !cand ? "cand" : !amb_af ? "amb_af" : nullptr, "rho_max", rho_max, any_out, why, n)) return 1;
   for (int64_t i = 0; i < C * n_cand; ++i)
     if (cand[i] < -1 || cand[i] >= n_what)
       return snprintf(why, n, "%s: cand[%lld][%d] (%d) is neither -1 nor a %s in [0,%d)", who, (long long)(i / n_cand),
@@ -250,30 +301,32 @@ inline int bad_args(const char* who, const char* what, const double* amb_af, int
   return 0;
 }
 
-// amb_af and cand to the device, launch(n_units, d_af, d_cand, d_dout, d_iout) between the call's own events, the wanted
-// outputs to the host.  Nothing proportional to nnz is allocated; the handle's timing slots keep their values.
+// amb_af (NULL: the call has none, and nothing is copied) and the slots' indices (`width` per slot: a candidate, or a pair)
+// to the device, launch(n_units, d_af, d_slot, d_dout, d_iout) between the call's own events, the wanted ones of the `rows`
+// (4, or 5 with ll_top) double rows and the two int rows to the host.  Nothing proportional to nnz is allocated; the
+// handle's timing slots keep their values.
 template <class Launch>
-int host_run(muxgl_handle* h, const char* who, const double* amb_af, int n_cand, const int32_t* cand, const outputs& o,
-             float* kernel_ms, Launch&& launch) {
+int host_run(muxgl_handle* h, const char* who, const double* amb_af, int n_cand, int width, const int32_t* slot, int rows,
+             const outputs& o, float* kernel_ms, Launch&& launch) {
   const int64_t C = h->C, S = h->S, n_units = C * n_cand;
   if (n_units == 0) return 0;
   if ((n_units + 3) / 4 > 0x7fffffffLL)
-    MUXGL_FAIL(h, "%s: %lld droplets x %d candidates exceed one launch", who, (long long)C, n_cand);
+    MUXGL_FAIL(h, "%s: %lld droplets x %d %s exceed one launch", who, (long long)C, n_cand, width == 2 ? "slots" : "candidates");
   dev_tmp<double> d_af, d_dout;
-  dev_tmp<int32_t> d_cand, d_iout;
-  if (dev_alloc(h, &d_af.p, (size_t)S)) return 1;
-  if (dev_alloc(h, &d_cand.p, (size_t)n_units)) return 1;
-  if (dev_alloc(h, &d_dout.p, (size_t)n_units * 4)) return 1;
+  dev_tmp<int32_t> d_slot, d_iout;
+  if (amb_af && dev_alloc(h, &d_af.p, (size_t)S)) return 1;
+  if (dev_alloc(h, &d_slot.p, (size_t)n_units * width)) return 1;
+  if (dev_alloc(h, &d_dout.p, (size_t)n_units * rows)) return 1;
   if (dev_alloc(h, &d_iout.p, (size_t)n_units * 2)) return 1;
   call_events ev;  // (the handle's timing slots keep their values)
   if (ev.create(h, kernel_ms, who)) return 1;
-  if (S > 0) HIPCHK(h, hipMemcpyAsync(d_af.p, amb_af, sizeof(double) * (size_t)S, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(d_cand.p, cand, sizeof(int32_t) * (size_t)n_units, hipMemcpyHostToDevice, h->stream));
+  if (amb_af && S > 0) HIPCHK(h, hipMemcpyAsync(d_af.p, amb_af, sizeof(double) * (size_t)S, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_slot.p, slot, sizeof(int32_t) * (size_t)n_units * width, hipMemcpyHostToDevice, h->stream));
   if (ev.start(h)) return 1;
-  if (launch(n_units, d_af.p, d_cand.p, d_dout.p, d_iout.p)) return 1;
+  if (launch(n_units, d_af.p, d_slot.p, d_dout.p, d_iout.p)) return 1;
   if (ev.stop(h)) return 1;
-  double* const dst[4] = {o.rho_hat, o.ll_hat, o.ll_zero, o.info};
-  for (int k = 0; k < 4; ++k)
+  double* const dst[5] = {o.rho_hat, o.ll_hat, o.ll_zero, o.info, o.ll_top};
+  for (int k = 0; k < rows; ++k)
     if (dst[k])
       HIPCHK(h, hipMemcpyAsync(dst[k], d_dout.p + (size_t)k * n_units, sizeof(double) * (size_t)n_units, hipMemcpyDeviceToHost,
                                h->stream));

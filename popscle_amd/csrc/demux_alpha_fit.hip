@@ -13,8 +13,10 @@
 //
 // The three diagonal elements do not depend on alpha: they are the grid's own elements (l, l) of alpha[0], which the pass
 // forms anyway, so a lane carries the six off-diagonal ones only: (a, a', a'') of one share, 18 doubles, or a of three
-// shares, 18 doubles.  The grid's NA x 9 products are formed operation for operation as row_entry_pg forms them, so
-// q_max_e is the same number, and the pair's elements are rescaled with them every 32 reads, by the grid's maximum only.
+// shares, 18 doubles.  The grid's NA x 9 products are formed by grid_walk (demux_entry.hpp, where the argument that
+// q_max_e is the same number stands), and the pair's elements are rescaled with them every 32 reads, by the grid's maximum
+// only.  The product rule, the step from (D, D', D'') to the three sums, the end of a pass and the host side of the call
+// are ambient_fit_search.hpp's, shared with demux_ambient_fit.hip.
 // p is formed by one fma from the reference's expression and is exact at the ends: at alpha = 0 every element (l, m) has
 // p = 0.5 l (sample j alone), at alpha = 1 p = 0.5 m (sample k alone).
 //
@@ -36,10 +38,6 @@
 #include "demux_entry.hpp"
 
 namespace {
-
-struct fit_grid {
-  double a[MUXGL_MAX_ALPHA];
-};
 
 // the six off-diagonal elements i <-> (l, m): (0,1) (0,2) (1,0) (1,2) (2,0) (2,1); p = P0[i] + P1[i] alpha (:673)
 __device__ constexpr double P0[6] = {0.0, 0.0, 0.5, 0.5, 1.0, 1.0};
@@ -80,7 +78,7 @@ __device__ __forceinline__ double dot6_paired(const double (&gg)[9], double wo0,
 template <int NA, bool DERIV, int NC>
 __device__ __forceinline__ void fit_pass(int64_t e0, int64_t e1, int lane, const int32_t* __restrict__ entry_snp,
                                          const int64_t* __restrict__ entry_rptr, const uint8_t* __restrict__ reads,
-                                         const double* lut, const fit_grid& al, const uint8_t* __restrict__ has_gp,
+                                         const double* lut, const demux_grid& al, const uint8_t* __restrict__ has_gp,
                                          const double* __restrict__ gpj, const double* __restrict__ gpk, size_t V3,
                                          const double (&x)[3], double (&out)[3], int* n_scored) {
   // p per (share, element); the same for every entry, and wave-uniform
@@ -96,69 +94,24 @@ __device__ __forceinline__ void fit_pass(int64_t e0, int64_t e1, int lane, const
     const int32_t s = entry_snp[e];
     if (!has_gp[s]) continue;  // (no genotypes: the reference skips the marker, :733)
     ++ns;
-    const int64_t r0 = entry_rptr[e], r1 = entry_rptr[e + 1];
     // am: DERIV ? (a_i, a_i', a_i'') at i, 6 + i, 12 + i : a_i of share c at c * 6 + i
     double pG[NA * 9], am[18];
 #pragma unroll
-    for (int i = 0; i < NA * 9; ++i) pG[i] = 1.0;
-#pragma unroll
     for (int i = 0; i < 18; ++i) am[i] = (DERIV && i >= 6) ? 0.0 : 1.0;
-    int since_norm = 0;
-    for (int64_t r = r0; r < r1; ++r) {
-      const uint32_t b = (uint32_t)reads[r];
-      if (b == MUXGL_READ_OTHER) continue;  // :664
-      const uint32_t alt = b >> 7, bq = b & 0x7f;
-      const double e3 = lut[256 + bq], mt = lut[128 + bq];  // Err/3.0, Mat
-      const double pR = (alt == 0) ? mt : e3;  // :666
-      const double pA = (alt == 0) ? e3 : mt;  // :667
-      const double d = pA - pR;
+    // the grid's walk (demux_entry.hpp); the wide grids with the hoist barrier.  The pair's elements follow the grid's
+    // rescale, all together.
+    const double mx = grid_walk<NA, (DERIV ? 18 : NM), (NA > 8)>(
+        reads, entry_rptr[e], entry_rptr[e + 1], al.a, lut, pG, am, [&](double pR, double pA, double d) {
+          if (DERIV) {
+            ambient_fit::product_rule<6>(am, [&](int i, double& t, double& v) {
+              t = fma(pA, pv[i], pR * (1.0 - pv[i]));
+              v = d * P1[i];
+            });
+          } else {
 #pragma unroll
-      for (int n = 0; n < NA; ++n) {  // the grid's products, operation for operation those of row_entry_pg
-        double an = al.a[n];
-        // (the wide grids: kept from being hoisted out of the read loop as registers of ha, hb, 2 ha; same operations)
-        if (NA > 8) asm volatile("" : "+v"(an));
-        const double ha = 0.5 * an, hb = 0.5 - ha;
-        const double A1 = fma(d, hb, pR);
-        const double B1 = d * ha, B2 = d * (ha + ha);
-        double* q = &pG[n * 9];
-        q[0] *= pR;
-        q[1] *= pR + B1;
-        q[2] *= pR + B2;
-        q[3] *= A1;
-        q[4] *= A1 + B1;
-        q[5] *= A1 + B2;
-        q[6] *= pA - B2;
-        q[7] *= pA - B1;
-        q[8] *= pA;
-      }
-      if (DERIV) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-          const double t = fma(pA, pv[i], pR * (1.0 - pv[i]));
-          const double v = d * P1[i];
-          am[12 + i] = fma(am[12 + i], t, (am[6 + i] + am[6 + i]) * v);
-          am[6 + i] = fma(am[6 + i], t, am[i] * v);
-          am[i] *= t;
-        }
-      } else {
-#pragma unroll
-        for (int i = 0; i < NM; ++i) am[i] *= fma(pA, pv[i], pR * (1.0 - pv[i]));
-      }
-      if (++since_norm == 32) {  // the grid's maximum only: the pair's elements follow it, all together
-        since_norm = 0;
-        double mx = 0.0;
-#pragma unroll
-        for (int i = 0; i < NA * 9; ++i) mx = fmax(mx, pG[i]);
-        const double inv = 1.0 / mx;
-#pragma unroll
-        for (int i = 0; i < NA * 9; ++i) pG[i] *= inv;
-#pragma unroll
-        for (int i = 0; i < (DERIV ? 18 : NM); ++i) am[i] *= inv;
-      }
-    }
-    double mx = 0.0;
-#pragma unroll
-    for (int i = 0; i < NA * 9; ++i) mx = fmax(mx, pG[i]);
+            for (int i = 0; i < NM; ++i) am[i] *= fma(pA, pv[i], pR * (1.0 - pv[i]));
+          }
+        });
     const double c1 = 1.0 / (1.0 + 1e-10);
     const double sc = c1 / mx, t10 = 1e-10 * c1;
     // the diagonal: the grid's elements (l, l) of alpha[0]
@@ -177,29 +130,17 @@ __device__ __forceinline__ void fit_pass(int64_t e0, int64_t e1, int lane, const
                   fma(a[4], sc, t10), fma(a[5], sc, t10));
     };
     if (DERIV) {
-      const double D = D_of(&am[0]);
       // (the offset's derivative is 0, and so is the diagonal's)
       const double D1 = dot6_paired(gg, am[6] * sc, am[7] * sc, am[8] * sc, am[9] * sc, am[10] * sc, am[11] * sc);
       const double D2 = dot6_paired(gg, am[12] * sc, am[13] * sc, am[14] * sc, am[15] * sc, am[16] * sc, am[17] * sc);
-      const double iD = 1.0 / D;
-      const double q1 = D1 * iD;
-      s0 += pos_log(D, 0.0);
-      s1 += q1;
-      s2 += fma(-q1, q1, D2 * iD);
+      ambient_fit::add_entry(D_of(&am[0]), D1, D2, s0, s1, s2);
     } else {
       s0 += pos_log(D_of(&am[0]), 0.0);
       if (NC > 1) s1 += pos_log(D_of(&am[6]), 0.0);
       if (NC > 2) s2 += pos_log(D_of(&am[12]), 0.0);
     }
   }
-  out[0] = ambient_fit::wave_sum(s0);
-  out[1] = (DERIV || NC > 1) ? ambient_fit::wave_sum(s1) : 0.0;
-  out[2] = (DERIV || NC > 2) ? ambient_fit::wave_sum(s2) : 0.0;
-  if (n_scored) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ns += __shfl_xor(ns, off, 64);
-    *n_scored = ns;
-  }
+  ambient_fit::pass_sums<DERIV ? 3 : NC>(s0, s1, s2, ns, out, n_scored);
 }
 
 // coarse shares per pass, 1 or 3 (ambient_fit::search): three where the NA * 9 + 18 products of a lane stay in registers
@@ -216,7 +157,7 @@ __global__ void __launch_bounds__(256)
     alpha_fit_kernel(int64_t n_units, int n_cand, const int32_t* __restrict__ pair, double alpha_max,
                      const int64_t* __restrict__ cell_ptr, const int32_t* __restrict__ entry_snp,
                      const int64_t* __restrict__ entry_rptr, const uint8_t* __restrict__ reads,
-                     const double* __restrict__ lut_g, fit_grid al, const uint8_t* __restrict__ has_gp,
+                     const double* __restrict__ lut_g, demux_grid al, const uint8_t* __restrict__ has_gp,
                      const double* __restrict__ gp, int V, double* __restrict__ dout, int32_t* __restrict__ iout) {
   __shared__ double lut[384];
   for (int i = threadIdx.x; i < 384; i += 256) lut[i] = lut_g[i];
@@ -227,7 +168,7 @@ __global__ void __launch_bounds__(256)
   const int64_t c = unit / n_cand;
   const int32_t j = pair[2 * unit], k = pair[2 * unit + 1];
   ambient_fit::result res;  // (a negative index: status 4, all outputs 0)
-  double ll_top = 0.0;
+  double ll_top = 0.0;  // (its own variable: the coarse callable writes it while the search runs)
   if (j >= 0 && k >= 0) {
     const int64_t e0 = cell_ptr[c], e1 = cell_ptr[c + 1];
     const size_t V3 = (size_t)V * 3;
@@ -246,14 +187,13 @@ __global__ void __launch_bounds__(256)
       L = o[0], d1 = o[1], d2 = o[2];
     };
     res = ambient_fit::search<NC, false>(alpha_max, coarse, deriv, [&] { return n_scored == 0; });
-    if (res.status == ambient_fit::NO_ENTRY) ll_top = 0.0;
+    res.ll_top = res.status == ambient_fit::NO_ENTRY ? 0.0 : ll_top;
   }
-  ambient_fit::store(res, lane, unit, n_units, dout, iout);
-  if (lane == 0) dout[4 * n_units + unit] = ll_top;
+  ambient_fit::store<5>(res, lane, unit, n_units, dout, iout);
 }
 
 template <int NA>
-int launch_fit(muxgl_handle* h, int64_t n_units, int n_cand, const int32_t* d_pair, double alpha_max, const fit_grid& al,
+int launch_fit(muxgl_handle* h, int64_t n_units, int n_cand, const int32_t* d_pair, double alpha_max, const demux_grid& al,
                double* d_dout, int32_t* d_iout) {
   hipLaunchKernelGGL((alpha_fit_kernel<NA>), dim3((unsigned)((n_units + 3) / 4)), dim3(256), 0, h->stream, n_units, n_cand,
                      d_pair, alpha_max, h->d_cell_ptr, h->d_entry_snp, h->d_entry_rptr, h->d_reads, h->d_lut, al,
@@ -263,7 +203,7 @@ int launch_fit(muxgl_handle* h, int64_t n_units, int n_cand, const int32_t* d_pa
 }
 
 int fit_dispatch(muxgl_handle* h, int A, int64_t n_units, int n_cand, const int32_t* d_pair, double alpha_max,
-                 const fit_grid& al, double* d_dout, int32_t* d_iout) {
+                 const demux_grid& al, double* d_dout, int32_t* d_iout) {
 #define CALL_F(N) launch_fit<N>(h, n_units, n_cand, d_pair, alpha_max, al, d_dout, d_iout)
   DISPATCH_NA(A, CALL_F);
 #undef CALL_F
@@ -275,12 +215,7 @@ int fit_dispatch(muxgl_handle* h, int A, int64_t n_units, int n_cand, const int3
 int demux_alpha_fit_bad_args(int32_t n_cand, const int32_t* pair, int64_t C, int V, double alpha_max, bool any_out, char* why,
                              size_t n) {
   const char* who = "muxgl_demux_alpha_fit";
-  if (!any_out) return snprintf(why, n, "%s: every output is NULL", who), 1;
-  if (n_cand < 1 || n_cand > MUXGL_MAX_FIT_CAND)
-    return snprintf(why, n, "%s: n_cand=%d outside [1,%d]", who, n_cand, MUXGL_MAX_FIT_CAND), 1;
-  if (!pair) return snprintf(why, n, "%s: pair is NULL", who), 1;
-  if (!(std::isfinite(alpha_max) && alpha_max > 0.0 && alpha_max <= 1.0))
-    return snprintf(why, n, "%s: alpha_max (%g) is not a finite number in (0, 1]", who, alpha_max), 1;
+  if (ambient_fit::bad_head(who, n_cand, pair ? nullptr : "pair", "alpha_max", alpha_max, any_out, why, n)) return 1;
   for (int64_t i = 0; i < C * n_cand; ++i) {
     const int32_t j = pair[2 * i], k = pair[2 * i + 1];
     for (int t = 0; t < 2; ++t)
@@ -294,41 +229,14 @@ int demux_alpha_fit_bad_args(int32_t n_cand, const int32_t* pair, int64_t C, int
   return 0;
 }
 
-// pair to the device, the one launch between the call's own events, the wanted outputs to the host.  The handle's timing
-// slots keep their values.
+// ambient_fit::host_run without an amb_af, with two indices per slot and ll_top as the fifth double row
 int demux_alpha_fit_run(muxgl_handle* h, const muxgl_demux_params* p, int n_cand, const int32_t* pair, double alpha_max,
                         double* alpha_hat, double* ll_hat, double* ll_zero, double* ll_top, double* info, int32_t* status,
                         int32_t* n_steps, float* kernel_ms) {
-  const char* who = "muxgl_demux_alpha_fit";
-  const int A = p->n_alpha;
-  fit_grid al;
-  for (int i = 0; i < MUXGL_MAX_ALPHA; ++i) al.a[i] = i < A ? p->alpha[i] : p->alpha[0];  // (repeats of alpha[0] change no maximum)
-  const int64_t n_units = h->C * n_cand;
-  if (n_units == 0) return 0;
-  if ((n_units + 3) / 4 > 0x7fffffffLL)
-    MUXGL_FAIL(h, "%s: %lld droplets x %d slots exceed one launch", who, (long long)h->C, n_cand);
-  dev_tmp<double> d_dout;
-  dev_tmp<int32_t> d_pair, d_iout;
-  if (dev_alloc(h, &d_pair.p, (size_t)n_units * 2)) return 1;
-  if (dev_alloc(h, &d_dout.p, (size_t)n_units * 5)) return 1;
-  if (dev_alloc(h, &d_iout.p, (size_t)n_units * 2)) return 1;
-  call_events ev;
-  if (ev.create(h, kernel_ms, who)) return 1;
-  HIPCHK(h, hipMemcpyAsync(d_pair.p, pair, sizeof(int32_t) * (size_t)n_units * 2, hipMemcpyHostToDevice, h->stream));
-  if (ev.start(h)) return 1;
-  if (fit_dispatch(h, A, n_units, n_cand, d_pair.p, alpha_max, al, d_dout.p, d_iout.p)) return 1;
-  if (ev.stop(h)) return 1;
-  double* const dst[5] = {alpha_hat, ll_hat, ll_zero, info, ll_top};
-  for (int t = 0; t < 5; ++t)
-    if (dst[t])
-      HIPCHK(h, hipMemcpyAsync(dst[t], d_dout.p + (size_t)t * n_units, sizeof(double) * (size_t)n_units, hipMemcpyDeviceToHost,
-                               h->stream));
-  int32_t* const idst[2] = {status, n_steps};
-  for (int t = 0; t < 2; ++t)
-    if (idst[t])
-      HIPCHK(h, hipMemcpyAsync(idst[t], d_iout.p + (size_t)t * n_units, sizeof(int32_t) * (size_t)n_units, hipMemcpyDeviceToHost,
-                               h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  ev.add();
-  return 0;
+  const demux_grid al = demux_grid_of(p);
+  const ambient_fit::outputs out = {alpha_hat, ll_hat, ll_zero, info, status, n_steps, ll_top};
+  return ambient_fit::host_run(h, "muxgl_demux_alpha_fit", nullptr, n_cand, 2, pair, 5, out, kernel_ms,
+                               [&](int64_t n_units, const double*, const int32_t* d_pair, double* d_dout, int32_t* d_iout) {
+                                 return fit_dispatch(h, p->n_alpha, n_units, n_cand, d_pair, alpha_max, al, d_dout, d_iout);
+                               });
 }

@@ -11,12 +11,12 @@
 // The ambient products take part in no maximum: they are only divided by the grid's, so the table is on the scale of the
 // records' log-likelihoods and of the singlet table.  The design is that of demux_unknown.hip with one weight triple per
 // (entry, rho) and one orientation:
-//   * amb_weight_kernel, lane = entry: the NA x 9 products of the grid as row_entry_pg<NA> forms them (the same
-//     operations in the same order, so q_max is the same number) and beside them 3 x RC ambient products through the same
-//     reads; both rescaled every 32 reads by the grid's maximum only.  The rhos are swept in chunks of RC (4, 8 or 16 by
-//     the size of the grid, to hold the register count); every chunk repeats the grid products identically and every
-//     ambient product belongs to one rho, so the chunking changes no bit.  A marker without genotypes gets ones: its row
-//     of gp is (1, 0, 0), so its factor is exactly 1 and the sweep has no branch.
+//   * amb_weight_kernel, lane = entry: the NA x 9 products of the grid as row_entry_pg<NA> forms them (grid_walk of
+//     demux_entry.hpp: the same operations in the same order, so q_max is the same number) and beside them 3 x RC ambient
+//     products through the same reads; both rescaled every 32 reads by the grid's maximum only.  The rhos are swept in
+//     chunks of RC (4, 8 or 16 by the size of the grid, to hold the register count); every chunk repeats the grid
+//     products identically and every ambient product belongs to one rho, so the chunking changes no bit.  A marker
+//     without genotypes gets ones: its row of gp is (1, 0, 0), so its factor is exactly 1 and the sweep has no branch.
 //   * amb_sweep_kernel, lane = sample column of a 64-column block: one dot gp_j . w_e[r] per (entry, column, rho),
 //     multiplied into a product kept as mantissa x 2^exponent, one log per (cell part, column, rho).  A wave is one work
 //     unit: a part of a cell (at most 2048 entries) x a block x a chunk of CH <= 4 rhos.  Every accumulator belongs to
@@ -42,9 +42,7 @@
 
 namespace {
 
-struct amb_grid {
-  double a[MUXGL_MAX_ALPHA];
-};
+using amb_grid = demux_grid;  // the alpha grid, and the call's rhos in the same sixteen slots
 using amb_item = table_plan::item;  // the entries [e0, e1) of one cell, result row `row` of the slab
 // the further parts of a cell: its value = slab[cell row] + slab[first] + ... + slab[first + count - 1], in this order
 using amb_cell = table_plan::cell;
@@ -75,34 +73,9 @@ __global__ void __launch_bounds__(256)
   for (int rb = 0; rb < NR; rb += RC) {
     double pG[NA * 9], am[RC * 3];
 #pragma unroll
-    for (int i = 0; i < NA * 9; ++i) pG[i] = 1.0;
-#pragma unroll
     for (int i = 0; i < RC * 3; ++i) am[i] = 1.0;
-    int since_norm = 0;
-    for (int64_t r = r0; r < r1; ++r) {
-      const uint32_t b = (uint32_t)reads[r];
-      if (b == MUXGL_READ_OTHER) continue;  // :664
-      const uint32_t alt = b >> 7, bq = b & 0x7f;
-      const double e3 = lut[256 + bq], mt = lut[128 + bq];  // Err/3.0, Mat
-      const double pR = (alt == 0) ? mt : e3;  // :666
-      const double pA = (alt == 0) ? e3 : mt;  // :667
-      const double d = pA - pR;
-#pragma unroll
-      for (int n = 0; n < NA; ++n) {  // the grid's products, operation for operation those of row_entry_pg
-        const double ha = 0.5 * al.a[n], hb = 0.5 - ha;
-        const double A1 = fma(d, hb, pR);
-        const double B1 = d * ha, B2 = d * (ha + ha);
-        double* q = &pG[n * 9];
-        q[0] *= pR;
-        q[1] *= pR + B1;
-        q[2] *= pR + B2;
-        q[3] *= A1;
-        q[4] *= A1 + B1;
-        q[5] *= A1 + B2;
-        q[6] *= pA - B2;
-        q[7] *= pA - B1;
-        q[8] *= pA;
-      }
+    // the grid's walk (demux_entry.hpp), without the hoist barrier; the ambient products follow the grid's rescale
+    const double mx = grid_walk<NA, RC * 3, false>(reads, r0, r1, al.a, lut, pG, am, [&](double pR, double pA, double) {
 #pragma unroll
       for (int k = 0; k < RC; ++k) {
         const double hr = 0.5 * rh.a[rb + k];  // (rb + k < 16: a slot past the end holds the last rho again)
@@ -111,21 +84,7 @@ __global__ void __launch_bounds__(256)
         am[k * 3 + 1] *= fma(pA, p1, pR * (1.0 - p1));
         am[k * 3 + 2] *= fma(pA, p2, pR * (1.0 - p2));
       }
-      if (++since_norm == 32) {  // the grid's maximum only: the ambient products follow it
-        since_norm = 0;
-        double mx = 0.0;
-#pragma unroll
-        for (int i = 0; i < NA * 9; ++i) mx = fmax(mx, pG[i]);
-        const double inv = 1.0 / mx;
-#pragma unroll
-        for (int i = 0; i < NA * 9; ++i) pG[i] *= inv;
-#pragma unroll
-        for (int i = 0; i < RC * 3; ++i) am[i] *= inv;
-      }
-    }
-    double mx = 0.0;
-#pragma unroll
-    for (int i = 0; i < NA * 9; ++i) mx = fmax(mx, pG[i]);
+    });
     const double c = 1.0 / (1.0 + 1e-10);
     const double sc = c / mx, t = 1e-10 * c;
 #pragma unroll
@@ -365,11 +324,9 @@ int demux_ambient_run(muxgl_handle* h, const muxgl_demux_params* p, const double
       table_plan::exceeds_one_launch((double)bt.max_cells * V * NR, 256.0))
     MUXGL_FAIL(h, "muxgl_demux_ambient: a batch of %lld rows x %d samples x %d rhos exceeds one launch (lower MUXGL_DEMUX_SLAB_MB)",
                (long long)bt.max_rows, V, NR);
-  amb_grid al, rh;
-  for (int i = 0; i < MUXGL_MAX_ALPHA; ++i) {
-    al.a[i] = i < A ? p->alpha[i] : p->alpha[0];  // (repeats of alpha[0] change no maximum)
-    rh.a[i] = i < NR ? rho[i] : rho[NR - 1];      // (a slot past the end repeats the last rho and is not written)
-  }
+  const amb_grid al = demux_grid_of(p);
+  amb_grid rh;
+  for (int i = 0; i < MUXGL_MAX_ALPHA; ++i) rh.a[i] = i < NR ? rho[i] : rho[NR - 1];  // (a repeated rho is not written)
 
   dev_tmp<double> d_af, d_wt, d_slab, d_out;
   dev_tmp<amb_item> d_items;

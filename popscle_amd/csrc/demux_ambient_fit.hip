@@ -11,9 +11,10 @@
 //   LL = sum_e log D,   LL' = sum_e D' / D,   LL'' = sum_e (D'' / D - (D' / D)^2)       over entries whose marker has genotypes
 //
 // t is formed exactly as amb_weight_kernel forms it (p is exactly 0 at (l = 0, f = 0) and exactly 1 at (l = 2, f = 1),
-// where v is exactly 0), the grid's NA x 9 products run beside the triples operation for operation as row_entry_pg forms
-// them, so q_max_e is the same number, and all nine of (a, a', a'') are rescaled together every 32 reads by the grid's
-// maximum only.
+// where v is exactly 0); the grid's NA x 9 products run beside the triples in grid_walk (demux_entry.hpp, where the
+// argument that q_max_e is the same number stands), and all nine of (a, a', a'') are rescaled together every 32 reads by
+// the grid's maximum only.  The product rule, the step from (D, D', D'') to the three sums and the end of a pass are
+// ambient_fit_search.hpp's, shared with demux_alpha_fit.hip.
 //
 // amb_fit_kernel, one wave per (cell, candidate): the lanes stride the cell's entries, each lane walks its entry's read
 // bytes through the Phred table in LDS, dots the three triples with the candidate's gp row and adds its share of
@@ -34,10 +35,6 @@
 
 namespace {
 
-struct fit_grid {
-  double a[MUXGL_MAX_ALPHA];
-};
-
 // One pass of a wave over the entries [e0, e1) of a cell for candidate column j.
 //   DERIV = false: out[k] = LL(x[k]) for the NC <= 3 shares x[0..NC-1]
 //   DERIV = true:  out = (LL, LL', LL'') at x[0]
@@ -45,7 +42,7 @@ struct fit_grid {
 template <int NA, bool DERIV, int NC>
 __device__ __forceinline__ void fit_pass(int64_t e0, int64_t e1, int lane, const int32_t* __restrict__ entry_snp,
                                          const int64_t* __restrict__ entry_rptr, const uint8_t* __restrict__ reads,
-                                         const double* lut, const fit_grid& al, const double* __restrict__ af,
+                                         const double* lut, const demux_grid& al, const double* __restrict__ af,
                                          const uint8_t* __restrict__ has_gp, const double* __restrict__ gpj, size_t V3,
                                          const double (&x)[3], double (&out)[3], int* n_scored) {
   double s0 = 0.0, s1 = 0.0, s2 = 0.0;
@@ -54,7 +51,6 @@ __device__ __forceinline__ void fit_pass(int64_t e0, int64_t e1, int lane, const
     const int32_t s = entry_snp[e];
     if (!has_gp[s]) continue;  // (no genotypes: the reference skips the marker, :733)
     ++ns;
-    const int64_t r0 = entry_rptr[e], r1 = entry_rptr[e + 1];
     const double tf = af[s] + af[s];
     const double tf1 = tf - 1.0, tf2 = tf - 2.0;
     // p per (share, l) as amb_weight_kernel forms it; DERIV: dp/drho per l in pv[3..5]
@@ -75,92 +71,36 @@ __device__ __forceinline__ void fit_pass(int64_t e0, int64_t e1, int lane, const
     constexpr int NM = DERIV ? 9 : NC * 3;
     double pG[NA * 9], am[9];
 #pragma unroll
-    for (int i = 0; i < NA * 9; ++i) pG[i] = 1.0;
-#pragma unroll
     for (int i = 0; i < 9; ++i) am[i] = (DERIV && i >= 3) ? 0.0 : 1.0;
-    int since_norm = 0;
-    for (int64_t r = r0; r < r1; ++r) {
-      const uint32_t b = (uint32_t)reads[r];
-      if (b == MUXGL_READ_OTHER) continue;  // :664
-      const uint32_t alt = b >> 7, bq = b & 0x7f;
-      const double e3 = lut[256 + bq], mt = lut[128 + bq];  // Err/3.0, Mat
-      const double pR = (alt == 0) ? mt : e3;  // :666
-      const double pA = (alt == 0) ? e3 : mt;  // :667
-      const double d = pA - pR;
+    // the grid's walk (demux_entry.hpp); the widest grid with the hoist barrier.  All of am follows the grid's rescale.
+    const double mx = grid_walk<NA, NM, (NA > 12)>(
+        reads, entry_rptr[e], entry_rptr[e + 1], al.a, lut, pG, am, [&](double pR, double pA, double d) {
+          if (DERIV) {
+            ambient_fit::product_rule<3>(am, [&](int l, double& t, double& v) {
+              t = fma(pA, pv[l], pR * (1.0 - pv[l]));
+              v = d * pv[3 + l];
+            });
+          } else {
 #pragma unroll
-      for (int n = 0; n < NA; ++n) {  // the grid's products, operation for operation those of row_entry_pg
-        double an = al.a[n];
-        // (the widest grid: kept from being hoisted out of the read loop as 48 registers of ha, hb, 2 ha; same operations)
-        if (NA > 12) asm volatile("" : "+v"(an));
-        const double ha = 0.5 * an, hb = 0.5 - ha;
-        const double A1 = fma(d, hb, pR);
-        const double B1 = d * ha, B2 = d * (ha + ha);
-        double* q = &pG[n * 9];
-        q[0] *= pR;
-        q[1] *= pR + B1;
-        q[2] *= pR + B2;
-        q[3] *= A1;
-        q[4] *= A1 + B1;
-        q[5] *= A1 + B2;
-        q[6] *= pA - B2;
-        q[7] *= pA - B1;
-        q[8] *= pA;
-      }
-      if (DERIV) {
-#pragma unroll
-        for (int l = 0; l < 3; ++l) {
-          const double t = fma(pA, pv[l], pR * (1.0 - pv[l]));
-          const double v = d * pv[3 + l];
-          am[6 + l] = fma(am[6 + l], t, (am[3 + l] + am[3 + l]) * v);
-          am[3 + l] = fma(am[3 + l], t, am[l] * v);
-          am[l] *= t;
-        }
-      } else {
-#pragma unroll
-        for (int i = 0; i < NM; ++i) am[i] *= fma(pA, pv[i], pR * (1.0 - pv[i]));
-      }
-      if (++since_norm == 32) {  // the grid's maximum only: the triples follow it, all nine together
-        since_norm = 0;
-        double mx = 0.0;
-#pragma unroll
-        for (int i = 0; i < NA * 9; ++i) mx = fmax(mx, pG[i]);
-        const double inv = 1.0 / mx;
-#pragma unroll
-        for (int i = 0; i < NA * 9; ++i) pG[i] *= inv;
-#pragma unroll
-        for (int i = 0; i < NM; ++i) am[i] *= inv;
-      }
-    }
-    double mx = 0.0;
-#pragma unroll
-    for (int i = 0; i < NA * 9; ++i) mx = fmax(mx, pG[i]);
+            for (int i = 0; i < NM; ++i) am[i] *= fma(pA, pv[i], pR * (1.0 - pv[i]));
+          }
+        });
     const double c = 1.0 / (1.0 + 1e-10);
     const double sc = c / mx, t10 = 1e-10 * c;
     const double* g = gpj + (size_t)s * V3;
     const double g0 = g[0], g1 = g[1], g2 = g[2];
+    auto D_of = [&](const double* a) { return fma(g2, fma(a[2], sc, t10), fma(g1, fma(a[1], sc, t10), g0 * fma(a[0], sc, t10))); };
     if (DERIV) {
-      const double D = fma(g2, fma(am[2], sc, t10), fma(g1, fma(am[1], sc, t10), g0 * fma(am[0], sc, t10)));
       const double D1 = fma(g2, am[5] * sc, fma(g1, am[4] * sc, g0 * (am[3] * sc)));  // (the offset's derivative is 0)
       const double D2 = fma(g2, am[8] * sc, fma(g1, am[7] * sc, g0 * (am[6] * sc)));
-      const double iD = 1.0 / D;
-      const double q1 = D1 * iD;
-      s0 += pos_log(D, 0.0);
-      s1 += q1;
-      s2 += fma(-q1, q1, D2 * iD);
+      ambient_fit::add_entry(D_of(&am[0]), D1, D2, s0, s1, s2);
     } else {
-      s0 += pos_log(fma(g2, fma(am[2], sc, t10), fma(g1, fma(am[1], sc, t10), g0 * fma(am[0], sc, t10))), 0.0);
-      if (NC > 1) s1 += pos_log(fma(g2, fma(am[5], sc, t10), fma(g1, fma(am[4], sc, t10), g0 * fma(am[3], sc, t10))), 0.0);
-      if (NC > 2) s2 += pos_log(fma(g2, fma(am[8], sc, t10), fma(g1, fma(am[7], sc, t10), g0 * fma(am[6], sc, t10))), 0.0);
+      s0 += pos_log(D_of(&am[0]), 0.0);
+      if (NC > 1) s1 += pos_log(D_of(&am[3]), 0.0);
+      if (NC > 2) s2 += pos_log(D_of(&am[6]), 0.0);
     }
   }
-  out[0] = ambient_fit::wave_sum(s0);
-  out[1] = (DERIV || NC > 1) ? ambient_fit::wave_sum(s1) : 0.0;
-  out[2] = (DERIV || NC > 2) ? ambient_fit::wave_sum(s2) : 0.0;
-  if (n_scored) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ns += __shfl_xor(ns, off, 64);
-    *n_scored = ns;
-  }
+  ambient_fit::pass_sums<DERIV ? 3 : NC>(s0, s1, s2, ns, out, n_scored);
 }
 
 // grid: ceil(C * n_cand / 4) workgroups of four waves; wave unit <-> (cell, candidate), the candidate fastest, so the
@@ -171,7 +111,7 @@ __global__ void __launch_bounds__(256)
     amb_fit_kernel(int64_t n_units, int n_cand, const int32_t* __restrict__ cand, double rho_max,
                    const int64_t* __restrict__ cell_ptr, const int32_t* __restrict__ entry_snp,
                    const int64_t* __restrict__ entry_rptr, const uint8_t* __restrict__ reads,
-                   const double* __restrict__ lut_g, fit_grid al, const double* __restrict__ af,
+                   const double* __restrict__ lut_g, demux_grid al, const double* __restrict__ af,
                    const uint8_t* __restrict__ has_gp, const double* __restrict__ gp, int V, double* __restrict__ dout,
                    int32_t* __restrict__ iout) {
   __shared__ double lut[384];
@@ -206,7 +146,7 @@ __global__ void __launch_bounds__(256)
 }
 
 template <int NA>
-int launch_fit(muxgl_handle* h, int64_t n_units, int n_cand, const int32_t* d_cand, double rho_max, const fit_grid& al,
+int launch_fit(muxgl_handle* h, int64_t n_units, int n_cand, const int32_t* d_cand, double rho_max, const demux_grid& al,
                const double* d_af, double* d_dout, int32_t* d_iout) {
   hipLaunchKernelGGL((amb_fit_kernel<NA>), dim3((unsigned)((n_units + 3) / 4)), dim3(256), 0, h->stream, n_units, n_cand,
                      d_cand, rho_max, h->d_cell_ptr, h->d_entry_snp, h->d_entry_rptr, h->d_reads, h->d_lut, al, d_af,
@@ -216,7 +156,7 @@ int launch_fit(muxgl_handle* h, int64_t n_units, int n_cand, const int32_t* d_ca
 }
 
 int fit_dispatch(muxgl_handle* h, int A, int64_t n_units, int n_cand, const int32_t* d_cand, double rho_max,
-                 const fit_grid& al, const double* d_af, double* d_dout, int32_t* d_iout) {
+                 const demux_grid& al, const double* d_af, double* d_dout, int32_t* d_iout) {
 #define CALL_F(N) launch_fit<N>(h, n_units, n_cand, d_cand, rho_max, al, d_af, d_dout, d_iout)
   DISPATCH_NA(A, CALL_F);
 #undef CALL_F
@@ -233,12 +173,10 @@ int demux_ambient_fit_run(muxgl_handle* h, const muxgl_demux_params* p, const do
                           const int32_t* cand, double rho_max, double* rho_hat, double* ll_hat, double* ll_zero,
                           double* info, int32_t* status, int32_t* n_steps, float* kernel_ms) {
   if (demux_ambient_check_af(h, amb_af, "muxgl_demux_ambient_fit")) return 1;
-  const int A = p->n_alpha;
-  fit_grid al;
-  for (int i = 0; i < MUXGL_MAX_ALPHA; ++i) al.a[i] = i < A ? p->alpha[i] : p->alpha[0];  // (repeats of alpha[0] change no maximum)
+  const demux_grid al = demux_grid_of(p);
   const ambient_fit::outputs out = {rho_hat, ll_hat, ll_zero, info, status, n_steps};
-  return ambient_fit::host_run(h, "muxgl_demux_ambient_fit", amb_af, n_cand, cand, out, kernel_ms,
+  return ambient_fit::host_run(h, "muxgl_demux_ambient_fit", amb_af, n_cand, 1, cand, 4, out, kernel_ms,
                                [&](int64_t n_units, const double* d_af, const int32_t* d_cand, double* d_dout, int32_t* d_iout) {
-                                 return fit_dispatch(h, A, n_units, n_cand, d_cand, rho_max, al, d_af, d_dout, d_iout);
+                                 return fit_dispatch(h, p->n_alpha, n_units, n_cand, d_cand, rho_max, al, d_af, d_dout, d_iout);
                                });
 }

@@ -33,16 +33,12 @@ namespace {
 constexpr int SNG_UNR = 8;          // entries per lane between two renormalisations, all of their loads in flight: a
                                     // factor is >= ~1e-11 (pG >= 1e-10 / (1 + 1e-10)), eight cannot underflow
 
-struct sng_alpha {
-  double a[MUXGL_MAX_ALPHA];
-};
-
 using sng_item = table_plan::item;  // the entries [e0, e1) of one cell, result row `row` of the slab
 
 template <int NA>
 __global__ void __launch_bounds__(256)
     sng_weight_kernel(int64_t nnz, const int32_t* __restrict__ entry_snp, const int64_t* __restrict__ entry_rptr,
-                      const uint8_t* __restrict__ reads, const double* __restrict__ lut_g, sng_alpha al,
+                      const uint8_t* __restrict__ reads, const double* __restrict__ lut_g, demux_grid al,
                       const double* __restrict__ gp, const uint8_t* __restrict__ has_gp, int V, double* __restrict__ wt) {
   __shared__ double lut[384];
   for (int i = threadIdx.x; i < 384; i += 256) lut[i] = lut_g[i];
@@ -117,14 +113,14 @@ __global__ void __launch_bounds__(256)
 }
 
 template <int NA>
-int launch_weights(muxgl_handle* h, const sng_alpha& al, double* d_wt) {
+int launch_weights(muxgl_handle* h, const demux_grid& al, double* d_wt) {
   hipLaunchKernelGGL((sng_weight_kernel<NA>), dim3((unsigned)((h->nnz + 255) / 256)), dim3(256), 0, h->stream, h->nnz,
                      h->d_entry_snp, h->d_entry_rptr, h->d_reads, h->d_lut, al, h->d_gp, h->d_has_gp, h->V, d_wt);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
 
-int weights_dispatch(muxgl_handle* h, int A, const sng_alpha& al, double* d_wt) {
+int weights_dispatch(muxgl_handle* h, int A, const demux_grid& al, double* d_wt) {
 #define CALL_W(N) launch_weights<N>(h, al, d_wt)
   DISPATCH_NA(A, CALL_W);
 #undef CALL_W
@@ -156,8 +152,7 @@ int demux_singlets_run(muxgl_handle* h, const muxgl_demux_params* p, double* sng
 
   int VH = 64;
   while (VH > 1 && VH / 2 >= V) VH /= 2;
-  sng_alpha al;
-  for (int i = 0; i < MUXGL_MAX_ALPHA; ++i) al.a[i] = i < A ? p->alpha[i] : p->alpha[0];  // (repeats of alpha[0] change no maximum)
+  const demux_grid al = demux_grid_of(p);
 
   dev_tmp<double> d_wt, d_slab;
   dev_tmp<sng_item> d_items;

@@ -39,9 +39,6 @@
 
 namespace {
 
-struct unk_alpha {
-  double a[MUXGL_MAX_ALPHA];
-};
 using unk_item = table_plan::item;  // the entries [e0, e1) of one cell, result row `row` of the slab
 // the further parts of a cell: its value = slab[cell row] + slab[first] + ... + slab[first + count - 1], in this order
 using unk_cell = table_plan::cell;
@@ -81,7 +78,7 @@ __global__ void __launch_bounds__(256) unk_neutral_kernel(int64_t S, const uint8
 template <int NA>
 __global__ void __launch_bounds__(256)
     unk_weight_kernel(int64_t eb0, int64_t eb1, int A, const int32_t* __restrict__ entry_snp, const int64_t* __restrict__ entry_rptr,
-                      const uint8_t* __restrict__ reads, const double* __restrict__ lut_g, unk_alpha al,
+                      const uint8_t* __restrict__ reads, const double* __restrict__ lut_g, demux_grid al,
                       const double* __restrict__ u, const uint8_t* __restrict__ has_gp, double* __restrict__ wt) {
   __shared__ double lut[384];
   for (int i = threadIdx.x; i < 384; i += 256) lut[i] = lut_g[i];
@@ -239,14 +236,14 @@ struct unk_batch {  // what one launch of the three kernels needs
 };
 
 template <int NA>
-int launch_weights(muxgl_handle* h, int A, const unk_alpha& al, const unk_batch& b) {
+int launch_weights(muxgl_handle* h, int A, const demux_grid& al, const unk_batch& b) {
   hipLaunchKernelGGL((unk_weight_kernel<NA>), dim3((unsigned)((b.eb1 - b.eb0 + 255) / 256)), dim3(256), 0, h->stream, b.eb0,
                      b.eb1, A, h->d_entry_snp, h->d_entry_rptr, h->d_reads, h->d_lut, al, b.d_u, h->d_has_gp, b.d_wt);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
 
-int weights_dispatch(muxgl_handle* h, int A, const unk_alpha& al, const unk_batch& b) {
+int weights_dispatch(muxgl_handle* h, int A, const demux_grid& al, const unk_batch& b) {
 #define CALL_W(N) launch_weights<N>(h, A, al, b)
   DISPATCH_NA(A, CALL_W);
 #undef CALL_W
@@ -307,8 +304,7 @@ int demux_unknown_run(muxgl_handle* h, const muxgl_demux_params* p, const double
       table_plan::exceeds_one_launch((double)bt.max_cells * VC * A, 256.0))
     MUXGL_FAIL(h, "muxgl_demux_unknown: a batch of %lld rows x %d samples x %d alphas exceeds one launch (lower MUXGL_DEMUX_SLAB_MB)",
                (long long)bt.max_rows, V, A);
-  unk_alpha al;
-  for (int i = 0; i < MUXGL_MAX_ALPHA; ++i) al.a[i] = i < A ? p->alpha[i] : p->alpha[0];  // (repeats of alpha[0] change no maximum)
+  const demux_grid al = demux_grid_of(p);
 
   dev_tmp<double> d_u, d_wt, d_slab, d_ju, d_uj, d_uu;
   dev_tmp<unk_item> d_items;

@@ -101,15 +101,11 @@ __device__ __forceinline__ void fam_fit_pass(int64_t e0, int64_t e1, int lane, c
       asm volatile("" : "+v"(one));
       if (DERIV) {
         const double sm = (al == 0) ? -mat : mat;
-#pragma unroll
-        for (int l = 0; l < 3; ++l) {
+        ambient_fit::product_rule<3>(am, [&](int l, double& fac, double& v) {
           const double xl = (al == 0) ? one - pv[l] : pv[l];
-          const double fac = (mat * xl + e4);
-          const double v = sm * pv[3 + l];
-          am[6 + l] = fma(am[6 + l], fac, (am[3 + l] + am[3 + l]) * v);
-          am[3 + l] = fma(am[3 + l], fac, am[l] * v);
-          am[l] *= fac;
-        }
+          fac = (mat * xl + e4);
+          v = sm * pv[3 + l];
+        });
       } else {
 #pragma unroll
         for (int i = 0; i < 9; ++i) {
@@ -136,11 +132,7 @@ __device__ __forceinline__ void fam_fit_pass(int64_t e0, int64_t e1, int lane, c
       const double D = fma(q2, am[2] * inv, fma(q1, am[1] * inv, q0 * (am[0] * inv)));
       const double D1 = fma(q2, am[5] * inv, fma(q1, am[4] * inv, q0 * (am[3] * inv)));
       const double D2 = fma(q2, am[8] * inv, fma(q1, am[7] * inv, q0 * (am[6] * inv)));
-      const double iD = 1.0 / D;
-      const double g1 = D1 * iD;
-      s0 += pos_log(D, 0.0);
-      s1 += g1;
-      s2 += fma(-g1, g1, D2 * iD);
+      ambient_fit::add_entry(D, D1, D2, s0, s1, s2);
     } else {
 #pragma unroll
       for (int l = 0; l < 3; ++l) {
@@ -245,7 +237,7 @@ extern "C" int muxgl_fmx_ambient_fit(muxgl_handle* h, const double* amb_af, int3
     return 0;
   }
   // (no clear_timing, no timing slot: records, timings and every other state of the handle keep their values)
-  return ambient_fit::host_run(h, "muxgl_fmx_ambient_fit", amb_af, n_cand, cand, out, kernel_ms,
+  return ambient_fit::host_run(h, "muxgl_fmx_ambient_fit", amb_af, n_cand, 1, cand, 4, out, kernel_ms,
                                [&](int64_t n_units, const double* d_af, const int32_t* d_cand, double* d_dout, int32_t* d_iout) {
                                  hipLaunchKernelGGL(fam_fit_kernel, dim3((unsigned)((n_units + 3) / 4)), dim3(256), 0, h->stream,
                                                     n_units, (int)n_cand, d_cand, rho_max, h->d_cell_ptr, h->d_entry_snp,

@@ -54,6 +54,21 @@ int for_members(muxgl_handle* h, F f) {
   return 0;
 }
 
+// The members of a fit call, each on its own cells: run(member, o, at, ms) with o = the member's first cell x n_cand and
+// at(q) = q + o, or NULL for an output the caller does not want.  kernel_ms: the slowest member's.
+template <class Run>
+int fit_members(muxgl_handle* h, int32_t n_cand, float* kernel_ms, Run run) {
+  muxgl_group* g = h->group;
+  std::vector<float> ms((size_t)g->n, 0.f);
+  if (for_members(h, [&](int r) {
+        const size_t o = (size_t)g->cb[(size_t)r] * (size_t)n_cand;
+        return run(g->m[(size_t)r], o, [o](auto* q) { return q ? q + o : nullptr; }, kernel_ms ? &ms[(size_t)r] : nullptr);
+      }))
+    return 1;
+  if (kernel_ms) *kernel_ms = *std::max_element(ms.begin(), ms.end());
+  return 0;
+}
+
 void max_timing(muxgl_group* g) {
   for (int i = 0; i < MUXGL_T_COUNT; ++i) {
     g->ms[i] = 0.f;
@@ -379,17 +394,11 @@ int group_demux_ambient_fit(muxgl_handle* h, const muxgl_demux_params* p, const 
   if (demux_ambient_fit_bad_args(amb_af, n_cand, cand, g->C, g->V, rho_max,
                                  rho_hat || ll_hat || ll_zero || info || status || n_steps, why, sizeof(why)))
     MUXGL_FAIL(h, "%s", why);
-  std::vector<float> ms((size_t)g->n, 0.f);
-  if (for_members(h, [&](int r) {  // (every member checks amb_af against its copy of has_gp)
-        const size_t o = (size_t)g->cb[(size_t)r] * (size_t)n_cand;
-        return muxgl_demux_ambient_fit(g->m[(size_t)r], p, amb_af, n_cand, cand + o, rho_max, rho_hat ? rho_hat + o : nullptr,
-                                       ll_hat ? ll_hat + o : nullptr, ll_zero ? ll_zero + o : nullptr, info ? info + o : nullptr,
-                                       status ? status + o : nullptr, n_steps ? n_steps + o : nullptr,
-                                       kernel_ms ? &ms[(size_t)r] : nullptr);
-      }))
-    return 1;
-  if (kernel_ms) *kernel_ms = *std::max_element(ms.begin(), ms.end());
-  return 0;
+  // (every member checks amb_af against its copy of has_gp)
+  return fit_members(h, n_cand, kernel_ms, [&](muxgl_handle* m, size_t o, auto at, float* ms) {
+    return muxgl_demux_ambient_fit(m, p, amb_af, n_cand, cand + o, rho_max, at(rho_hat), at(ll_hat), at(ll_zero), at(info),
+                                   at(status), at(n_steps), ms);
+  });
 }
 
 // every member fits its own cells and writes their rows of the caller's arrays; kernel_ms: the slowest member's
@@ -405,16 +414,10 @@ int group_demux_alpha_fit(muxgl_handle* h, const muxgl_demux_params* p, int32_t 
   if (demux_alpha_fit_bad_args(n_cand, pair, g->C, g->V, alpha_max,
                                alpha_hat || ll_hat || ll_zero || ll_top || info || status || n_steps, why, sizeof(why)))
     MUXGL_FAIL(h, "%s", why);
-  std::vector<float> ms((size_t)g->n, 0.f);
-  if (for_members(h, [&](int r) {
-        const size_t o = (size_t)g->cb[(size_t)r] * (size_t)n_cand;
-        auto at = [o](auto* q) { return q ? q + o : nullptr; };
-        return muxgl_demux_alpha_fit(g->m[(size_t)r], p, n_cand, pair + 2 * o, alpha_max, at(alpha_hat), at(ll_hat), at(ll_zero),
-                                     at(ll_top), at(info), at(status), at(n_steps), kernel_ms ? &ms[(size_t)r] : nullptr);
-      }))
-    return 1;
-  if (kernel_ms) *kernel_ms = *std::max_element(ms.begin(), ms.end());
-  return 0;
+  return fit_members(h, n_cand, kernel_ms, [&](muxgl_handle* m, size_t o, auto at, float* ms) {
+    return muxgl_demux_alpha_fit(m, p, n_cand, pair + 2 * o, alpha_max, at(alpha_hat), at(ll_hat), at(ll_zero), at(ll_top),
+                                 at(info), at(status), at(n_steps), ms);
+  });
 }
 
 // every member counts the reads of its own cells; the counts are added here (integers: exact in any order)
@@ -813,17 +816,10 @@ int group_fmx_ambient_fit(muxgl_handle* h, const double* amb_af, int32_t n_cand,
   if (fmx_ambient_fit_bad_args(amb_af, g->S, n_cand, cand, g->C, g->K, rho_max,
                                rho_hat || ll_hat || ll_zero || info || status || n_steps, why, sizeof(why)))
     MUXGL_FAIL(h, "%s", why);
-  std::vector<float> ms((size_t)g->n, 0.f);
-  if (for_members(h, [&](int r) {
-        const size_t o = (size_t)g->cb[(size_t)r] * (size_t)n_cand;
-        return muxgl_fmx_ambient_fit(g->m[(size_t)r], amb_af, n_cand, cand + o, rho_max, rho_hat ? rho_hat + o : nullptr,
-                                     ll_hat ? ll_hat + o : nullptr, ll_zero ? ll_zero + o : nullptr, info ? info + o : nullptr,
-                                     status ? status + o : nullptr, n_steps ? n_steps + o : nullptr,
-                                     kernel_ms ? &ms[(size_t)r] : nullptr);
-      }))
-    return 1;
-  if (kernel_ms) *kernel_ms = *std::max_element(ms.begin(), ms.end());
-  return 0;
+  return fit_members(h, n_cand, kernel_ms, [&](muxgl_handle* m, size_t o, auto at, float* ms) {
+    return muxgl_fmx_ambient_fit(m, amb_af, n_cand, cand + o, rho_max, at(rho_hat), at(ll_hat), at(ll_zero), at(info),
+                                 at(status), at(n_steps), ms);
+  });
 }
 
 // every member folds its own cells and writes their rows of the caller's tables

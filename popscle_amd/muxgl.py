@@ -79,6 +79,18 @@ class _DemuxParams(C.Structure):
                 ("doublet_prior", C.c_double)]
 
 
+def _demux_params(alphas, doublet_prior=0.5):
+    """the muxgl_demux_params of an alpha sequence (doublet_prior: 0.5 where the call does not read it)"""
+    if len(alphas) > MAX_ALPHA:
+        raise ValueError("too many alphas")
+    p = _DemuxParams()
+    p.n_alpha = len(alphas)
+    for i, a in enumerate(alphas):
+        p.alpha[i] = float(a)
+    p.doublet_prior = float(doublet_prior)
+    return p
+
+
 class _FmxParams(C.Structure):
     _fields_ = [("doublet_prior", C.c_double), ("geno_error", C.c_double)]
 
@@ -343,6 +355,40 @@ def _arr(a, dtype, name):
     return a
 
 
+_NO_AF = object()  # _fit: the call takes no amb_af
+
+
+def _fit(eng, fn, fields, want, params, amb_af, slots, pair, x_max):
+    """What the three fit methods of Engine share: the library's fn(handle, [params,] [amb_af,] n_cand, slots, x_max, one
+    pointer per field (NULL where not wanted), &kernel_ms).  slots: int32 [C][n_cand] (or [C]) candidates, or with `pair`
+    [C][n_cand][2] (or [C][2]) pairs, which the dict then holds under "pair".  params None: the call takes none; amb_af
+    _NO_AF likewise."""
+    unknown = set(want) - set(fields)
+    if unknown:
+        raise ValueError(f"unknown fields {sorted(unknown)}")
+    head = [] if params is None else [C.byref(params)]
+    if amb_af is not _NO_AF:
+        amb_af = _arr(amb_af, np.float64, "amb_af")
+        if amb_af.shape != (eng.S,):
+            raise ValueError("amb_af must be [S]")
+        head.append(_ptr(amb_af))
+    name, last = ("pairs", (2,)) if pair else ("cand", ())
+    slots = _arr(slots, np.int32, name)
+    if slots.ndim == 1 + len(last):
+        slots = slots.reshape((-1, 1) + last)
+    if slots.ndim != 2 + len(last) or slots.shape[0] != eng.C or slots.shape[2:] != last:
+        raise ValueError(f"{name} must be [C][n_cand]" + "[2]" * len(last))
+    out = {n: np.zeros(slots.shape[:2], dtype=np.int32 if n in ("status", "n_steps") else np.float64)
+           for n in fields if n in want}
+    ms = C.c_float(0.0)
+    eng._check(getattr(eng.lib, fn)(eng.h, *head, slots.shape[1], _ptr(slots), float(x_max), *[_ptr(out.get(n)) for n in fields],
+                                    C.byref(ms)))
+    if pair:
+        out["pair"] = slots
+    out["kernel_ms"] = float(ms.value)
+    return out
+
+
 class Engine:
     """One muxgl handle: one GPU (device_id an int) or a device group (a list of device ordinals; the same ordinal may
     appear more than once = virtual ranks on one GPU).  Methods mirror the C-ABI one to one."""
@@ -444,14 +490,7 @@ class Engine:
     def demux_run(self, alphas=(0.0, 0.5), doublet_prior=0.5, want_cells=True, want_full_ll=False):
         key = (tuple(alphas), float(doublet_prior))
         if getattr(self, "_dp_key", None) != key:  # (the struct of the last call is kept: a tight loop re-uses it)
-            if len(alphas) > MAX_ALPHA:
-                raise ValueError("too many alphas")
-            p = _DemuxParams()
-            p.n_alpha = len(alphas)
-            for i, a in enumerate(alphas):
-                p.alpha[i] = float(a)
-            p.doublet_prior = float(doublet_prior)
-            self._dp, self._dp_key = p, key
+            self._dp, self._dp_key = _demux_params(alphas, doublet_prior), key
         p = self._dp
         out = np.zeros(self.C, dtype=DEMUX_CELL) if want_cells else None
         full = np.zeros((self.C, self.V, self.V, len(alphas)), dtype=np.float64) if want_full_ll else None
@@ -465,13 +504,7 @@ class Engine:
         """muxgl_demux_singlets: float64 [C][V], the singlet log-likelihood llksAB[(j, 0, 0)] of every droplet against
         every sample (full_ll[:, :, 0, 0] where that tensor exists), at any V, without a previous demux_run.  The grid
         matters: the per-entry likelihoods are normalised over all of its alphas."""
-        if len(alphas) > MAX_ALPHA:
-            raise ValueError("too many alphas")
-        p = _DemuxParams()
-        p.n_alpha = len(alphas)
-        for i, a in enumerate(alphas):
-            p.alpha[i] = float(a)
-        p.doublet_prior = 0.5  # (not read by the call)
+        p = _demux_params(alphas)  # (doublet_prior is not read by the call)
         out = np.zeros((self.C, self.V), dtype=np.float64)
         self._check(self.lib.muxgl_demux_singlets(self.h, C.byref(p), _ptr(out)))
         return out
@@ -485,16 +518,10 @@ class Engine:
         dbl float64 [C][V], the best doublet log-likelihood with s in it (-1e300: none); partner, alpha_idx, first
         int32 [C][V]: the other sample of that doublet, its alpha index and whether s is its first sample (-1: none).
         At any V, without a previous demux_run.  want: the subset of the six to fetch (the others are passed as NULL)."""
-        if len(alphas) > MAX_ALPHA:
-            raise ValueError("too many alphas")
+        p = _demux_params(alphas, doublet_prior)
         unknown = set(want) - set(self.INCLUSION_FIELDS)
         if unknown:
             raise ValueError(f"unknown inclusion fields {sorted(unknown)}")
-        p = _DemuxParams()
-        p.n_alpha = len(alphas)
-        for i, a in enumerate(alphas):
-            p.alpha[i] = float(a)
-        p.doublet_prior = float(doublet_prior)
         out = {}
         for name in self.INCLUSION_FIELDS:
             if name in want:
@@ -512,16 +539,10 @@ class Engine:
         kernel_ms, the event time of the call's kernels.  gp0: the unknown donor's genotype prior [S][3], or None for the
         panel mean.  want: the subset of the three to fetch (the others are passed as NULL).  At any V, without a previous
         demux_run.  unknown_summary() turns the tables into per-droplet calls."""
-        if len(alphas) > MAX_ALPHA:
-            raise ValueError("too many alphas")
+        p = _demux_params(alphas)  # (doublet_prior is not read by the call)
         unknown = set(want) - set(self.UNKNOWN_FIELDS)
         if unknown:
             raise ValueError(f"unknown fields {sorted(unknown)}")
-        p = _DemuxParams()
-        p.n_alpha = len(alphas)
-        for i, a in enumerate(alphas):
-            p.alpha[i] = float(a)
-        p.doublet_prior = 0.5  # (not read by the call)
         if gp0 is not None:
             gp0 = _arr(gp0, np.float64, "gp0")
             if gp0.shape != (self.S, 3):
@@ -543,13 +564,7 @@ class Engine:
         log-likelihoods under the grid `alphas`, and kernel_ms, the event time of the call's kernels.  At any V, without
         a previous demux_run; ambient_profile() makes amb_af from pileup_allele_counts(), ambient_summary() turns the
         table into per-droplet calls."""
-        if len(alphas) > MAX_ALPHA:
-            raise ValueError("too many alphas")
-        p = _DemuxParams()
-        p.n_alpha = len(alphas)
-        for i, a in enumerate(alphas):
-            p.alpha[i] = float(a)
-        p.doublet_prior = 0.5  # (not read by the call)
+        p = _demux_params(alphas)  # (doublet_prior is not read by the call)
         amb_af = _arr(amb_af, np.float64, "amb_af")
         if amb_af.shape != (self.S,):
             raise ValueError("amb_af must be [S]")
@@ -568,35 +583,8 @@ class Engine:
         sequence of alphas); cand: int32 [C][n_cand] (or [C]), a sample or -1 per slot.  dict of rho_hat, ll_hat, ll_zero,
         info float64 [C][n_cand], status, n_steps int32 [C][n_cand], and kernel_ms.  want: the subset of the six to fetch
         (the others are passed as NULL).  ambient_fit_summary() gives the standard error and the likelihood ratio."""
-        alphas = params
-        if len(alphas) > MAX_ALPHA:
-            raise ValueError("too many alphas")
-        unknown = set(want) - set(self.AMBIENT_FIT_FIELDS)
-        if unknown:
-            raise ValueError(f"unknown fields {sorted(unknown)}")
-        p = _DemuxParams()
-        p.n_alpha = len(alphas)
-        for i, a in enumerate(alphas):
-            p.alpha[i] = float(a)
-        p.doublet_prior = 0.5  # (not read by the call)
-        amb_af = _arr(amb_af, np.float64, "amb_af")
-        if amb_af.shape != (self.S,):
-            raise ValueError("amb_af must be [S]")
-        cand = _arr(cand, np.int32, "cand")
-        if cand.ndim == 1:
-            cand = cand.reshape(-1, 1)
-        if cand.ndim != 2 or cand.shape[0] != self.C:
-            raise ValueError("cand must be [C][n_cand]")
-        out = {}
-        for name in self.AMBIENT_FIT_FIELDS:
-            if name in want:
-                out[name] = np.zeros(cand.shape, dtype=np.int32 if name in ("status", "n_steps") else np.float64)
-        ms = C.c_float(0.0)
-        self._check(self.lib.muxgl_demux_ambient_fit(self.h, C.byref(p), _ptr(amb_af), cand.shape[1], _ptr(cand),
-                                                      float(rho_max), *[_ptr(out.get(n)) for n in self.AMBIENT_FIT_FIELDS],
-                                                      C.byref(ms)))
-        out["kernel_ms"] = float(ms.value)
-        return out
+        return _fit(self, "muxgl_demux_ambient_fit", self.AMBIENT_FIT_FIELDS, want, _demux_params(params), amb_af, cand, False,
+                    rho_max)
 
     ALPHA_FIT_FIELDS = ("alpha_hat", "ll_hat", "ll_zero", "ll_top", "info", "status", "n_steps")
 
@@ -607,32 +595,9 @@ class Engine:
         alpha_hat, ll_hat, ll_zero, ll_top, info float64 [C][n_cand], status, n_steps int32 [C][n_cand], the pairs under
         "pair", alpha_max, and kernel_ms.  want: the subset of the seven to fetch (the others are passed as NULL).
         alpha_fit_summary() gives the standard error, the likelihood ratio and the major sample."""
-        alphas = params
-        if len(alphas) > MAX_ALPHA:
-            raise ValueError("too many alphas")
-        unknown = set(want) - set(self.ALPHA_FIT_FIELDS)
-        if unknown:
-            raise ValueError(f"unknown fields {sorted(unknown)}")
-        p = _DemuxParams()
-        p.n_alpha = len(alphas)
-        for i, a in enumerate(alphas):
-            p.alpha[i] = float(a)
-        p.doublet_prior = 0.5  # (not read by the call)
-        pairs = _arr(pairs, np.int32, "pairs")
-        if pairs.ndim == 2:
-            pairs = pairs.reshape(-1, 1, 2)
-        if pairs.ndim != 3 or pairs.shape[0] != self.C or pairs.shape[2] != 2:
-            raise ValueError("pairs must be [C][n_cand][2]")
-        out = {}
-        for name in self.ALPHA_FIT_FIELDS:
-            if name in want:
-                out[name] = np.zeros(pairs.shape[:2], dtype=np.int32 if name in ("status", "n_steps") else np.float64)
-        ms = C.c_float(0.0)
-        self._check(self.lib.muxgl_demux_alpha_fit(self.h, C.byref(p), pairs.shape[1], _ptr(pairs), float(alpha_max),
-                                                    *[_ptr(out.get(n)) for n in self.ALPHA_FIT_FIELDS], C.byref(ms)))
-        out["pair"] = pairs
+        out = _fit(self, "muxgl_demux_alpha_fit", self.ALPHA_FIT_FIELDS, want, _demux_params(params), _NO_AF, pairs, True,
+                   alpha_max)
         out["alpha_max"] = float(alpha_max)
-        out["kernel_ms"] = float(ms.value)
         return out
 
     def pileup_allele_counts(self, mask=None):
@@ -837,26 +802,7 @@ class Engine:
         rho_hat, ll_hat, ll_zero, info float64 [C][n_cand], status, n_steps int32 [C][n_cand], and kernel_ms.  want: the
         subset of the six to fetch (the others are passed as NULL).  freemuxlet.ambient_fit_summary() gives the standard
         error and the likelihood ratio."""
-        unknown = set(want) - set(self.AMBIENT_FIT_FIELDS)
-        if unknown:
-            raise ValueError(f"unknown fields {sorted(unknown)}")
-        amb_af = _arr(amb_af, np.float64, "amb_af")
-        if amb_af.shape != (self.S,):
-            raise ValueError("amb_af must be [S]")
-        cand = _arr(cand, np.int32, "cand")
-        if cand.ndim == 1:
-            cand = cand.reshape(-1, 1)
-        if cand.ndim != 2 or cand.shape[0] != self.C:
-            raise ValueError("cand must be [C][n_cand]")
-        out = {}
-        for name in self.AMBIENT_FIT_FIELDS:
-            if name in want:
-                out[name] = np.zeros(cand.shape, dtype=np.int32 if name in ("status", "n_steps") else np.float64)
-        ms = C.c_float(0.0)
-        self._check(self.lib.muxgl_fmx_ambient_fit(self.h, _ptr(amb_af), cand.shape[1], _ptr(cand), float(rho_max),
-                                                    *[_ptr(out.get(n)) for n in self.AMBIENT_FIT_FIELDS], C.byref(ms)))
-        out["kernel_ms"] = float(ms.value)
-        return out
+        return _fit(self, "muxgl_fmx_ambient_fit", self.AMBIENT_FIT_FIELDS, want, None, amb_af, cand, False, rho_max)
 
     # ---- freemuxlet-old: pairwise distance matrix and voting passes (cmd_cram_freemuxlet.cpp:176-343)
     def fmxold_pair_dist(self, bf_thres=5.41, want_full=False):
