@@ -17,6 +17,7 @@
 #include <unordered_set>
 
 #include "../../include/muxgl.h"
+#include "fmx_refusal.hpp"
 #include "path_choice.hpp"
 #include "stream_plan.hpp"
 
@@ -92,9 +93,7 @@ enum { MUXGL_ROLE_FULL = 0, MUXGL_ROLE_ROWS = 1, MUXGL_ROLE_COLS = 2 };
 
 struct muxgl_group;
 
-// muxgl_handle::fmx_sng_state: no E-step since muxgl_fmx_set_clusters; d_cgp holds the posteriors the last E-step read;
-// a posterior phase has rewritten them since
-enum { FMX_SNG_NONE = 0, FMX_SNG_READY = 1, FMX_SNG_STALE = 2 };
+constexpr double kMinNormGL = 1e-6;  // freemuxlet's floor of a normalised likelihood, MIN_NORM_GL (sc_drop_seq.h:14)
 
 // records of the wave E-step's entry streams (fmx_wave.hip)
 struct fmx_lrec {  // a linear entry: glis[g1][g2] = c0 + c1 (g1 + g2)
@@ -734,17 +733,28 @@ int64_t fmx_wave_fll_rows(const muxgl_handle* h);  // rows of d_fll: C + extra p
 int fmx_stream_estep_launch(muxgl_handle* h, const muxgl_fmx_params* p, int64_t c0, int64_t nc);  // fmx_stream.hip
 int fmx_stream_call_launch(muxgl_handle* h, int64_t c0, int64_t c1, double lsp, double ldp);
 int fmx_stream_rows(muxgl_handle* h, const std::vector<int32_t>& cells, double* rows);  // deep-tie rows, host
-const char* fmx_singlets_refusal(const muxgl_handle* h);  // fmx_singlets.hip: why muxgl_fmx_singlets cannot run now, or NULL
-const char* fmx_inclusion_refusal(const muxgl_handle* h);  // fmx_incl.hip: the same for muxgl_fmx_inclusion
-const char* fmx_unknown_refusal(const muxgl_handle* h);    // fmx_unknown.hip: the same for muxgl_fmx_unknown
+// what every demuxlet call on a panel asks first: 0, or 1 with h's message set.  The two "is it set" facts are the caller's:
+// a handle knows them as d_cell_ptr and d_gp, a device group as have_pileup and V
+static inline int demux_preconditions(muxgl_handle* h, const muxgl_demux_params* p, bool have_pileup, bool have_gp) {
+  if (!p) MUXGL_FAIL(h, "demux params NULL");
+  if (p->n_alpha < 1 || p->n_alpha > MUXGL_MAX_ALPHA) MUXGL_FAIL(h, "n_alpha=%d outside [1,%d]", p->n_alpha, MUXGL_MAX_ALPHA);
+  if (!have_pileup) MUXGL_FAIL(h, "no pileup set (muxgl_set_pileup)");
+  if (!have_gp) MUXGL_FAIL(h, "no GP tensor set (muxgl_demux_set_gp)");
+  return 0;
+}
+// fmx_refusal.hpp's rule on the state of m (the handle itself, or a member of its group): 0, or 1 with h's message set
+static inline int fmx_refuse(muxgl_handle* h, const muxgl_handle* m, const char* who, const char* what) {
+  char why[256];
+  if (fmx_table_refusal(who, what, m->d_cell_ptr != nullptr, m->fmx_prepared, m->K, m->fmx_sng_state, why, sizeof(why)))
+    MUXGL_FAIL(h, "%s", why);
+  return 0;
+}
 // fmx_unknown.hip: the first row of gp0[S][3] that is no probability triple (muxgl_fmx_unknown's rule), or -1
 int64_t fmx_unknown_bad_prior(const double* gp0, int64_t S);
-const char* fmx_ambient_refusal(const muxgl_handle* h);    // fmx_ambient.hip: the same for muxgl_fmx_ambient
 // fmx_ambient.hip: muxgl_fmx_ambient's checks of its arguments, on the host: 0, or 1 with the reason written to `why`
 int fmx_ambient_bad_args(const double* amb_af, int64_t S, int32_t n_rho, const double* rho, double* ll_amb, char* why,
                          size_t why_len);
-// fmx_ambient_fit.hip: the same two for muxgl_fmx_ambient_fit
-const char* fmx_ambient_fit_refusal(const muxgl_handle* h);
+// fmx_ambient_fit.hip: the same for muxgl_fmx_ambient_fit
 int fmx_ambient_fit_bad_args(const double* amb_af, int64_t S, int32_t n_cand, const int32_t* cand, int64_t C, int K,
                              double rho_max, bool any_out, char* why, size_t n);
 void fmx_wave_streams_release(muxgl_handle* h);  // the linear/general entry streams and their rank table

@@ -17,42 +17,36 @@
 //     chunks of RC (4, 8 or 16 by the size of the grid, to hold the register count); every chunk repeats the grid
 //     products identically and every ambient product belongs to one rho, so the chunking changes no bit.  A marker
 //     without genotypes gets ones: its row of gp is (1, 0, 0), so its factor is exactly 1 and the sweep has no branch.
-//   * amb_sweep_kernel, lane = sample column of a 64-column block: one dot gp_j . w_e[r] per (entry, column, rho),
-//     multiplied into a product kept as mantissa x 2^exponent, one log per (cell part, column, rho).  A wave is one work
-//     unit: a part of a cell (at most 2048 entries) x a block x a chunk of CH <= 4 rhos.  Every accumulator belongs to
-//     one rho, so this chunking changes no bit either.  Below 64 columns a wave holds G = 64 / VH entries side by side,
-//     multiplied in a fixed butterfly at the end.
-//   * amb_emit_kernel: the logs of the parts of a cell added in entry order and written in the caller's layout.
+//   * the sweep (lane = sample column of a 64-column block, one dot gp_j . w_e[r] per (entry, column, rho)), the emit
+//     kernel, the batches and the host run are ambient_table.hpp's, shared with fmx_ambient.hip; what they guarantee --
+//     no bit depends on the chunking, the budget, the split of the rhos or the devices -- is written there.  This unit
+//     cuts a long cell into fixed parts of 2048 entries and sweeps inside the streamed call's budget (4 GiB or a third
+//     of the device, MUXGL_DEMUX_SLAB_MB).
 //   * amb_count_kernel, lane = entry: the usable reads of the entry by allele, added to its marker's two counters with
 //     integer atomics (exact, and the same in any order); the entry's droplet, for the mask, by bisection of cell_ptr.
-// Which cell goes into which batch, its cut into parts (fixed parts of 2048 entries) and the order of the work items
-// are table_plan.hpp's.  The cut of a cell depends on the cell alone and every reduction tree is fixed: the table is
-// bit-identical from call to call, for any budget, for any split of the rhos over calls, on one device, on a group and
-// through the sharded driver.
-//
-// Memory: nothing proportional to nnz x n_rho is held for the whole pileup.  Cells are swept in batches of whole cells
-// whose weights ([entries][n_rho][3]), slab rows and output rows (table_plan::ambient_bytes) fit the streamed call's
-// budget (4 GiB or a third of the device, MUXGL_DEMUX_SLAB_MB); each batch is copied out before the next.
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
+#include "ambient_table.hpp"
 #include "demux_entry.hpp"
-#include "table_call.hpp"
 
 namespace {
 
-using amb_grid = demux_grid;  // the alpha grid, and the call's rhos in the same sixteen slots
-using amb_item = table_plan::item;  // the entries [e0, e1) of one cell, result row `row` of the slab
-// the further parts of a cell: its value = slab[cell row] + slab[first] + ... + slab[first + count - 1], in this order
-using amb_cell = table_plan::cell;
+static_assert(AMBIENT_MAX_RHO == MUXGL_MAX_ALPHA, "the call's rhos take the sixteen slots of an alpha grid");
+
+// entries per lane between two renormalisations of the sweep, their loads in flight: a factor is >= ~1e-11 for triples
+// that sum to ~1, eight cannot underflow
+struct amb_sweep {
+  static constexpr int unr(int /*VH*/, int CH) { return CH == 1 ? 8 : 4; }
+};
 
 // wt[(e - eb0)][r][0..2] = w_e[r][l], for the entries [eb0, eb1) of a batch
 template <int NA, int RC>
 __global__ void __launch_bounds__(256)
     amb_weight_kernel(int64_t eb0, int64_t eb1, int NR, const int32_t* __restrict__ entry_snp,
                       const int64_t* __restrict__ entry_rptr, const uint8_t* __restrict__ reads,
-                      const double* __restrict__ lut_g, amb_grid al, amb_grid rh, const double* __restrict__ af,
+                      const double* __restrict__ lut_g, demux_grid al, ambient_rhos rh, const double* __restrict__ af,
                       const uint8_t* __restrict__ has_gp, double* __restrict__ wt) {
   __shared__ double lut[384];
   for (int i = threadIdx.x; i < 384; i += 256) lut[i] = lut_g[i];
@@ -97,98 +91,6 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-// grid: ceil(n_units / 4) workgroups of four waves; wave unit <-> (item, column block, rho chunk), the chunk fastest,
-// so the waves of a workgroup walk the same entries and read the same or neighbouring pieces of the genotype rows.
-// slab[row][r][V]
-template <int VH, int CH>
-__global__ void __launch_bounds__(256)
-    amb_sweep_kernel(int64_t n_units, int nblk, int nch, int NR, const amb_item* __restrict__ items,
-                     const int32_t* __restrict__ entry_snp, int64_t eb0, const double* __restrict__ wt,
-                     const double* __restrict__ gp, int V, double* __restrict__ slab) {
-  constexpr int G = 64 / VH;            // entries side by side in a wave
-  constexpr int UNR = CH == 1 ? 8 : 4;  // entries per lane between two renormalisations, their loads in flight: a factor
-                                        // is >= ~1e-11 for triples that sum to ~1, eight cannot underflow
-  const int64_t unit = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (unit >= n_units) return;
-  const int ch = (int)(unit % nch);
-  const int64_t rest = unit / nch;
-  const int blk = (int)(rest % nblk);
-  const int64_t it = rest / nblk;
-  const int lane = threadIdx.x & 63;
-  const int sub = G == 1 ? 0 : lane / VH;  // entry slot of the lane
-  const int j = G == 1 ? blk * 64 + lane : lane % VH;
-  const bool jl = j < V;
-  const size_t jo = (size_t)(jl ? j : V - 1) * 3;
-  const size_t V3 = (size_t)V * 3;
-  const int64_t e0 = items[it].e0, e1 = items[it].e1;
-  int rr[CH];
-#pragma unroll
-  for (int c = 0; c < CH; ++c) rr[c] = ch * CH + c < NR ? ch * CH + c : NR - 1;  // (a slot past the end repeats the last rho)
-
-  double acc[CH];
-  int32_t ex[CH];
-#pragma unroll
-  for (int c = 0; c < CH; ++c) {
-    acc[c] = 1.0;
-    ex[c] = 0;
-  }
-  for (int64_t eb = e0; eb < e1; eb += (int64_t)UNR * G) {
-    double f[UNR][CH];
-#pragma unroll
-    for (int i = 0; i < UNR; ++i) {
-      const int64_t e = eb + (int64_t)i * G + sub;
-      const bool ok = e < e1;
-      const int64_t ec = ok ? e : e1 - 1;  // (a slot past the end reads the last entry again and counts as 1)
-      const double* g = gp + (size_t)entry_snp[ec] * V3 + jo;
-      const double g0 = g[0], g1 = g[1], g2 = g[2];
-      const double* we = wt + (size_t)(ec - eb0) * NR * 3;
-#pragma unroll
-      for (int c = 0; c < CH; ++c) {
-        const double* w = we + rr[c] * 3;
-        const double v = fma(g2, w[2], fma(g1, w[1], g0 * w[0]));
-        f[i][c] = ok ? v : 1.0;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < UNR; ++i)
-#pragma unroll
-      for (int c = 0; c < CH; ++c) acc[c] *= f[i][c];
-#pragma unroll
-    for (int c = 0; c < CH; ++c) prodacc_renorm(acc[c], ex[c]);
-  }
-  if (G > 1) {  // the G partial products of a column, in a fixed butterfly (a product commutes: both lanes get the same bits)
-#pragma unroll
-    for (int off = VH; off < 64; off <<= 1)
-#pragma unroll
-      for (int c = 0; c < CH; ++c) {
-        acc[c] *= __shfl_xor(acc[c], off, 64);
-        ex[c] += __shfl_xor(ex[c], off, 64);
-      }
-  }
-  if (jl && sub == 0) {
-    double* out = slab + (size_t)items[it].row * NR * V + j;
-#pragma unroll
-    for (int c = 0; c < CH; ++c)
-      if (ch * CH + c < NR) out[(size_t)rr[c] * V] = prodacc_log(acc[c], ex[c]);
-  }
-}
-
-// lane = (cell, sample, rho), rho fastest: out[nc][V][NR]
-__global__ void __launch_bounds__(256)
-    amb_emit_kernel(int64_t nc, const amb_cell* __restrict__ cells, int V, int NR, const double* __restrict__ slab,
-                    double* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= nc * V * NR) return;
-  const int r = (int)(i % NR);
-  const int j = (int)((i / NR) % V);
-  const int64_t c = i / ((int64_t)NR * V);
-  const size_t rs = (size_t)NR * V, off = (size_t)r * V + j;
-  const amb_cell ct = cells[c];
-  double s = slab[(size_t)c * rs + off];
-  for (int64_t k = 0; k < ct.count; ++k) s += slab[(size_t)(ct.first + k) * rs + off];
-  out[i] = s;
-}
-
 // cnt[s][0] / [s][1] += the entry's usable reads with bit 7 clear / set; mask: one byte per cell, or NULL
 __global__ void __launch_bounds__(256)
     amb_count_kernel(int64_t nnz, int64_t C, const int64_t* __restrict__ cell_ptr, const int32_t* __restrict__ entry_snp,
@@ -215,16 +117,8 @@ __global__ void __launch_bounds__(256)
   if (n1) atomicAdd(o + 1, n1);
 }
 
-struct amb_batch {  // what one launch of the three kernels needs
-  int64_t eb0, eb1, n_items, nc;
-  const amb_item* d_items;
-  const amb_cell* d_cells;
-  double *d_wt, *d_slab, *d_out;
-  const double* d_af;
-};
-
 template <int NA, int RC>
-int launch_weights(muxgl_handle* h, int NR, const amb_grid& al, const amb_grid& rh, const amb_batch& b) {
+int launch_weights(muxgl_handle* h, int NR, const demux_grid& al, const ambient_rhos& rh, const ambient_batch& b) {
   hipLaunchKernelGGL((amb_weight_kernel<NA, RC>), dim3((unsigned)((b.eb1 - b.eb0 + 255) / 256)), dim3(256), 0, h->stream,
                      b.eb0, b.eb1, NR, h->d_entry_snp, h->d_entry_rptr, h->d_reads, h->d_lut, al, rh, b.d_af, h->d_has_gp,
                      b.d_wt);
@@ -235,7 +129,7 @@ int launch_weights(muxgl_handle* h, int NR, const amb_grid& al, const amb_grid& 
 // rhos per pass of the weight kernel: as many as the call has, rounded up to 4, 8 or 16, within what a lane holds beside
 // the grid's NA x 9 products (NA <= 4: 16, NA <= 8: 8, above: 4)
 template <int NA>
-int launch_weights_rc(muxgl_handle* h, int NR, const amb_grid& al, const amb_grid& rh, const amb_batch& b) {
+int launch_weights_rc(muxgl_handle* h, int NR, const demux_grid& al, const ambient_rhos& rh, const ambient_batch& b) {
   constexpr int CAP = NA <= 4 ? 16 : NA <= 8 ? 8 : 4;
   if constexpr (CAP >= 16)
     if (NR > 8) return launch_weights<NA, 16>(h, NR, al, rh, b);
@@ -244,38 +138,10 @@ int launch_weights_rc(muxgl_handle* h, int NR, const amb_grid& al, const amb_gri
   return launch_weights<NA, 4>(h, NR, al, rh, b);
 }
 
-int weights_dispatch(muxgl_handle* h, int A, int NR, const amb_grid& al, const amb_grid& rh, const amb_batch& b) {
+int weights_dispatch(muxgl_handle* h, int A, int NR, const demux_grid& al, const ambient_rhos& rh, const ambient_batch& b) {
 #define CALL_W(N) launch_weights_rc<N>(h, NR, al, rh, b)
   DISPATCH_NA(A, CALL_W);
 #undef CALL_W
-}
-
-template <int VH, int CH>
-void launch_sweep(muxgl_handle* h, int NR, int nch, const amb_batch& b) {
-  const int nblk = (h->V + 63) / 64;
-  const int64_t n_units = b.n_items * nblk * nch;
-  hipLaunchKernelGGL((amb_sweep_kernel<VH, CH>), dim3((unsigned)((n_units + 3) / 4)), dim3(256), 0, h->stream, n_units, nblk,
-                     nch, NR, b.d_items, h->d_entry_snp, b.eb0, b.d_wt, h->d_gp, h->V, b.d_slab);
-}
-
-template <int CH>
-void sweep_dispatch_vh(muxgl_handle* h, int NR, int nch, const amb_batch& b) {
-  int VH = 64;
-  while (VH > 1 && VH / 2 >= h->V) VH /= 2;
-#define CALL_S(W) launch_sweep<W, CH>(h, NR, nch, b)
-  DISPATCH_WIDTH(VH, CALL_S);
-#undef CALL_S
-}
-
-int sweep_dispatch(muxgl_handle* h, int CH, int NR, int nch, const amb_batch& b) {
-  switch (CH) {
-    case 1: sweep_dispatch_vh<1>(h, NR, nch, b); break;
-    case 2: sweep_dispatch_vh<2>(h, NR, nch, b); break;
-    case 3: sweep_dispatch_vh<3>(h, NR, nch, b); break;
-    default: sweep_dispatch_vh<4>(h, NR, nch, b); break;
-  }
-  HIPCHK(h, hipGetLastError());
-  return 0;
 }
 
 }  // namespace
@@ -300,73 +166,13 @@ int demux_ambient_check_af(muxgl_handle* h, const double* amb_af, const char* wh
 
 int demux_ambient_run(muxgl_handle* h, const muxgl_demux_params* p, const double* amb_af, int NR, const double* rho,
                       double* ll_amb, float* kernel_ms) {
-  const int V = h->V, A = p->n_alpha;
-  const int64_t C = h->C, S = h->S;
-  if (demux_ambient_check_af(h, amb_af, "muxgl_demux_ambient")) return 1;
-  std::vector<int64_t> cell_ptr((size_t)C + 1);
-  HIPCHK(h, hipMemcpyAsync(cell_ptr.data(), h->d_cell_ptr, sizeof(int64_t) * (size_t)(C + 1), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-
-  // batches of whole cells whose device bytes fit the budget (table_plan.hpp)
-  const size_t budget = dev_slab_budget("MUXGL_DEMUX_SLAB_MB");
-  auto bytes_of = [&](int64_t len, int64_t np) { return table_plan::ambient_bytes(len, np, NR, V); };
-  const table_plan::batches bt = table_plan::plan(cell_ptr.data(), C, budget, bytes_of);
-  if (bt.over >= 0) {
-    const int64_t len = cell_ptr[(size_t)bt.over + 1] - cell_ptr[(size_t)bt.over];
-    MUXGL_FAIL(h, "muxgl_demux_ambient: droplet %lld alone (%lld entries x %d rhos x %d samples: %.1f MB) exceeds the "
-                  "budget of %.1f MB (raise MUXGL_DEMUX_SLAB_MB)",
-               (long long)(h->cell_base + bt.over), (long long)len, NR, V,
-               (double)bytes_of(len, table_plan::parts(len)) / 1048576.0, (double)budget / 1048576.0);
-  }
-  const int nblk = (V + 63) / 64;
-  const int nch = (NR + 3) / 4, CH = (NR + nch - 1) / nch;  // chunks of the rhos, rhos per chunk (1..4)
-  if (table_plan::exceeds_one_launch((double)bt.max_rows * nblk * nch, 4.0) ||
-      table_plan::exceeds_one_launch((double)bt.max_cells * V * NR, 256.0))
-    MUXGL_FAIL(h, "muxgl_demux_ambient: a batch of %lld rows x %d samples x %d rhos exceeds one launch (lower MUXGL_DEMUX_SLAB_MB)",
-               (long long)bt.max_rows, V, NR);
-  const amb_grid al = demux_grid_of(p);
-  amb_grid rh;
-  for (int i = 0; i < MUXGL_MAX_ALPHA; ++i) rh.a[i] = i < NR ? rho[i] : rho[NR - 1];  // (a repeated rho is not written)
-
-  dev_tmp<double> d_af, d_wt, d_slab, d_out;
-  dev_tmp<amb_item> d_items;
-  dev_tmp<amb_cell> d_cells;
-  if (dev_alloc(h, &d_af.p, (size_t)S)) return 1;
-  if (dev_alloc(h, &d_wt.p, (size_t)bt.max_entries * NR * 3)) return 1;
-  if (dev_alloc(h, &d_slab.p, (size_t)bt.max_rows * NR * V)) return 1;
-  if (dev_alloc(h, &d_out.p, (size_t)bt.max_cells * V * NR)) return 1;
-  if (dev_alloc(h, &d_items.p, (size_t)bt.max_rows)) return 1;
-  if (dev_alloc(h, &d_cells.p, (size_t)bt.max_cells)) return 1;
-  call_events ev;  // (the handle's timing slots keep their values)
-  if (ev.create(h, kernel_ms, "muxgl_demux_ambient")) return 1;
-
-  if (S > 0) HIPCHK(h, hipMemcpyAsync(d_af.p, amb_af, sizeof(double) * (size_t)S, hipMemcpyHostToDevice, h->stream));
-  std::vector<amb_item> items;
-  std::vector<amb_cell> cells;
-  int64_t c0 = 0;
-  for (const int64_t c1 : bt.end) {
-    const int64_t nc = c1 - c0;
-    table_plan::fill(cell_ptr.data(), c0, c1, table_plan::fixed_begin, items, nullptr, &cells);
-    const amb_batch b = {cell_ptr[(size_t)c0], cell_ptr[(size_t)c1], (int64_t)items.size(), nc, d_items.p, d_cells.p,
-                         d_wt.p, d_slab.p, d_out.p, d_af.p};
-    if (table_upload(h, items, d_items.p, cells, d_cells.p)) return 1;
-    if (ev.start(h)) return 1;
-    if (b.eb1 > b.eb0 && weights_dispatch(h, A, NR, al, rh, b)) return 1;
-    if (sweep_dispatch(h, CH, NR, nch, b)) return 1;
-    {
-      const int64_t n = nc * V * NR;
-      hipLaunchKernelGGL(amb_emit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, nc, d_cells.p, V, NR,
-                         d_slab.p, d_out.p);
-      HIPCHK(h, hipGetLastError());
-    }
-    if (ev.stop(h)) return 1;
-    HIPCHK(h, hipMemcpyAsync(ll_amb + (size_t)c0 * V * NR, d_out.p, sizeof(double) * (size_t)nc * V * NR, hipMemcpyDeviceToHost,
-                             h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    ev.add();
-    c0 = c1;
-  }
-  return 0;
+  if (demux_ambient_check_af(h, amb_af, "muxgl_demux_ambient")) return 1;  // (first, and with no cell too)
+  const ambient_call call = {"muxgl_demux_ambient", h->V, "samples", h->d_gp, "MUXGL_DEMUX_SLAB_MB", table_plan::fixed_begin};
+  const demux_grid al = demux_grid_of(p);
+  return ambient_table_run<amb_sweep>(h, call, amb_af, NR, rho, ll_amb, kernel_ms,
+                                      [&](const ambient_rhos& rh, const ambient_batch& b) {
+                                        return weights_dispatch(h, p->n_alpha, NR, al, rh, b);
+                                      });
 }
 
 int pileup_allele_counts_run(muxgl_handle* h, const uint8_t* cell_mask, int64_t* n_ref, int64_t* n_alt) {

@@ -11,9 +11,8 @@
 //   D = fma(q2, w2, fma(q1, w1, q0 w0)),   D', D'' likewise                              q = d_cgp[s_e][j]
 //   LL = sum_e log D,   LL' = sum_e D' / D,   LL'' = sum_e (D'' / D - (D' / D)^2)         over ALL entries (no has_gp here)
 //
-// The nine, their per-read sum t, the reciprocal-multiply, the final floor and T are formed exactly as fam_weight_kernel /
-// fmx_entry_kernel form them, and the factor operation for operation as fam_weight_kernel does: a_l(rho) at a grid point
-// is the number muxgl_fmx_ambient multiplies.  The floor makes LL piecewise: on a floored element the derivative is that
+// The nine, their per-read sum t, the reciprocal-multiply, the final floor and T are fmx_nine_walk's (fmx_entry.hpp), the
+// text fam_weight_kernel and fmx_entry_kernel walk; the factor is fam_weight_kernel's expression.  The floor makes LL piecewise: on a floored element the derivative is that
 // of the constant 1e-6, which is the derivative of the floored function on that piece.  LL is continuous; where an element
 // crosses the floor LL' jumps, and always upward, because max(a, 1e-6) is convex in a.  So a maximum of LL cannot sit on
 // such a kink, and a bracket with LL'(lo) > 0 > LL'(hi) narrowed by the sign of LL' closes on a smooth zero of LL'
@@ -35,10 +34,9 @@
 #include <vector>
 
 #include "ambient_fit_search.hpp"
+#include "fmx_entry.hpp"
 
 namespace {
-
-constexpr double kMinNormGL = 1e-6;  // sc_drop_seq.h:14
 
 // One pass of a wave over the entries [e0, e1) of a cell for candidate cluster j (qj = cgp + j * 3, K3 = K * 3).
 //   DERIV = false: out[k] = LL(x[k]) for the three shares x[0..2]
@@ -75,26 +73,8 @@ __device__ __forceinline__ void fam_fit_pass(int64_t e0, int64_t e1, int lane, c
     // am: DERIV ? (a_0, a_1, a_2, a_0', a_1', a_2', a_0'', a_1'', a_2'') : a_l of share k at k * 3 + l
     double gls[9], am[9];
 #pragma unroll
-    for (int i = 0; i < 9; ++i) gls[i] = 1.0;
-#pragma unroll
     for (int i = 0; i < 9; ++i) am[i] = (DERIV && i >= 3) ? 0.0 : 1.0;
-    for (int64_t r = r0; r < r1; ++r) {
-      const uint32_t b = reads[r];
-      if (b == MUXGL_READ_OTHER) continue;  // :468
-      const uint32_t al = b >> 7, bq = b & 0x7f;
-      const double mat = lut[128 + bq], e4 = lut[bq] / 4.;
-      // the nine, operation for operation those of fmx_entry_kernel (:472-494)
-      const double fr[9] = {1.0, .75, .5, .75, .5, .25, .5, .25, 0.0};
-      double tmp = 0.0;
-#pragma unroll
-      for (int i = 0; i < 9; ++i) {
-        const double fi = (al == 0) ? fr[i] : fr[8 - i];
-        gls[i] *= (mat * fi + e4);
-        tmp += gls[i];
-      }
-      const double inv = 1.0 / tmp;
-#pragma unroll
-      for (int i = 0; i < 9; ++i) gls[i] *= inv;
+    const double inv = fmx_nine_walk(reads, r0, r1, lut, gls, [&](uint32_t al, double mat, double e4, double inv_t) {
       // (a 1 the compiler cannot see through: 1 - p stays in the read loop instead of nine more doubles held across it;
       // the same operations)
       double one = 1.0;
@@ -114,15 +94,8 @@ __device__ __forceinline__ void fam_fit_pass(int64_t e0, int64_t e1, int lane, c
         }
       }
 #pragma unroll
-      for (int i = 0; i < 9; ++i) am[i] *= inv;
-    }
-    double tmp = 0.0;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-      if (gls[i] < kMinNormGL) gls[i] = kMinNormGL;  // :498-501
-      tmp += gls[i];
-    }
-    const double inv = 1.0 / tmp;
+      for (int i = 0; i < 9; ++i) am[i] *= inv_t;
+    });
     const double* q = qj + (size_t)s * K3;
     const double q0 = q[0], q1 = q[1], q2 = q[2];
     if (DERIV) {
@@ -192,21 +165,6 @@ __global__ void __launch_bounds__(256)
 
 }  // namespace
 
-// why the handle cannot fit now (NULL: it can): fmx_ambient_refusal's rules under this call's name; shared with the group
-const char* fmx_ambient_fit_refusal(const muxgl_handle* h) {
-  if (!h->d_cell_ptr) return "muxgl_fmx_ambient_fit: no pileup set (muxgl_set_pileup)";
-  if (!h->fmx_prepared) return "muxgl_fmx_ambient_fit: call muxgl_fmx_prepare first";
-  if (h->K < 1)
-    return "muxgl_fmx_ambient_fit: no clusters set and no E-step run (muxgl_fmx_set_clusters, then muxgl_fmx_iterate)";
-  if (h->fmx_sng_state == FMX_SNG_NONE)
-    return "muxgl_fmx_ambient_fit: no E-step since muxgl_fmx_set_clusters (run muxgl_fmx_iterate or muxgl_fmx_iter_estep "
-           "first)";
-  if (h->fmx_sng_state != FMX_SNG_READY)
-    return "muxgl_fmx_ambient_fit: the cluster posteriors were rewritten (muxgl_fmx_iter_gp) since the last E-step; the fit "
-           "belongs to an E-step's own posteriors: call it before the next iteration's posterior phase";
-  return nullptr;
-}
-
 // the caller's arguments, on the host, before any device work: 0, or 1 with the reason in `why`
 int fmx_ambient_fit_bad_args(const double* amb_af, int64_t S, int32_t n_cand, const int32_t* cand, int64_t C, int K,
                              double rho_max, bool any_out, char* why, size_t n) {
@@ -227,7 +185,7 @@ extern "C" int muxgl_fmx_ambient_fit(muxgl_handle* h, const double* amb_af, int3
   if (h->group)
     return group_fmx_ambient_fit(h, amb_af, n_cand, cand, rho_max, rho_hat, ll_hat, ll_zero, info, status, n_steps, kernel_ms);
   HIPCHK(h, hipSetDevice(h->device));
-  if (const char* why = fmx_ambient_fit_refusal(h)) MUXGL_FAIL(h, "%s", why);
+  if (fmx_refuse(h, h, "muxgl_fmx_ambient_fit", "the fit belongs")) return 1;
   const ambient_fit::outputs out = {rho_hat, ll_hat, ll_zero, info, status, n_steps};
   char why[256];
   if (fmx_ambient_fit_bad_args(amb_af, h->S, n_cand, cand, h->C, h->K, rho_max, out.any(), why, sizeof(why)))

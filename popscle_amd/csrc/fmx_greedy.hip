@@ -63,7 +63,6 @@ __device__ __forceinline__ double greedy_score(double m2, int32_t e2, double m0,
   return (!empty && fabs(sc) <= fmin(eps, 1e-6)) ? 1e-300 : sc;  // (tests raise eps to 1e300: flags, not scores, change)
 }
 
-constexpr double kMinNormGL = 1e-6;  // sc_drop_seq.h:14
 constexpr int GT = 1024;             // threads of the persistent workgroup
 static_assert(MUXGL_MAX_CLUSTERS <= GT, "the serial kernel holds one stripe of Kp clusters in its threads");
 constexpr int GU = 6;                // gathers a thread has in flight in the distance phase

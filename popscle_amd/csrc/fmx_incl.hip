@@ -182,27 +182,13 @@ int fmx_inclusion_run(muxgl_handle* h, const muxgl_fmx_params* p, double* incl, 
 
 }  // namespace
 
-// why the handle cannot give the tables now (NULL: it can): muxgl_fmx_singlets' rules under this call's name; shared with
-// the device group
-const char* fmx_inclusion_refusal(const muxgl_handle* h) {
-  if (!h->d_cell_ptr) return "muxgl_fmx_inclusion: no pileup set (muxgl_set_pileup)";
-  if (!h->fmx_prepared) return "muxgl_fmx_inclusion: call muxgl_fmx_prepare first";
-  if (h->K < 1) return "muxgl_fmx_inclusion: no clusters set and no E-step run (muxgl_fmx_set_clusters, then muxgl_fmx_iterate)";
-  if (h->fmx_sng_state == FMX_SNG_NONE)
-    return "muxgl_fmx_inclusion: no E-step since muxgl_fmx_set_clusters (run muxgl_fmx_iterate or muxgl_fmx_iter_estep first)";
-  if (h->fmx_sng_state != FMX_SNG_READY)
-    return "muxgl_fmx_inclusion: the cluster posteriors were rewritten (muxgl_fmx_iter_gp) since the last E-step; the tables "
-           "belong to an E-step's own posteriors: call it before the next iteration's posterior phase";
-  return nullptr;
-}
-
 extern "C" int muxgl_fmx_inclusion(muxgl_handle* h, const muxgl_fmx_params* p, double* incl, double* tot, double* dbl,
                                    int32_t* partner) {
   if (!h) return 1;
   if (h->group) return group_fmx_inclusion(h, p, incl, tot, dbl, partner);
   HIPCHK(h, hipSetDevice(h->device));
   if (!p) MUXGL_FAIL(h, "muxgl_fmx_inclusion: fmx params NULL");
-  if (const char* why = fmx_inclusion_refusal(h)) MUXGL_FAIL(h, "%s", why);
+  if (fmx_refuse(h, h, "muxgl_fmx_inclusion", "the tables belong")) return 1;
   if (h->C == 0 || (!incl && !tot && !dbl && !partner)) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;

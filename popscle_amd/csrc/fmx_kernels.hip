@@ -22,11 +22,10 @@
 #include "common.hpp"
 #include "demux_call_body.hpp"
 #include "fmx_call_body.hpp"
+#include "fmx_entry.hpp"
 #include "score_exact.hpp"
 
 namespace {
-
-constexpr double kMinNormGL = 1e-6;  // sc_drop_seq.h:14
 
 // 1/x by v_rcp_f64 and two Newton steps: within 1 ulp of the division at a fifth of its instructions
 __device__ __forceinline__ double fast_rcp(double x) {
@@ -53,38 +52,14 @@ __global__ void __launch_bounds__(256)
     bool linear = false;
     if (in) {
     double gls[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) gls[i] = 1.0;
-    int32_t nreads = 0, nref = 0, nalt = 0;
-    const int64_t r1 = entry_rptr[e + 1];
-    for (int64_t r = entry_rptr[e]; r < r1; ++r) {
-      const uint32_t b = reads[r];
-      ++nreads;                               // sc_drop_seq.cpp:466
-      if (b == MUXGL_READ_OTHER) continue;    // :468
-      const uint32_t al = b >> 7, bq = b & 0x7f;
+    int32_t nref = 0, nalt = 0;
+    const int64_t r0 = entry_rptr[e], r1 = entry_rptr[e + 1];
+    const int32_t nreads = (int32_t)(r1 - r0);  // every read counts, usable or not (sc_drop_seq.cpp:466)
+    // the nine (fmx_entry.hpp), and the usable reads by allele
+    const double inv = fmx_nine_walk(reads, r0, r1, lut, gls, [&](uint32_t al, double, double, double) {
       if (al == 0) ++nref;
       else ++nalt;
-      const double mat = lut[128 + bq], e4 = lut[bq] / 4.;
-      // fraction of reference reads expected for genotype pair (g1,g2) at alpha = 0.5: 1 - (g1+g2)/4 (:472-491)
-      const double fr[9] = {1.0, .75, .5, .75, .5, .25, .5, .25, 0.0};
-      double tmp = 0.0;
-#pragma unroll
-      for (int i = 0; i < 9; ++i) {
-        const double f = (al == 0) ? fr[i] : fr[8 - i];
-        gls[i] *= (mat * f + e4);
-        tmp += gls[i];
-      }
-      const double inv = 1.0 / tmp;
-#pragma unroll
-      for (int i = 0; i < 9; ++i) gls[i] *= inv;
-    }
-    double tmp = 0.0;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-      if (gls[i] < kMinNormGL) gls[i] = kMinNormGL;  // :498-501
-      tmp += gls[i];
-    }
-    const double inv = 1.0 / tmp;
+    });
 #pragma unroll
     for (int i = 0; i < 9; ++i) {
       gls[i] *= inv;

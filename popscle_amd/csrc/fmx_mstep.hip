@@ -23,8 +23,6 @@
 
 namespace {
 
-constexpr double kMinNormGL = 1e-6;  // sc_drop_seq.h:14
-
 __device__ __forceinline__ double mstep_rcp(double x) {  // as fast_rcp of fmx_kernels.hip
   double r = __builtin_amdgcn_rcp(x);
   r = fma(r, fma(-x, r, 1.0), r);

@@ -156,24 +156,11 @@ int fmx_singlets_run(muxgl_handle* h, double* sng) {
 
 }  // namespace
 
-// why the handle cannot give the table now (NULL: it can); shared with the device group
-const char* fmx_singlets_refusal(const muxgl_handle* h) {
-  if (!h->d_cell_ptr) return "muxgl_fmx_singlets: no pileup set (muxgl_set_pileup)";
-  if (!h->fmx_prepared) return "muxgl_fmx_singlets: call muxgl_fmx_prepare first";
-  if (h->K < 1) return "muxgl_fmx_singlets: no clusters set and no E-step run (muxgl_fmx_set_clusters, then muxgl_fmx_iterate)";
-  if (h->fmx_sng_state == FMX_SNG_NONE)
-    return "muxgl_fmx_singlets: no E-step since muxgl_fmx_set_clusters (run muxgl_fmx_iterate or muxgl_fmx_iter_estep first)";
-  if (h->fmx_sng_state != FMX_SNG_READY)
-    return "muxgl_fmx_singlets: the cluster posteriors were rewritten (muxgl_fmx_iter_gp) since the last E-step; the table "
-           "belongs to an E-step's own posteriors: call it before the next iteration's posterior phase";
-  return nullptr;
-}
-
 extern "C" int muxgl_fmx_singlets(muxgl_handle* h, double* sng) {
   if (!h) return 1;
   if (h->group) return group_fmx_singlets(h, sng);
   HIPCHK(h, hipSetDevice(h->device));
-  if (const char* why = fmx_singlets_refusal(h)) MUXGL_FAIL(h, "%s", why);
+  if (fmx_refuse(h, h, "muxgl_fmx_singlets", "the table belongs")) return 1;
   if (!sng) MUXGL_FAIL(h, "muxgl_fmx_singlets: NULL output");
   if (h->C == 0) {
     HIPCHK(h, hipStreamSynchronize(h->stream));

@@ -292,20 +292,6 @@ int fmx_unknown_run(muxgl_handle* h, const double* gp0, double* ll_ju, double* l
 
 }  // namespace
 
-// why the handle cannot give the tables now (NULL: it can): muxgl_fmx_singlets' rules under this call's name; shared with
-// the device group
-const char* fmx_unknown_refusal(const muxgl_handle* h) {
-  if (!h->d_cell_ptr) return "muxgl_fmx_unknown: no pileup set (muxgl_set_pileup)";
-  if (!h->fmx_prepared) return "muxgl_fmx_unknown: call muxgl_fmx_prepare first";
-  if (h->K < 1) return "muxgl_fmx_unknown: no clusters set and no E-step run (muxgl_fmx_set_clusters, then muxgl_fmx_iterate)";
-  if (h->fmx_sng_state == FMX_SNG_NONE)
-    return "muxgl_fmx_unknown: no E-step since muxgl_fmx_set_clusters (run muxgl_fmx_iterate or muxgl_fmx_iter_estep first)";
-  if (h->fmx_sng_state != FMX_SNG_READY)
-    return "muxgl_fmx_unknown: the cluster posteriors were rewritten (muxgl_fmx_iter_gp) since the last E-step; the tables "
-           "belong to an E-step's own posteriors: call it before the next iteration's posterior phase";
-  return nullptr;
-}
-
 // the caller's prior, on the host: every row a probability triple (entries in [0, 1], sum within 1e-6 of 1), which is
 // what the renormalisation bound above rests on; the first offending marker, or -1
 int64_t fmx_unknown_bad_prior(const double* gp0, int64_t S) {
@@ -322,7 +308,7 @@ extern "C" int muxgl_fmx_unknown(muxgl_handle* h, const double* gp0, double* ll_
   if (kernel_ms) *kernel_ms = 0.f;
   if (h->group) return group_fmx_unknown(h, gp0, ll_ju, ll_u, ll_uu, kernel_ms);
   HIPCHK(h, hipSetDevice(h->device));
-  if (const char* why = fmx_unknown_refusal(h)) MUXGL_FAIL(h, "%s", why);
+  if (fmx_refuse(h, h, "muxgl_fmx_unknown", "the tables belong")) return 1;
   if (!ll_ju && !ll_u && !ll_uu) MUXGL_FAIL(h, "muxgl_fmx_unknown: all three outputs are NULL");
   if (gp0) {
     const int64_t bad = fmx_unknown_bad_prior(gp0, h->S);

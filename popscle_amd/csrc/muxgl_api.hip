@@ -589,12 +589,7 @@ int muxgl_demux_set_gp(muxgl_handle* h, int32_t V, const double* gp, const uint8
 }
 
 static int check_demux_params(muxgl_handle* h, const muxgl_demux_params* p) {
-  if (!p) MUXGL_FAIL(h, "demux params NULL");
-  if (p->n_alpha < 1 || p->n_alpha > MUXGL_MAX_ALPHA)
-    MUXGL_FAIL(h, "n_alpha=%d outside [1,%d]", p->n_alpha, MUXGL_MAX_ALPHA);
-  if (!h->d_cell_ptr) MUXGL_FAIL(h, "no pileup set (muxgl_set_pileup)");
-  if (!h->d_gp) MUXGL_FAIL(h, "no GP tensor set (muxgl_demux_set_gp)");
-  return 0;
+  return demux_preconditions(h, p, h->d_cell_ptr != nullptr, h->d_gp != nullptr);
 }
 
 int muxgl_demux_run(muxgl_handle* h, const muxgl_demux_params* p, muxgl_demux_cell* out, double* full_ll) {

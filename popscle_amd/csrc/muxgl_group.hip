@@ -69,6 +69,37 @@ int fit_members(muxgl_handle* h, int32_t n_cand, float* kernel_ms, Run run) {
   return 0;
 }
 
+// The members of a table call, each on its own cells: run(member, at, ms) with at(q, w) = q + the member's first cell x w
+// (w: the output's values per cell), or NULL for an output the caller does not want.  kernel_ms: the slowest member's.
+// slot >= 0: the call reports through that timing slot of a handle, and the group's is the members' maximum.
+template <class Run>
+int table_members(muxgl_handle* h, int slot, float* kernel_ms, Run run) {
+  muxgl_group* g = h->group;
+  std::vector<float> ms((size_t)g->n, 0.f);
+  if (for_members(h, [&](int r) {
+        const size_t c = (size_t)g->cb[(size_t)r];
+        return run(g->m[(size_t)r], [c](auto* q, size_t w) { return q ? q + c * w : nullptr; },
+                   kernel_ms ? &ms[(size_t)r] : nullptr);
+      }))
+    return 1;
+  if (kernel_ms) *kernel_ms = *std::max_element(ms.begin(), ms.end());
+  if (slot >= 0) {
+    g->ms[slot] = 0.f;
+    for (auto* m : g->m) g->ms[slot] = std::max(g->ms[slot], m->ms[slot]);
+  }
+  return 0;
+}
+
+// fmx_refusal.hpp's rule for a group: the group's own two facts first, then the state of every member
+int fmx_group_refuse(muxgl_handle* h, const char* who, const char* what) {
+  muxgl_group* g = h->group;
+  char why[256];
+  if (fmx_table_refusal(who, what, g->have_pileup, g->prepared, 1, FMX_SNG_READY, why, sizeof(why))) MUXGL_FAIL(h, "%s", why);
+  for (const muxgl_handle* m : g->m)
+    if (fmx_refuse(h, m, who, what)) return 1;
+  return 0;
+}
+
 void max_timing(muxgl_group* g) {
   for (int i = 0; i < MUXGL_T_COUNT; ++i) {
     g->ms[i] = 0.f;
@@ -305,80 +336,50 @@ int group_demux_run(muxgl_handle* h, const muxgl_demux_params* p, muxgl_demux_ce
 // every member sweeps its own cells and writes their rows of the caller's [C][V] table
 int group_demux_singlets(muxgl_handle* h, const muxgl_demux_params* p, double* sng) {
   muxgl_group* g = h->group;
-  if (!p) MUXGL_FAIL(h, "demux params NULL");
-  if (p->n_alpha < 1 || p->n_alpha > MUXGL_MAX_ALPHA) MUXGL_FAIL(h, "n_alpha=%d outside [1,%d]", p->n_alpha, MUXGL_MAX_ALPHA);
-  if (!g->have_pileup) MUXGL_FAIL(h, "no pileup set (muxgl_set_pileup)");
-  if (g->V < 1) MUXGL_FAIL(h, "no GP tensor set (muxgl_demux_set_gp)");
+  if (demux_preconditions(h, p, g->have_pileup, g->V >= 1)) return 1;
   if (!sng) MUXGL_FAIL(h, "muxgl_demux_singlets: NULL output");
-  if (for_members(h, [&](int r) {
-        return muxgl_demux_singlets(g->m[(size_t)r], p, sng + (size_t)g->cb[(size_t)r] * (size_t)g->V);
-      }))
-    return 1;
-  g->ms[MUXGL_T_DEMUX_SINGLETS] = 0.f;
-  for (auto* m : g->m) g->ms[MUXGL_T_DEMUX_SINGLETS] = std::max(g->ms[MUXGL_T_DEMUX_SINGLETS], m->ms[MUXGL_T_DEMUX_SINGLETS]);
-  return 0;
+  return table_members(h, MUXGL_T_DEMUX_SINGLETS, nullptr, [&](muxgl_handle* m, auto at, float*) {
+    return muxgl_demux_singlets(m, p, at(sng, (size_t)g->V));
+  });
 }
 
 // every member folds its own cells and writes their rows of the caller's tables
 int group_demux_inclusion(muxgl_handle* h, const muxgl_demux_params* p, const demux_incl_out& out) {
   muxgl_group* g = h->group;
-  if (!p) MUXGL_FAIL(h, "demux params NULL");
-  if (p->n_alpha < 1 || p->n_alpha > MUXGL_MAX_ALPHA) MUXGL_FAIL(h, "n_alpha=%d outside [1,%d]", p->n_alpha, MUXGL_MAX_ALPHA);
-  if (!g->have_pileup) MUXGL_FAIL(h, "no pileup set (muxgl_set_pileup)");
-  if (g->V < 1) MUXGL_FAIL(h, "no GP tensor set (muxgl_demux_set_gp)");
-  if (for_members(h, [&](int r) {
-        const size_t c = (size_t)g->cb[(size_t)r], o = c * (size_t)g->V;
-        return muxgl_demux_inclusion(g->m[(size_t)r], p, out.incl ? out.incl + o : nullptr, out.tot ? out.tot + c : nullptr,
-                                     out.dbl ? out.dbl + o : nullptr, out.partner ? out.partner + o : nullptr,
-                                     out.alpha_idx ? out.alpha_idx + o : nullptr, out.first ? out.first + o : nullptr);
-      }))
-    return 1;
-  g->ms[MUXGL_T_DEMUX_INCLUSION] = 0.f;
-  for (auto* m : g->m) g->ms[MUXGL_T_DEMUX_INCLUSION] = std::max(g->ms[MUXGL_T_DEMUX_INCLUSION], m->ms[MUXGL_T_DEMUX_INCLUSION]);
-  return 0;
+  if (demux_preconditions(h, p, g->have_pileup, g->V >= 1)) return 1;
+  const size_t V = (size_t)g->V;
+  return table_members(h, MUXGL_T_DEMUX_INCLUSION, nullptr, [&](muxgl_handle* m, auto at, float*) {
+    return muxgl_demux_inclusion(m, p, at(out.incl, V), at(out.tot, 1), at(out.dbl, V), at(out.partner, V), at(out.alpha_idx, V),
+                                 at(out.first, V));
+  });
 }
 
 // every member sweeps its own cells and writes their rows of the caller's tables; kernel_ms: the slowest member's
 int group_demux_unknown(muxgl_handle* h, const muxgl_demux_params* p, const double* gp0, double* ll_ju, double* ll_uj,
                         double* ll_uu, float* kernel_ms) {
   muxgl_group* g = h->group;
-  if (!p) MUXGL_FAIL(h, "demux params NULL");
-  if (p->n_alpha < 1 || p->n_alpha > MUXGL_MAX_ALPHA) MUXGL_FAIL(h, "n_alpha=%d outside [1,%d]", p->n_alpha, MUXGL_MAX_ALPHA);
-  if (!g->have_pileup) MUXGL_FAIL(h, "no pileup set (muxgl_set_pileup)");
-  if (g->V < 1) MUXGL_FAIL(h, "no GP tensor set (muxgl_demux_set_gp)");
+  if (demux_preconditions(h, p, g->have_pileup, g->V >= 1)) return 1;
   if (!ll_ju && !ll_uj && !ll_uu) MUXGL_FAIL(h, "muxgl_demux_unknown: all three outputs are NULL");
-  std::vector<float> ms((size_t)g->n, 0.f);
-  if (for_members(h, [&](int r) {
-        const size_t c = (size_t)g->cb[(size_t)r], o = c * (size_t)g->V * (size_t)p->n_alpha;
-        return muxgl_demux_unknown(g->m[(size_t)r], p, gp0, ll_ju ? ll_ju + o : nullptr, ll_uj ? ll_uj + o : nullptr,
-                                   ll_uu ? ll_uu + c * (size_t)p->n_alpha : nullptr, kernel_ms ? &ms[(size_t)r] : nullptr);
-      }))
-    return 1;
-  if (kernel_ms) *kernel_ms = *std::max_element(ms.begin(), ms.end());
-  return 0;
+  const size_t A = (size_t)p->n_alpha, VA = (size_t)g->V * A;
+  return table_members(h, -1, kernel_ms, [&](muxgl_handle* m, auto at, float* ms) {
+    return muxgl_demux_unknown(m, p, gp0, at(ll_ju, VA), at(ll_uj, VA), at(ll_uu, A), ms);
+  });
 }
 
 // every member sweeps its own cells and writes their rows of the caller's table; kernel_ms: the slowest member's
 int group_demux_ambient(muxgl_handle* h, const muxgl_demux_params* p, const double* amb_af, int32_t n_rho, const double* rho,
                         double* ll_amb, float* kernel_ms) {
   muxgl_group* g = h->group;
-  if (!p) MUXGL_FAIL(h, "demux params NULL");
-  if (p->n_alpha < 1 || p->n_alpha > MUXGL_MAX_ALPHA) MUXGL_FAIL(h, "n_alpha=%d outside [1,%d]", p->n_alpha, MUXGL_MAX_ALPHA);
-  if (!g->have_pileup) MUXGL_FAIL(h, "no pileup set (muxgl_set_pileup)");
-  if (g->V < 1) MUXGL_FAIL(h, "no GP tensor set (muxgl_demux_set_gp)");
+  if (demux_preconditions(h, p, g->have_pileup, g->V >= 1)) return 1;
   if (!ll_amb) MUXGL_FAIL(h, "muxgl_demux_ambient: NULL output");
   if (n_rho < 1 || n_rho > MUXGL_MAX_ALPHA) MUXGL_FAIL(h, "muxgl_demux_ambient: n_rho=%d outside [1,%d]", n_rho, MUXGL_MAX_ALPHA);
   if (!rho || !amb_af) MUXGL_FAIL(h, "muxgl_demux_ambient: %s is NULL", rho ? "amb_af" : "rho");
   if (const int r = demux_ambient_bad_rho(n_rho, rho); r >= 0)
     MUXGL_FAIL(h, "muxgl_demux_ambient: rho[%d] (%g) is not a finite number in [0, 1]", r, rho[r]);
-  std::vector<float> ms((size_t)g->n, 0.f);
-  if (for_members(h, [&](int r) {  // (every member checks amb_af against its copy of has_gp)
-        const size_t o = (size_t)g->cb[(size_t)r] * (size_t)g->V * (size_t)n_rho;
-        return muxgl_demux_ambient(g->m[(size_t)r], p, amb_af, n_rho, rho, ll_amb + o, kernel_ms ? &ms[(size_t)r] : nullptr);
-      }))
-    return 1;
-  if (kernel_ms) *kernel_ms = *std::max_element(ms.begin(), ms.end());
-  return 0;
+  // (every member checks amb_af against its copy of has_gp)
+  return table_members(h, -1, kernel_ms, [&](muxgl_handle* m, auto at, float* ms) {
+    return muxgl_demux_ambient(m, p, amb_af, n_rho, rho, at(ll_amb, (size_t)g->V * (size_t)n_rho), ms);
+  });
 }
 
 // every member fits its own cells and writes their rows of the caller's arrays; kernel_ms: the slowest member's
@@ -386,10 +387,7 @@ int group_demux_ambient_fit(muxgl_handle* h, const muxgl_demux_params* p, const 
                             const int32_t* cand, double rho_max, double* rho_hat, double* ll_hat, double* ll_zero, double* info,
                             int32_t* status, int32_t* n_steps, float* kernel_ms) {
   muxgl_group* g = h->group;
-  if (!p) MUXGL_FAIL(h, "demux params NULL");
-  if (p->n_alpha < 1 || p->n_alpha > MUXGL_MAX_ALPHA) MUXGL_FAIL(h, "n_alpha=%d outside [1,%d]", p->n_alpha, MUXGL_MAX_ALPHA);
-  if (!g->have_pileup) MUXGL_FAIL(h, "no pileup set (muxgl_set_pileup)");
-  if (g->V < 1) MUXGL_FAIL(h, "no GP tensor set (muxgl_demux_set_gp)");
+  if (demux_preconditions(h, p, g->have_pileup, g->V >= 1)) return 1;
   char why[256];
   if (demux_ambient_fit_bad_args(amb_af, n_cand, cand, g->C, g->V, rho_max,
                                  rho_hat || ll_hat || ll_zero || info || status || n_steps, why, sizeof(why)))
@@ -406,10 +404,7 @@ int group_demux_alpha_fit(muxgl_handle* h, const muxgl_demux_params* p, int32_t 
                           double* alpha_hat, double* ll_hat, double* ll_zero, double* ll_top, double* info, int32_t* status,
                           int32_t* n_steps, float* kernel_ms) {
   muxgl_group* g = h->group;
-  if (!p) MUXGL_FAIL(h, "demux params NULL");
-  if (p->n_alpha < 1 || p->n_alpha > MUXGL_MAX_ALPHA) MUXGL_FAIL(h, "n_alpha=%d outside [1,%d]", p->n_alpha, MUXGL_MAX_ALPHA);
-  if (!g->have_pileup) MUXGL_FAIL(h, "no pileup set (muxgl_set_pileup)");
-  if (g->V < 1) MUXGL_FAIL(h, "no GP tensor set (muxgl_demux_set_gp)");
+  if (demux_preconditions(h, p, g->have_pileup, g->V >= 1)) return 1;
   char why[256];
   if (demux_alpha_fit_bad_args(n_cand, pair, g->C, g->V, alpha_max,
                                alpha_hat || ll_hat || ll_zero || ll_top || info || status || n_steps, why, sizeof(why)))
@@ -744,27 +739,17 @@ int group_fmx_get_cluster_pileup(muxgl_handle* h, double* gls, int32_t* counts) 
 // every member sweeps its own cells and writes their rows of the caller's [C][K] table
 int group_fmx_singlets(muxgl_handle* h, double* sng) {
   muxgl_group* g = h->group;
-  if (!g->have_pileup) MUXGL_FAIL(h, "muxgl_fmx_singlets: no pileup set (muxgl_set_pileup)");
-  if (!g->prepared) MUXGL_FAIL(h, "muxgl_fmx_singlets: call muxgl_fmx_prepare first");
-  for (const muxgl_handle* m : g->m)
-    if (const char* why = fmx_singlets_refusal(m)) MUXGL_FAIL(h, "%s", why);
+  if (fmx_group_refuse(h, "muxgl_fmx_singlets", "the table belongs")) return 1;
   if (!sng) MUXGL_FAIL(h, "muxgl_fmx_singlets: NULL output");
-  if (for_members(h, [&](int r) {
-        return muxgl_fmx_singlets(g->m[(size_t)r], sng + (size_t)g->cb[(size_t)r] * (size_t)g->K);
-      }))
-    return 1;
-  g->ms[MUXGL_T_FMX_SINGLETS] = 0.f;
-  for (auto* m : g->m) g->ms[MUXGL_T_FMX_SINGLETS] = std::max(g->ms[MUXGL_T_FMX_SINGLETS], m->ms[MUXGL_T_FMX_SINGLETS]);
-  return 0;
+  return table_members(h, MUXGL_T_FMX_SINGLETS, nullptr, [&](muxgl_handle* m, auto at, float*) {
+    return muxgl_fmx_singlets(m, at(sng, (size_t)g->K));
+  });
 }
 
 // every member sweeps its own cells and writes their rows of the caller's tables; kernel_ms: the slowest member's
 int group_fmx_unknown(muxgl_handle* h, const double* gp0, double* ll_ju, double* ll_u, double* ll_uu, float* kernel_ms) {
   muxgl_group* g = h->group;
-  if (!g->have_pileup) MUXGL_FAIL(h, "muxgl_fmx_unknown: no pileup set (muxgl_set_pileup)");
-  if (!g->prepared) MUXGL_FAIL(h, "muxgl_fmx_unknown: call muxgl_fmx_prepare first");
-  for (const muxgl_handle* m : g->m)
-    if (const char* why = fmx_unknown_refusal(m)) MUXGL_FAIL(h, "%s", why);
+  if (fmx_group_refuse(h, "muxgl_fmx_unknown", "the tables belong")) return 1;
   if (!ll_ju && !ll_u && !ll_uu) MUXGL_FAIL(h, "muxgl_fmx_unknown: all three outputs are NULL");
   if (gp0) {  // (once here, so that the group's handle carries the message; the members find nothing)
     const int64_t bad = fmx_unknown_bad_prior(gp0, g->S);
@@ -773,34 +758,20 @@ int group_fmx_unknown(muxgl_handle* h, const double* gp0, double* ll_ju, double*
                     "sum within 1e-6 of 1)",
                  (long long)bad, gp0[3 * bad], gp0[3 * bad + 1], gp0[3 * bad + 2]);
   }
-  std::vector<float> ms((size_t)g->n, 0.f);
-  if (for_members(h, [&](int r) {
-        const size_t c = (size_t)g->cb[(size_t)r];
-        return muxgl_fmx_unknown(g->m[(size_t)r], gp0, ll_ju ? ll_ju + c * (size_t)g->K : nullptr, ll_u ? ll_u + c : nullptr,
-                                 ll_uu ? ll_uu + c : nullptr, kernel_ms ? &ms[(size_t)r] : nullptr);
-      }))
-    return 1;
-  if (kernel_ms) *kernel_ms = *std::max_element(ms.begin(), ms.end());
-  return 0;
+  return table_members(h, -1, kernel_ms, [&](muxgl_handle* m, auto at, float* ms) {
+    return muxgl_fmx_unknown(m, gp0, at(ll_ju, (size_t)g->K), at(ll_u, 1), at(ll_uu, 1), ms);
+  });
 }
 
 // every member sweeps its own cells and writes their rows of the caller's table; kernel_ms: the slowest member's
 int group_fmx_ambient(muxgl_handle* h, const double* amb_af, int32_t n_rho, const double* rho, double* ll_amb, float* kernel_ms) {
   muxgl_group* g = h->group;
-  if (!g->have_pileup) MUXGL_FAIL(h, "muxgl_fmx_ambient: no pileup set (muxgl_set_pileup)");
-  if (!g->prepared) MUXGL_FAIL(h, "muxgl_fmx_ambient: call muxgl_fmx_prepare first");
-  for (const muxgl_handle* m : g->m)
-    if (const char* why = fmx_ambient_refusal(m)) MUXGL_FAIL(h, "%s", why);
+  if (fmx_group_refuse(h, "muxgl_fmx_ambient", "the table belongs")) return 1;
   char why[256];  // (once here, so that the group's handle carries the message; the members find nothing)
   if (fmx_ambient_bad_args(amb_af, g->S, n_rho, rho, ll_amb, why, sizeof(why))) MUXGL_FAIL(h, "%s", why);
-  std::vector<float> ms((size_t)g->n, 0.f);
-  if (for_members(h, [&](int r) {
-        const size_t o = (size_t)g->cb[(size_t)r] * (size_t)g->K * (size_t)n_rho;
-        return muxgl_fmx_ambient(g->m[(size_t)r], amb_af, n_rho, rho, ll_amb + o, kernel_ms ? &ms[(size_t)r] : nullptr);
-      }))
-    return 1;
-  if (kernel_ms) *kernel_ms = *std::max_element(ms.begin(), ms.end());
-  return 0;
+  return table_members(h, -1, kernel_ms, [&](muxgl_handle* m, auto at, float* ms) {
+    return muxgl_fmx_ambient(m, amb_af, n_rho, rho, at(ll_amb, (size_t)g->K * (size_t)n_rho), ms);
+  });
 }
 
 // every member fits its own cells and writes their rows of the caller's arrays; kernel_ms: the slowest member's
@@ -808,10 +779,7 @@ int group_fmx_ambient_fit(muxgl_handle* h, const double* amb_af, int32_t n_cand,
                           double* rho_hat, double* ll_hat, double* ll_zero, double* info, int32_t* status, int32_t* n_steps,
                           float* kernel_ms) {
   muxgl_group* g = h->group;
-  if (!g->have_pileup) MUXGL_FAIL(h, "muxgl_fmx_ambient_fit: no pileup set (muxgl_set_pileup)");
-  if (!g->prepared) MUXGL_FAIL(h, "muxgl_fmx_ambient_fit: call muxgl_fmx_prepare first");
-  for (const muxgl_handle* m : g->m)
-    if (const char* why = fmx_ambient_fit_refusal(m)) MUXGL_FAIL(h, "%s", why);
+  if (fmx_group_refuse(h, "muxgl_fmx_ambient_fit", "the fit belongs")) return 1;
   char why[256];  // (once here, so that the group's handle carries the message; the members find nothing)
   if (fmx_ambient_fit_bad_args(amb_af, g->S, n_cand, cand, g->C, g->K, rho_max,
                                rho_hat || ll_hat || ll_zero || info || status || n_steps, why, sizeof(why)))
@@ -826,19 +794,11 @@ int group_fmx_ambient_fit(muxgl_handle* h, const double* amb_af, int32_t n_cand,
 int group_fmx_inclusion(muxgl_handle* h, const muxgl_fmx_params* p, double* incl, double* tot, double* dbl, int32_t* partner) {
   muxgl_group* g = h->group;
   if (!p) MUXGL_FAIL(h, "muxgl_fmx_inclusion: fmx params NULL");
-  if (!g->have_pileup) MUXGL_FAIL(h, "muxgl_fmx_inclusion: no pileup set (muxgl_set_pileup)");
-  if (!g->prepared) MUXGL_FAIL(h, "muxgl_fmx_inclusion: call muxgl_fmx_prepare first");
-  for (const muxgl_handle* m : g->m)
-    if (const char* why = fmx_inclusion_refusal(m)) MUXGL_FAIL(h, "%s", why);
-  if (for_members(h, [&](int r) {
-        const size_t c = (size_t)g->cb[(size_t)r], o = c * (size_t)g->K;
-        return muxgl_fmx_inclusion(g->m[(size_t)r], p, incl ? incl + o : nullptr, tot ? tot + c : nullptr,
-                                   dbl ? dbl + o : nullptr, partner ? partner + o : nullptr);
-      }))
-    return 1;
-  g->ms[MUXGL_T_FMX_INCLUSION] = 0.f;
-  for (auto* m : g->m) g->ms[MUXGL_T_FMX_INCLUSION] = std::max(g->ms[MUXGL_T_FMX_INCLUSION], m->ms[MUXGL_T_FMX_INCLUSION]);
-  return 0;
+  if (fmx_group_refuse(h, "muxgl_fmx_inclusion", "the tables belong")) return 1;
+  const size_t K = (size_t)g->K;
+  return table_members(h, MUXGL_T_FMX_INCLUSION, nullptr, [&](muxgl_handle* m, auto at, float*) {
+    return muxgl_fmx_inclusion(m, p, at(incl, K), at(tot, 1), at(dbl, K), at(partner, K));
+  });
 }
 
 int group_get_timing(const muxgl_handle* h, float* ms) {

@@ -81,8 +81,9 @@ inline size_t unknown_bytes(int64_t len, int64_t np, int A, int VC) {
   return (size_t)len * A * 6 * sizeof(double) + (size_t)np * (row_bytes + sizeof(item)) + row_bytes + sizeof(cell);
 }
 
-// device bytes of a cell in a batch of the ambient call at NR rhos and V samples: its entries' weights (three per rho),
-// its slab rows (one per part) with their items, and its row of the table with its record
+// device bytes of a cell in a batch of an ambient call (ambient_table.hpp) at NR rhos and V columns: its entries' weights
+// (three per rho, 24 bytes per entry and rho), its slab rows (one per part) with their items, and its row of the table with
+// its record
 inline size_t ambient_bytes(int64_t len, int64_t np, int NR, int V) {
   const size_t row_bytes = sizeof(double) * (size_t)NR * V;
   return (size_t)len * NR * 3 * sizeof(double) + (size_t)np * (row_bytes + sizeof(item)) + row_bytes + sizeof(cell);
@@ -96,13 +97,8 @@ inline size_t fmx_unknown_bytes(int64_t len, int64_t np, int K) {
   return (size_t)len * 5 * sizeof(double) + (size_t)np * (row_bytes + sizeof(item)) + row_bytes;
 }
 
-// device bytes of a cell in a batch of freemuxlet's ambient call at NR rhos and K clusters: its entries' weights (three per
-// rho, 24 bytes per entry and rho), its slab rows of NR x K doubles (one per part) with their items, and its row of the
-// table with its record
-inline size_t fmx_ambient_bytes(int64_t len, int64_t np, int NR, int K) {
-  const size_t row_bytes = sizeof(double) * (size_t)NR * (size_t)K;
-  return (size_t)len * NR * 3 * sizeof(double) + (size_t)np * (row_bytes + sizeof(item)) + row_bytes + sizeof(cell);
-}
+// freemuxlet's ambient call at NR rhos and K clusters: the same table (ambient_table.hpp), the same bytes
+inline size_t fmx_ambient_bytes(int64_t len, int64_t np, int NR, int K) { return ambient_bytes(len, np, NR, K); }
 
 // the items of the batch [c0, c1), and per cell of several parts its cut and/or per cell its record (NULL: not wanted)
 inline void fill(const int64_t* cell_ptr, int64_t c0, int64_t c1, begin_fn begin, std::vector<item>& items,

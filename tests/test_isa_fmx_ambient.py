@@ -7,7 +7,7 @@ from test_isa import isa, kernels
 
 def test_no_kernel_uses_scratch_and_the_sweeps_stay_in_128_vgprs(tmp_path_factory):
     text = isa(tmp_path_factory, "fmx_ambient")
-    ks = kernels(text, "fam_sweep_kernel")
+    ks = kernels(text, "ambient_sweep_kernel")
     assert len(ks) == 28  # KH = 1, 2, 4, 8, 16, 32, 64 x CH = 1, 2, 3, 4
     for name, (_body, meta) in ks.items():
         assert meta["private_seg_size"] == 0, f"{name}: scratch in a sweep kernel"
@@ -16,7 +16,7 @@ def test_no_kernel_uses_scratch_and_the_sweeps_stay_in_128_vgprs(tmp_path_factor
         assert meta.get("group_segment_fixed_size", 0) == 0, (name, meta)
     wk = kernels(text, "fam_weight_kernel")
     assert len(wk) == 3  # RC = 4, 8, 16
-    ek = kernels(text, "fam_emit_kernel")
+    ek = kernels(text, "ambient_emit_kernel")
     assert len(ek) == 1
     seen = {**ks, **wk, **ek}
     assert set(kernels(text, "")) == set(seen)  # every kernel of the unit is one of these
