@@ -761,6 +761,54 @@ int muxgl_fmx_ambient_fit(muxgl_handle* h, const double* amb_af /* [S] */, int32
                           double* rho_hat, double* ll_hat, double* ll_zero, double* info, /* [C][n_cand] or NULL */
                           int32_t* status, int32_t* n_steps, float* kernel_ms);
 
+/* The mixing share alpha of a freemuxlet doublet as a per-droplet maximum-likelihood estimate, for n_cand slots per droplet
+ * (pair[c][t] = (j, k), two clusters, or (-1, -1) to skip the slot; j == k is allowed): the counterpart of
+ * muxgl_demux_alpha_fit.  The reference fixes the share at one half (calculate_snp_droplet_pileup(..., 0.5),
+ * sc_drop_seq.cpp:452-509; the pair loop is cmd_cram_freemux2.cpp:394-455), so a 15 : 85 doublet is scored as a 50 : 50 one.
+ * Here alpha is the share of k.  The genotype pair (l, m), l from j and m from k, element l * 3 + m
+ * (sc_drop_seq.cpp:472-480), has
+ *   p(l, m, alpha) = 0.5 * l + (m - l) * 0.5 * alpha      the ALT-read probability; one fma; exact at alpha = 0, 0.5, 1
+ *   x = ALT read ? p : 1 - p
+ *   per usable read:  a[l][m] *= (mat * x + e4);  then a[l][m] *= 1 / t     t = the read's sum of the REFERENCE nine (alpha = 0.5)
+ *   after the reads:  a[l][m] = max(a[l][m], 1e-6);  w[l][m] = a[l][m] * (1 / T)    T = the final sum of the floored reference nine
+ *   D_e = sum_l sum_m (q[s_e][j][l] * q[s_e][k][m]) * w_e[l][m]     q = the posteriors the last E-step read (MUXGL_BUF_CGP)
+ *   LL(alpha) = sum over ALL entries e of droplet c of log D_e
+ * The reference renormalises its nine after every read by a sum that depends on alpha, so its function called with
+ * another alpha is on another scale per alpha and is no likelihood in alpha: the six off-diagonal elements take the read's
+ * 1 / t and the final 1 / T of the alpha = 0.5 nine and take part in neither sum, as the ambient elements of
+ * muxgl_fmx_ambient do; the three diagonal elements do not depend on alpha.  At alpha = 0.5 LL is the reference's
+ * llks[j * (j + 1) / 2 + k] of the last E-step (k < j); at alpha = 0 every element (l, m) is the diagonal element (l, l) and
+ * LL is cluster j's entry of muxgl_fmx_singlets, at alpha = 1 cluster k's (sum_m q[m] = 1 to rounding): both singlets nest.
+ * Every read's factor is linear in alpha with slope v = +-mat * (m - l) * 0.5 (+ for an ALT read), so the derivatives
+ * follow from the product rule along the reads as for muxgl_fmx_ambient_fit; a floored element is the constant 1e-6 with
+ * derivatives 0.  D' and D'' are summed with (l, m) next to (m, l), without a fused step: exactly 0 where the two
+ * posterior rows hold the same numbers.  Each element is a product of positive linear factors, above the floor on an
+ * interval, and the coefficients q * q are >= 0: LL' jumps only upward at a crossing, a maximum never sits on a kink, and
+ * a bracket in which an element changes sides is first scanned on 65 points, as for muxgl_fmx_ambient_fit.
+ * Per (c, t), each array [C][n_cand]: alpha_hat, ll_hat = LL(alpha_hat), ll_zero = LL(0), ll_top = LL(alpha_max), info =
+ * -LL''(alpha_hat), status and n_steps, found by muxgl_fmx_ambient_fit's search on [0, alpha_max], with its statuses
+ *   0 interior and converged; 1 at the lower bound (ll_hat == ll_zero bit for bit); 2 at the upper bound (ll_hat == ll_top
+ *   bit for bit); 3 step cap reached; 4 slot skipped (all outputs 0); 5 droplet without entries (all outputs 0); 6 LL at a
+ *   coarse point is not finite -- a posterior row of exactly 0: alpha_hat = 0, ll_hat = ll_zero = ll_top = -inf, info = 0,
+ *   n_steps = 0; no NaN is written.
+ * The standard error of alpha_hat is info^(-1/2) where status is 0 and info > 0.
+ * State rules are muxgl_fmx_ambient's under this call's name: call it after muxgl_fmx_iterate, or after
+ * muxgl_fmx_iter_estep and before the next muxgl_fmx_iter_gp.  1 <= n_cand <= MUXGL_MAX_FIT_CAND; 0 < alpha_max <= 1,
+ * finite; every index in [-1, K); a slot with exactly one negative index, pair == NULL and every output NULL are refused.
+ * Every refusal names its reason and leaves the handle usable.  Any K up to MUXGL_MAX_CLUSTERS on every E-step path, with
+ * anchors held or as priors; one device, a device group (every member fits its own cells) and a slabbed or sharded handle
+ * (the outputs cover the handle's own cells).  With C == 0 the call succeeds and writes nothing.  It reads state and
+ * changes none and touches no timing slot; kernel_ms (NULL allowed) receives the hipEvent time of the call's one kernel
+ * from events of its own (a group: the slowest member's).
+ * Device memory: the inputs, pair and the outputs.  Nothing proportional to nnz is allocated, so no slab budget applies and
+ * MUXGL_FMX_SLAB_MB is not read.  The whole fit of a (droplet, slot) runs in one wave of one launch with every reduction
+ * tree fixed by the droplet alone: the outputs are bit-identical from call to call, for any order, grouping or repetition
+ * of slots, for any subset of outputs, on one device, on a group and through the sharded driver. */
+int muxgl_fmx_alpha_fit(muxgl_handle* h, int32_t n_cand, const int32_t* pair /* [C][n_cand][2]: (j, k) or (-1, -1) */,
+                        double alpha_max,
+                        double* alpha_hat, double* ll_hat, double* ll_zero, double* ll_top, double* info, /* [C][n_cand] or NULL */
+                        int32_t* status, int32_t* n_steps, float* kernel_ms);
+
 /* Near-tie calls of the EM iterations since muxgl_fmx_set_clusters.  The kernels' log-likelihoods equal the reference's to
  * ~1e-12, not to the last bit; a cell where a comparison of cmd_cram_freemux2.cpp:469-497,521-584 has a margin within
  * 1e-9 x max(1, |LL|) is therefore not decided by them but listed, and its contested hypotheses are recomputed in the

@@ -757,6 +757,9 @@ int fmx_ambient_bad_args(const double* amb_af, int64_t S, int32_t n_rho, const d
 // fmx_ambient_fit.hip: the same for muxgl_fmx_ambient_fit
 int fmx_ambient_fit_bad_args(const double* amb_af, int64_t S, int32_t n_cand, const int32_t* cand, int64_t C, int K,
                              double rho_max, bool any_out, char* why, size_t n);
+// fmx_alpha_fit.hip: the same for muxgl_fmx_alpha_fit
+int fmx_alpha_fit_bad_args(int32_t n_cand, const int32_t* pair, int64_t C, int K, double alpha_max, bool any_out, char* why,
+                           size_t n);
 void fmx_wave_streams_release(muxgl_handle* h);  // the linear/general entry streams and their rank table
 int demux_ensure_ll(muxgl_handle* h, const muxgl_demux_params* p);  // standard LL tensor allocated and zeroed
 int demux_call_wave_launch(muxgl_handle* h, const muxgl_demux_params* p);
@@ -837,6 +840,9 @@ int group_fmx_ambient(muxgl_handle* h, const double* amb_af, int32_t n_rho, cons
 int group_fmx_ambient_fit(muxgl_handle* h, const double* amb_af, int32_t n_cand, const int32_t* cand, double rho_max,
                           double* rho_hat, double* ll_hat, double* ll_zero, double* info, int32_t* status, int32_t* n_steps,
                           float* kernel_ms);
+int group_fmx_alpha_fit(muxgl_handle* h, int32_t n_cand, const int32_t* pair, double alpha_max, double* alpha_hat,
+                        double* ll_hat, double* ll_zero, double* ll_top, double* info, int32_t* status, int32_t* n_steps,
+                        float* kernel_ms);
 void group_fmx_exact_stats(const muxgl_handle* h, int64_t* cells, int64_t* changed, int64_t* unresolved);
 void group_peer_stats(const muxgl_handle* h, int32_t* out);
 int group_get_timing(const muxgl_handle* h, float* ms);

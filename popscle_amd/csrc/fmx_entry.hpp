@@ -1,6 +1,7 @@
 // fmx_entry.hpp -- the per-entry genotype-pair likelihoods of freemuxlet (calculate_snp_droplet_pileup,
 // sc_drop_seq.cpp:452-509, alpha = 0.5): the walk of the nine that fmx_entry_kernel (fmx_kernels.hip), fam_weight_kernel
-// (fmx_ambient.hip) and fam_fit_pass (fmx_ambient_fit.hip) share, the counterpart of demux_entry.hpp's grid_walk.
+// (fmx_ambient.hip), fam_fit_pass (fmx_ambient_fit.hip) and fma_fit_pass (fmx_alpha_fit.hip) share, the counterpart of
+// demux_entry.hpp's grid_walk.
 #pragma once
 #include "common.hpp"
 
@@ -12,12 +13,12 @@
 // After the reads every element below MIN_NORM_GL becomes MIN_NORM_GL (:498-501) and T is their sum, added in the same
 // order; the walk returns 1 / T and leaves the floored, not yet divided nine in gls (:502-504 is gls[i] * (1 / T)).
 //
-// A caller's companion products (the ambient tables' a[r][l]) move in per_read alone: they see the read's al, mat, e4
-// and 1 / t and take part in neither t nor T.  Why the three users form the same numbers: this is one text, inlined
-// three times, and every operation on the nine has its operands inside the walk -- a multiply-add the compiler fuses (or
+// A caller's companion products (the ambient tables' a[r][l], the mixing-share fit's a[l][m]) move in per_read alone: they
+// see the read's al, mat, e4 and 1 / t and take part in neither t nor T.  Why the users form the same numbers: this is one
+// text, inlined once per user, and every operation on the nine has its operands inside the walk -- a multiply-add the compiler fuses (or
 // does not) in mat * fr + e4 is fused by a rule that sees this expression only, never a caller's.  So t, T and the nine
 // of an entry are the numbers behind d_egls whichever kernel walks it, which is what puts the ambient table and the
-// ambient fit on the scale of the records' log-likelihoods.
+// two fits on the scale of the records' log-likelihoods.
 template <class PerRead>
 __device__ __forceinline__ double fmx_nine_walk(const uint8_t* __restrict__ reads, int64_t r0, int64_t r1, const double* lut,
                                                 double (&gls)[9], PerRead&& per_read) {

@@ -790,6 +790,22 @@ int group_fmx_ambient_fit(muxgl_handle* h, const double* amb_af, int32_t n_cand,
   });
 }
 
+// every member fits its own cells and writes their rows of the caller's arrays; kernel_ms: the slowest member's
+int group_fmx_alpha_fit(muxgl_handle* h, int32_t n_cand, const int32_t* pair, double alpha_max, double* alpha_hat,
+                        double* ll_hat, double* ll_zero, double* ll_top, double* info, int32_t* status, int32_t* n_steps,
+                        float* kernel_ms) {
+  muxgl_group* g = h->group;
+  if (fmx_group_refuse(h, "muxgl_fmx_alpha_fit", "the fit belongs")) return 1;
+  char why[256];  // (once here, so that the group's handle carries the message; the members find nothing)
+  if (fmx_alpha_fit_bad_args(n_cand, pair, g->C, g->K, alpha_max,
+                             alpha_hat || ll_hat || ll_zero || ll_top || info || status || n_steps, why, sizeof(why)))
+    MUXGL_FAIL(h, "%s", why);
+  return fit_members(h, n_cand, kernel_ms, [&](muxgl_handle* m, size_t o, auto at, float* ms) {
+    return muxgl_fmx_alpha_fit(m, n_cand, pair + 2 * o, alpha_max, at(alpha_hat), at(ll_hat), at(ll_zero), at(ll_top), at(info),
+                               at(status), at(n_steps), ms);
+  });
+}
+
 // every member folds its own cells and writes their rows of the caller's tables
 int group_fmx_inclusion(muxgl_handle* h, const muxgl_fmx_params* p, double* incl, double* tot, double* dbl, int32_t* partner) {
   muxgl_group* g = h->group;

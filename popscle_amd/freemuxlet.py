@@ -25,6 +25,7 @@ import time
 import numpy as np
 
 from . import shard
+from .muxgl import alpha_fit_summary as muxgl_alpha_fit_summary
 from .muxgl import ambient_fit_summary as muxgl_ambient_fit_summary
 from .muxgl import ambient_summary as muxgl_ambient_summary
 
@@ -172,7 +173,7 @@ def settle_near_ties(engs, gather, doublet_prior, geno_error):
 def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early_stop=True, exchange=None,
            exchange_tensor=engine_exchange_tensor, log=None, per=None, timings=None, sync=None, stream_ctx=None,
            want_singlets=False, want_inclusion=False, *, want_unknown=False, anchors=None, anchor_modes=None,
-           want_ambient=None, want_ambient_fit=None):
+           want_ambient=None, want_ambient_fit=None, want_alpha_fit=None):
     """EM loop of cmd_cram_freemux2.cpp:373-605 on a prepared engine.  One rank: a plain engine holding the whole
     pileup.  Several ranks: an engine holding the rank's slabs (load_rank), `exchange` a TorchExchange and
     per = (cells per rank, SNPs per rank) of the equal-slice plan the slabs were cut by.  clust0 spans the whole job.
@@ -189,7 +190,10 @@ def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early
     ambient_summary() turns it into per-droplet calls.  want_ambient_fit = (amb_af, rho_max, n_top) (keyword only): also
     the job-wide dict of Engine.fmx_ambient_fit of the last iteration for the n_top best clusters of every droplet's row of
     the singlet table (ties to the lower index), with those candidates under "cand" ([C][n_top]), gathered the same way,
-    as the last element; ambient_fit_summary() gives the standard errors.  anchors (keyword only): a list of columns of the panel the
+    as the last element; ambient_fit_summary() gives the standard errors.  want_alpha_fit = (alpha_max,) (keyword only):
+    also the job-wide dict of Engine.fmx_alpha_fit of the last iteration for the two pairs of call_pairs() of every droplet,
+    with those pairs under "pair" ([C][2][2]) and alpha_max, gathered the same way, as the last element;
+    alpha_fit_summary() gives the standard errors.  anchors (keyword only): a list of columns of the panel the
     engine holds (demux_set_gp); clusters 0 .. len(anchors)-1 are held to those donors' genotypes and the others are
     learned (Engine.fmx_set_anchors, after fmx_set_clusters; anchor_start() makes a clust0 for it).  One engine with the
     whole pileup or a device group only: refused with more than one rank or always=True.  anchor_modes (keyword only,
@@ -297,7 +301,8 @@ def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early
     out = np.zeros(eng.C_total, dtype=cells.dtype)
     for b, e, raw in parts:
         out[b:e] = np.frombuffer(raw, dtype=cells.dtype)
-    if not want_singlets and not want_inclusion and not want_unknown and want_ambient is None and want_ambient_fit is None:
+    if not want_singlets and not want_inclusion and not want_unknown and want_ambient is None and want_ambient_fit is None \
+            and want_alpha_fit is None:
         return out, history
     res = [out, history]
     if want_singlets:
@@ -335,6 +340,16 @@ def run_em(eng, K, clust0, doublet_prior=0.5, geno_error=0.1, max_iter=10, early
         for b, e, raw in ex.gather_objects((c0, c0 + len(cells), {k: v.tobytes() for k, v in mine.items()})):
             for k, v in fit.items():
                 v[b:e] = np.frombuffer(raw[k], dtype=v.dtype).reshape(e - b, n_top)
+        res.append(fit)
+    if want_alpha_fit is not None:
+        (alpha_max,) = want_alpha_fit
+        got = eng.fmx_alpha_fit(call_pairs(cells), alpha_max)
+        mine = {k: got[k] for k in eng.ALPHA_FIT_FIELDS + ("pair",)}
+        fit = {k: np.zeros((eng.C_total,) + v.shape[1:], dtype=v.dtype) for k, v in mine.items()}
+        for b, e, raw in ex.gather_objects((c0, c0 + len(cells), {k: v.tobytes() for k, v in mine.items()})):
+            for k, v in fit.items():
+                v[b:e] = np.frombuffer(raw[k], dtype=v.dtype).reshape((e - b,) + v.shape[1:])
+        fit["alpha_max"] = float(alpha_max)
         res.append(fit)
     return tuple(res)
 
@@ -447,6 +462,30 @@ def ambient_fit_summary(fit):
     -inf)."""
     with np.errstate(invalid="ignore"):
         return muxgl_ambient_fit_summary(fit)
+
+
+def call_pairs(records):
+    """int32 [C][2][2]: per record of the EM loop (FMX_CELL) the pairs (dBest1, dBest2) and (sBest, sNext), each (-1, -1)
+    where either index is missing (negative; K == 1 has no second cluster): the slots Engine.fmx_alpha_fit takes"""
+    rec = np.asarray(records)
+    out = np.full((rec.shape[0], 2, 2), -1, dtype=np.int32)
+    for slot, (a, b) in enumerate((("dBest1", "dBest2"), ("sBest", "sNext"))):
+        ok = (rec[a] >= 0) & (rec[b] >= 0)
+        out[ok, slot, 0] = rec[a][ok]
+        out[ok, slot, 1] = rec[b][ok]
+    return out
+
+
+def alpha_fit_summary(fit):
+    """What a caller reads off the dict of Engine.fmx_alpha_fit (with its "pair" and "alpha_max"): muxgl.alpha_fit_summary as
+    it is, with clusters for samples -- se, the standard error of alpha_hat where status is 0 and info > 0 and NaN
+    elsewhere; lrt, the likelihood ratio against the better of the two clusters alone where alpha_max is 1 and against the
+    first alone where it is smaller (NaN at status 6, where all are -inf); major, the cluster of the pair that holds the
+    larger share, also under major_clust."""
+    with np.errstate(invalid="ignore"):
+        out = muxgl_alpha_fit_summary(fit)
+    out["major_clust"] = out["major"]
+    return out
 
 
 def unknown_summary(tables, best_llk):

@@ -80,6 +80,16 @@
 //       NUM.READS, CLUST, SNG.LLK (the cluster's singlet LLK), AMB.RHO.MLE, AMB.RHO.SE (NA on a bound or where the
 //       information is not positive), AMB.LLK.MLE, AMB.LRT = 2 (AMB.LLK.MLE - SNG.LLK) (NA at status 6), STATUS (0 interior,
 //       1 lower bound, 2 upper bound, 3 step cap, 5 no entries, 6 a posterior row of exactly 0); all %.4lf
+//       --fit-alpha: also <O>.clust1.alphafit.gz (BGZF), per droplet of .clust1.samples.gz one row DBL for the two clusters of
+//       DBL.BEST.GUESS and one row SNG for (SNG.BEST.GUESS, SNG.NEXT.GUESS) (none where the record has no such cluster): the
+//       maximum-likelihood share of the second cluster on [0, --alpha-fit-max x] (default 1.0) under the reference's doublet
+//       model with the share set free, from the last EM iteration (muxgl_fmx_alpha_fit; the reference fixes the share at
+//       0.5).  The columns of demuxlet's .alphafit.gz with CLUST1 CLUST2 in place of SM1_ID SM2_ID: BARCODE, NUM.SNPS,
+//       NUM.READS, PAIR, CLUST1, CLUST2, SNG1.LLK (the first cluster alone), SNG2.LLK (the second alone; NA where x < 1),
+//       ALPHA.MLE, ALPHA.SE (NA on a bound or where the information is not positive), MIX.LLK.MLE, MIX.LRT = 2 (MIX.LLK.MLE
+//       - the better of SNG1.LLK and SNG2.LLK; SNG1.LLK alone where x < 1; NA at status 6), STATUS; all %.4lf.  A notice
+//       counts the droplets called SNG that the mix explains better by more than 2.  The calls and every other file are
+//       unchanged
 //       --write-cluster-pairs: did the run split one donor over two clusters.  After the EM every pair of final cluster
 //       pileups is scored as one donor against two unrelated donors on the device (muxgl_fmx_cluster_pairs).  Writes
 //       <O>.clust1.ldist.gz (BGZF), one row per pair a > b in ascending (a, b) order: ID1, ID2, NSNP (markers both have
@@ -760,6 +770,8 @@ int cmd_freemuxlet(int argc, char** argv) {
   bool writeAmbient = false;    // (ours) <out>.clust1.amb.gz: every droplet as one cell plus a share of ambient RNA
   bool fitAmbient = false;      // (ours) <out>.clust1.ambfit.gz: the maximum-likelihood ambient share with its standard error
   double ambFitMax = 0.5;
+  bool fitAlpha = false;        // (ours) <out>.clust1.alphafit.gz: the maximum-likelihood mixing share of the best doublet and of the two best singlets (muxgl_fmx_alpha_fit)
+  double alphaFitMax = 1.0;
   std::vector<double> ambRho;
   std::string ambAfFile;
   int32_t ambMaxReads = 0;
@@ -798,6 +810,8 @@ int cmd_freemuxlet(int argc, char** argv) {
   a.add_bool("write-ambient", &writeAmbient);
   a.add_bool("fit-ambient", &fitAmbient);
   a.add_double("ambient-fit-max", &ambFitMax);
+  a.add_bool("fit-alpha", &fitAlpha);
+  a.add_double("alpha-fit-max", &alphaFitMax);
   a.add_multi_double("ambient-rho", &ambRho);
   a.add_string("ambient-af", &ambAfFile);
   a.add_int("ambient-max-reads", &ambMaxReads);
@@ -822,6 +836,7 @@ int cmd_freemuxlet(int argc, char** argv) {
   if ((int)ambRho.size() > MUXGL_MAX_ALPHA) fatal("at most %d --ambient-rho values are supported", MUXGL_MAX_ALPHA);
   if (ambMaxReads < 0) fatal("--ambient-max-reads must not be negative");
   if (!(std::isfinite(ambFitMax) && ambFitMax > 0.0 && ambFitMax <= 1.0)) fatal("--ambient-fit-max must lie in (0, 1]");
+  if (!(std::isfinite(alphaFitMax) && alphaFitMax > 0.0 && alphaFitMax <= 1.0)) fatal("--alpha-fit-max must lie in (0, 1]");
   if (wantMatch && wantAnchor)
     fatal("freemuxlet: --match-vcf cannot be combined with --anchor-vcf: an anchored run's match tables (.clust1.match.gz, "
           ".clust1.match.best.gz) are written against the anchor panel");
@@ -1268,6 +1283,61 @@ int cmd_freemuxlet(int argc, char** argv) {
     });
     wf.close();
     tmr.lap("freemuxlet: write .clust1.ambfit.gz");
+  }
+  if (fitAlpha) {
+    // .clust1.alphafit.gz: per droplet (the order of .clust1.samples.gz) one row DBL for the two clusters of DBL.BEST.GUESS
+    // and one row SNG for (SNG.BEST.GUESS, SNG.NEXT.GUESS) (none where the record has no such cluster), from the posteriors of
+    // the last E-step
+    const size_t n = (size_t)C * 2;
+    std::vector<int32_t> pair(n * 2), status(n);
+    auto ok = [&](int32_t s) { return s >= 0 && s < K; };
+    for (int64_t i = 0; i < C; ++i) {
+      const muxgl_fmx_cell& c = cells[(size_t)i];
+      int32_t* q = &pair[(size_t)i * 4];
+      const bool dbl = ok(c.dBest1) && ok(c.dBest2), sng = ok(c.sBest) && ok(c.sNext);
+      q[0] = dbl ? c.dBest1 : -1, q[1] = dbl ? c.dBest2 : -1;
+      q[2] = sng ? c.sBest : -1, q[3] = sng ? c.sNext : -1;
+    }
+    std::vector<double> ah(n), llh(n), ll0(n), llt(n), info(n);
+    check(h, muxgl_fmx_alpha_fit(h, 2, pair.data(), alphaFitMax, ah.data(), llh.data(), ll0.data(), llt.data(), info.data(),
+                                 status.data(), nullptr, nullptr),
+          "muxgl_fmx_alpha_fit");
+    tmr.lap("freemuxlet: muxgl_fmx_alpha_fit");
+    const bool whole = alphaFitMax == 1.0;  // (only then is ll_top the second cluster alone)
+    int64_t mixed = 0;
+    for (int64_t i = 0; i < C; ++i) {
+      const size_t x = (size_t)i * 2 + 1;
+      if (pair[x * 2] < 0) continue;
+      const double one = whole ? std::max(ll0[x], llt[x]) : ll0[x];
+      mixed += cells[(size_t)i].type == 0 && llh[x] > one + 2.0;
+    }
+    OutFile wf(cf.outPrefix + ".clust1.alphafit.gz", true);
+    wf.printf("BARCODE\tNUM.SNPS\tNUM.READS\tPAIR\tCLUST1\tCLUST2\tSNG1.LLK\tSNG2.LLK\tALPHA.MLE\tALPHA.SE\tMIX.LLK.MLE\tMIX.LRT\t"
+              "STATUS\n");
+    write_rows_parallel(wf, C, [&](int64_t i, std::string& o) {
+      for (size_t k = 0; k < 2; ++k) {
+        const size_t x = (size_t)i * 2 + k;
+        if (pair[x * 2] < 0) continue;
+        const double one = whole ? std::max(ll0[x], llt[x]) : ll0[x];
+        char num[400], top[32], se[32], lrt[32];
+        if (whole) snprintf(top, sizeof(top), "%.4lf", llt[x]);
+        else snprintf(top, sizeof(top), "NA");
+        if (status[x] == 0 && info[x] > 0.0) snprintf(se, sizeof(se), "%.4lf", 1.0 / sqrt(info[x]));  // (on a bound: no standard error)
+        else snprintf(se, sizeof(se), "NA");
+        const double r = 2.0 * (llh[x] - one);
+        if (std::isfinite(r)) snprintf(lrt, sizeof(lrt), "%.4lf", r);
+        else snprintf(lrt, sizeof(lrt), "NA");
+        const int m = snprintf(num, sizeof(num), "\t%d\t%d\t%s\t%d\t%d\t%.4lf\t%s\t%.4lf\t%s\t%.4lf\t%s\t%d\n", nSNPs[(size_t)i],
+                               nReads[(size_t)i], k == 0 ? "DBL" : "SNG", pair[x * 2], pair[x * 2 + 1], ll0[x], top, ah[x], se,
+                               llh[x], lrt, (int)status[x]);
+        o.append(p.bcs[(size_t)i]);
+        o.append(num, (size_t)std::min<int>(m, (int)sizeof(num) - 1));
+      }
+    });
+    wf.close();
+    notice("Mixing share: %lld droplets called SNG are explained better, by more than 2 in log-likelihood, as a mix of their "
+           "best and next singlet cluster at the fitted share than as the better of the two alone", (long long)mixed);
+    tmr.lap("freemuxlet: write .clust1.alphafit.gz");
   }
   if (wantAnchor) {
     // .clust1.anchors.gz: one row per cluster -- the donor it is held to, the greedy cluster it started from with the log
@@ -1837,6 +1907,9 @@ int main(int argc, char** argv) {
                     "  freemuxlet --fit-ambient [--ambient-fit-max x] [--ambient-af FILE] [--ambient-max-reads N]: also\n"
                     "    <out>.clust1.ambfit.gz, per droplet and for its best and next singlet cluster the maximum-likelihood ambient\n"
                     "    share on [0, x] (default 0.5) with its standard error and the likelihood ratio against no ambient RNA\n"
+                    "  freemuxlet --fit-alpha [--alpha-fit-max x]: also <out>.clust1.alphafit.gz, per droplet the maximum-likelihood\n"
+                    "    mixing share on [0, x] (default 1.0) of its best doublet's two clusters (row DBL) and of its best and next\n"
+                    "    singlet cluster (row SNG), with its standard error and the likelihood ratio against the better singlet\n"
                     "  freemuxlet --write-unknown: also <out>.clust1.unk.gz, per droplet how well a donor that no cluster holds\n"
                     "    explains it in the last iteration (BARCODE NUM.SNPS NUM.READS BEST.LLK UNK.SNG.LLK UNK.DBL.LLK HALF.CLUST\n"
                     "    HALF.LLK DIFF.LLK.CLUST.UNK); a notice counts the droplets it explains better by more than 2\n");

@@ -135,6 +135,7 @@ SYMBOLS = {
     "muxgl_fmx_unknown": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP]),
     "muxgl_fmx_ambient": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, _VP]),
     "muxgl_fmx_ambient_fit": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "muxgl_fmx_alpha_fit": (C.c_int, [_VP, C.c_int32, _VP, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "muxgl_fmx_get_cluster_pileup": (C.c_int, [_VP, _VP, _VP]),
     "muxgl_fmx_match_donors": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
     "muxgl_fmx_cluster_pairs": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
@@ -803,6 +804,18 @@ class Engine:
         subset of the six to fetch (the others are passed as NULL).  freemuxlet.ambient_fit_summary() gives the standard
         error and the likelihood ratio."""
         return _fit(self, "muxgl_fmx_ambient_fit", self.AMBIENT_FIT_FIELDS, want, None, amb_af, cand, False, rho_max)
+
+    def fmx_alpha_fit(self, pairs, alpha_max=1.0, want=ALPHA_FIT_FIELDS):
+        """muxgl_fmx_alpha_fit: per droplet (of the handle's own cells) and pair of clusters (j, k), the maximum-likelihood
+        share alpha of k on [0, alpha_max] under the reference's doublet model with the share set free, with its observed
+        information, from the posteriors the last E-step read (include/muxgl.h).  pairs: int32 [C][n_cand][2] (or [C][2]),
+        (j, k) or (-1, -1) per slot.  dict of alpha_hat, ll_hat, ll_zero, ll_top, info float64 [C][n_cand], status, n_steps
+        int32 [C][n_cand], the pairs under "pair", alpha_max, and kernel_ms.  want: the subset of the seven to fetch (the
+        others are passed as NULL).  freemuxlet.alpha_fit_summary() gives the standard error, the likelihood ratio and the
+        major cluster."""
+        out = _fit(self, "muxgl_fmx_alpha_fit", self.ALPHA_FIT_FIELDS, want, None, _NO_AF, pairs, True, alpha_max)
+        out["alpha_max"] = float(alpha_max)
+        return out
 
     # ---- freemuxlet-old: pairwise distance matrix and voting passes (cmd_cram_freemuxlet.cpp:176-343)
     def fmxold_pair_dist(self, bf_thres=5.41, want_full=False):
