@@ -1,7 +1,8 @@
 // ambient_fit_search.hpp -- what the per-droplet fits share: muxgl_demux_ambient_fit (demux_ambient_fit.hip),
-// muxgl_fmx_ambient_fit (fmx_ambient_fit.hip) and muxgl_demux_alpha_fit (demux_alpha_fit.hip, DESIGN 4.1h,
-// where rho reads alpha): the search, the pieces of a pass that do not depend on the model, the store of a result and the
-// host side of the call.  The search: one wave maximises LL(rho) on [0, rho_max] for one (droplet, candidate).  The model
+// muxgl_fmx_ambient_fit (fmx_ambient_fit.hip), muxgl_demux_alpha_fit (demux_alpha_fit.hip) and
+// muxgl_fmx_alpha_fit (fmx_alpha_fit.hip), where rho reads alpha: the search, the pieces of a pass that do not
+// depend on the model, the ll_top rule, the kernel's frame with the store of a result, and the host side of the call (its
+// argument rules: fit_args.hpp).  The search: one wave maximises LL(rho) on [0, rho_max] for one (droplet, candidate).  The model
 // is the caller's: two callables that return, in every lane the same bits,
 //   coarse(x[3], o[3])   o[k] = LL(x[k]) for k < NC
 //   deriv(x, L, d1, d2)  (LL, LL', LL'') at x
@@ -269,6 +270,47 @@ __device__ __forceinline__ void store(const result& r, int lane, int64_t unit, i
   }
 }
 
+// ---- ll_top, LL at the upper bound: the fifth double row of the two mixing-share fits ----
+// Coarse point 8 is x_max bit for bit, the last of the NC shares of the coarse pass that ends on it, and the coarse
+// callable keeps its LL while the search runs.  (A later pass that ends on x_max, the bracket's or the scan's of
+// search_piecewise, goes through the same inlined text and writes the same bits again.)  A coarse pass and a derivative
+// pass form a and D by the same operations, so ll_hat on a bound is ll_zero resp. ll_top bit for bit.
+template <int NC>
+__device__ __forceinline__ void keep_top(const double (&x)[3], const double (&o)[3], double x_max, double& ll_top) {
+  if (x[NC - 1] == x_max) ll_top = o[NC - 1];
+}
+
+// what the call reports: 0 for a droplet without a scored entry, as every output; ll_zero (-inf) where LL is not finite
+__device__ __forceinline__ double top_of(const result& res, double ll_top) {
+  return res.status == NO_ENTRY ? 0.0 : res.status == NOT_FINITE ? res.ll_zero : ll_top;
+}
+
+// ---- the kernel frame of the four fits ----
+// grid: ceil(C * n_cand / 4) workgroups of four waves of one launch; wave unit <-> (cell, slot), the slot fastest, so the
+// waves of a workgroup walk the same entries.  A slot is WIDTH indices (a candidate, or a pair); one that is negative skips
+// the unit (status 4, all outputs 0).  The Phred table, LUT doubles, goes to LDS; fit(lut, lane, e0, e1, j, k) is the
+// model's search over the cell's entries [e0, e1) and returns in every lane the same result, of which lane 0 stores ROWS
+// double rows.  Every reduction tree under `fit` is fixed by the cell alone (lane = entry index modulo 64, then
+// wave_sum's butterfly), there is no atomic and nothing depends on the batch, the device or the other slots: the outputs
+// are bit-identical from call to call, for any order, grouping or repetition of the slots, on one device, on a group and
+// through the sharded driver.
+template <int LUT, int WIDTH, int ROWS, class Fit>
+__device__ __forceinline__ void frame(int64_t n_units, int n_cand, const int32_t* __restrict__ slot,
+                                      const int64_t* __restrict__ cell_ptr, const double* __restrict__ lut_g,
+                                      double* __restrict__ dout, int32_t* __restrict__ iout, Fit&& fit) {
+  __shared__ double lut[LUT];
+  for (int i = threadIdx.x; i < LUT; i += 256) lut[i] = lut_g[i];
+  __syncthreads();
+  const int64_t unit = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (unit >= n_units) return;
+  const int lane = threadIdx.x & 63;
+  const int64_t c = unit / n_cand;
+  const int32_t j = slot[WIDTH * unit], k = slot[WIDTH * unit + WIDTH - 1];
+  result res;
+  if (j >= 0 && k >= 0) res = fit(lut, lane, cell_ptr[c], cell_ptr[c + 1], j, k);
+  store<ROWS>(res, lane, unit, n_units, dout, iout);
+}
+
 // ---- the host side of a fit call ----
 struct outputs {  // each host [C][n_cand] or NULL; ll_top: the calls with five double rows only
   double *rho_hat, *ll_hat, *ll_zero, *info;
@@ -276,30 +318,6 @@ struct outputs {  // each host [C][n_cand] or NULL; ll_top: the calls with five 
   double* ll_top = nullptr;
   bool any() const { return rho_hat || ll_hat || ll_zero || info || ll_top || status || n_steps; }
 };
-
-// the arguments every fit checks alike before its indices, on the host: 0, or 1 with the reason in `why`.  null_arg: the
-// name of a pointer argument that is NULL, or NULL; bound: the name of x_max ("rho_max", "alpha_max")
-inline int bad_head(const char* who, int32_t n_cand, const char* null_arg, const char* bound, double x_max, bool any_out,
-                    char* why, size_t n) {
-  if (!any_out) return snprintf(why, n, "%s: every output is NULL", who), 1;
-  if (n_cand < 1 || n_cand > MUXGL_MAX_FIT_CAND)
-    return snprintf(why, n, "%s: n_cand=%d outside [1,%d]", who, n_cand, MUXGL_MAX_FIT_CAND), 1;
-  if (null_arg) return snprintf(why, n, "%s: %s is NULL", who, null_arg), 1;
-  if (!(std::isfinite(x_max) && x_max > 0.0 && x_max <= 1.0))
-    return snprintf(why, n, "%s: %s (%g) is not a finite number in (0, 1]", who, bound, x_max), 1;
-  return 0;
-}
-
-// the arguments of the two ambient fits.  what: "sample" or "cluster", n_what of them
-inline int bad_args(const char* who, const char* what, const double* amb_af, int32_t n_cand, const int32_t* cand, int64_t C,
-                    int n_what, double rho_max, bool any_out, char* why, size_t n) {
-  if (bad_head(who, n_cand, !cand ? "cand" : !amb_af ? "amb_af" : nullptr, "rho_max", rho_max, any_out, why, n)) return 1;
-  for (int64_t i = 0; i < C * n_cand; ++i)
-    if (cand[i] < -1 || cand[i] >= n_what)
-      return snprintf(why, n, "%s: cand[%lld][%d] (%d) is neither -1 nor a %s in [0,%d)", who, (long long)(i / n_cand),
-                      (int)(i % n_cand), cand[i], what, n_what), 1;
-  return 0;
-}
 
 // amb_af (NULL: the call has none, and nothing is copied) and the slots' indices (`width` per slot: a candidate, or a pair)
 // to the device, launch(n_units, d_af, d_slot, d_dout, d_iout) between the call's own events, the wanted ones of the `rows`
@@ -337,6 +355,14 @@ int host_run(muxgl_handle* h, const char* who, const double* amb_af, int n_cand,
                                h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   ev.add();
+  return 0;
+}
+
+// a fit kernel on the frame's grid, on the handle's stream; its first argument is n_units
+template <class... P, class... A>
+int launch(muxgl_handle* h, void (*kernel)(int64_t, P...), int64_t n_units, A... args) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((n_units + 3) / 4)), dim3(256), 0, h->stream, n_units, args...);
+  HIPCHK(h, hipGetLastError());
   return 0;
 }
 

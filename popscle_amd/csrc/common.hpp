@@ -17,6 +17,7 @@
 #include <unordered_set>
 
 #include "../../include/muxgl.h"
+#include "fit_args.hpp"
 #include "fmx_refusal.hpp"
 #include "path_choice.hpp"
 #include "stream_plan.hpp"
@@ -684,19 +685,15 @@ int demux_ambient_bad_rho(int n_rho, const double* rho);  // the first rho that 
 // the call named `who`
 int demux_ambient_check_af(muxgl_handle* h, const double* amb_af, const char* who);
 // demux_ambient_fit.hip: the fit of muxgl_demux_ambient_fit to the host, rows of the handle's own cells; the arguments but
-// amb_af are checked by the caller (demux_ambient_fit_bad_args: 0, or 1 with the reason written to `why`)
+// amb_af are checked by the caller (demux_ambient_fit_bad_args, fit_args.hpp)
 int demux_ambient_fit_run(muxgl_handle* h, const muxgl_demux_params* p, const double* amb_af, int n_cand, const int32_t* cand,
                           double rho_max, double* rho_hat, double* ll_hat, double* ll_zero, double* info, int32_t* status,
                           int32_t* n_steps, float* kernel_ms);
-int demux_ambient_fit_bad_args(const double* amb_af, int32_t n_cand, const int32_t* cand, int64_t C,
-                               int V, double rho_max, bool any_out, char* why, size_t n);
 // demux_alpha_fit.hip: the fit of muxgl_demux_alpha_fit to the host, rows of the handle's own cells; the arguments are
-// checked by the caller (demux_alpha_fit_bad_args: 0, or 1 with the reason written to `why`)
+// checked by the caller (demux_alpha_fit_bad_args, fit_args.hpp)
 int demux_alpha_fit_run(muxgl_handle* h, const muxgl_demux_params* p, int n_cand, const int32_t* pair, double alpha_max,
                         double* alpha_hat, double* ll_hat, double* ll_zero, double* ll_top, double* info, int32_t* status,
                         int32_t* n_steps, float* kernel_ms);
-int demux_alpha_fit_bad_args(int32_t n_cand, const int32_t* pair, int64_t C, int V, double alpha_max, bool any_out, char* why,
-                             size_t n);
 // demux_ambient.hip: usable reads by marker and allele of the handle's own cells whose mask byte is set (cell_mask: host
 // [C] or NULL), to n_ref / n_alt (host [S])
 int pileup_allele_counts_run(muxgl_handle* h, const uint8_t* cell_mask, int64_t* n_ref, int64_t* n_alt);
@@ -754,12 +751,7 @@ int64_t fmx_unknown_bad_prior(const double* gp0, int64_t S);
 // fmx_ambient.hip: muxgl_fmx_ambient's checks of its arguments, on the host: 0, or 1 with the reason written to `why`
 int fmx_ambient_bad_args(const double* amb_af, int64_t S, int32_t n_rho, const double* rho, double* ll_amb, char* why,
                          size_t why_len);
-// fmx_ambient_fit.hip: the same for muxgl_fmx_ambient_fit
-int fmx_ambient_fit_bad_args(const double* amb_af, int64_t S, int32_t n_cand, const int32_t* cand, int64_t C, int K,
-                             double rho_max, bool any_out, char* why, size_t n);
-// fmx_alpha_fit.hip: the same for muxgl_fmx_alpha_fit
-int fmx_alpha_fit_bad_args(int32_t n_cand, const int32_t* pair, int64_t C, int K, double alpha_max, bool any_out, char* why,
-                           size_t n);
+// (the same for muxgl_fmx_ambient_fit and muxgl_fmx_alpha_fit: fmx_ambient_fit_bad_args, fmx_alpha_fit_bad_args, fit_args.hpp)
 void fmx_wave_streams_release(muxgl_handle* h);  // the linear/general entry streams and their rank table
 int demux_ensure_ll(muxgl_handle* h, const muxgl_demux_params* p);  // standard LL tensor allocated and zeroed
 int demux_call_wave_launch(muxgl_handle* h, const muxgl_demux_params* p);

@@ -13,18 +13,13 @@
 // t is formed exactly as amb_weight_kernel forms it (p is exactly 0 at (l = 0, f = 0) and exactly 1 at (l = 2, f = 1),
 // where v is exactly 0); the grid's NA x 9 products run beside the triples in grid_walk (demux_entry.hpp, where the
 // argument that q_max_e is the same number stands), and all nine of (a, a', a'') are rescaled together every 32 reads by
-// the grid's maximum only.  The product rule, the step from (D, D', D'') to the three sums and the end of a pass are
-// ambient_fit_search.hpp's, shared with demux_alpha_fit.hip.
+// the grid's maximum only.  The product rule, the step from (D, D', D'') to the three sums, the end of a pass, the
+// kernel's frame and the host side of the call are ambient_fit_search.hpp's, shared with all the fits.
 //
-// amb_fit_kernel, one wave per (cell, candidate): the lanes stride the cell's entries, each lane walks its entry's read
-// bytes through the Phred table in LDS, dots the three triples with the candidate's gp row and adds its share of
-// (LL, LL', LL'') in entry order; a fixed xor butterfly adds the 64 shares (a + b commutes, so every lane holds the same
-// bits and every decision below is wave-uniform).  The whole fit runs in this one launch:
-// the search of ambient_fit_search.hpp, shared with muxgl_fmx_ambient_fit, three coarse points per pass (nine products per
-// lane, as in a derivative pass).
-// Every reduction tree is fixed by the cell alone (lane = entry index modulo 64, then the butterfly), there is no atomic
-// and nothing depends on the batch, the device or the other candidates: the outputs are bit-identical from call to call,
-// for any budget, any order or grouping of the candidates, on one device, on a group and through the sharded driver.
+// amb_fit_kernel, one wave per (cell, candidate) in ambient_fit::frame: the lanes stride the cell's entries, each lane
+// walks its entry's read bytes through the Phred table in LDS, dots the three triples with the candidate's gp row and adds
+// its share of (LL, LL', LL'') in entry order, and the search is ambient_fit::search, three coarse points per pass (nine
+// products per lane, as in a derivative pass).
 //
 // Memory: the inputs, cand and the six output arrays.  Nothing proportional to nnz is allocated, so no slab budget applies.
 #include <cmath>
@@ -103,9 +98,7 @@ __device__ __forceinline__ void fit_pass(int64_t e0, int64_t e1, int lane, const
   ambient_fit::pass_sums<DERIV ? 3 : NC>(s0, s1, s2, ns, out, n_scored);
 }
 
-// grid: ceil(C * n_cand / 4) workgroups of four waves; wave unit <-> (cell, candidate), the candidate fastest, so the
-// waves of a workgroup walk the same entries.  dout: [4][n_units] rho_hat, ll_hat, ll_zero, info; iout: [2][n_units]
-// status, n_steps
+// dout: [4][n_units] rho_hat, ll_hat, ll_zero, info; iout: [2][n_units] status, n_steps
 template <int NA>
 __global__ void __launch_bounds__(256)
     amb_fit_kernel(int64_t n_units, int n_cand, const int32_t* __restrict__ cand, double rho_max,
@@ -114,60 +107,29 @@ __global__ void __launch_bounds__(256)
                    const double* __restrict__ lut_g, demux_grid al, const double* __restrict__ af,
                    const uint8_t* __restrict__ has_gp, const double* __restrict__ gp, int V, double* __restrict__ dout,
                    int32_t* __restrict__ iout) {
-  __shared__ double lut[384];
-  for (int i = threadIdx.x; i < 384; i += 256) lut[i] = lut_g[i];
-  __syncthreads();
-  const int64_t unit = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (unit >= n_units) return;
-  const int lane = threadIdx.x & 63;
-  const int64_t c = unit / n_cand;
-  const int32_t j = cand[unit];
-  ambient_fit::result res;  // (cand == -1: status 4, all outputs 0)
-  if (j >= 0) {
-    const int64_t e0 = cell_ptr[c], e1 = cell_ptr[c + 1];
-    const size_t V3 = (size_t)V * 3;
-    const double* gpj = gp + (size_t)j * 3;
-    // shares per coarse pass: three (nine products per lane, as in a derivative pass); one at the widest grid, whose 144
-    // products leave a lane no room for more.  Every sum belongs to one share, so the chunking changes no bit.
-    constexpr int NC = NA > 12 ? 1 : 3;
-    auto coarse = [&](const double (&x)[3], double (&o)[3]) {
-      fit_pass<NA, false, NC>(e0, e1, lane, entry_snp, entry_rptr, reads, lut, al, af, has_gp, gpj, V3, x, o, nullptr);
-    };
-    int n_scored = 0;
-    auto deriv = [&](double x, double& L, double& d1, double& d2) {
-      const double xs[3] = {x, 0.0, 0.0};
-      double o[3];
-      fit_pass<NA, true, 1>(e0, e1, lane, entry_snp, entry_rptr, reads, lut, al, af, has_gp, gpj, V3, xs, o, &n_scored);
-      L = o[0], d1 = o[1], d2 = o[2];
-    };
-    res = ambient_fit::search<NC, false>(rho_max, coarse, deriv, [&] { return n_scored == 0; });
-  }
-  ambient_fit::store(res, lane, unit, n_units, dout, iout);
-}
-
-template <int NA>
-int launch_fit(muxgl_handle* h, int64_t n_units, int n_cand, const int32_t* d_cand, double rho_max, const demux_grid& al,
-               const double* d_af, double* d_dout, int32_t* d_iout) {
-  hipLaunchKernelGGL((amb_fit_kernel<NA>), dim3((unsigned)((n_units + 3) / 4)), dim3(256), 0, h->stream, n_units, n_cand,
-                     d_cand, rho_max, h->d_cell_ptr, h->d_entry_snp, h->d_entry_rptr, h->d_reads, h->d_lut, al, d_af,
-                     h->d_has_gp, h->d_gp, h->V, d_dout, d_iout);
-  HIPCHK(h, hipGetLastError());
-  return 0;
-}
-
-int fit_dispatch(muxgl_handle* h, int A, int64_t n_units, int n_cand, const int32_t* d_cand, double rho_max,
-                 const demux_grid& al, const double* d_af, double* d_dout, int32_t* d_iout) {
-#define CALL_F(N) launch_fit<N>(h, n_units, n_cand, d_cand, rho_max, al, d_af, d_dout, d_iout)
-  DISPATCH_NA(A, CALL_F);
-#undef CALL_F
+  ambient_fit::frame<384, 1, 4>(
+      n_units, n_cand, cand, cell_ptr, lut_g, dout, iout,
+      [&](const double* lut, int lane, int64_t e0, int64_t e1, int32_t j, int32_t) {
+        const size_t V3 = (size_t)V * 3;
+        const double* gpj = gp + (size_t)j * 3;
+        // shares per coarse pass: three (nine products per lane, as in a derivative pass); one at the widest grid, whose
+        // 144 products leave a lane no room for more.  Every sum belongs to one share, so the chunking changes no bit.
+        constexpr int NC = NA > 12 ? 1 : 3;
+        auto coarse = [&](const double (&x)[3], double (&o)[3]) {
+          fit_pass<NA, false, NC>(e0, e1, lane, entry_snp, entry_rptr, reads, lut, al, af, has_gp, gpj, V3, x, o, nullptr);
+        };
+        int n_scored = 0;
+        auto deriv = [&](double x, double& L, double& d1, double& d2) {
+          const double xs[3] = {x, 0.0, 0.0};
+          double o[3];
+          fit_pass<NA, true, 1>(e0, e1, lane, entry_snp, entry_rptr, reads, lut, al, af, has_gp, gpj, V3, xs, o, &n_scored);
+          L = o[0], d1 = o[1], d2 = o[2];
+        };
+        return ambient_fit::search<NC, false>(rho_max, coarse, deriv, [&] { return n_scored == 0; });
+      });
 }
 
 }  // namespace
-
-int demux_ambient_fit_bad_args(const double* amb_af, int32_t n_cand, const int32_t* cand,
-                               int64_t C, int V, double rho_max, bool any_out, char* why, size_t n) {
-  return ambient_fit::bad_args("muxgl_demux_ambient_fit", "sample", amb_af, n_cand, cand, C, V, rho_max, any_out, why, n);
-}
 
 int demux_ambient_fit_run(muxgl_handle* h, const muxgl_demux_params* p, const double* amb_af, int n_cand,
                           const int32_t* cand, double rho_max, double* rho_hat, double* ll_hat, double* ll_zero,
@@ -177,6 +139,10 @@ int demux_ambient_fit_run(muxgl_handle* h, const muxgl_demux_params* p, const do
   const ambient_fit::outputs out = {rho_hat, ll_hat, ll_zero, info, status, n_steps};
   return ambient_fit::host_run(h, "muxgl_demux_ambient_fit", amb_af, n_cand, 1, cand, 4, out, kernel_ms,
                                [&](int64_t n_units, const double* d_af, const int32_t* d_cand, double* d_dout, int32_t* d_iout) {
-                                 return fit_dispatch(h, p->n_alpha, n_units, n_cand, d_cand, rho_max, al, d_af, d_dout, d_iout);
+#define CALL_F(N)                                                                                                \
+  ambient_fit::launch(h, amb_fit_kernel<N>, n_units, n_cand, d_cand, rho_max, h->d_cell_ptr, h->d_entry_snp,    \
+                      h->d_entry_rptr, h->d_reads, h->d_lut, al, d_af, h->d_has_gp, h->d_gp, h->V, d_dout, d_iout)
+                                 DISPATCH_NA(p->n_alpha, CALL_F);
+#undef CALL_F
                                });
 }

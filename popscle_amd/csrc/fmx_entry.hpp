@@ -1,6 +1,6 @@
 // fmx_entry.hpp -- the per-entry genotype-pair likelihoods of freemuxlet (calculate_snp_droplet_pileup,
 // sc_drop_seq.cpp:452-509, alpha = 0.5): the walk of the nine that fmx_entry_kernel (fmx_kernels.hip), fam_weight_kernel
-// (fmx_ambient.hip), fam_fit_pass (fmx_ambient_fit.hip) and fma_fit_pass (fmx_alpha_fit.hip) share, the counterpart of
+// (fmx_ambient.hip) and fmx_fit_pass (fmx_fit.hpp: fmx_ambient_fit.hip, fmx_alpha_fit.hip) share, the counterpart of
 // demux_entry.hpp's grid_walk.
 #pragma once
 #include "common.hpp"

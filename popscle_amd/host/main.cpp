@@ -212,6 +212,32 @@ struct RefRand {
 
 const char* sid(const Pileup& p, int i) { return (i >= 0 && i < p.nv) ? p.sample_ids[(size_t)i].c_str() : "NA"; }
 
+// ---- what the four --fit-ambient / --fit-alpha writers share ----
+struct FitField {  // a number of a fit's row as "%.4lf", or NA
+  char s[32];
+  FitField(bool have, double v) { have ? snprintf(s, sizeof(s), "%.4lf", v) : snprintf(s, sizeof(s), "NA"); }
+};
+// the standard error of an interior estimate (on a bound: none)
+static FitField fit_se(int32_t status, double info) { return FitField(status == 0 && info > 0.0, 1.0 / sqrt(info)); }
+// the likelihood ratio against `alone`; NA where it is not finite (freemuxlet: a posterior row of exactly 0 makes LL -inf.
+// Demuxlet's LL is finite whatever the input, by the 1e-10 offset of every weight, so its writers never print NA here)
+static FitField fit_lrt(double ll_hat, double alone) { return FitField(std::isfinite(2.0 * (ll_hat - alone)), 2.0 * (ll_hat - alone)); }
+// what a mix is held against: the first column alone, or, where the fit's interval is the whole [0, 1] (only then is ll_top
+// the second column alone), the better of the two
+static double fit_alone(bool whole, double ll_zero, double ll_top) { return whole ? std::max(ll_zero, ll_top) : ll_zero; }
+// a droplet's slots, -1 where the record has no such column among the n.  An ambient fit, q[2]: SNG.BEST and SNG.NEXT; a
+// mixing-share fit, q[4]: DBL, the two columns of DBL.BEST, and SNG, (SNG.BEST, SNG.NEXT), both -1 where one is missing
+static void fit_cands(int32_t* q, bool valid, int sBest, int sNext, int n) {
+  q[0] = (valid && sBest >= 0 && sBest < n) ? sBest : -1;
+  q[1] = (valid && sNext >= 0 && sNext < n) ? sNext : -1;
+}
+static void fit_pairs(int32_t* q, bool valid, int dBest1, int dBest2, int sBest, int sNext, int n) {
+  auto ok = [&](int s) { return s >= 0 && s < n; };
+  const bool dbl = valid && ok(dBest1) && ok(dBest2), sng = valid && ok(sBest) && ok(sNext);
+  q[0] = dbl ? dBest1 : -1, q[1] = dbl ? dBest2 : -1;
+  q[2] = sng ? sBest : -1, q[3] = sng ? sNext : -1;
+}
+
 // ------------------------------------------------------------------------------------------------ demuxlet
 int cmd_demuxlet(int argc, char** argv) {
   CommonFlags cf;
@@ -521,8 +547,7 @@ int cmd_demuxlet(int argc, char** argv) {
     std::vector<int32_t> cand(n), status(n);
     for (int64_t i = 0; i < p.C(); ++i) {
       const muxgl_demux_cell& c = cells[(size_t)i];
-      cand[(size_t)i * 2] = (c.valid && c.sBest >= 0 && c.sBest < p.nv) ? c.sBest : -1;
-      cand[(size_t)i * 2 + 1] = (c.valid && c.sNext >= 0 && c.sNext < p.nv) ? c.sNext : -1;
+      fit_cands(&cand[(size_t)i * 2], c.valid, c.sBest, c.sNext, p.nv);
     }
     std::vector<double> rho(n), llh(n), ll0(n), info(n);
     check(h, muxgl_demux_ambient_fit(h, &dp, f.data(), 2, cand.data(), ambFitMax, rho.data(), llh.data(), ll0.data(), info.data(),
@@ -540,11 +565,9 @@ int cmd_demuxlet(int argc, char** argv) {
       for (size_t k = 0; k < 2; ++k) {
         const size_t x = (size_t)i * 2 + k;
         if (cand[x] < 0) continue;
-        wf.printf("%s\t%u\t%d\t%s\t%.4lf\t%.4lf\t", it->first.c_str(), (unsigned)c.nsnps, p.cell_uniq_reads[(size_t)i],
-                  sid(p, cand[x]), ll0[x], rho[x]);
-        if (status[x] == 0 && info[x] > 0.0) wf.printf("%.4lf", 1.0 / sqrt(info[x]));  // (on a bound: no standard error)
-        else wf.printf("NA");
-        wf.printf("\t%.4lf\t%.4lf\t%d\n", llh[x], 2.0 * (llh[x] - ll0[x]), (int)status[x]);
+        wf.printf("%s\t%u\t%d\t%s\t%.4lf\t%.4lf\t%s\t%.4lf\t%s\t%d\n", it->first.c_str(), (unsigned)c.nsnps,
+                  p.cell_uniq_reads[(size_t)i], sid(p, cand[x]), ll0[x], rho[x], fit_se(status[x], info[x]).s, llh[x],
+                  fit_lrt(llh[x], ll0[x]).s, (int)status[x]);
       }
     }
     wf.close();
@@ -555,13 +578,9 @@ int cmd_demuxlet(int argc, char** argv) {
     // and one row SNG for (SNG.BEST, SNG.NEXT) (none where .best has NA there)
     const size_t n = (size_t)p.C() * 2;
     std::vector<int32_t> pair(n * 2), status(n);
-    auto ok = [&](int32_t s) { return s >= 0 && s < p.nv; };
     for (int64_t i = 0; i < p.C(); ++i) {
       const muxgl_demux_cell& c = cells[(size_t)i];
-      int32_t* q = &pair[(size_t)i * 4];
-      const bool dbl = c.valid && ok(c.dBest1) && ok(c.dBest2), sng = c.valid && ok(c.sBest) && ok(c.sNext);
-      q[0] = dbl ? c.dBest1 : -1, q[1] = dbl ? c.dBest2 : -1;
-      q[2] = sng ? c.sBest : -1, q[3] = sng ? c.sNext : -1;
+      fit_pairs(&pair[(size_t)i * 4], c.valid, c.dBest1, c.dBest2, c.sBest, c.sNext, p.nv);
     }
     std::vector<double> ah(n), llh(n), ll0(n), llt(n), info(n);
     check(h, muxgl_demux_alpha_fit(h, &dp, 2, pair.data(), alphaFitMax, ah.data(), llh.data(), ll0.data(), llt.data(), info.data(),
@@ -571,7 +590,7 @@ int cmd_demuxlet(int argc, char** argv) {
     OutFile wf(cf.outPrefix + ".alphafit.gz", true);
     wf.printf("BARCODE\tNUM.SNPS\tNUM.READS\tPAIR\tSM1_ID\tSM2_ID\tSNG1.LLK\tSNG2.LLK\tALPHA.MLE\tALPHA.SE\tMIX.LLK.MLE\tMIX.LRT\t"
               "STATUS\n");
-    const bool whole = alphaFitMax == 1.0;  // (only then is ll_top the second sample alone)
+    const bool whole = alphaFitMax == 1.0;
     int64_t mixed = 0;
     for (auto it = bc_map.begin(); it != bc_map.end(); ++it) {
       const int32_t i = it->second;
@@ -582,15 +601,11 @@ int cmd_demuxlet(int argc, char** argv) {
       for (size_t k = 0; k < 2; ++k) {
         const size_t x = (size_t)i * 2 + k;
         if (pair[x * 2] < 0) continue;
-        const double one = whole ? std::max(ll0[x], llt[x]) : ll0[x];
-        wf.printf("%s\t%u\t%d\t%s\t%s\t%s\t%.4lf\t", it->first.c_str(), (unsigned)c.nsnps, p.cell_uniq_reads[(size_t)i],
-                  k == 0 ? "DBL" : "SNG", sid(p, pair[x * 2]), sid(p, pair[x * 2 + 1]), ll0[x]);
-        if (whole) wf.printf("%.4lf", llt[x]);
-        else wf.printf("NA");
-        wf.printf("\t%.4lf\t", ah[x]);
-        if (status[x] == 0 && info[x] > 0.0) wf.printf("%.4lf", 1.0 / sqrt(info[x]));  // (on a bound: no standard error)
-        else wf.printf("NA");
-        wf.printf("\t%.4lf\t%.4lf\t%d\n", llh[x], 2.0 * (llh[x] - one), (int)status[x]);
+        const double one = fit_alone(whole, ll0[x], llt[x]);
+        wf.printf("%s\t%u\t%d\t%s\t%s\t%s\t%.4lf\t%s\t%.4lf\t%s\t%.4lf\t%s\t%d\n", it->first.c_str(), (unsigned)c.nsnps,
+                  p.cell_uniq_reads[(size_t)i], k == 0 ? "DBL" : "SNG", sid(p, pair[x * 2]), sid(p, pair[x * 2 + 1]), ll0[x],
+                  FitField(whole, llt[x]).s, ah[x], fit_se(status[x], info[x]).s, llh[x], fit_lrt(llh[x], one).s,
+                  (int)status[x]);
         if (k == 1 && c.type == 0 && llh[x] > one + 2.0) ++mixed;
       }
     }
@@ -1255,8 +1270,7 @@ int cmd_freemuxlet(int argc, char** argv) {
     std::vector<int32_t> cand(n), status(n);
     for (int64_t i = 0; i < C; ++i) {
       const muxgl_fmx_cell& c = cells[(size_t)i];
-      cand[(size_t)i * 2] = (c.sBest >= 0 && c.sBest < K) ? c.sBest : -1;
-      cand[(size_t)i * 2 + 1] = (c.sNext >= 0 && c.sNext < K) ? c.sNext : -1;
+      fit_cands(&cand[(size_t)i * 2], true, c.sBest, c.sNext, K);
     }
     std::vector<double> rho(n), llh(n), ll0(n), info(n);
     check(h, muxgl_fmx_ambient_fit(h, f.data(), 2, cand.data(), ambFitMax, rho.data(), llh.data(), ll0.data(), info.data(),
@@ -1269,14 +1283,10 @@ int cmd_freemuxlet(int argc, char** argv) {
       for (size_t k = 0; k < 2; ++k) {
         const size_t x = (size_t)i * 2 + k;
         if (cand[x] < 0) continue;
-        char num[320], se[32], lrt[32];
-        if (status[x] == 0 && info[x] > 0.0) snprintf(se, sizeof(se), "%.4lf", 1.0 / sqrt(info[x]));  // (on a bound: no standard error)
-        else snprintf(se, sizeof(se), "NA");
-        const double r = 2.0 * (llh[x] - ll0[x]);
-        if (std::isfinite(r)) snprintf(lrt, sizeof(lrt), "%.4lf", r);
-        else snprintf(lrt, sizeof(lrt), "NA");
+        char num[320];
         const int m = snprintf(num, sizeof(num), "\t%d\t%d\t%d\t%.4lf\t%.4lf\t%s\t%.4lf\t%s\t%d\n", nSNPs[(size_t)i],
-                               nReads[(size_t)i], cand[x], ll0[x], rho[x], se, llh[x], lrt, (int)status[x]);
+                               nReads[(size_t)i], cand[x], ll0[x], rho[x], fit_se(status[x], info[x]).s, llh[x],
+                               fit_lrt(llh[x], ll0[x]).s, (int)status[x]);
         o.append(p.bcs[(size_t)i]);
         o.append(num, (size_t)std::min<int>(m, (int)sizeof(num) - 1));
       }
@@ -1290,26 +1300,22 @@ int cmd_freemuxlet(int argc, char** argv) {
     // the last E-step
     const size_t n = (size_t)C * 2;
     std::vector<int32_t> pair(n * 2), status(n);
-    auto ok = [&](int32_t s) { return s >= 0 && s < K; };
     for (int64_t i = 0; i < C; ++i) {
       const muxgl_fmx_cell& c = cells[(size_t)i];
-      int32_t* q = &pair[(size_t)i * 4];
-      const bool dbl = ok(c.dBest1) && ok(c.dBest2), sng = ok(c.sBest) && ok(c.sNext);
-      q[0] = dbl ? c.dBest1 : -1, q[1] = dbl ? c.dBest2 : -1;
-      q[2] = sng ? c.sBest : -1, q[3] = sng ? c.sNext : -1;
+      fit_pairs(&pair[(size_t)i * 4], true, c.dBest1, c.dBest2, c.sBest, c.sNext, K);
     }
     std::vector<double> ah(n), llh(n), ll0(n), llt(n), info(n);
     check(h, muxgl_fmx_alpha_fit(h, 2, pair.data(), alphaFitMax, ah.data(), llh.data(), ll0.data(), llt.data(), info.data(),
                                  status.data(), nullptr, nullptr),
           "muxgl_fmx_alpha_fit");
     tmr.lap("freemuxlet: muxgl_fmx_alpha_fit");
-    const bool whole = alphaFitMax == 1.0;  // (only then is ll_top the second cluster alone)
+    const bool whole = alphaFitMax == 1.0;
+    auto one_of = [&](size_t x) { return fit_alone(whole, ll0[x], llt[x]); };
     int64_t mixed = 0;
     for (int64_t i = 0; i < C; ++i) {
       const size_t x = (size_t)i * 2 + 1;
       if (pair[x * 2] < 0) continue;
-      const double one = whole ? std::max(ll0[x], llt[x]) : ll0[x];
-      mixed += cells[(size_t)i].type == 0 && llh[x] > one + 2.0;
+      mixed += cells[(size_t)i].type == 0 && llh[x] > one_of(x) + 2.0;
     }
     OutFile wf(cf.outPrefix + ".clust1.alphafit.gz", true);
     wf.printf("BARCODE\tNUM.SNPS\tNUM.READS\tPAIR\tCLUST1\tCLUST2\tSNG1.LLK\tSNG2.LLK\tALPHA.MLE\tALPHA.SE\tMIX.LLK.MLE\tMIX.LRT\t"
@@ -1318,18 +1324,11 @@ int cmd_freemuxlet(int argc, char** argv) {
       for (size_t k = 0; k < 2; ++k) {
         const size_t x = (size_t)i * 2 + k;
         if (pair[x * 2] < 0) continue;
-        const double one = whole ? std::max(ll0[x], llt[x]) : ll0[x];
-        char num[400], top[32], se[32], lrt[32];
-        if (whole) snprintf(top, sizeof(top), "%.4lf", llt[x]);
-        else snprintf(top, sizeof(top), "NA");
-        if (status[x] == 0 && info[x] > 0.0) snprintf(se, sizeof(se), "%.4lf", 1.0 / sqrt(info[x]));  // (on a bound: no standard error)
-        else snprintf(se, sizeof(se), "NA");
-        const double r = 2.0 * (llh[x] - one);
-        if (std::isfinite(r)) snprintf(lrt, sizeof(lrt), "%.4lf", r);
-        else snprintf(lrt, sizeof(lrt), "NA");
+        char num[400];
         const int m = snprintf(num, sizeof(num), "\t%d\t%d\t%s\t%d\t%d\t%.4lf\t%s\t%.4lf\t%s\t%.4lf\t%s\t%d\n", nSNPs[(size_t)i],
-                               nReads[(size_t)i], k == 0 ? "DBL" : "SNG", pair[x * 2], pair[x * 2 + 1], ll0[x], top, ah[x], se,
-                               llh[x], lrt, (int)status[x]);
+                               nReads[(size_t)i], k == 0 ? "DBL" : "SNG", pair[x * 2], pair[x * 2 + 1], ll0[x],
+                               FitField(whole, llt[x]).s, ah[x], fit_se(status[x], info[x]).s, llh[x],
+                               fit_lrt(llh[x], one_of(x)).s, (int)status[x]);
         o.append(p.bcs[(size_t)i]);
         o.append(num, (size_t)std::min<int>(m, (int)sizeof(num) - 1));
       }

@@ -128,34 +128,8 @@ class Cell(ffr.Cell):
         return bool((low != low[:, :1, :]).any())
 
 
-def bracket(cell, alpha_max):
-    """(lo, hi, best index) by the coarse rule; LL in float64"""
-    xs = coarse_points(alpha_max)
-    L = cell.eval(xs, np.float64)[0]
-    i = int(np.argmax(L))                                        # (first maximum: ties to the lowest index)
-    return xs[max(i - 1, 0)], xs[min(i + 1, 8)], i
-
-
-def maximise(cell, lo, hi, n_scan=64):
-    """the maximiser of LL in [lo, hi]: dense scan in longdouble, then bisection on the sign of LL' to 1e-12.  Returns
-    (alpha_hat as float, at_lo, at_hi): on the bracket's own end where the scan's best point is that end and LL' points
-    out"""
-    ld = np.longdouble
-    xs = np.array([ld(lo) + (ld(hi) - ld(lo)) * ld(i) / ld(n_scan) for i in range(n_scan + 1)], dtype=ld)
-    xs[-1] = ld(hi)
-    i = int(np.argmax(cell.eval(xs, ld)[0]))
-    a, b = xs[max(i - 1, 0)], xs[min(i + 1, n_scan)]
-    if i == 0 and cell.eval([xs[0]], ld)[1][0] <= 0:
-        return float(lo), True, False
-    if i == n_scan and cell.eval([xs[-1]], ld)[1][0] >= 0:
-        return float(hi), False, True
-    while b - a > ld(1e-12):
-        m = (a + b) / ld(2)
-        if cell.eval([m], ld)[1][0] > 0:
-            a = m
-        else:
-            b = m
-    return float((a + b) / ld(2)), False, False
+# the coarse bracket, the Newton-free maximiser and the sign changes of LL' ask a cell for eval() only: fmx_ambient_fit_ref's
+bracket, maximise, sign_changes = ffr.bracket, ffr.maximise, ffr.sign_changes
 
 
 def fit(p, q, c, j, k, alpha_max):
@@ -237,15 +211,6 @@ def search(cell, alpha_max):
     if status == 3:
         x, Lx, d2 = xb, Lb, d2b
     return dict(alpha_hat=x, ll_hat=Lx, info=-d2, status=status, n_steps=steps, scanned=scanned)
-
-
-def sign_changes(cell, lo, hi, n=129):
-    """the sign changes of LL' (longdouble) along an n-point scan of [lo, hi], zeros dropped"""
-    ld = np.longdouble
-    xs = np.array([ld(lo) + (ld(hi) - ld(lo)) * ld(i) / ld(n - 1) for i in range(n)], dtype=ld)
-    s = np.sign(cell.eval(xs, ld)[1].astype(np.float64))
-    s = s[s != 0]
-    return int((s[1:] != s[:-1]).sum())
 
 
 # ---- pileups ------------------------------------------------------------------------------------------------------------

@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 
 import fmx_alpha_fit_ref as far
+import fmx_fit_check
 import parity
 from popscle_amd import freemuxlet, muxgl, synth
 from test_fmx_alpha_fit import check_clean, check_mixed, oracle_case
@@ -33,88 +34,18 @@ pytestmark = pytest.mark.gpu
 
 XE = muxgl.FLAG_FORCE_STREAMED_ESTEP
 FIELDS = muxgl.Engine.ALPHA_FIT_FIELDS
-WORST = {}   # what -> worst figure seen, printed by every check
 
 
 def same(a, b, fields=FIELDS):
     return all(a[k].tobytes() == b[k].tobytes() for k in fields)
 
 
-def note(what, v):
-    WORST[what] = max(WORST.get(what, 0.0), float(v))
-
-
 def check_fit(p, q, pair, alpha_max, got, what, pairs=None, ll_tol=parity.LL_TOL):
-    """every bar of the module's docstring on the (droplet, slot) pairs of `pairs` (None: all); returns the number of
-    interior fits and of those with restated info >= 1"""
-    ld = np.longdouble
-    pair = np.asarray(pair).reshape(p.C, -1, 2)
-    assert all(got[k].shape == pair.shape[:2] for k in FIELDS)
-    assert (got["n_steps"] <= 48).all() and (got["n_steps"] >= 0).all() and not (got["status"] == 3).any()
-    assert not any(np.isnan(got[k]).any() for k in FIELDS)
-    b1, b2 = got["status"] == 1, got["status"] == 2
-    assert got["ll_hat"][b1].tobytes() == got["ll_zero"][b1].tobytes() and (got["alpha_hat"][b1] == 0.0).all()
-    assert got["ll_hat"][b2].tobytes() == got["ll_top"][b2].tobytes() and (got["alpha_hat"][b2] == alpha_max).all()
-    fitted = strong = checked = on_kink = 0
-    seen = {}
-    for c, t in (pairs if pairs is not None else [(c, t) for c in range(p.C) for t in range(pair.shape[1])]):
-        j, k = int(pair[c, t, 0]), int(pair[c, t, 1])
-        g = {n: got[n][c, t] for n in FIELDS}
-        if j < 0:
-            assert k < 0 and g["status"] == 4 and all(g[n] == 0 for n in FIELDS if n != "status"), (c, t, g)
-            continue
-        if (c, j, k) not in seen:
-            seen[(c, j, k)] = far.fit(p, q, c, j, k, alpha_max)
-        r = seen[(c, j, k)]
-        cell = r["cell"]
-        if cell.n == 0:
-            assert g["status"] == 5 and all(g[n] == 0 for n in FIELDS if n != "status"), (c, t, g)
-            continue
-        if r["status"] == 6:
-            assert g["status"] == 6 and g["alpha_hat"] == 0 and g["ll_hat"] == g["ll_zero"] == g["ll_top"] == -np.inf \
-                and g["info"] == 0 and g["n_steps"] == 0, (c, t, g)
-            continue
-        x = float(g["alpha_hat"])
-        assert g["status"] in (0, 1, 2) and 0.0 <= x <= alpha_max, (c, t, g)
-        L, d1, d2, aL, a1, a2, s1, s2, near = [float(v[0]) for v in cell.eval([x], ld)]
-        L64, d164, d264 = [float(v[0]) for v in cell.eval([x], np.float64)[:3]]
-        tol1 = max(1000.0 * abs(d164 - d1), 1e-9 * a1)
-        tol2 = max(1000.0 * abs(d264 - d2), 1e-9 * a2)
-        if tol1 == 0.0 or tol2 == 0.0:   # every term exactly 0 in both precisions: the floor over absolute summands
-            tol1, tol2 = max(tol1, 1e-9 * s1), max(tol2, 1e-9 * s2)
-        kink = near < 1e-6 or float(cell.eval([r["alpha_hat"]], ld)[8][0]) < 1e-6
-        checked += 1
-        on_kink += kink
-        for n in ("ll_hat", "ll_zero", "ll_top"):
-            ref = L if n == "ll_hat" else r[n]
-            note(f"{what}: |{n} - ref|", abs(g[n] - ref))
-            assert abs(g[n] - ref) <= ll_tol, (c, t, n, g, ref)
-        if not kink:
-            note(f"{what}: |info - ref| / tol", abs(g["info"] + d2) / tol2)
-            assert abs(g["info"] + d2) <= tol2, (c, t, g, d2, tol2)
-        if g["status"] == 1:
-            assert x == 0.0 and (kink or d1 <= tol1), (c, t, g, d1)
-        elif g["status"] == 2:
-            assert x == alpha_max and (kink or d1 >= -tol1), (c, t, g, d1)
-        else:
-            if not kink:
-                note(f"{what}: |LL'(alpha_hat)| / tol", abs(d1) / tol1)
-                assert abs(d1) <= tol1, (c, t, g, d1, tol1)
-            fitted += 1
-        note(f"{what}: LL(ref alpha) - LL(device alpha)", r["ll_hat"] - L)
-        assert L >= r["ll_hat"] - 1e-9, (c, t, g, r["alpha_hat"], r["ll_hat"], L)
-        if r["info"] >= 1.0:
-            strong += g["status"] == 0
-            note(f"{what}: |alpha_hat - ref|", abs(x - r["alpha_hat"]))
-            assert abs(x - r["alpha_hat"]) <= 1e-6, (c, t, g, r["alpha_hat"], r["info"])
-            assert g["status"] == r["status"], (c, t, g, r["status"])
-    assert on_kink == 0, (on_kink, checked)
-    for key in sorted(WORST):
-        if key.startswith(what + ":"):
-            print(f"fmx alpha fit {key} {WORST[key]:.3e}")
-    print(f"fmx alpha fit {what}: {fitted} interior fits, {strong} with info >= 1, {on_kink} on a kink, mean n_steps "
-          f"{float(got['n_steps'][got['status'] == 0].mean()) if (got['status'] == 0).any() else 0.0:.2f}")
-    return fitted, strong
+    """every bar of the module's docstring (fmx_fit_check.check_fit, with ll_top and no slot on a kink) on the (droplet,
+    slot) pairs of `pairs` (None: all); returns the number of interior fits and of those with restated info >= 1"""
+    return fmx_fit_check.check_fit("fmx alpha fit", "alpha", FIELDS, lambda c, j, k: far.fit(p, q, c, j, k, alpha_max),
+                                   top=True, kink_at_ref=True, kink_frac=0.0, C=p.C, slots=pair, x_max=alpha_max, got=got,
+                                   what=what, pairs=pairs, ll_tol=ll_tol)
 
 
 # ---- 1. parity and optimality over the shapes, and the mirror -----------------------------------------------------------------

@@ -22,6 +22,7 @@ import pytest
 
 import ambient_ref as ar
 import fmx_ambient_fit_ref as ffr
+import fmx_fit_check
 import fmx_ambient_ref as fr
 import parity
 from popscle_amd import freemuxlet, muxgl, synth
@@ -33,84 +34,19 @@ pytestmark = pytest.mark.gpu
 XE = muxgl.FLAG_FORCE_STREAMED_ESTEP
 DEFAULT_RHOS = fr.DEFAULT_RHOS
 FIELDS = muxgl.Engine.AMBIENT_FIT_FIELDS
-WORST = {}   # what -> worst figure seen, printed by every check
 
 
 def same(a, b, fields=FIELDS):
     return all(a[k].tobytes() == b[k].tobytes() for k in fields)
 
 
-def note(what, v):
-    WORST[what] = max(WORST.get(what, 0.0), float(v))
-
-
 def check_fit(p, q, f, cand, rho_max, got, what, pairs=None, ll_tol=parity.LL_TOL):
-    """every bar of the module's docstring on the (droplet, slot) pairs of `pairs` (None: all); returns the number of
-    interior fits and of those with restated info >= 1"""
-    ld = np.longdouble
-    cand = np.asarray(cand).reshape(p.C, -1)
-    assert all(got[k].shape == cand.shape for k in FIELDS)
-    assert (got["n_steps"] <= 48).all() and (got["n_steps"] >= 0).all() and not (got["status"] == 3).any()
-    assert not any(np.isnan(got[k]).any() for k in FIELDS)
-    fitted = strong = checked = on_kink = 0
-    seen = {}
-    for c, k in (pairs if pairs is not None else [(c, k) for c in range(p.C) for k in range(cand.shape[1])]):
-        j = int(cand[c, k])
-        g = {n: got[n][c, k] for n in FIELDS}
-        if j < 0:
-            assert g["status"] == 4 and all(g[n] == 0 for n in FIELDS if n != "status"), (c, k, g)
-            continue
-        if (c, j) not in seen:
-            seen[(c, j)] = ffr.fit(p, q, f, c, j, rho_max)
-        r = seen[(c, j)]
-        cell = r["cell"]
-        if cell.n == 0:
-            assert g["status"] == 5 and all(g[n] == 0 for n in FIELDS if n != "status"), (c, k, g)
-            continue
-        if r["status"] == 6:
-            assert g["status"] == 6 and g["rho_hat"] == 0 and g["ll_hat"] == g["ll_zero"] == -np.inf and g["info"] == 0 \
-                and g["n_steps"] == 0, (c, k, g)
-            continue
-        x = float(g["rho_hat"])
-        assert g["status"] in (0, 1, 2) and 0.0 <= x <= rho_max, (c, k, g)
-        L, d1, d2, aL, a1, a2, s1, s2, near = [float(v[0]) for v in cell.eval([x], ld)]
-        L64, d164, d264 = [float(v[0]) for v in cell.eval([x], np.float64)[:3]]
-        tol1 = max(1000.0 * abs(d164 - d1), 1e-9 * a1)
-        tol2 = max(1000.0 * abs(d264 - d2), 1e-9 * a2)
-        if tol1 == 0.0 or tol2 == 0.0:   # every term exactly 0 in both precisions: the floor over absolute summands
-            tol1, tol2 = max(tol1, 1e-9 * s1), max(tol2, 1e-9 * s2)
-        kink = near < 1e-6               # an element on the floor's edge: the derivative bars do not apply
-        checked += 1
-        on_kink += kink
-        note(f"{what}: |ll_hat - ref|", abs(g["ll_hat"] - L))
-        note(f"{what}: |ll_zero - ref|", abs(g["ll_zero"] - r["ll_zero"]))
-        assert abs(g["ll_hat"] - L) <= ll_tol and abs(g["ll_zero"] - r["ll_zero"]) <= ll_tol, (c, k, g, L)
-        if not kink:
-            note(f"{what}: |info - ref| / tol", abs(g["info"] + d2) / tol2)
-            assert abs(g["info"] + d2) <= tol2, (c, k, g, d2, tol2)
-        if g["status"] == 1:
-            assert x == 0.0 and (kink or d1 <= tol1), (c, k, g, d1)
-        elif g["status"] == 2:
-            assert x == rho_max and (kink or d1 >= -tol1), (c, k, g, d1)
-        else:
-            if not kink:
-                note(f"{what}: |LL'(rho_hat)| / tol", abs(d1) / tol1)
-                assert abs(d1) <= tol1, (c, k, g, d1, tol1)
-            fitted += 1
-        note(f"{what}: LL(ref rho) - LL(device rho)", r["ll_hat"] - L)
-        assert L >= r["ll_hat"] - 1e-9, (c, k, g, r["rho_hat"], r["ll_hat"], L)
-        if r["info"] >= 1.0:
-            strong += g["status"] == 0
-            note(f"{what}: |rho_hat - ref|", abs(x - r["rho_hat"]))
-            assert abs(x - r["rho_hat"]) <= 1e-6, (c, k, g, r["rho_hat"], r["info"])
-            assert g["status"] == r["status"], (c, k, g, r["status"])
-    assert on_kink <= 0.01 * checked, (on_kink, checked)
-    for key in sorted(WORST):
-        if key.startswith(what + ":"):
-            print(f"fmx ambient fit {key} {WORST[key]:.3e}")
-    print(f"fmx ambient fit {what}: {fitted} interior fits, {strong} with info >= 1, {on_kink} on a kink, mean n_steps "
-          f"{float(got['n_steps'][got['status'] == 0].mean()) if (got['status'] == 0).any() else 0.0:.2f}")
-    return fitted, strong
+    """every bar of the module's docstring (fmx_fit_check.check_fit, without ll_top, at most 1 % of the slots on a kink) on
+    the (droplet, slot) pairs of `pairs` (None: all); returns the number of interior fits and of those with restated
+    info >= 1"""
+    return fmx_fit_check.check_fit("fmx ambient fit", "rho", FIELDS, lambda c, j: ffr.fit(p, q, f, c, j, rho_max),
+                                   top=False, kink_at_ref=False, kink_frac=0.01, C=p.C, slots=cand, x_max=rho_max, got=got,
+                                   what=what, pairs=pairs, ll_tol=ll_tol)
 
 
 def ready(p, K, init, devs=0, flags=0, anchors=None, modes=None, ge=0.1):
