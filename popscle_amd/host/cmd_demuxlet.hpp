@@ -1,0 +1,173 @@
+// cmd_demuxlet.hpp -- popscle-amd demuxlet: mirrors cmdCramDemuxlet (cmd_cram_demuxlet.cpp).  Flags, load, hand-over, run,
+// then one step per requested output: the library call for its arrays, the writer (table_writers.hpp), the timer.
+#pragma once
+
+#include "cli_common.hpp"
+
+namespace pa {
+
+// .best, cmd_cram_demuxlet.cpp:629,636-641,993-1013: rows in barcode-sorted order, INT_ID counts skipped cells too
+inline void write_best(OutFile&& w, const Table& t, const Pileup& p, const muxgl_demux_params& dp, const muxgl_demux_cell* cells) {
+  w.printf("INT_ID\tBARCODE\tNUM.SNPS\tNUM.READS\tDROPLET.TYPE\tBEST.GUESS\tBEST.LLK\tNEXT.GUESS\tNEXT.LLK\t"
+           "DIFF.LLK.BEST.NEXT\tBEST.POSTERIOR\tSNG.POSTERIOR\tSNG.BEST.GUESS\tSNG.BEST.LLK\tSNG.NEXT.GUESS\t"
+           "SNG.NEXT.LLK\tSNG.ONLY.POSTERIOR\tDBL.BEST.GUESS\tDBL.BEST.LLK\tDIFF.LLK.SNG.DBL\n");
+  auto al = [&](int n) { return (n >= 0 && n < dp.n_alpha) ? dp.alpha[n] : NAN; };
+  for (const TableRow& d : t.rows) {
+    const muxgl_demux_cell& c = cells[d.cell];
+    w.printf("%d\t%s\t%u\t%d\t%s\t%s,%s,%.2lf\t%.2lf\t%s,%s,%.2lf\t%.2lf\t%.2lf\t%.2lg\t%.2lg\t%s\t%.2lf\t%s\t%.2lf\t"
+             "%.5lf\t%s,%s,%.2lf\t%.2lf\t%.2lf\n",
+             d.pos, t.bc(d), (unsigned)d.nsnps, d.nreads, type_name(c.type),
+             sid(p, c.jBest), sid(p, c.kBest), al(c.aBest), c.bestLLK, sid(p, c.jNext), sid(p, c.kNext), al(c.aNext),
+             c.nextLLK, c.bestLLK - c.nextLLK, c.bestPP, c.sngPP, sid(p, c.sBest), c.sngBestLLK, sid(p, c.sNext),
+             c.sngNextLLK, c.sngOnlyPP, sid(p, c.dBest1), sid(p, c.dBest2), al(c.dBestA), c.dblBestLLK,
+             c.sngBestLLK - c.dblBestLLK);
+  }
+  w.close();
+}
+
+inline int cmd_demuxlet(int argc, char** argv) {
+  CommonFlags cf;
+  GenotypeFlags gf;
+  TableFlags tf;  // (ours) the reference's disabled .sing2 (:580,839-848) and .pair (:852-877) writers, and the tables it lacks
+  VcfReader vr;
+  std::vector<double> gridAlpha;
+  double doublet_prior = 0.5;  // cmd_cram_demuxlet.cpp:32
+  std::string sam, tagGroup, tagUMI;
+  int32_t dummy_i = 0;
+  bool deviceCalls = false;  // (ours) skip the host pass that settles mirrored alpha = 0.5 pairs and near-tie calls as the reference does
+  Args a;
+  cf.add(a);
+  tf.add(a);
+  gf.add(a, cf.lo, vr);
+  a.add_bool("device-calls", &deviceCalls);
+  a.add_string("vcf", &vr.path);
+  a.add_multi_double("alpha", &gridAlpha);
+  a.add_double("doublet-prior", &doublet_prior);
+  a.add_string("sam", &sam);  // BAM-direct mode needs htslib: accepted and rejected
+  a.add_string("tag-group", &tagGroup);
+  a.add_string("tag-UMI", &tagUMI);
+  a.add_int("sam-verbose", &dummy_i);
+  a.add_int("vcf-verbose", &dummy_i);
+  a.add_int("min-MQ", &dummy_i);
+  a.add_int("min-TD", &dummy_i);
+  a.add_int("excl-flag", &dummy_i);
+  a.parse(argc, argv);
+  if (!sam.empty()) fatal("--sam (BAM-direct mode) is not available in this build: run dsc-pileup first and pass --plp");
+  if (cf.plpPrefix.empty() || vr.path.empty() || cf.outPrefix.empty()) fatal("Missing required option(s) : --plp, --vcf, --out");
+  if (gridAlpha.empty()) gridAlpha = {0, 0.5};  // :85-89
+  if ((int)gridAlpha.size() > MUXGL_MAX_ALPHA) fatal("at most %d --alpha values are supported", MUXGL_MAX_ALPHA);
+  tf.validate();
+  gf.init(vr);
+  Pileup p;
+  StageTimer tm;
+  load_from_plp(cf.plpPrefix, cf.lo, &vr, p);
+  tm.lap("demuxlet: load");
+
+  muxgl_config cfg = cf.config(MUXGL_FLAG_DEMUX_ONLY);  // cells are independent: a group needs no column slabs
+  muxgl_handle* h = nullptr;
+  if (muxgl_create(&cfg, &h) != 0) fatal("%s", muxgl_last_error(nullptr));
+  tm.lap("demuxlet: device init");
+  upload(h, p);
+  check(h, muxgl_demux_set_gp(h, p.nv, p.gp.data(), p.has_gp.data()), "muxgl_demux_set_gp");
+  tm.lap("demuxlet: hand-over (H2D+plans)");
+  muxgl_demux_params dp;
+  memset(&dp, 0, sizeof(dp));
+  dp.n_alpha = (int32_t)gridAlpha.size();
+  std::copy(gridAlpha.begin(), gridAlpha.end(), dp.alpha);
+  dp.doublet_prior = doublet_prior;
+  notice("Starting to identify best matching individual IDs");
+  std::vector<muxgl_demux_cell> cells((size_t)p.C());
+  check(h, muxgl_demux_run(h, &dp, cells.data(), nullptr), "muxgl_demux_run");
+  tm.lap("demuxlet: muxgl_demux_run");
+  if (!deviceCalls) {
+    // the calls rounding noise could decide -- the order of a mirrored alpha = 0.5 pair in DBL.BEST.GUESS / NEXT.GUESS
+    // (cmd_cram_demuxlet.cpp:738-746,883-906) and near ties of the scans and thresholds (:827-837,925-988) -- settled in
+    // the reference's own arithmetic (exact_calls.hpp)
+    int64_t st[6];
+    check(h, muxgl_demux_exact_calls(p.C(), p.nv, p.cell_ptr.data(), p.entry_snp.data(), p.entry_rptr.data(), p.reads.data(),
+                                     p.gp.data(), p.has_gp.data(), &dp, cells.data(), compute_threads(), st),
+          "muxgl_demux_exact_calls");
+    notice("Exact-call pass: %lld droplets looked at (%lld near ties besides mirrored pairs, %lld needing every hypothesis, "
+           "%lld calls changed)", (long long)st[0], (long long)st[3], (long long)st[4], (long long)st[5]);
+    tm.lap("demuxlet: exact calls (host)");
+  }
+
+  // every table has the rows of .best, in its order, and names a column by its sample
+  const Table t{p.bcs,
+                printed_droplets(p.bcs, p.cell_totl_reads.data(), p.cell_uniq_reads.data(), cells.data(), cf.lo.minRead, cf.lo.minUMI,
+                                 cf.lo.minSNP),
+                Label::samples(p.sample_ids)};
+  const std::string& out = cf.outPrefix;
+  const size_t C = (size_t)p.C(), V = (size_t)p.nv, A = (size_t)dp.n_alpha;
+  write_best(OutFile(out + ".best", false), t, p, dp, cells.data());
+  tm.lap("demuxlet: write .best");
+  if (tf.writeSinglets) {  // samples in VCF column order
+    std::vector<double> sng(C * V);
+    check(h, muxgl_demux_singlets(h, &dp, sng.data()), "muxgl_demux_singlets");
+    tm.lap("demuxlet: muxgl_demux_singlets");
+    write_singlets(OutFile(out + ".sing2.gz", true), t, V, sng.data());
+    tm.lap("demuxlet: write .sing2.gz");
+  }
+  if (tf.writeInclusion) {
+    std::vector<double> incl(C * V), tot(C), dbl(C * V);
+    std::vector<int32_t> partner(C * V), aidx(C * V), first(C * V);
+    check(h, muxgl_demux_inclusion(h, &dp, incl.data(), tot.data(), dbl.data(), partner.data(), aidx.data(), first.data()),
+          "muxgl_demux_inclusion");
+    tm.lap("demuxlet: muxgl_demux_inclusion");
+    write_inclusion(OutFile(out + ".incl.gz", true), t, V, incl.data(), tot.data(), dbl.data(), partner.data(), dp.alpha,
+                    aidx.data(), first.data());
+    tm.lap("demuxlet: write .incl.gz");
+  }
+  if (tf.writeUnknown) {
+    std::vector<double> ju(C * V * A), uj(C * V * A), uu(C * A);
+    check(h, muxgl_demux_unknown(h, &dp, nullptr, ju.data(), uj.data(), uu.data(), nullptr), "muxgl_demux_unknown");
+    tm.lap("demuxlet: muxgl_demux_unknown");
+    write_unknown_demux(OutFile(out + ".unk.gz", true), t, cells.data(), V, A, dp.alpha, ju.data(), uj.data(), uu.data());
+    tm.lap("demuxlet: write .unk.gz");
+  }
+  std::vector<double> ambProfile;  // of --write-ambient and --fit-ambient, made by the first of them
+  auto profile = [&]() {
+    return ambient_profile(ambProfile, h, p, tf, p.cell_uniq_reads.data(), tm, "demuxlet: muxgl_pileup_allele_counts").data();
+  };
+  if (tf.writeAmbient) {
+    const double* f = profile();
+    std::vector<double> amb(C * V * tf.ambRho.size());
+    check(h, muxgl_demux_ambient(h, &dp, f, (int32_t)tf.ambRho.size(), tf.ambRho.data(), amb.data(), nullptr), "muxgl_demux_ambient");
+    tm.lap("demuxlet: muxgl_demux_ambient");
+    const int64_t rescued = write_ambient(OutFile(out + ".amb.gz", true), t, cells.data(), V, tf.ambRho, amb.data(), false);
+    notice("Ambient RNA: %lld droplets called DBL are explained better, by more than 2 in log-likelihood, as one cell plus "
+           "ambient RNA than as their best doublet", (long long)rescued);
+    tm.lap("demuxlet: write .amb.gz");
+  }
+  if (tf.fitAmbient) {  // (no row where .best has NA for the sample)
+    const double* f = profile();
+    const std::vector<int32_t> cand = all_fit_cands(cells.data(), C, p.nv);
+    std::vector<int32_t> status(C * 2);
+    std::vector<double> rho(C * 2), llh(C * 2), ll0(C * 2), info(C * 2);
+    check(h, muxgl_demux_ambient_fit(h, &dp, f, 2, cand.data(), tf.ambFitMax, rho.data(), llh.data(), ll0.data(), info.data(),
+                                     status.data(), nullptr, nullptr),
+          "muxgl_demux_ambient_fit");
+    tm.lap("demuxlet: muxgl_demux_ambient_fit");
+    write_ambient_fit(OutFile(out + ".ambfit.gz", true), t, cand.data(), status.data(), rho.data(), llh.data(), ll0.data(), info.data());
+    tm.lap("demuxlet: write .ambfit.gz");
+  }
+  if (tf.fitAlpha) {  // (no row where .best has NA for a sample of the pair)
+    const std::vector<int32_t> pair = all_fit_pairs(cells.data(), C, p.nv);
+    std::vector<int32_t> status(C * 2);
+    std::vector<double> ah(C * 2), llh(C * 2), ll0(C * 2), llt(C * 2), info(C * 2);
+    check(h, muxgl_demux_alpha_fit(h, &dp, 2, pair.data(), tf.alphaFitMax, ah.data(), llh.data(), ll0.data(), llt.data(), info.data(),
+                                   status.data(), nullptr, nullptr),
+          "muxgl_demux_alpha_fit");
+    tm.lap("demuxlet: muxgl_demux_alpha_fit");
+    const int64_t mixed = write_alpha_fit(OutFile(out + ".alphafit.gz", true), t, cells.data(), tf.alphaFitMax == 1.0, pair.data(),
+                                          status.data(), ah.data(), llh.data(), ll0.data(), llt.data(), info.data());
+    notice("Mixing share: %lld droplets called SNG are explained better, by more than 2 in log-likelihood, as a mix of their "
+           "best and next singlet at the fitted share than as the better of the two alone", (long long)mixed);
+    tm.lap("demuxlet: write .alphafit.gz");
+  }
+  notice("Finished writing output files");
+  muxgl_destroy(h);
+  return 0;
+}
+
+}  // namespace pa

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import table_rows
 from popscle_amd import muxgl, plpio, synth
 from test_cli_gpu import BIN, as_pileup
 
@@ -38,21 +39,8 @@ def best_pairs(best_rows, index, ids, C):
 
 
 def expected_rows(best_rows, index, ids, fit):
-    sm = muxgl.alpha_fit_summary(fit)
-    whole = fit["alpha_max"] == 1.0
-    rows = []
-    for brow in best_rows:
-        i = index[brow[1]]
-        for k in range(2):
-            j1, j2 = (int(v) for v in fit["pair"][i, k])
-            if j1 < 0:
-                continue
-            se = "NA" if np.isnan(sm["se"][i, k]) else "%.4f" % sm["se"][i, k]
-            rows.append("\t".join(brow[1:4] + [("DBL", "SNG")[k], ids[j1], ids[j2], "%.4f" % fit["ll_zero"][i, k],
-                                               "%.4f" % fit["ll_top"][i, k] if whole else "NA", "%.4f" % fit["alpha_hat"][i, k],
-                                               se, "%.4f" % fit["ll_hat"][i, k], "%.4f" % sm["lrt"][i, k],
-                                               "%d" % fit["status"][i, k]]))
-    return rows
+    return table_rows.alpha_fit_rows([(index[brow[1]], brow[1:4]) for brow in best_rows], lambda j: ids[j], fit,
+                                     muxgl.alpha_fit_summary(fit))
 
 
 @pytest.mark.parametrize("devices", [None, "0,0"])

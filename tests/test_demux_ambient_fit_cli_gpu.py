@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import table_rows
 from popscle_amd import muxgl, plpio, synth
 from test_cli_gpu import BIN, as_pileup
 
@@ -24,16 +25,10 @@ def run(cmd):
 
 
 def expected_rows(best_rows, index, ids, fit, cand):
-    sm = muxgl.ambient_fit_summary(fit)
-    rows = []
     for brow in best_rows:
-        i = index[brow[1]]
-        assert [ids[int(c)] for c in cand[i]] == [brow[12], brow[14]]          # SNG.BEST.GUESS, SNG.NEXT.GUESS of .best
-        for k in range(2):
-            se = "NA" if np.isnan(sm["se"][i, k]) else "%.4f" % sm["se"][i, k]
-            rows.append("\t".join(brow[1:4] + [ids[int(cand[i, k])], "%.4f" % fit["ll_zero"][i, k], "%.4f" % fit["rho_hat"][i, k], se,
-                                               "%.4f" % fit["ll_hat"][i, k], "%.4f" % sm["lrt"][i, k], "%d" % fit["status"][i, k]]))
-    return rows
+        assert [ids[int(c)] for c in cand[index[brow[1]]]] == [brow[12], brow[14]]   # SNG.BEST.GUESS, SNG.NEXT.GUESS of .best
+    return table_rows.ambient_fit_rows([(index[brow[1]], brow[1:4]) for brow in best_rows], lambda j: ids[j], cand, fit,
+                                       muxgl.ambient_fit_summary(fit))
 
 
 @pytest.mark.parametrize("devices", [None, "0,0"])

@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import table_rows
 from popscle_amd import freemuxlet, plpio, synth
 from test_cli_gpu import BIN, as_pileup
 from test_fmx_singlets_gpu import _read, prepared, spread_init
@@ -27,22 +28,9 @@ def run(cmd):
 
 
 def expected_rows(srows, fit):
-    sm = freemuxlet.alpha_fit_summary(fit)
-    whole = fit["alpha_max"] == 1.0
-    pair = fit["pair"]
-    rows = []
     for i, srow in enumerate(srows):
-        assert [str(int(c)) for c in pair[i, 1]] == [srow[12], srow[14]]         # SNG.BEST.GUESS, SNG.NEXT.GUESS
-        for k in range(2):
-            if pair[i, k, 0] < 0:
-                continue
-            se = "NA" if np.isnan(sm["se"][i, k]) else "%.4f" % sm["se"][i, k]
-            lrt = "NA" if not np.isfinite(sm["lrt"][i, k]) else "%.4f" % sm["lrt"][i, k]
-            rows.append("\t".join(srow[1:4] + ["DBL" if k == 0 else "SNG", str(int(pair[i, k, 0])), str(int(pair[i, k, 1])),
-                                               "%.4f" % fit["ll_zero"][i, k], "%.4f" % fit["ll_top"][i, k] if whole else "NA",
-                                               "%.4f" % fit["alpha_hat"][i, k], se, "%.4f" % fit["ll_hat"][i, k], lrt,
-                                               "%d" % fit["status"][i, k]]))
-    return rows
+        assert [str(int(c)) for c in fit["pair"][i, 1]] == [srow[12], srow[14]]  # SNG.BEST.GUESS, SNG.NEXT.GUESS
+    return table_rows.alpha_fit_rows([(i, srow[1:4]) for i, srow in enumerate(srows)], str, fit, freemuxlet.alpha_fit_summary(fit))
 
 
 @pytest.mark.parametrize("devices", [None, "0,0"])

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import table_rows
 from popscle_amd import freemuxlet, muxgl, plpio, synth
 from test_cli_gpu import BIN, as_pileup
 from test_fmx_singlets_gpu import _read, prepared, spread_init
@@ -26,17 +27,10 @@ def run(cmd):
 
 
 def expected_rows(srows, fit, cand):
-    sm = freemuxlet.ambient_fit_summary(fit)
-    rows = []
     for i, srow in enumerate(srows):
         assert [str(int(c)) for c in cand[i]] == [srow[12], srow[14]]            # SNG.BEST.GUESS, SNG.NEXT.GUESS
-        for k in range(2):
-            if cand[i, k] < 0:
-                continue
-            se = "NA" if np.isnan(sm["se"][i, k]) else "%.4f" % sm["se"][i, k]
-            rows.append("\t".join(srow[1:4] + [str(int(cand[i, k])), "%.4f" % fit["ll_zero"][i, k], "%.4f" % fit["rho_hat"][i, k], se,
-                                               "%.4f" % fit["ll_hat"][i, k], "%.4f" % sm["lrt"][i, k], "%d" % fit["status"][i, k]]))
-    return rows
+    return table_rows.ambient_fit_rows([(i, srow[1:4]) for i, srow in enumerate(srows)], str, cand, fit,
+                                       freemuxlet.ambient_fit_summary(fit))
 
 
 @pytest.mark.parametrize("devices", [None, "0,0"])

@@ -170,7 +170,7 @@ def test_vote_rounding_path_is_a_function_of_four_integers():
 
 
 def test_private_random_r_state_equals_rand():
-    """the front end draws from a private glibc state (popscle_amd/host/main.cpp: RefRand) because the HIP runtime
+    """the front end draws from a private glibc state (popscle_amd/host/cli_common.hpp: RefRand) because the HIP runtime
     disturbs the process-wide rand(); both must yield the same values for the same seed"""
     import ctypes
 

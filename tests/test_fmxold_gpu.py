@@ -115,7 +115,7 @@ def test_golden(eng):
         cl, ch, _ = eng.fmxold_vote_refine(K, g["orands"][it], g["jitters"][it], cl, it == 0)
         assert np.array_equal(cl, g["clusts"][it]) and ch == g["changed"][it]
     # the EM loop from those clusters against THE REFERENCE'S OWN run of cmd_cram_freemuxlet.cpp:456-653 (em_* arrays,
-    # tests/golden/make_golden.py): driven the way popscle-amd freemuxlet-old drives the C-ABI (host/main.cpp): ten
+    # tests/golden/make_golden.py): driven the way popscle-amd freemuxlet-old drives the C-ABI (host/cmd_freemuxlet_old.hpp): ten
     # iterations, geno_error only in the last, no early stop
     eng.fmx_set_clusters(K, cl)
     ge, dp = float(g["em_geno_error"]), float(g["em_doublet_prior"])
