@@ -13,8 +13,8 @@ LL = sum log D, LL' = sum D'/D, LL'' = sum (D''/D - (D'/D)^2) over the entries w
 float64 and in np.longdouble.  At an alpha of the grid the nine elements are the grid's own, operation for operation, so
 ll_exact() (float64, math.log, the entries added one after the other as :746 does) is the reference's llksAB[j][k][n].
 
-bracket() is ambient_fit_ref's (it uses eval() only): the coarse rule of the header.  maximise(): the maximiser inside the
-bracket WITHOUT Newton.
+bracket(), maximise() and fit() are fit_ref_core.py's (they use eval() only); the scan of maximise() has 17 points in
+float64 here, cheaper on the nine elements of a pair: LL differs by whole units between them, rounding by 1e-12.
 
 doublet_pileup() / shaped_pileup(): pileups whose droplets hold cells of two samples."""
 import math
@@ -23,10 +23,11 @@ import numpy as np
 
 import ambient_fit_ref as afr
 import ambient_ref as ar
+import fit_ref_core as core
 
 READ_OTHER = ar.READ_OTHER
-coarse_points = afr.coarse_points
-bracket = afr.bracket
+coarse_points, bracket = core.coarse_points, core.bracket
+SCAN = (16, np.float64)
 
 
 class Cell(afr.Cell):
@@ -82,14 +83,9 @@ class Cell(afr.Cell):
         """(LL, LL', LL'', sum |log D|, sum |D'/D|, sum (|D''/D| + (D'/D)^2), sum A'/D, sum (A''/D + (A'/D)^2)), each
         [len(xs)], as ambient_fit_ref.Cell.eval returns them: the fourth to sixth are the sums of absolute per-entry
         terms, the last two the same over absolute summands"""
-        R = np.asarray(xs).reshape(-1).size
         if self.n == 0:
-            z = np.zeros(R, dtype=dtype)
-            return tuple(z.copy() for _ in range(8))
-        D, D1, D2, A1, A2 = self._terms(xs, dtype)
-        lg, q1, q2 = np.log(D), D1 / D, D2 / D
-        return (lg.sum(axis=0), q1.sum(axis=0), (q2 - q1 * q1).sum(axis=0), np.abs(lg).sum(axis=0), np.abs(q1).sum(axis=0),
-                (np.abs(q2) + q1 * q1).sum(axis=0), (A1 / D).sum(axis=0), (A2 / D + (A1 / D) ** 2).sum(axis=0))
+            return core.eval_empty(np.asarray(xs).reshape(-1).size, dtype)
+        return core.eval_tail(*self._terms(xs, dtype))
 
     def ll_exact(self, xs):
         """LL in float64 as the reference adds it (:746): glibc's log per entry, the entries one after the other from 0"""
@@ -106,40 +102,14 @@ class Cell(afr.Cell):
         return out
 
 
-def maximise(cell, lo, hi, n_scan=16):
-    """the maximiser of LL in [lo, hi] without Newton, as ambient_fit_ref.maximise finds it but cheaper on the nine
-    elements of a pair: a scan of n_scan + 1 points in float64 (LL differs by whole units between them, rounding by 1e-12),
-    then bisection on the sign of LL' in longdouble between the neighbours of the best scan point to 1e-12.  Returns
-    (alpha_hat as float, at_lo, at_hi): on the bracket's own end where the scan's best point is that end and LL' points out"""
-    ld = np.longdouble
-    xs = np.array([lo + (hi - lo) * i / n_scan for i in range(n_scan + 1)])
-    xs[-1] = hi
-    i = int(np.argmax(cell.eval(xs, np.float64)[0]))
-    a, b = ld(xs[max(i - 1, 0)]), ld(xs[min(i + 1, n_scan)])
-    if i == 0 and cell.eval([xs[0]], ld)[1][0] <= 0:
-        return float(lo), True, False
-    if i == n_scan and cell.eval([xs[-1]], ld)[1][0] >= 0:
-        return float(hi), False, True
-    while b - a > ld(1e-12):
-        m = (a + b) / ld(2)
-        if cell.eval([m], ld)[1][0] > 0:
-            a = m
-        else:
-            b = m
-    return float((a + b) / ld(2)), False, False
+def maximise(cell, lo, hi, n_scan=SCAN[0]):
+    """fit_ref_core.maximise with this module's scan"""
+    return core.maximise(cell, lo, hi, n_scan, SCAN[1])
 
 
 def fit(p, alphas, c, j, k, alpha_max):
     """dict of the restated outputs of one (droplet, pair): alpha_hat, ll_hat, ll_zero, ll_top, info, status (0, 1, 2 or 5)"""
-    cell = Cell(p, alphas, c, j, k)
-    if cell.n == 0:
-        return dict(alpha_hat=0.0, ll_hat=0.0, ll_zero=0.0, ll_top=0.0, info=0.0, status=5, cell=cell)
-    lo, hi, _ = bracket(cell, alpha_max)
-    x, at_lo, at_hi = maximise(cell, lo, hi)
-    L, _, d2 = [float(v[0]) for v in cell.eval([x], np.longdouble)[:3]]
-    ends = cell.eval([0.0, float(alpha_max)], np.longdouble)[0]
-    status = 1 if (at_lo and x == 0.0) else 2 if (at_hi and x == float(alpha_max)) else 0
-    return dict(alpha_hat=x, ll_hat=L, ll_zero=float(ends[0]), ll_top=float(ends[1]), info=-d2, status=status, cell=cell)
+    return core.fit(Cell(p, alphas, c, j, k), "alpha", alpha_max, top=True, can_fail=False, scan=SCAN)
 
 
 def second_sample(C, V):
@@ -180,35 +150,14 @@ def doublet_pileup(C, S, V, markers, shares, seed, reads_mean=2.0, bq=30, geno_e
     return p, first, second
 
 
-def shaped_pileup(cell_entries, S, V, seed, share=0.3, depths=(1, 2, 33, 60), depth_p=(0.55, 0.35, 0.05, 0.05), other=0.03,
-                  missing_gp_frac=0.03, min_bq=2, max_bq=93):
-    """A pileup whose droplets have exactly the given numbers of entries (0 allowed; each <= S), with the depths, base
-    qualities, READ_OTHER share and missing-genotype share of ambient_fit_ref.shaped_pileup; droplet c holds cells of samples
-    c % V and second_sample(C, V)[c] (the same one where V == 1) and a read comes from the second with probability `share`.
-    Returns (pileup, first [C], second [C])."""
-    rng = np.random.default_rng(seed)
+def shaped_pileup(cell_entries, S, V, seed, share=0.3, **kw):
+    """ambient_fit_ref.shaped_pileup (its depths, base qualities, READ_OTHER share and missing-genotype share, and its
+    keywords) with another donor rule: droplet c holds cells of samples c % V and second_sample(C, V)[c] (the same one where
+    V == 1) and a read comes from the second with probability `share`.  Returns (pileup, first [C], second [C])."""
     C = len(cell_entries)
-    af, G = _draw(rng, S, V)
     first, second = np.arange(C) % V, second_sample(C, V)
-    cell_ptr = np.concatenate([[0], np.cumsum(cell_entries)]).astype(np.int64)
-    snp = np.concatenate([np.sort(rng.choice(S, size=n, replace=False)) for n in cell_entries] + [np.zeros(0, dtype=np.int64)])
-    snp = snp.astype(np.int32)
-    nreads = rng.choice(depths, size=snp.size, p=depth_p).astype(np.int64)
-    rptr = np.concatenate([[0], np.cumsum(nreads)]).astype(np.int64)
-    ent = np.repeat(np.arange(snp.size), nreads)
-    cell_of = np.repeat(np.arange(C), cell_entries)[ent]
-    s_of = snp[ent]
-    from_second = rng.random(ent.size) < share
-    p_alt = G[s_of, np.where(from_second, second[cell_of], first[cell_of])] / 2.0
-    bq = rng.integers(min_bq, max_bq + 1, size=ent.size)
-    alt = (rng.random(ent.size) < p_alt) ^ (rng.random(ent.size) < 10.0 ** (-bq / 10.0))
-    reads = ((alt.astype(np.uint8) << 7) | bq.astype(np.uint8)).astype(np.uint8)
-    reads[rng.random(ent.size) < other] = READ_OTHER
-    has_gp = (rng.random(S) >= missing_gp_frac).astype(np.uint8)
-    gp = ar.synth.gt_to_gp(G, 0.01)
-    gp[has_gp == 0] = (1.0, 0.0, 0.0)
-    p = ar.synth.Pileup(C, S, cell_ptr, snp, rptr, reads, af, gp, has_gp)
-    return p, first, second
+    donor = lambda G, s_of, cell_of, from_second: G[s_of, np.where(from_second, second[cell_of], first[cell_of])] / 2.0
+    return afr.shaped_pileup(cell_entries, S, V, seed, share, p_alt_of=donor, **kw)[0], first, second
 
 
 # the pileups of the sanity tests (CPU: the restatement, tests/test_demux_alpha_fit.py; GPU: the device,

@@ -10,12 +10,14 @@ D = sum_l gp[j][l] * w[l], D', D'' likewise, and LL = sum log D, LL' = sum D'/D,
 entries whose marker has genotypes.  It runs in float64 and in np.longdouble; the entries of a droplet are walked side by
 side (numpy rows), every row in the per-read order above.
 
-bracket(): the coarse rule of the header: LL at i * rho_max / 8, the best (ties to the lowest index), its neighbours.
-maximise(): the maximiser inside the bracket WITHOUT Newton: a dense scan of LL, then bisection on the sign of LL' in
-longdouble between the neighbours of the best scan point to a width of 1e-12."""
+bracket(), maximise() (a 65-point scan in longdouble) and fit() are fit_ref_core.py's: they ask a cell for eval() only.
+
+shaped_pileup(): the pileups of the shape tests, for this fit and, through its hook for the donor of a read, for
+alpha_fit_ref.shaped_pileup."""
 import numpy as np
 
 import ambient_ref as ar
+import fit_ref_core as core
 
 READ_OTHER = ar.READ_OTHER
 
@@ -73,8 +75,7 @@ class Cell:
         rh = np.asarray(rhos, dtype=dtype).reshape(-1)
         R = rh.size
         if self.n == 0:
-            z = np.zeros(R, dtype=dtype)
-            return tuple(z.copy() for _ in range(8))
+            return core.eval_empty(R, dtype)
         mxs, mxf = self.grid_maxima(dtype)
         l = np.arange(3).astype(dtype)
         tfl = dtype(2.0) * self.f.astype(dtype)[:, None] - l[None, :]              # 2 f - l, [n][3]
@@ -107,9 +108,7 @@ class Cell:
             D2 = D2 + g[:, :, k] * a2[:, :, k]
             A1 = A1 + np.abs(g[:, :, k] * a1[:, :, k])
             A2 = A2 + np.abs(g[:, :, k] * a2[:, :, k])
-        lg, q1, q2 = np.log(D), D1 / D, D2 / D
-        return (lg.sum(axis=0), q1.sum(axis=0), (q2 - q1 * q1).sum(axis=0), np.abs(lg).sum(axis=0), np.abs(q1).sum(axis=0),
-                (np.abs(q2) + q1 * q1).sum(axis=0), (A1 / D).sum(axis=0), (A2 / D + (A1 / D) ** 2).sum(axis=0))
+        return core.eval_tail(D, D1, D2, A1, A2)
 
 
 def ll_d1_d2(p, alphas, amb_af, c, j, rho, dtype=np.float64):
@@ -118,59 +117,23 @@ def ll_d1_d2(p, alphas, amb_af, c, j, rho, dtype=np.float64):
     return L[0], d1[0], d2[0]
 
 
-def coarse_points(rho_max):
-    return [i * float(rho_max) / 8 for i in range(9)]
-
-
-def bracket(cell, rho_max):
-    """(lo, hi, best index) by the coarse rule; LL in float64"""
-    xs = coarse_points(rho_max)
-    L = cell.eval(xs, np.float64)[0]
-    i = int(np.argmax(L))                                        # (first maximum: ties to the lowest index)
-    return xs[max(i - 1, 0)], xs[min(i + 1, 8)], i
-
-
-def maximise(cell, lo, hi, n_scan=64):
-    """the maximiser of LL in [lo, hi]: dense scan in longdouble, then bisection on the sign of LL' to 1e-12.  Returns
-    (rho_hat as float, at_lo, at_hi): on the bracket's own end where the scan's best point is that end and LL' points out"""
-    ld = np.longdouble
-    xs = np.array([ld(lo) + (ld(hi) - ld(lo)) * ld(i) / ld(n_scan) for i in range(n_scan + 1)], dtype=ld)
-    xs[-1] = ld(hi)
-    L = cell.eval(xs, ld)[0]
-    i = int(np.argmax(L))
-    a, b = xs[max(i - 1, 0)], xs[min(i + 1, n_scan)]
-    if i == 0 and cell.eval([xs[0]], ld)[1][0] <= 0:
-        return float(lo), True, False
-    if i == n_scan and cell.eval([xs[-1]], ld)[1][0] >= 0:
-        return float(hi), False, True
-    while b - a > ld(1e-12):
-        m = (a + b) / ld(2)
-        if cell.eval([m], ld)[1][0] > 0:
-            a = m
-        else:
-            b = m
-    return float((a + b) / ld(2)), False, False
+coarse_points, bracket, maximise = core.coarse_points, core.bracket, core.maximise
 
 
 def fit(p, alphas, amb_af, c, j, rho_max):
     """dict of the restated outputs of one (droplet, candidate): rho_hat, ll_hat, ll_zero, info, status (0, 1, 2 or 5)"""
-    cell = Cell(p, alphas, amb_af, c, j)
-    if cell.n == 0:
-        return dict(rho_hat=0.0, ll_hat=0.0, ll_zero=0.0, info=0.0, status=5, cell=cell)
-    lo, hi, _ = bracket(cell, rho_max)
-    x, at_lo, at_hi = maximise(cell, lo, hi)
-    L, _, d2 = [float(v[0]) for v in cell.eval([x], np.longdouble)[:3]]
-    status = 1 if (at_lo and x == 0.0) else 2 if (at_hi and x == float(rho_max)) else 0
-    return dict(rho_hat=x, ll_hat=L, ll_zero=float(cell.eval([0.0], np.longdouble)[0][0]), info=-d2, status=status, cell=cell)
+    return core.fit(Cell(p, alphas, amb_af, c, j), "rho", rho_max, top=False, can_fail=False)
 
 
 def shaped_pileup(cell_entries, S, V, seed, soup=0.2, depths=(1, 2, 33, 60), depth_p=(0.55, 0.35, 0.05, 0.05), other=0.03,
-                  missing_gp_frac=0.03, min_bq=2, max_bq=93):
+                  missing_gp_frac=0.03, min_bq=2, max_bq=93, p_alt_of=None):
     """A pileup whose droplets have exactly the given numbers of entries (0 allowed; each <= S): droplet c holds one cell of
     sample c % V, a read comes with probability `soup` from the pool and else from the cell (as ambient_ref.soup_pileup
     draws them) and is miscalled with the probability of its base quality, uniform in [min_bq, max_bq]; an entry has
     one of `depths` reads; a share `other` of the read bytes is READ_OTHER; a share `missing_gp_frac` of the markers has
-    no genotypes (1.0: none has).  Returns (pileup, sample of every droplet, the pool's fractions)."""
+    no genotypes (1.0: none has).  p_alt_of(G, s_of, cell_of, drawn): another donor rule -- the ALT probability of every
+    read from the genotypes G [S][V], the read's marker and droplet and whether the share `soup` drew it (it takes no draw of
+    its own, so the stream of draws is one for every rule).  Returns (pileup, sample of every droplet, the pool's fractions)."""
     rng = np.random.default_rng(seed)
     C = len(cell_entries)
     af = rng.uniform(0.1, 0.9, size=S)
@@ -186,7 +149,7 @@ def shaped_pileup(cell_entries, S, V, seed, soup=0.2, depths=(1, 2, 33, 60), dep
     cell_of = np.repeat(np.arange(C), cell_entries)[ent]
     s_of = snp[ent]
     from_soup = rng.random(ent.size) < soup
-    p_alt = np.where(from_soup, pool[s_of], G[s_of, who[cell_of]] / 2.0)
+    p_alt = p_alt_of(G, s_of, cell_of, from_soup) if p_alt_of else np.where(from_soup, pool[s_of], G[s_of, who[cell_of]] / 2.0)
     bq = rng.integers(min_bq, max_bq + 1, size=ent.size)
     alt = (rng.random(ent.size) < p_alt) ^ (rng.random(ent.size) < 10.0 ** (-bq / 10.0))
     reads = ((alt.astype(np.uint8) << 7) | bq.astype(np.uint8)).astype(np.uint8)

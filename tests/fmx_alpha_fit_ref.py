@@ -16,9 +16,9 @@ formed as (w * q_j) * q_k (cmd_cram_freemux2.cpp:441-445); D', D'' over the six 
 and in np.longdouble.  ll_exact() (float64, math.log, the entries one after the other from 0, as :455 adds them) at
 alpha = 0.5 is the reference's llks[j (j + 1) / 2 + k] for k < j.
 
-bracket(): the coarse rule of the header.  maximise(): the maximiser inside the bracket WITHOUT Newton (a dense scan, then
-bisection on the sign of LL' in longdouble).  search(): the device's search rule restated on the float64 evaluation, the
-65-point scan of a bracket in which an element crosses the floor included.  sign_changes(): of LL' along a scan."""
+bracket(), maximise() (a 65-point scan in longdouble), fit() and sign_changes() are fit_ref_core.py's (they use eval()
+only).  search(): the device's search rule restated on the float64 evaluation, the 65-point scan of a bracket in which an
+element crosses the floor included."""
 import math
 
 import numpy as np
@@ -26,9 +26,10 @@ import numpy as np
 import alpha_fit_ref as dfr
 import fmx_ambient_fit_ref as ffr
 import fmx_ambient_ref as fr
+import fit_ref_core as core
 
 READ_OTHER = fr.READ_OTHER
-coarse_points = ffr.coarse_points
+coarse_points, bracket, maximise, sign_changes = core.coarse_points, core.bracket, core.maximise, core.sign_changes
 LM = [(l, m) for l in range(3) for m in range(3)]
 OFF = [i for i, (l, m) in enumerate(LM) if l != m]
 
@@ -95,15 +96,10 @@ class Cell(ffr.Cell):
     def eval(self, xs, dtype=np.float64):
         """(LL, LL', LL'', sum |log D|, sum |D'/D|, sum (|D''/D| + (D'/D)^2), sum A'/D, sum (A''/D + (A'/D)^2), nearest),
         each [len(xs)], as fmx_ambient_fit_ref.Cell.eval returns them"""
-        R = np.asarray(xs).reshape(-1).size
         if self.n == 0:
-            z = np.zeros(R, dtype=dtype)
-            return tuple(z.copy() for _ in range(8)) + (np.full(R, np.inf),)
-        D, D1, D2, A1, A2, nearest = self._terms(xs, dtype)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            lg, q1, q2 = np.log(D), D1 / D, D2 / D
-            return (lg.sum(axis=0), q1.sum(axis=0), (q2 - q1 * q1).sum(axis=0), np.abs(lg).sum(axis=0), np.abs(q1).sum(axis=0),
-                    (np.abs(q2) + q1 * q1).sum(axis=0), (A1 / D).sum(axis=0), (A2 / D + (A1 / D) ** 2).sum(axis=0), nearest)
+            return core.eval_empty(np.asarray(xs).reshape(-1).size, dtype, nearest=True)
+        with np.errstate(divide="ignore", invalid="ignore"):          # (a posterior row of exactly 0: log(0), 0 / 0)
+            return core.eval_tail(*self._terms(xs, dtype))
 
     def ll_exact(self, xs):
         """LL in float64 as the reference adds it (:455): glibc's log per entry, the entries one after the other from 0"""
@@ -128,24 +124,10 @@ class Cell(ffr.Cell):
         return bool((low != low[:, :1, :]).any())
 
 
-# the coarse bracket, the Newton-free maximiser and the sign changes of LL' ask a cell for eval() only: fmx_ambient_fit_ref's
-bracket, maximise, sign_changes = ffr.bracket, ffr.maximise, ffr.sign_changes
-
-
 def fit(p, q, c, j, k, alpha_max):
     """dict of the restated outputs of one (droplet, pair): alpha_hat, ll_hat, ll_zero, ll_top, info, status (0, 1, 2, 5 or
     6)"""
-    cell = Cell(p, q, c, j, k)
-    if cell.n == 0:
-        return dict(alpha_hat=0.0, ll_hat=0.0, ll_zero=0.0, ll_top=0.0, info=0.0, status=5, cell=cell)
-    if not np.isfinite(cell.eval(coarse_points(alpha_max), np.float64)[0]).all():
-        return dict(alpha_hat=0.0, ll_hat=-np.inf, ll_zero=-np.inf, ll_top=-np.inf, info=0.0, status=6, cell=cell)
-    lo, hi, _ = bracket(cell, alpha_max)
-    x, at_lo, at_hi = maximise(cell, lo, hi)
-    L, _, d2 = [float(v[0]) for v in cell.eval([x], np.longdouble)[:3]]
-    ends = cell.eval([0.0, float(alpha_max)], np.longdouble)[0]
-    status = 1 if (at_lo and x == 0.0) else 2 if (at_hi and x == float(alpha_max)) else 0
-    return dict(alpha_hat=x, ll_hat=L, ll_zero=float(ends[0]), ll_top=float(ends[1]), info=-d2, status=status, cell=cell)
+    return core.fit(Cell(p, q, c, j, k), "alpha", alpha_max, top=True, can_fail=True)
 
 
 def search(cell, alpha_max):

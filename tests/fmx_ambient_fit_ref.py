@@ -13,18 +13,17 @@ w = a / T, D = (q[0] * w[0] + q[1] * w[1]) + q[2] * w[2], D', D'' likewise, and 
 LL'' = sum (D''/D - (D'/D)^2) over ALL entries of the droplet (freemuxlet has no has_gp).  It runs in float64 and in
 np.longdouble; the entries of a droplet are walked side by side (numpy rows), every row in the per-read order above.
 
-bracket(): the coarse rule of the header: LL at i * rho_max / 8, the best (ties to the lowest index), its neighbours.
-maximise(): the maximiser inside the bracket WITHOUT Newton: a dense scan of LL, then bisection on the sign of LL' in
-longdouble between the neighbours of the best scan point to a width of 1e-12.  LL' may jump where an element crosses the
-floor, but only upward (max(a, 1e-6) is convex in a), so the bisection closes on a zero LL' crosses downward: a maximum."""
+bracket(), maximise() (a 65-point scan in longdouble), fit() and sign_changes() are fit_ref_core.py's: they ask a cell for
+eval() only."""
 import numpy as np
 
 import ambient_fit_ref as afr
+import fit_ref_core as core
 import fmx_ambient_ref as fr
 
 READ_OTHER = fr.READ_OTHER
 shaped_pileup = afr.shaped_pileup
-coarse_points = afr.coarse_points
+coarse_points, bracket, maximise, sign_changes = core.coarse_points, core.bracket, core.maximise, core.sign_changes
 
 
 class Cell:
@@ -86,8 +85,7 @@ class Cell:
         rh = np.asarray(rhos, dtype=dtype).reshape(-1)
         R = rh.size
         if self.n == 0:
-            z = np.zeros(R, dtype=dtype)
-            return tuple(z.copy() for _ in range(8)) + (np.full(R, np.inf),)
+            return core.eval_empty(R, dtype, nearest=True)
         ts, T = self.nine_sums(dtype)
         floor = dtype(fr.MIN_NORM_GL)
         l = np.arange(3).astype(dtype)
@@ -120,63 +118,13 @@ class Cell:
         D2 = (g[:, :, 0] * a2[:, :, 0] + g[:, :, 1] * a2[:, :, 1]) + g[:, :, 2] * a2[:, :, 2]
         A1 = np.abs(g * a1).sum(axis=2)
         A2 = np.abs(g * a2).sum(axis=2)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            lg, q1, q2 = np.log(D), D1 / D, D2 / D
-            return (lg.sum(axis=0), q1.sum(axis=0), (q2 - q1 * q1).sum(axis=0), np.abs(lg).sum(axis=0), np.abs(q1).sum(axis=0),
-                    (np.abs(q2) + q1 * q1).sum(axis=0), (A1 / D).sum(axis=0), (A2 / D + (A1 / D) ** 2).sum(axis=0), nearest)
-
-
-def bracket(cell, rho_max):
-    """(lo, hi, best index) by the coarse rule; LL in float64"""
-    xs = coarse_points(rho_max)
-    L = cell.eval(xs, np.float64)[0]
-    i = int(np.argmax(L))                                        # (first maximum: ties to the lowest index)
-    return xs[max(i - 1, 0)], xs[min(i + 1, 8)], i
-
-
-def maximise(cell, lo, hi, n_scan=64):
-    """the maximiser of LL in [lo, hi]: dense scan in longdouble, then bisection on the sign of LL' to 1e-12.  Returns
-    (rho_hat as float, at_lo, at_hi): on the bracket's own end where the scan's best point is that end and LL' points out"""
-    ld = np.longdouble
-    xs = np.array([ld(lo) + (ld(hi) - ld(lo)) * ld(i) / ld(n_scan) for i in range(n_scan + 1)], dtype=ld)
-    xs[-1] = ld(hi)
-    L = cell.eval(xs, ld)[0]
-    i = int(np.argmax(L))
-    a, b = xs[max(i - 1, 0)], xs[min(i + 1, n_scan)]
-    if i == 0 and cell.eval([xs[0]], ld)[1][0] <= 0:
-        return float(lo), True, False
-    if i == n_scan and cell.eval([xs[-1]], ld)[1][0] >= 0:
-        return float(hi), False, True
-    while b - a > ld(1e-12):
-        m = (a + b) / ld(2)
-        if cell.eval([m], ld)[1][0] > 0:
-            a = m
-        else:
-            b = m
-    return float((a + b) / ld(2)), False, False
+        with np.errstate(divide="ignore", invalid="ignore"):          # (a posterior row of exactly 0: log(0), 0 / 0)
+            return core.eval_tail(D, D1, D2, A1, A2, nearest)
 
 
 def fit(p, q, amb_af, c, j, rho_max):
     """dict of the restated outputs of one (droplet, candidate): rho_hat, ll_hat, ll_zero, info, status (0, 1, 2, 5 or 6)"""
-    cell = Cell(p, q, amb_af, c, j)
-    if cell.n == 0:
-        return dict(rho_hat=0.0, ll_hat=0.0, ll_zero=0.0, info=0.0, status=5, cell=cell)
-    if not np.isfinite(cell.eval(coarse_points(rho_max), np.float64)[0]).all():
-        return dict(rho_hat=0.0, ll_hat=-np.inf, ll_zero=-np.inf, info=0.0, status=6, cell=cell)
-    lo, hi, _ = bracket(cell, rho_max)
-    x, at_lo, at_hi = maximise(cell, lo, hi)
-    L, _, d2 = [float(v[0]) for v in cell.eval([x], np.longdouble)[:3]]
-    status = 1 if (at_lo and x == 0.0) else 2 if (at_hi and x == float(rho_max)) else 0
-    return dict(rho_hat=x, ll_hat=L, ll_zero=float(cell.eval([0.0], np.longdouble)[0][0]), info=-d2, status=status, cell=cell)
-
-
-def sign_changes(cell, lo, hi, n=129):
-    """the sign changes of LL' (longdouble) along an n-point scan of [lo, hi], zeros dropped"""
-    ld = np.longdouble
-    xs = np.array([ld(lo) + (ld(hi) - ld(lo)) * ld(i) / ld(n - 1) for i in range(n)], dtype=ld)
-    s = np.sign(cell.eval(xs, ld)[1].astype(np.float64))
-    s = s[s != 0]
-    return int((s[1:] != s[:-1]).sum())
+    return core.fit(Cell(p, q, amb_af, c, j), "rho", rho_max, top=False, can_fail=True)
 
 
 # the inputs of the GPU shape tests (tests/test_fmx_ambient_fit_gpu.py); the CPU test holds the kink claim on them

@@ -5,19 +5,17 @@ restatement's Newton-free maximiser, against the reference's own slots (the orac
 mirror (j, k) <-> (k, j), the two sanity pileups, bit identity across calls, budgets, device groups, the sharded driver,
 orders and groupings of slots and subsets of outputs, the state the call must leave alone, and the refusals.
 
-Bars (check_fit; those of tests/test_demux_ambient_fit_gpu.py restated for pairs): ll_hat, ll_zero and ll_top within
-parity.LL_TOL of the longdouble restatement; info and the implied LL' (0 at an interior estimate) within 1000 x the
-float64-to-longdouble disagreement of the restatement on the case, floored at 1e-9 x the sum of absolute per-entry terms
-(where that is exactly 0 -- every per-entry term exactly 0 in both precisions -- at 1e-9 x the same sum over absolute
-summands); the restated LL at the device's estimate within 1e-9 of the LL at the restatement's; where the restated info
-is >= 1 the two estimates within 1e-6 and the same status; no status 3."""
-import ctypes
+Bars: check_fit, tests/fit_check.py, as CALL describes this call: with ll_top, so ll_hat on a bound is ll_zero resp. ll_top
+bit for bit on the checked slots; no floor, hence no kink and no slot that skips a derivative bar.  The bodies shared with
+the other three fits: tests/fit_suite.py."""
 import functools
 
 import numpy as np
 import pytest
 
 import alpha_fit_ref as alr
+import fit_check
+import fit_suite as suite
 import many_samples
 import parity
 import unknown_ref as ur
@@ -28,88 +26,24 @@ pytestmark = pytest.mark.gpu
 G2 = (0.0, 0.5)
 G6 = (0.0, 0.13, 0.37, 0.5, 0.71, 1.0)
 FIELDS = muxgl.Engine.ALPHA_FIT_FIELDS
-WORST = {}   # what -> worst figure seen, printed by every check
+CALL = fit_check.Call(
+    name="alpha fit", share="alpha", fields=FIELDS, width=2, top=True, fit=alr.fit,
+    closing="n_steps mean {mean:.2f} max {max}", guard_info_note=True,
+    method="demux_alpha_fit", grid=True, x_name="alpha_max", slot_name="pair", extra=("pair", "alpha_max"),
+    subsets=(("alpha_hat",), ("status", "n_steps"), ("info", "ll_zero"), ("ll_top",), ("ll_hat", "n_steps", "alpha_hat")),
+    x_identity=0.87)
+load = suite.demux_load
+same = functools.partial(suite.same, CALL)
 
 
-def load(e, p):
-    e.set_pileup(p.S, p.cell_ptr, p.entry_snp, p.entry_rptr, p.reads)
-    e.demux_set_gp(p.gp, p.has_gp)
-
-
-def fit(p, alphas, pairs, alpha_max=1.0, flags=0, devs=0, want=FIELDS):
-    with muxgl.Engine(devs, flags) as e:
-        load(e, p)
-        return e.demux_alpha_fit(alphas, pairs, alpha_max, want=want)
-
-
-def same(a, b, fields=FIELDS):
-    return all(a[k].tobytes() == b[k].tobytes() for k in fields)
-
-
-def note(what, v):
-    WORST[what] = max(WORST.get(what, 0.0), float(v))
+def fit(p, alphas, pairs, alpha_max=1.0, **kw):
+    return suite.demux_fit(CALL, p, (alphas,), pairs, alpha_max, **kw)
 
 
 def check_fit(p, alphas, pairs, alpha_max, got, what, slots=None):
-    """every bar of the module's docstring on the (droplet, slot) pairs of `slots` (None: all); returns the number of
-    fitted cases and of those with restated info >= 1"""
-    ld = np.longdouble
-    pairs = np.asarray(pairs).reshape(p.C, -1, 2)
-    assert all(got[k].shape == pairs.shape[:2] for k in FIELDS)
-    assert (got["n_steps"] <= 48).all() and (got["n_steps"] >= 0).all() and not (got["status"] == 3).any()
-    fitted = strong = 0
-    seen = {}
-    for c, s in (slots if slots is not None else [(c, s) for c in range(p.C) for s in range(pairs.shape[1])]):
-        j, k = int(pairs[c, s, 0]), int(pairs[c, s, 1])
-        g = {n: got[n][c, s] for n in FIELDS}
-        if j < 0:
-            assert g["status"] == 4 and all(g[n] == 0 for n in FIELDS if n != "status"), (c, s, g)
-            continue
-        if (c, j, k) not in seen:
-            seen[(c, j, k)] = alr.fit(p, alphas, c, j, k, alpha_max)
-        r = seen[(c, j, k)]
-        cell = r["cell"]
-        if cell.n == 0:
-            assert g["status"] == 5 and all(g[n] == 0 for n in FIELDS if n != "status"), (c, s, g)
-            continue
-        x = float(g["alpha_hat"])
-        assert g["status"] in (0, 1, 2) and 0.0 <= x <= alpha_max, (c, s, g)
-        L, d1, d2, aL, a1, a2, s1, s2 = [float(v[0]) for v in cell.eval([x], ld)]
-        L64, d164, d264 = [float(v[0]) for v in cell.eval([x], np.float64)[:3]]
-        tol1 = max(1000.0 * abs(d164 - d1), 1e-9 * a1)
-        tol2 = max(1000.0 * abs(d264 - d2), 1e-9 * a2)
-        if tol1 == 0.0 or tol2 == 0.0:   # every term exactly 0 in both precisions: the floor over absolute summands
-            tol1, tol2 = max(tol1, 1e-9 * s1), max(tol2, 1e-9 * s2)
-        for name, ref in (("ll_hat", L), ("ll_zero", r["ll_zero"]), ("ll_top", r["ll_top"])):
-            note(f"{what}: |{name} - ref|", abs(g[name] - ref))
-            assert abs(g[name] - ref) <= parity.LL_TOL, (c, s, name, g, ref)
-        if tol2 > 0.0:
-            note(f"{what}: |info - ref| / tol", abs(g["info"] + d2) / tol2)
-        assert abs(g["info"] + d2) <= tol2, (c, s, g, d2, tol2)
-        if g["status"] == 1:
-            assert x == 0.0 and d1 <= tol1, (c, s, g, d1)
-            assert g["ll_hat"].tobytes() == g["ll_zero"].tobytes() and g["n_steps"] == 0, (c, s, g)
-        elif g["status"] == 2:
-            assert x == alpha_max and d1 >= -tol1, (c, s, g, d1)
-            assert g["ll_hat"].tobytes() == g["ll_top"].tobytes() and g["n_steps"] == 0, (c, s, g)
-        else:
-            note(f"{what}: |LL'(alpha_hat)| / tol", abs(d1) / tol1)
-            assert abs(d1) <= tol1, (c, s, g, d1, tol1)
-            fitted += 1
-        note(f"{what}: LL(ref alpha) - LL(device alpha)", r["ll_hat"] - L)
-        assert L >= r["ll_hat"] - 1e-9, (c, s, g, r["alpha_hat"], r["ll_hat"], L)
-        if r["info"] >= 1.0:
-            strong += g["status"] == 0
-            note(f"{what}: |alpha_hat - ref|", abs(x - r["alpha_hat"]))
-            assert abs(x - r["alpha_hat"]) <= 1e-6, (c, s, g, r["alpha_hat"], r["info"])
-            assert g["status"] == r["status"], (c, s, g, r["status"])
-    for key in sorted(WORST):
-        if key.startswith(what + ":"):
-            print(f"alpha fit {key} {WORST[key]:.3e}")
-    on = got["status"] == 0
-    print(f"alpha fit {what}: {fitted} interior fits, {strong} with info >= 1, n_steps mean "
-          f"{float(got['n_steps'][on].mean()) if on.any() else 0.0:.2f} max {int(got['n_steps'].max()) if got['n_steps'].size else 0}")
-    return fitted, strong
+    """every bar of fit_check.check_fit on the (droplet, slot) pairs of `slots` (None: all); returns the number of fitted
+    cases and of those with restated info >= 1"""
+    return fit_check.check_fit(CALL, (p, alphas), pairs, alpha_max, got, what, slots, parity.LL_TOL)
 
 
 # ---- 1. parity and optimality over the shapes ----------------------------------------------------------------------------
@@ -159,9 +93,7 @@ def test_sixteen_slots_with_skips_and_repeats():
     pairs[:, 5, 1] = pairs[:, 5, 0] = np.abs(pairs[:, 5, 0])                             # j == k
     pairs[:, 7] = -1
     got = fit(p, G6, pairs, 0.9)
-    check_fit(p, G6, pairs, 0.9, got, "16 slots")
-    assert all(got[k][:, 3].tobytes() == got[k][:, 0].tobytes() for k in FIELDS)
-    assert (got["status"][:, 7] == 4).all()
+    suite.sixteen_slots(CALL, (p, G6), pairs, 0.9, got, "16 slots")
 
 
 def test_no_marker_has_genotypes():
@@ -175,10 +107,9 @@ def test_no_marker_has_genotypes():
 def test_zero_cells():
     p, first, second = alr.shaped_pileup([3, 4], 50, 3, seed=8)
     with muxgl.Engine(0) as e:
-        e.set_pileup(p.S, np.zeros(1, np.int64), np.zeros(0, np.int32), np.zeros(1, np.int64), np.zeros(0, np.uint8))
+        suite.empty_pileup(e, p)
         e.demux_set_gp(p.gp, p.has_gp)
-        got = e.demux_alpha_fit(G2, np.zeros((0, 2, 2), np.int32))
-    assert got["alpha_hat"].shape == (0, 2) and got["kernel_ms"] == 0.0
+        suite.zero_cells(CALL, e, (G2,))
 
 
 # ---- 2. the reference's own slots ----------------------------------------------------------------------------------------
@@ -276,20 +207,9 @@ def identity_case(V):
 
 def test_call_to_call_budget_permutation_split_and_null_outputs(monkeypatch):
     p, pairs, want = identity_case(24)
-    assert (want["status"] == 0).any() and (want["status"] == 4).any()
     assert all(want[k][:, 9].tobytes() == want[k][:, 2].tobytes() for k in FIELDS)
-    with muxgl.Engine(0) as e:
-        load(e, p)
-        assert same(e.demux_alpha_fit(G6, pairs, 0.87), want) and same(e.demux_alpha_fit(G6, pairs, 0.87), want)
-        perm = np.random.default_rng(1).permutation(16)
-        got = e.demux_alpha_fit(G6, np.ascontiguousarray(pairs[:, perm]), 0.87)
-        assert same(got, {k: np.ascontiguousarray(want[k][:, perm]) for k in FIELDS})
-        lo = e.demux_alpha_fit(G6, np.ascontiguousarray(pairs[:, :8]), 0.87)
-        hi = e.demux_alpha_fit(G6, np.ascontiguousarray(pairs[:, 8:]), 0.87)
-        assert same({k: np.concatenate([lo[k], hi[k]], axis=1) for k in FIELDS}, want)
-        for sub in (("alpha_hat",), ("status", "n_steps"), ("info", "ll_zero"), ("ll_top",), ("ll_hat", "n_steps", "alpha_hat")):
-            got = e.demux_alpha_fit(G6, pairs, 0.87, want=sub)
-            assert set(got) == set(sub) | {"kernel_ms", "pair", "alpha_max"} and same(got, want, sub)
+    with suite.demux_open(p) as e:
+        suite.identity(CALL, e, (G6,), pairs, want)
     monkeypatch.setenv("MUXGL_DEMUX_SLAB_MB", "1")
     assert same(fit(p, G6, pairs, 0.87), want)
 
@@ -297,9 +217,7 @@ def test_call_to_call_budget_permutation_split_and_null_outputs(monkeypatch):
 @pytest.mark.parametrize("V", [24, 300])
 def test_device_group_and_sharded_driver(V):
     p, pairs, want = identity_case(V)
-    for devs in ([0, 0], [0, 0, 0]):
-        got = fit(p, G6, pairs, 0.87, flags=muxgl.FLAG_DEMUX_ONLY, devs=devs)
-        assert same(got, want) and got["kernel_ms"] > 0.0
+    suite.device_groups(CALL, functools.partial(suite.demux_open, p), (G6,), pairs, want, flags=muxgl.FLAG_DEMUX_ONLY)
     with muxgl.Engine(0) as e:
         load(e, p)
         records = e.demux_run(G6, 0.5)
@@ -317,20 +235,7 @@ def test_the_call_leaves_the_demuxlet_state_alone(V, flags):
     p = many_samples.pileup(30, 2000, V, seed=800 + V, mean_entries=80)
     pairs = np.random.default_rng(V).integers(0, V, size=(p.C, 2, 2)).astype(np.int32)
     pairs[::7, 1] = -1
-    with muxgl.Engine(0, flags) as e:
-        load(e, p)
-        full = flags == 0                                    # (the streamed call keeps no LL tensor)
-        run = lambda: e.demux_run(G6, 0.5, want_full_ll=True) if full else (e.demux_run(G6, 0.5), np.zeros(0))
-        r0, full0 = run()
-        view, t0, pg0 = e.demux_results_view().tobytes(), e.timing().copy(), e.demux_entry_pg().tobytes()
-        a0 = e.demux_alpha_fit(G6, pairs, 1.0)
-        assert e.demux_results_view().tobytes() == view and np.array_equal(e.timing(), t0)
-        e.demux_alpha_fit(G2, pairs, 0.25)                   # another grid between two runs
-        assert e.demux_results_view().tobytes() == view and np.array_equal(e.timing(), t0)
-        assert e.demux_entry_pg().tobytes() == pg0           # the cached grid is still the run's
-        r1, full1 = run()
-        a1 = e.demux_alpha_fit(G6, pairs, 1.0)
-    assert r0.tobytes() == r1.tobytes() == view and full0.tobytes() == full1.tobytes() and same(a0, a1)
+    suite.demux_state_alone(CALL, p, flags, pairs, (G6,), (G2,), 1.0, G6)
 
 
 # ---- 7. refusals ---------------------------------------------------------------------------------------------------------
@@ -340,55 +245,21 @@ def test_refusals_leave_the_handle_usable(devs):
     p, first, second = alr.shaped_pileup([5, 0, 130, 64], 400, 8, seed=612)
     pairs = shape_pairs(8, first, second, ("own", "wrong"))
     fresh = fit(p, G2, pairs, 1.0, flags=muxgl.FLAG_DEMUX_ONLY, devs=devs)
-    VP = ctypes.c_void_p
-
-    def raw(e, n_alpha=2, n_cand=2, prs=pairs, alpha_max=1.0, outs=True):
-        dp = muxgl._DemuxParams()
-        dp.n_alpha = n_alpha
-        dp.alpha[1] = 0.5
-        dp.doublet_prior = 0.5
-        shape = pairs.shape[:2]
-        bufs = [np.zeros(shape) for _ in range(5)] + [np.zeros(shape, np.int32) for _ in range(2)]
-        rc = e.lib.muxgl_demux_alpha_fit(e.h, ctypes.byref(dp), n_cand, None if prs is None else prs.ctypes.data_as(VP),
-                                         ctypes.c_double(alpha_max), *[b.ctypes.data_as(VP) if outs else None for b in bufs],
-                                         None)
-        return rc, e.lib.muxgl_last_error(e.h)
-
-    def refused(e, word, **kw):
-        rc, why = raw(e, **kw)
-        assert rc != 0 and word in why, (kw, why)
-
     with muxgl.Engine(devs, muxgl.FLAG_DEMUX_ONLY) as e:
-        def still_good():
-            assert same(e.demux_alpha_fit(G2, pairs, 1.0), fresh)
-
-        refused(e, b"pileup")
+        refused, still_good = suite.refusal_frame(CALL, e, (G2,), pairs, 1.0, fresh, named=False)
+        refused(b"pileup")
         e.set_pileup(p.S, p.cell_ptr, p.entry_snp, p.entry_rptr, p.reads)
-        refused(e, b"GP tensor")
+        refused(b"GP tensor")
         e.demux_set_gp(p.gp, p.has_gp)
         still_good()
-        refused(e, b"every output is NULL", outs=False)
-        still_good()
-        refused(e, b"pair is NULL", prs=None)
-        still_good()
-        for n_cand in (0, 17, -1):
-            refused(e, b"n_cand", n_cand=n_cand)
+        suite.common_refusals(CALL, refused, still_good, pairs, 8)
         for n_alpha in (0, muxgl.MAX_ALPHA + 1):
-            refused(e, b"n_alpha", n_alpha=n_alpha)
+            refused(b"n_alpha", n_alpha=n_alpha)
         still_good()
-        for bad in (0.0, -0.1, 1.5, float("nan"), float("inf")):
-            refused(e, b"alpha_max", alpha_max=bad)
-        still_good()
-        for bad in (-2, 8, 1 << 20):
-            for t in (0, 1):
-                q = pairs.copy()
-                q[2, 1, t] = bad
-                refused(e, f"pair[2][1][{t}]".encode(), prs=q)
-            still_good()
         for t in (0, 1):
             q = pairs.copy()
             q[3, 0, t] = -1
-            refused(e, b"exactly one negative index", prs=q)
+            refused(b"exactly one negative index", slots=q)
             still_good()
         with pytest.raises(ValueError):
             e.demux_alpha_fit(G2, pairs[:-1])

@@ -9,43 +9,42 @@ The posteriors of the shape tests are handed in: the clusters are set from the t
 panel's genotypes (muxgl_fmx_set_anchors), and one E-step runs; the restatement reads the posteriors that E-step read
 (muxgl_fmx_get_cluster_gp).
 
-Bars (check_fit), the project's own (tests/test_fmx_ambient_fit_gpu.py): ll_hat, ll_zero, ll_top within parity.LL_TOL; info and
-the implied LL' (0 at an interior estimate) within 1000 x the float64-to-longdouble disagreement of the restatement on the
-case, floored at 1e-9 x the sum of absolute per-entry terms (over absolute summands where that is exactly 0); the restated
-LL at the device's estimate within 1e-9 of the LL at the restatement's; where the restated info is >= 1 the two estimates
-within 1e-6 and the statuses equal; at status 1 ll_hat == ll_zero and at status 2 ll_hat == ll_top bit for bit.  A pair with
-an element within 1e-6 relative of the 1e-6 floor at the estimate would skip the two derivative bars only; the seeds are
-such that there is none, at the device's estimate or at the restatement's, and the count is asserted to be 0."""
-import ctypes
+Bars: check_fit, tests/fit_check.py, as CALL describes this call: with ll_top, and ll_hat on a bound is ll_zero resp. ll_top
+bit for bit on every slot; status 6 and no NaN.  A pair with an element within 1e-6 relative of the 1e-6 floor at the
+estimate would skip the two derivative bars only; the seeds are such that there is none, at the device's estimate or at the
+restatement's, and the count is asserted to be 0.  The bodies shared with the other three fits: tests/fit_suite.py."""
 import functools
 
 import numpy as np
 import pytest
 
 import fmx_alpha_fit_ref as far
-import fmx_fit_check
+import fit_check
+import fit_suite as suite
 import parity
 from popscle_amd import freemuxlet, muxgl, synth
 from test_fmx_alpha_fit import check_clean, check_mixed, oracle_case
 from test_fmx_ambient_fit_gpu import ready, small_case
-from test_fmx_singlets_gpu import _clust_buffer, _local_allgather, prepared, spread_init
+from test_fmx_singlets_gpu import prepared, spread_init
 
 pytestmark = pytest.mark.gpu
 
 XE = muxgl.FLAG_FORCE_STREAMED_ESTEP
 FIELDS = muxgl.Engine.ALPHA_FIT_FIELDS
-
-
-def same(a, b, fields=FIELDS):
-    return all(a[k].tobytes() == b[k].tobytes() for k in fields)
+CALL = fit_check.Call(
+    name="fmx alpha fit", share="alpha", fields=FIELDS, width=2, top=True, fit=far.fit,
+    closing="{on_kink} on a kink, mean n_steps {mean:.2f}", nearest=True, kink_at_ref=True, kink_frac=0.0, no_nan=True,
+    bounds_everywhere=True,
+    method="fmx_alpha_fit", x_name="alpha_max", slot_name="pair", extra=("pair", "alpha_max"),
+    subsets=(("alpha_hat",), ("status", "n_steps"), ("info", "ll_zero"), ("ll_top",), ("ll_hat", "n_steps", "alpha_hat")),
+    x_identity=0.87)
+same = functools.partial(suite.same, CALL)
 
 
 def check_fit(p, q, pair, alpha_max, got, what, pairs=None, ll_tol=parity.LL_TOL):
-    """every bar of the module's docstring (fmx_fit_check.check_fit, with ll_top and no slot on a kink) on the (droplet,
-    slot) pairs of `pairs` (None: all); returns the number of interior fits and of those with restated info >= 1"""
-    return fmx_fit_check.check_fit("fmx alpha fit", "alpha", FIELDS, lambda c, j, k: far.fit(p, q, c, j, k, alpha_max),
-                                   top=True, kink_at_ref=True, kink_frac=0.0, C=p.C, slots=pair, x_max=alpha_max, got=got,
-                                   what=what, pairs=pairs, ll_tol=ll_tol)
+    """every bar of fit_check.check_fit on the (droplet, slot) pairs of `pairs` (None: all); returns the number of interior
+    fits and of those with restated info >= 1"""
+    return fit_check.check_fit(CALL, (p, q), pair, alpha_max, got, what, pairs, ll_tol)
 
 
 # ---- 1. parity and optimality over the shapes, and the mirror -----------------------------------------------------------------
@@ -100,11 +99,10 @@ def test_sixteen_slots_with_skips_repeats_wrong_pairs_and_a_cap():
         got = e.fmx_alpha_fit(pair, 0.8)
         one = e.fmx_alpha_fit(np.ascontiguousarray(pair[:, :1]), 0.8)                    # n_cand = 1
         two = e.fmx_alpha_fit(np.ascontiguousarray(pair[:, 5:7]), 0.8)                   # n_cand = 2
-    check_fit(p, q, pair, 0.8, got, "16 slots")
-    assert all(got[k][:, 3].tobytes() == got[k][:, 0].tobytes() for k in FIELDS)
+    suite.sixteen_slots(CALL, (p, q), pair, 0.8, got, "16 slots")
     assert all(one[k].tobytes() == np.ascontiguousarray(got[k][:, :1]).tobytes() for k in FIELDS)
     assert all(two[k].tobytes() == np.ascontiguousarray(got[k][:, 5:7]).tobytes() for k in FIELDS)
-    assert (got["status"][:, 7] == 4).all() and (got["status"][0] >= 4).all()           # skipped slots; the empty droplet
+    assert (got["status"][0] >= 4).all()                                                 # the empty droplet
     assert (got["alpha_hat"] <= 0.8).all() and (got["status"][1:, 5] <= 2).all()
 
 
@@ -170,18 +168,7 @@ def test_droplets_without_entries_and_zero_cells():
         got = e.fmx_alpha_fit(np.array([[[0, 1], [-1, -1]], [[1, 2], [2, 2]], [[3, 0], [3, 3]], [[-1, -1], [0, 2]]], dtype=np.int32))
     assert got["status"][[1, 3]].tolist() == [[5, 5], [4, 5]] and got["status"][0, 1] == 4
     assert all(not got[k][[1, 3]].any() for k in FIELDS if k != "status")
-    with muxgl.Engine(0) as e:                                                           # C == 0: succeeds and writes nothing
-        e.set_pileup(p.S, np.zeros(1, np.int64), np.zeros(0, np.int32), np.zeros(1, np.int64), np.zeros(0, np.uint8))
-        e.fmx_prepare(p.af)
-        e.fmx_set_clusters(K, np.zeros(0, np.int32))
-        e.fmx_iterate(0.5, 0.1)
-        got = e.fmx_alpha_fit(np.zeros((0, 2, 2), np.int32))
-        assert got["alpha_hat"].shape == (0, 2) and got["kernel_ms"] == 0.0
-        VP = ctypes.c_void_p
-        canary = np.full(4, 7.0)
-        assert e.lib.muxgl_fmx_alpha_fit(e.h, 2, np.zeros(4, np.int32).ctypes.data_as(VP), ctypes.c_double(1.0),
-                                         canary.ctypes.data_as(VP), *[None] * 7) == 0
-        assert (canary == 7.0).all()
+    suite.fmx_zero_cells(CALL, p, K, ())
 
 
 # ---- 4. what the feature is for --------------------------------------------------------------------------------------------
@@ -241,25 +228,9 @@ def identity_case(K, C=30):
 def test_call_to_call_budget_permutation_split_and_null_outputs(monkeypatch):
     K = 24
     p, pair, init, want, _cells = identity_case(K)
-    assert (want["status"] == 0).any() and (want["status"] == 4).any()
     monkeypatch.delenv("MUXGL_FMX_SLAB_MB", raising=False)
-    with prepared(p) as e:
-        e.fmx_set_clusters(K, init)
-        for _ in range(2):
-            e.fmx_iterate(0.5, 0.1)
-        assert same(e.fmx_alpha_fit(pair, 0.87), want) and same(e.fmx_alpha_fit(pair, 0.87), want)
-        perm = np.random.default_rng(1).permutation(16)
-        got = e.fmx_alpha_fit(np.ascontiguousarray(pair[:, perm]), 0.87)
-        assert same(got, {k: np.ascontiguousarray(want[k][:, perm]) for k in FIELDS})
-        lo = e.fmx_alpha_fit(np.ascontiguousarray(pair[:, :8]), 0.87)
-        hi = e.fmx_alpha_fit(np.ascontiguousarray(pair[:, 8:]), 0.87)
-        assert same({k: np.concatenate([lo[k], hi[k]], axis=1) for k in FIELDS}, want)
-        twice = e.fmx_alpha_fit(np.ascontiguousarray(np.repeat(pair[:, :8], 2, axis=1)), 0.87)   # every pair twice
-        assert same({k: np.ascontiguousarray(twice[k][:, ::2]) for k in FIELDS}, lo)
-        assert same({k: np.ascontiguousarray(twice[k][:, 1::2]) for k in FIELDS}, lo)
-        for sub in (("alpha_hat",), ("status", "n_steps"), ("info", "ll_zero"), ("ll_top",), ("ll_hat", "n_steps", "alpha_hat")):
-            got = e.fmx_alpha_fit(pair, 0.87, want=sub)
-            assert set(got) == set(sub) | {"kernel_ms", "pair", "alpha_max"} and same(got, want, sub)
+    with suite.fmx_iterated(p, K, init) as e:
+        suite.identity(CALL, e, (), pair, want)
         for mb in ("1", "64"):
             monkeypatch.setenv("MUXGL_FMX_SLAB_MB", mb)                                   # (not read by the call)
             assert same(e.fmx_alpha_fit(pair, 0.87), want)
@@ -269,55 +240,17 @@ def test_call_to_call_budget_permutation_split_and_null_outputs(monkeypatch):
 @pytest.mark.parametrize("K", [24, 300])
 def test_device_groups(K):
     p, pair, init, want, cells = identity_case(K)
-    for devs in ([0, 0], [0, 0, 0]):
-        with prepared(p, devs) as e:
-            e.fmx_set_clusters(K, init)
-            for _ in range(2):
-                gcells, _st = e.fmx_iterate(0.5, 0.1)
-            got = e.fmx_alpha_fit(pair, 0.87)
-        parity.same_records(gcells, cells)
-        assert same(got, want) and got["kernel_ms"] > 0.0, devs
+    suite.device_groups(CALL, lambda devs, flags: suite.fmx_iterated(p, K, init, devs, flags, cells), (), pair, want)
 
 
 @pytest.mark.parametrize("K,world,flags", [(20, 2, 0), (300, 3, 0)])
 def test_slabbed_ranks_and_the_sharded_driver(K, world, flags):
-    """every rank holds its two slabs (freemuxlet.load_rank) and fits its own cells; the exchanges of the driver are device
-    copies between the handles here (as in test_fmx_ambient_fit_gpu.py).  The ranks' outputs, concatenated, are the one-handle
-    outputs bit for bit; and run_em(want_alpha_fit=...) returns them for the pairs of call_pairs()."""
-    import torch
-
+    """suite.fmx_slabbed_ranks: the ranks' outputs, concatenated, are the one-handle outputs bit for bit; and
+    run_em(want_alpha_fit=...) returns them for the pairs of call_pairs()."""
     p, pair, init, want, cells = identity_case(K, C=36)
-    (c_ranges, per_c), (s_ranges, per_s) = freemuxlet.plan_ranges(p.C, p.S, world)
-    engs = [muxgl.Engine(0, flags) for _ in range(world)]
-    for r, e in enumerate(engs):
-        freemuxlet.load_rank(e, p, c_ranges[r], s_ranges[r])
-        e.fmx_set_clusters(K, init)
-    for it in range(2):
-        for e in engs:
-            e.fmx_iter_gp(0.5, 0.1)
-        torch.cuda.synchronize()
-        _local_allgather(engs, muxgl.BUF_CGP, per_s, p.S, K * 3 * 8)
-        torch.cuda.synchronize()
-        for e in engs:
-            e.fmx_iter_estep(0.5, 0.1)
-        for e in engs:
-            e.fmx_iter_fetch()
-        if sum(e.fmx_exact_pending() for e in engs) > 0:
-            freemuxlet.settle_near_ties(engs, lambda obj: [obj], 0.5, 0.1)
-        torch.cuda.synchronize()
-        _local_allgather(engs, muxgl.BUF_CLUST, per_c, p.C, 4)
-        torch.cuda.synchronize()
-        for e in engs:
-            e.fmx_iter_mstep()
-    parts = [e.fmx_alpha_fit(np.ascontiguousarray(pair[c_ranges[r][0]:c_ranges[r][1]]), 0.87) for r, e in enumerate(engs)]
-    for e in engs:
-        e.close()
-    assert same({k: np.concatenate([x[k] for x in parts]) for k in FIELDS}, want)
+    suite.fmx_slabbed_ranks(CALL, p, K, world, flags, init, (), pair, want)
     slots = freemuxlet.call_pairs(cells)
-    with prepared(p) as e:
-        e.fmx_set_clusters(K, init)
-        for _ in range(2):
-            e.fmx_iterate(0.5, 0.1)
+    with suite.fmx_iterated(p, K, init) as e:
         direct = e.fmx_alpha_fit(slots, 0.87)
     with prepared(p) as e:
         out, hist, got = freemuxlet.run_em(e, K, init, max_iter=2, early_stop=False, want_alpha_fit=(0.87,))
@@ -332,36 +265,11 @@ def test_records_tables_pileups_and_timing_slots_stay(anchored):
     K = 6
     p, who, pool = small_case(K, seed=10200, entries=(40, 0, 90, 300, 7, 130, 64, 33, 2100, 12), S=2500)
     pair = drawn_pairs(np.random.default_rng(3), p.C, K, 3)
-    with prepared(p) as e:
-        if anchored:
-            e.demux_set_gp(p.gp, p.has_gp)
-        e.fmx_set_clusters(K, who)
-        if anchored:
-            e.fmx_set_anchors([0, 1, 2], None if anchored == "held" else [muxgl.ANCHOR_PRIOR, muxgl.ANCHOR_HELD, muxgl.ANCHOR_PRIOR])
-        e.fmx_iterate(0.5, 0.1)
-        e.fmx_iter_gp(0.5, 0.1)
-        e.fmx_iter_estep(0.5, 0.1)
+    def tables(e):
+        amb = e.fmx_ambient_fit(pool, np.ascontiguousarray(pair[:, :, 0]), 0.5)
+        return e.fmx_ambient(pool, (0.0, 0.1, 0.5))["ll"].tobytes(), tuple(amb[n].tobytes() for n in muxgl.Engine.AMBIENT_FIT_FIELDS)
 
-        def state():
-            cells, st, full = e.fmx_iter_fetch(want_full_ll=True)
-            unk = e.fmx_unknown()
-            amb = e.fmx_ambient_fit(pool, np.ascontiguousarray(pair[:, :, 0]), 0.5)
-            return (cells.tobytes(), tuple(st), full.tobytes(), e.fmx_singlets().tobytes(),
-                    e.fmx_ambient(pool, (0.0, 0.1, 0.5))["ll"].tobytes(),
-                    tuple(amb[n].tobytes() for n in muxgl.Engine.AMBIENT_FIT_FIELDS),
-                    tuple(unk[n].tobytes() for n in muxgl.FMX_UNKNOWN_FIELDS), tuple(x.tobytes() for x in e.fmx_cluster_pileup()),
-                    e.fmx_cluster_gp().tobytes(), _clust_buffer(e).tobytes())
-
-        s0 = state()
-        t0, (sum0, calls0) = e.timing().copy(), e.timing_sum()
-        a = e.fmx_alpha_fit(pair, 1.0)
-        e.fmx_alpha_fit(pair[:, :1], 0.25)
-        sum1, calls1 = e.timing_sum()
-        assert np.array_equal(e.timing(), t0) and np.array_equal(sum1, sum0) and calls1 == calls0   # every timing slot
-        assert state() == s0
-        e.fmx_iter_mstep()
-        assert same(e.fmx_alpha_fit(pair, 1.0), a)                        # behind the M-step: the same posteriors
-        assert (a["status"] == 0).any()
+    suite.fmx_state_stays(CALL, p, K, who, anchored, (), pair, 1.0, tables)
 
 
 @pytest.mark.parametrize("K,devs,flags", [(6, 0, 0), (40, 0, XE), (300, 0, 0), (24, [0, 0], 0)])
@@ -369,24 +277,7 @@ def test_the_call_leaves_the_em_alone(K, devs, flags):
     p = synth.make_pileup(300, 500, 4, seed=10300 + K, mean_entries=10, min_entries=2, reads_lambda=0.3, with_gp=False)
     init = (np.arange(p.C) % 3).astype(np.int32)
     pair = drawn_pairs(np.random.default_rng(K), p.C, K, 2)
-
-    def run(with_call):
-        out = []
-        with prepared(p, devs, flags) as e:
-            e.fmx_set_clusters(K, init)
-            for _ in range(4):
-                cells, st = e.fmx_iterate(0.5, 0.1)   # the twin handle never makes the call
-                if with_call:
-                    sng, t0 = e.fmx_singlets(), e.timing().copy()
-                    e.fmx_alpha_fit(pair, 1.0)
-                    assert np.array_equal(e.timing(), t0)
-                    assert e.fmx_singlets().tobytes() == sng.tobytes()   # the other table calls, before and after
-                    e.fmx_unknown()
-                    e.fmx_inclusion(0.5)
-                out.append((cells.tobytes(), tuple(st), tuple(x.tobytes() for x in e.fmx_cluster_pileup()), e.fmx_exact_stats()))
-        return out
-
-    assert run(False) == run(True)
+    suite.fmx_em_alone(CALL, p, K, devs, flags, init, (), pair, 1.0)
 
 
 # ---- 7. refusals ---------------------------------------------------------------------------------------------------------
@@ -398,53 +289,23 @@ def test_refusals_leave_the_handle_usable(devs):
     pair = np.stack([np.stack([who, (who + 3) % K], axis=1), np.stack([who, who], axis=1)], axis=1).astype(np.int32)
     with ready(p, K, who, devs) as e:
         fresh = e.fmx_alpha_fit(pair, 1.0)
-    VP = ctypes.c_void_p
-
-    def raw(e, n_cand=2, prs=pair, alpha_max=1.0, outs=True):
-        shape = pair.shape[:2]
-        bufs = [np.zeros(shape) for _ in range(5)] + [np.zeros(shape, np.int32), np.zeros(shape, np.int32)]
-        rc = e.lib.muxgl_fmx_alpha_fit(e.h, n_cand, None if prs is None else prs.ctypes.data_as(VP), ctypes.c_double(alpha_max),
-                                       *[b.ctypes.data_as(VP) if outs else None for b in bufs], None)
-        return rc, e.lib.muxgl_last_error(e.h)
-
-    def refused(e, word, **kw):
-        rc, why = raw(e, **kw)
-        assert rc != 0 and why.startswith(b"muxgl_fmx_alpha_fit: ") and word in why, (kw, why)
-
     with muxgl.Engine(devs) as e:
-        def still_good():
-            assert same(e.fmx_alpha_fit(pair, 1.0), fresh)
-
-        refused(e, b"no pileup")
+        refused, still_good = suite.refusal_frame(CALL, e, (), pair, 1.0, fresh, named=True)
+        refused(b"no pileup")
         e.set_pileup(p.S, p.cell_ptr, p.entry_snp, p.entry_rptr, p.reads)
-        refused(e, b"muxgl_fmx_prepare")
+        refused(b"muxgl_fmx_prepare")
         e.fmx_prepare(p.af)
-        refused(e, b"E-step")
+        refused(b"E-step")
         e.fmx_set_clusters(K, who)
-        refused(e, b"no E-step since muxgl_fmx_set_clusters")
+        refused(b"no E-step since muxgl_fmx_set_clusters")
         e.fmx_iterate(0.5, 0.1)
         still_good()
-        refused(e, b"every output is NULL", outs=False)
-        still_good()
-        refused(e, b"pair is NULL", prs=None)
-        still_good()
-        for n_cand in (0, 17, -1):
-            refused(e, b"n_cand", n_cand=n_cand)
-        still_good()
-        for bad in (0.0, -0.1, 1.5, float("nan"), float("inf")):
-            refused(e, b"alpha_max", alpha_max=bad)
-        still_good()
-        for bad in (-2, K, 1 << 20):
-            for t in (0, 1):
-                c2 = pair.copy()
-                c2[2, 1, t] = bad
-                refused(e, f"pair[2][1][{t}]".encode(), prs=c2)
-            still_good()
+        suite.common_refusals(CALL, refused, still_good, pair, K)
         for t in (0, 1):
             c2 = pair.copy()
             c2[3, 0, t] = -1
-            refused(e, b"pair[3][0] ", prs=c2)
-            refused(e, b"exactly one negative index", prs=c2)
+            refused(b"pair[3][0] ", slots=c2)
+            refused(b"exactly one negative index", slots=c2)
         still_good()
         with pytest.raises(ValueError):
             e.fmx_alpha_fit(pair[:-1])
@@ -452,8 +313,8 @@ def test_refusals_leave_the_handle_usable(devs):
             e.fmx_alpha_fit(pair[:, :, :1])
         if devs == 0:                    # (the phases run on a one-device handle)
             e.fmx_iter_gp(0.5, 0.1)      # the posteriors of the NEXT iteration
-            refused(e, b"the cluster posteriors were rewritten")
+            refused(b"the cluster posteriors were rewritten")
         e.fmx_set_clusters(K, who)       # fresh clusters: the fit of the old ones is gone
-        refused(e, b"no E-step since muxgl_fmx_set_clusters")
+        refused(b"no E-step since muxgl_fmx_set_clusters")
         e.fmx_iterate(0.5, 0.1)
         still_good()

@@ -8,13 +8,9 @@ The posteriors of the shape tests are handed in: the clusters are set from the t
 panel's genotypes (muxgl_fmx_set_anchors), and one E-step runs; the restatement reads the posteriors that E-step read
 (muxgl_fmx_get_cluster_gp).
 
-Bars (check_fit): ll_hat, ll_zero within parity.LL_TOL; info and the implied LL' (0 at an interior estimate) within 1000 x
-the float64-to-longdouble disagreement of the restatement on the case, floored at 1e-9 x the sum of absolute per-entry
-terms (over absolute summands where that is exactly 0); the restated LL at the device's estimate within 1e-9 of the LL at
-the restatement's; where the restated info is >= 1 the two estimates within 1e-6 and the statuses equal.  A pair with an
-element within 1e-6 relative of the 1e-6 floor at the device's rho_hat sits on a kink of LL' in one precision and beside it
-in the other: it skips the two derivative bars only, and such pairs may be at most 1 % of the fitted ones."""
-import ctypes
+Bars: check_fit, tests/fit_check.py, as CALL describes this call: no ll_top; status 6 and no NaN; a pair with an element
+within 1e-6 relative of the 1e-6 floor at the device's rho_hat skips the two derivative bars only, and such pairs may be at
+most 1 % of the checked ones.  The bodies shared with the other three fits: tests/fit_suite.py."""
 import functools
 
 import numpy as np
@@ -22,31 +18,31 @@ import pytest
 
 import ambient_ref as ar
 import fmx_ambient_fit_ref as ffr
-import fmx_fit_check
+import fit_check
+import fit_suite as suite
 import fmx_ambient_ref as fr
 import parity
 from popscle_amd import freemuxlet, muxgl, synth
 from test_fmx_ambient_fit import check_soup_fits
-from test_fmx_singlets_gpu import _clust_buffer, _local_allgather, prepared, spread_init
+from test_fmx_singlets_gpu import prepared, spread_init
 
 pytestmark = pytest.mark.gpu
 
 XE = muxgl.FLAG_FORCE_STREAMED_ESTEP
 DEFAULT_RHOS = fr.DEFAULT_RHOS
 FIELDS = muxgl.Engine.AMBIENT_FIT_FIELDS
-
-
-def same(a, b, fields=FIELDS):
-    return all(a[k].tobytes() == b[k].tobytes() for k in fields)
+CALL = fit_check.Call(
+    name="fmx ambient fit", share="rho", fields=FIELDS, width=1, top=False, fit=ffr.fit,
+    closing="{on_kink} on a kink, mean n_steps {mean:.2f}", nearest=True, kink_frac=0.01, no_nan=True,
+    method="fmx_ambient_fit", amb_af=True, x_name="rho_max", slot_name="cand",
+    subsets=(("rho_hat",), ("status", "n_steps"), ("info", "ll_zero"), ("ll_hat", "n_steps", "rho_hat")), x_identity=0.37)
+same = functools.partial(suite.same, CALL)
 
 
 def check_fit(p, q, f, cand, rho_max, got, what, pairs=None, ll_tol=parity.LL_TOL):
-    """every bar of the module's docstring (fmx_fit_check.check_fit, without ll_top, at most 1 % of the slots on a kink) on
-    the (droplet, slot) pairs of `pairs` (None: all); returns the number of interior fits and of those with restated
-    info >= 1"""
-    return fmx_fit_check.check_fit("fmx ambient fit", "rho", FIELDS, lambda c, j: ffr.fit(p, q, f, c, j, rho_max),
-                                   top=False, kink_at_ref=False, kink_frac=0.01, C=p.C, slots=cand, x_max=rho_max, got=got,
-                                   what=what, pairs=pairs, ll_tol=ll_tol)
+    """every bar of fit_check.check_fit on the (droplet, slot) pairs of `pairs` (None: all); returns the number of interior
+    fits and of those with restated info >= 1"""
+    return fit_check.check_fit(CALL, (p, q, f), cand, rho_max, got, what, pairs, ll_tol)
 
 
 def ready(p, K, init, devs=0, flags=0, anchors=None, modes=None, ge=0.1):
@@ -99,9 +95,8 @@ def test_sixteen_candidates_with_skips_and_repeats():
     with ready(p, K, who, anchors=list(range(K))) as e:
         q = e.fmx_cluster_gp()
         got = e.fmx_ambient_fit(pool, cand, 0.4)
-    check_fit(p, q, pool, cand, 0.4, got, "16 candidates")
-    assert all(got[k][:, 3].tobytes() == got[k][:, 0].tobytes() for k in FIELDS)
-    assert (got["status"][:, 7] == 4).all() and (got["status"][0] >= 4).all()           # skipped slots; the empty droplet
+    suite.sixteen_slots(CALL, (p, q, pool), cand, 0.4, got, "16 candidates")
+    assert (got["status"][0] >= 4).all()                                                 # the empty droplet
 
 
 def test_a_zeroed_posterior_row_gives_status_6_and_no_nan():
@@ -144,18 +139,7 @@ def test_zero_cells():
     """C == 0: the call succeeds and writes nothing"""
     K = 4
     p, who, pool = small_case(K, seed=9, entries=(3, 0, 70, 0))
-    with muxgl.Engine(0) as e:
-        e.set_pileup(p.S, np.zeros(1, np.int64), np.zeros(0, np.int32), np.zeros(1, np.int64), np.zeros(0, np.uint8))
-        e.fmx_prepare(p.af)
-        e.fmx_set_clusters(K, np.zeros(0, np.int32))
-        e.fmx_iterate(0.5, 0.1)
-        got = e.fmx_ambient_fit(pool, np.zeros((0, 2), np.int32))
-        assert got["rho_hat"].shape == (0, 2) and got["kernel_ms"] == 0.0
-        VP = ctypes.c_void_p
-        canary = np.full(4, 7.0)
-        assert e.lib.muxgl_fmx_ambient_fit(e.h, pool.ctypes.data_as(VP), 2, np.zeros(2, np.int32).ctypes.data_as(VP),
-                                           ctypes.c_double(0.5), canary.ctypes.data_as(VP), *[None] * 6) == 0
-        assert (canary == 7.0).all()
+    suite.fmx_zero_cells(CALL, p, K, (pool,))
 
 
 # ---- 2. consistency with the existing calls ------------------------------------------------------------------------------
@@ -252,25 +236,9 @@ def identity_case(K, C=30):
 def test_call_to_call_budget_permutation_split_and_null_outputs(monkeypatch):
     K = 24
     p, f, cand, init, want, _cells = identity_case(K)
-    assert (want["status"] == 0).any() and (want["status"] == 4).any()
     monkeypatch.delenv("MUXGL_FMX_SLAB_MB", raising=False)
-    with prepared(p) as e:
-        e.fmx_set_clusters(K, init)
-        for _ in range(2):
-            e.fmx_iterate(0.5, 0.1)
-        assert same(e.fmx_ambient_fit(f, cand, 0.37), want) and same(e.fmx_ambient_fit(f, cand, 0.37), want)
-        perm = np.random.default_rng(1).permutation(16)
-        got = e.fmx_ambient_fit(f, np.ascontiguousarray(cand[:, perm]), 0.37)
-        assert same(got, {k: np.ascontiguousarray(want[k][:, perm]) for k in FIELDS})
-        lo = e.fmx_ambient_fit(f, np.ascontiguousarray(cand[:, :8]), 0.37)
-        hi = e.fmx_ambient_fit(f, np.ascontiguousarray(cand[:, 8:]), 0.37)
-        assert same({k: np.concatenate([lo[k], hi[k]], axis=1) for k in FIELDS}, want)
-        twice = e.fmx_ambient_fit(f, np.ascontiguousarray(np.repeat(cand[:, :8], 2, axis=1)), 0.37)   # every candidate twice
-        assert same({k: np.ascontiguousarray(twice[k][:, ::2]) for k in FIELDS}, lo)
-        assert same({k: np.ascontiguousarray(twice[k][:, 1::2]) for k in FIELDS}, lo)
-        for sub in (("rho_hat",), ("status", "n_steps"), ("info", "ll_zero"), ("ll_hat", "n_steps", "rho_hat")):
-            got = e.fmx_ambient_fit(f, cand, 0.37, want=sub)
-            assert set(got) == set(sub) | {"kernel_ms"} and same(got, want, sub)
+    with suite.fmx_iterated(p, K, init) as e:
+        suite.identity(CALL, e, (f,), cand, want)
         for mb in ("1", "64"):
             monkeypatch.setenv("MUXGL_FMX_SLAB_MB", mb)                                   # (not read by the call)
             assert same(e.fmx_ambient_fit(f, cand, 0.37), want)
@@ -280,54 +248,16 @@ def test_call_to_call_budget_permutation_split_and_null_outputs(monkeypatch):
 @pytest.mark.parametrize("K", [24, 300])
 def test_device_groups(K):
     p, f, cand, init, want, cells = identity_case(K)
-    for devs in ([0, 0], [0, 0, 0]):
-        with prepared(p, devs) as e:
-            e.fmx_set_clusters(K, init)
-            for _ in range(2):
-                gcells, _st = e.fmx_iterate(0.5, 0.1)
-            got = e.fmx_ambient_fit(f, cand, 0.37)
-        parity.same_records(gcells, cells)
-        assert same(got, want) and got["kernel_ms"] > 0.0, devs
+    suite.device_groups(CALL, lambda devs, flags: suite.fmx_iterated(p, K, init, devs, flags, cells), (f,), cand, want)
 
 
 @pytest.mark.parametrize("K,world,flags", [(20, 2, 0), (300, 3, 0)])
 def test_slabbed_ranks_and_the_sharded_driver(K, world, flags):
-    """every rank holds its two slabs (freemuxlet.load_rank) and fits its own cells; the exchanges of the driver are device
-    copies between the handles here (as in test_fmx_ambient_gpu.py).  The ranks' outputs, concatenated, are the one-handle
-    outputs bit for bit; and run_em(want_ambient_fit=...) returns them for the best clusters of the singlet table."""
-    import torch
-
+    """suite.fmx_slabbed_ranks: the ranks' outputs, concatenated, are the one-handle outputs bit for bit; and
+    run_em(want_ambient_fit=...) returns them for the best clusters of the singlet table."""
     p, f, cand, init, want, cells = identity_case(K, C=36)
-    (c_ranges, per_c), (s_ranges, per_s) = freemuxlet.plan_ranges(p.C, p.S, world)
-    engs = [muxgl.Engine(0, flags) for _ in range(world)]
-    for r, e in enumerate(engs):
-        freemuxlet.load_rank(e, p, c_ranges[r], s_ranges[r])
-        e.fmx_set_clusters(K, init)
-    for it in range(2):
-        for e in engs:
-            e.fmx_iter_gp(0.5, 0.1)
-        torch.cuda.synchronize()
-        _local_allgather(engs, muxgl.BUF_CGP, per_s, p.S, K * 3 * 8)
-        torch.cuda.synchronize()
-        for e in engs:
-            e.fmx_iter_estep(0.5, 0.1)
-        for e in engs:
-            e.fmx_iter_fetch()
-        if sum(e.fmx_exact_pending() for e in engs) > 0:
-            freemuxlet.settle_near_ties(engs, lambda obj: [obj], 0.5, 0.1)
-        torch.cuda.synchronize()
-        _local_allgather(engs, muxgl.BUF_CLUST, per_c, p.C, 4)
-        torch.cuda.synchronize()
-        for e in engs:
-            e.fmx_iter_mstep()
-    parts = [e.fmx_ambient_fit(f, np.ascontiguousarray(cand[c_ranges[r][0]:c_ranges[r][1]]), 0.37) for r, e in enumerate(engs)]
-    for e in engs:
-        e.close()
-    assert same({k: np.concatenate([x[k] for x in parts]) for k in FIELDS}, want)
-    with prepared(p) as e:
-        e.fmx_set_clusters(K, init)
-        for _ in range(2):
-            e.fmx_iterate(0.5, 0.1)
+    suite.fmx_slabbed_ranks(CALL, p, K, world, flags, init, (f,), cand, want)
+    with suite.fmx_iterated(p, K, init) as e:
         top = freemuxlet.top_clusters(e.fmx_singlets(), 3)
         direct = e.fmx_ambient_fit(f, top, 0.37)
     with prepared(p) as e:
@@ -342,33 +272,7 @@ def test_records_tables_pileups_and_timing_slots_stay(anchored):
     K = 6
     p, who, pool = small_case(K, seed=10200, entries=(40, 0, 90, 300, 7, 130, 64, 33, 2100, 12), S=2500)
     cand = np.random.default_rng(3).integers(-1, K, size=(p.C, 3)).astype(np.int32)
-    with prepared(p) as e:
-        if anchored:
-            e.demux_set_gp(p.gp, p.has_gp)
-        e.fmx_set_clusters(K, who)
-        if anchored:
-            e.fmx_set_anchors([0, 1, 2], None if anchored == "held" else [muxgl.ANCHOR_PRIOR, muxgl.ANCHOR_HELD, muxgl.ANCHOR_PRIOR])
-        e.fmx_iterate(0.5, 0.1)
-        e.fmx_iter_gp(0.5, 0.1)
-        e.fmx_iter_estep(0.5, 0.1)
-
-        def state():
-            cells, st, full = e.fmx_iter_fetch(want_full_ll=True)
-            unk = e.fmx_unknown()
-            return (cells.tobytes(), tuple(st), full.tobytes(), e.fmx_singlets().tobytes(), e.fmx_ambient(pool, DEFAULT_RHOS)["ll"].tobytes(),
-                    tuple(unk[n].tobytes() for n in muxgl.FMX_UNKNOWN_FIELDS), tuple(x.tobytes() for x in e.fmx_cluster_pileup()),
-                    e.fmx_cluster_gp().tobytes(), _clust_buffer(e).tobytes())
-
-        s0 = state()
-        t0, (sum0, calls0) = e.timing().copy(), e.timing_sum()
-        a = e.fmx_ambient_fit(pool, cand, 0.5)
-        e.fmx_ambient_fit(pool, cand[:, :1], 0.25)
-        sum1, calls1 = e.timing_sum()
-        assert np.array_equal(e.timing(), t0) and np.array_equal(sum1, sum0) and calls1 == calls0   # every timing slot
-        assert state() == s0
-        e.fmx_iter_mstep()
-        assert same(e.fmx_ambient_fit(pool, cand, 0.5), a)                # behind the M-step: the same posteriors
-        assert (a["status"] == 0).any()
+    suite.fmx_state_stays(CALL, p, K, who, anchored, (pool,), cand, 0.5, lambda e: e.fmx_ambient(pool, DEFAULT_RHOS)["ll"].tobytes())
 
 
 @pytest.mark.parametrize("K,devs,flags", [(6, 0, 0), (40, 0, XE), (300, 0, 0), (24, [0, 0], 0)])
@@ -377,24 +281,7 @@ def test_the_call_leaves_the_em_alone(K, devs, flags):
     init = (np.arange(p.C) % 3).astype(np.int32)
     f = ar.draw_af(p.S, seed=K)
     cand = np.random.default_rng(K).integers(-1, K, size=(p.C, 2)).astype(np.int32)
-
-    def run(with_call):
-        out = []
-        with prepared(p, devs, flags) as e:
-            e.fmx_set_clusters(K, init)
-            for _ in range(4):
-                cells, st = e.fmx_iterate(0.5, 0.1)   # the twin handle never makes the call
-                if with_call:
-                    sng, t0 = e.fmx_singlets(), e.timing().copy()
-                    e.fmx_ambient_fit(f, cand, 0.5)
-                    assert np.array_equal(e.timing(), t0)
-                    assert e.fmx_singlets().tobytes() == sng.tobytes()   # the other table calls, before and after
-                    e.fmx_unknown()
-                    e.fmx_inclusion(0.5)
-                out.append((cells.tobytes(), tuple(st), tuple(x.tobytes() for x in e.fmx_cluster_pileup()), e.fmx_exact_stats()))
-        return out
-
-    assert run(False) == run(True)
+    suite.fmx_em_alone(CALL, p, K, devs, flags, init, (f,), cand, 0.5)
 
 
 # ---- 6. refusals ---------------------------------------------------------------------------------------------------------
@@ -407,55 +294,24 @@ def test_refusals_leave_the_handle_usable(devs):
     cand = np.stack([who, (who + 3) % K], axis=1).astype(np.int32)
     with ready(p, K, who, devs) as e:
         fresh = e.fmx_ambient_fit(f, cand, 0.5)
-    VP = ctypes.c_void_p
-
-    def raw(e, n_cand=2, cnd=cand, rho_max=0.5, outs=True, af=f):
-        bufs = [np.zeros(cand.shape), np.zeros(cand.shape), np.zeros(cand.shape), np.zeros(cand.shape),
-                np.zeros(cand.shape, np.int32), np.zeros(cand.shape, np.int32)]
-        rc = e.lib.muxgl_fmx_ambient_fit(e.h, None if af is None else af.ctypes.data_as(VP), n_cand,
-                                         None if cnd is None else cnd.ctypes.data_as(VP), ctypes.c_double(rho_max),
-                                         *[b.ctypes.data_as(VP) if outs else None for b in bufs], None)
-        return rc, e.lib.muxgl_last_error(e.h)
-
-    def refused(e, word, **kw):
-        rc, why = raw(e, **kw)
-        assert rc != 0 and why.startswith(b"muxgl_fmx_ambient_fit: ") and word in why, (kw, why)
-
     with muxgl.Engine(devs) as e:
-        def still_good():
-            assert same(e.fmx_ambient_fit(f, cand, 0.5), fresh)
-
-        refused(e, b"no pileup")
+        refused, still_good = suite.refusal_frame(CALL, e, (f,), cand, 0.5, fresh, named=True)
+        refused(b"no pileup")
         e.set_pileup(p.S, p.cell_ptr, p.entry_snp, p.entry_rptr, p.reads)
-        refused(e, b"muxgl_fmx_prepare")
+        refused(b"muxgl_fmx_prepare")
         e.fmx_prepare(p.af)
-        refused(e, b"E-step")
+        refused(b"E-step")
         e.fmx_set_clusters(K, who)
-        refused(e, b"no E-step since muxgl_fmx_set_clusters")
+        refused(b"no E-step since muxgl_fmx_set_clusters")
         e.fmx_iterate(0.5, 0.1)
         still_good()
-        refused(e, b"every output is NULL", outs=False)
-        still_good()
-        refused(e, b"cand is NULL", cnd=None)
-        refused(e, b"amb_af is NULL", af=None)
-        still_good()
-        for n_cand in (0, 17, -1):
-            refused(e, b"n_cand", n_cand=n_cand)
-        still_good()
-        for bad in (0.0, -0.1, 1.5, float("nan"), float("inf")):
-            refused(e, b"rho_max", rho_max=bad)
-        still_good()
-        for bad in (-2, K, 1 << 20):
-            c2 = cand.copy()
-            c2[2, 1] = bad
-            refused(e, b"cand[2][1]", cnd=c2)
-            still_good()
+        suite.common_refusals(CALL, refused, still_good, cand, K)
         for bad in (-0.01, 1.5, float("nan"), float("inf")):
             for s in (0, 17, p.S - 1):
                 g = f.copy()
                 g[s] = bad
                 g[min(s + 3, p.S - 1)] = bad                                             # (the first offending marker is named)
-                refused(e, f"amb_af of marker {s} ".encode(), af=g)
+                refused(f"amb_af of marker {s} ".encode(), af=g)
             still_good()
         with pytest.raises(ValueError):
             e.fmx_ambient_fit(f[:-1], cand)
@@ -463,8 +319,8 @@ def test_refusals_leave_the_handle_usable(devs):
             e.fmx_ambient_fit(f, cand[:-1])
         if devs == 0:                    # (the phases run on a one-device handle)
             e.fmx_iter_gp(0.5, 0.1)      # the posteriors of the NEXT iteration
-            refused(e, b"the cluster posteriors were rewritten")
+            refused(b"the cluster posteriors were rewritten")
         e.fmx_set_clusters(K, who)       # fresh clusters: the fit of the old ones is gone
-        refused(e, b"no E-step since muxgl_fmx_set_clusters")
+        refused(b"no E-step since muxgl_fmx_set_clusters")
         e.fmx_iterate(0.5, 0.1)
         still_good()
