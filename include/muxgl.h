@@ -419,6 +419,61 @@ int muxgl_demux_alpha_fit(muxgl_handle* h, const muxgl_demux_params* p,
                           int32_t* status, int32_t* n_steps,                                                /* [C][n_cand] or NULL */
                           float* kernel_ms);
 
+/* The usable reads of the pileup as a histogram: the number of reads per (marker, read byte) over the droplets whose byte
+ * of cell_mask is not 0 (cell_mask == NULL: over all of them), as records with keys[i] = marker * 256 + byte, strictly
+ * ascending, and counts[i] > 0; MUXGL_READ_OTHER never appears.  Every read with the same key has the same likelihood
+ * under any model of the marker, so this exact integer statistic is all muxgl_demux_soup_mix needs of the reads.
+ * Size query as muxgl_fmx_exact_snps: with keys == counts == NULL only *n is written; with room for cap records the call
+ * fails, naming the reason, when cap < *n.  A device pass over the entries (one key per usable read, a radix sort, a
+ * run-length pass; 32 bytes of device memory per usable read of the chosen droplets): integer work only, so the records
+ * are the same for any order of the droplets.  Summed per (marker, bit 7 of the byte) they are muxgl_pileup_allele_counts
+ * exactly.  Needs only muxgl_set_pileup; one device or a device group (every member counts its own droplets and the
+ * sorted lists are merged on the host with integer adds).  It reads the pileup and changes no state. */
+int muxgl_pileup_read_hist(muxgl_handle* h, const uint8_t* cell_mask /* NULL = all, or [C] */, int64_t* keys /* NULL or [cap] */,
+                           int64_t* counts /* NULL or [cap] */, int64_t cap, int64_t* n);
+
+/* The soup as a mixture of the donors: the ALT fraction of the pool's free-floating RNA at marker s is a weighted mean of
+ * the donors' genotype dosages, with shares pi that are the same at every marker -- M unknowns where the count route
+ * (muxgl_pileup_allele_counts) estimates S.  The components are the V samples of the panel and, with with_unknown != 0,
+ * component V: a donor missing from the VCF, whose genotype prior per marker is the panel mean as muxgl_demux_unknown
+ * forms it (gp0 == NULL) or the caller's gp0[S][3].  M = V + (with_unknown ? 1 : 0).  With (g0, g1, g2) = gp[s][v][0..2]:
+ *   r_v(s) = g0 + g1 / 2,   a_v(s) = g1 / 2 + g2               (rows need not sum to one)
+ *   R(s) = sum_v pi_v r_v(s),   A(s) = sum_v pi_v a_v(s)
+ *   D(s, b) = pR * R(s) + pA * A(s)       (pR, pA of read byte b from the Phred table as muxgl_demux_run takes them:
+ *                                          a REF read has pR = Mat, pA = Err / 3, an ALT read the other way round)
+ *   LL(pi) = sum over the records of n * log D
+ *   grad_v = (1 / N) * sum_s [ r_v(s) * sum_b n * pR / D + a_v(s) * sum_b n * pA / D ],   one EM step: pi'_v = pi_v * grad_v
+ * over the records (marker s, byte b, count n) of a read histogram (muxgl_pileup_read_hist) whose marker has genotypes
+ * and R(s) + A(s) > 0 at the start; N is their total count.  keys == NULL: the histogram of the handle's own pileup under
+ * cell_mask; else the caller's n_rec records (cell_mask must be NULL).  LL is concave in pi and the EM is monotone; it
+ * keeps sum pi = 1 up to rounding and is not renormalised; at the maximum grad_v == 1 where pi_v > 0 and <= 1 where
+ * pi_v == 0.  The start is pi0 divided by its sum (added in component order), or 1 / M everywhere (pi0 == NULL).
+ * For i = 0 .. n_iter_max: LL and grad at the current pi, ll[i] = LL; stop if i == n_iter_max (status 1); else step, and
+ * stop after a step with max_v |pi'_v - pi_v| <= tol (status 0): LL and grad are then taken once more at the final pi
+ * and stored in ll[i + 1].  grad and amb_af always belong to the returned pi; the unused tail of ll is NaN; n_iter = the
+ * steps taken.  n_iter_max == 0 only evaluates the start: the call is a scorer of a given pi as well.  Status 2: no
+ * record takes part; pi is the start, ll[0] and grad are 0.  amb_af[s] = A(s) / (R(s) + A(s)) at the returned pi, 0.5 at
+ * a marker without genotypes (the ambient calls do not read those) or with R + A == 0.  n_reads = N.
+ * Needs muxgl_set_pileup and muxgl_demux_set_gp, not a previous muxgl_demux_run; any V up to MUXGL_MAX_SAMPLES.  Any output
+ * may be NULL, not all.  It fails, naming the reason and leaving the handle usable: without a pileup or a GP tensor; with
+ * keys that are not strictly ascending, out of range or carry byte 0xFF; with a count <= 0; with a pi0 that has a negative
+ * or non-finite entry or sums to 0; with a gp0 entry that is negative or non-finite; with n_iter_max < 0 or tol negative
+ * or not finite; with every output NULL.  kernel_ms (NULL allowed) receives the hipEvent time between the call's first
+ * and last kernel (the 16-byte read-back of LL and the step after every iteration included).  The call reads state and
+ * changes none: records, full_ll, plans, timing slots, the cached grid and every freemuxlet state stay as they are;
+ * nothing is cached on the handle.  Device memory: the histogram, 24 bytes per active marker, one row of M doubles per
+ * 256 active markers, and [S][3] with the unknown component.  Every rounded sum has a tree fixed by the histogram and M
+ * alone: the outputs are bit-identical from call to call, for the handle's own pileup against the same histogram passed
+ * in, for any order of the droplets, on one device, on a group (one member fits, from the merged histogram) and through
+ * the sharded driver. */
+int muxgl_demux_soup_mix(muxgl_handle* h, const uint8_t* cell_mask /* NULL = all, or [C] */, int64_t n_rec,
+                         const int64_t* keys /* NULL, or [n_rec] */, const int64_t* counts /* [n_rec] with keys */,
+                         int32_t with_unknown, const double* gp0 /* NULL or [S][3] */, const double* pi0 /* NULL or [M] */,
+                         int32_t n_iter_max, double tol,
+                         double* pi /* [M] */, double* grad /* [M] */, double* ll /* [n_iter_max + 1] */,
+                         double* amb_af /* [S] */, int32_t* n_iter, int64_t* n_reads, int32_t* status,
+                         float* kernel_ms /* NULL or one float */);
+
 /* The calls rounding noise could decide, settled in the reference's own arithmetic -- HOST pass, no device work, no
  * handle (popscle_amd/host/exact_calls.hpp).  The kernels' log-likelihoods equal the reference's to ~1e-12, not to the last
  * bit, and every decision of cmd_cram_demuxlet.cpp:827-837,883-906,925-988 compares two of them.  For the cells of

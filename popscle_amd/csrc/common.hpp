@@ -278,6 +278,20 @@ struct muxgl_handle {
   int64_t ms_calls = 0;
 };
 
+// a device group behind one handle (muxgl_group.hip; soup_mix.hip walks the members for its two calls)
+struct muxgl_group {
+  int n = 0;
+  std::vector<muxgl_handle*> m;
+  std::vector<int64_t> cb, eb, sb;  // [n+1] cell, entry and SNP cuts
+  int64_t C = 0, S = 0, nnz = 0, R = 0;
+  int32_t V = 0, K = 0, n_alpha = 0;
+  bool have_pileup = false, have_cols = false, prepared = false;
+  muxgl_demux_cell* h_dcells = nullptr;  // [C] records of the last demuxlet run, in cell order
+  std::vector<hipEvent_t> ev_gp, ev_es;  // per member: posterior rows ready / assignments ready
+  float ms[MUXGL_T_COUNT] = {};
+  int32_t peer_pairs = 0, peer_enabled = 0, peer_refused = 0;  // of group_create's walk over the member pairs
+};
+
 extern thread_local std::string g_muxgl_create_error;
 
 // The anchors of muxgl_fmx_set_anchors go: with the clusters (muxgl_fmx_set_clusters, muxgl_fmx_prepare, a new pileup or

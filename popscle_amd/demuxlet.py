@@ -30,9 +30,22 @@ def call_pairs(records):
     return out
 
 
+def merge_hists(parts):
+    """(keys, counts) int64 of the read histograms `parts` (pairs of raw int64 bytes or arrays, as Engine.pileup_read_hist
+    returns them) merged: keys ascending and unique, the counts of equal keys added (integers: exact in any order)"""
+    ks = [np.frombuffer(k, dtype=np.int64) if isinstance(k, (bytes, bytearray)) else np.asarray(k, dtype=np.int64) for k, _ in parts]
+    cs = [np.frombuffer(c, dtype=np.int64) if isinstance(c, (bytes, bytearray)) else np.asarray(c, dtype=np.int64) for _, c in parts]
+    k = np.concatenate(ks) if ks else np.zeros(0, dtype=np.int64)
+    c = np.concatenate(cs) if cs else np.zeros(0, dtype=np.int64)
+    keys, inv = np.unique(k, return_inverse=True)
+    counts = np.zeros(keys.size, dtype=np.int64)
+    np.add.at(counts, inv, c)
+    return keys, counts
+
+
 def run_sharded(engine_factory, p, alphas=(0.0, 0.5), doublet_prior=0.5, exchange=None, want_singlets=False,
                 want_inclusion=False, *, want_unknown=False, want_ambient=None, want_ambient_fit=None,
-                want_alpha_fit=None):
+                want_alpha_fit=None, want_soup_mix=None):
     """engine_factory() -> object with set_pileup / demux_set_gp / demux_run (muxgl.Engine).  Returns the [C] records of
     the whole pileup on every rank, in the original cell order; with want_singlets also the [C][V] table of singlet
     log-likelihoods (Engine.demux_singlets), gathered the same way: (records, sng); with want_inclusion also the dict of
@@ -42,7 +55,10 @@ def run_sharded(engine_factory, p, alphas=(0.0, 0.5), doublet_prior=0.5, exchang
     n_top) (keyword only) also the dict of Engine.demux_ambient_fit for the n_top best samples of every droplet's row of the
     singlet table (ties to the lower index) with those candidates under "cand" ([C][n_top]); with want_alpha_fit =
     (alpha_max,) (keyword only) also the dict of Engine.demux_alpha_fit for the two pairs of call_pairs() of every droplet
-    with those pairs under "pair" ([C][2][2]), as the last element.
+    with those pairs under "pair" ([C][2][2]); with want_soup_mix = (mask or None, with_unknown, n_iter_max, tol) (keyword
+    only) also the dict of Engine.demux_soup_mix with the merged histogram under "hist", as the last element: every rank
+    counts the reads of its own droplets, the histograms are gathered and merged (np.unique and an integer add), and every
+    rank fits the same input, so all ranks hold the same bits.
     Cells are independent, so every rank fills the rows of its own cells."""
     ex = exchange or NoExchange()
     ranges = shard.cell_shards(p.cell_ptr, ex.world)
@@ -57,7 +73,7 @@ def run_sharded(engine_factory, p, alphas=(0.0, 0.5), doublet_prior=0.5, exchang
     for b, e, raw in parts:
         out[b:e] = np.frombuffer(raw, dtype=cells.dtype)
     if not want_singlets and not want_inclusion and not want_unknown and want_ambient is None and want_ambient_fit is None \
-            and want_alpha_fit is None:
+            and want_alpha_fit is None and want_soup_mix is None:
         return out
     ret = [out]
     V = p.gp.shape[1]
@@ -107,4 +123,12 @@ def run_sharded(engine_factory, p, alphas=(0.0, 0.5), doublet_prior=0.5, exchang
                 v[b:e] = np.frombuffer(raw[k], dtype=v.dtype).reshape((e - b,) + v.shape[1:])
         fit["alpha_max"] = float(alpha_max)
         ret.append(fit)
+    if want_soup_mix is not None:
+        mask, with_unknown, n_iter_max, tol = want_soup_mix
+        if mask is not None:
+            mask = np.asarray(mask)[c0:c1]
+        keys, counts = merge_hists(ex.gather_objects(tuple(a.tobytes() for a in eng.pileup_read_hist(mask))))
+        mix = eng.demux_soup_mix(hist=(keys, counts), with_unknown=with_unknown, n_iter_max=n_iter_max, tol=tol)
+        mix["hist"] = (keys, counts)
+        ret.append(mix)
     return tuple(ret)

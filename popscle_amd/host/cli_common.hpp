@@ -119,6 +119,18 @@ inline void upload(muxgl_handle* h, const Pileup& p) {
         "muxgl_set_pileup");
 }
 
+// The droplets the ambient profile is made from: those with at most --ambient-max-reads reads, or (empty) all of them
+inline std::vector<uint8_t> ambient_mask(const Pileup& p, const TableFlags& tf, const int32_t* nReads) {
+  std::vector<uint8_t> mask;
+  if (tf.ambMaxReads > 0) {
+    mask.resize((size_t)p.C());
+    int64_t kept = 0;
+    for (int64_t i = 0; i < p.C(); ++i) kept += mask[(size_t)i] = nReads[i] <= tf.ambMaxReads;
+    notice("Ambient profile from the %lld of %lld droplets with at most %d reads", (long long)kept, (long long)p.C(), tf.ambMaxReads);
+  }
+  return mask;
+}
+
 // The ambient profile of --write-ambient and --fit-ambient: the caller's file, or the pileup's own reads with one
 // pseudo-read at the population frequency.  Made once, into f: a second call returns it as it is.  nReads [C]: the
 // droplets' read counts that --ambient-max-reads is held against; lap: the stage's name for the timer
@@ -134,13 +146,7 @@ inline const std::vector<double>& ambient_profile(std::vector<double>& f, muxgl_
       if (n < S) f[n] = t.double_field_at(0);
     if (n != S) fatal("--ambient-af: %s holds %zu lines, the pileup has %zu markers", tf.ambAfFile.c_str(), n, S);
   } else {
-    std::vector<uint8_t> mask;
-    if (tf.ambMaxReads > 0) {
-      mask.resize((size_t)p.C());
-      int64_t kept = 0;
-      for (int64_t i = 0; i < p.C(); ++i) kept += mask[(size_t)i] = nReads[i] <= tf.ambMaxReads;
-      notice("Ambient profile from the %lld of %lld droplets with at most %d reads", (long long)kept, (long long)p.C(), tf.ambMaxReads);
-    }
+    const std::vector<uint8_t> mask = ambient_mask(p, tf, nReads);
     std::vector<int64_t> n_ref(S), n_alt(S);
     check(h, muxgl_pileup_allele_counts(h, mask.empty() ? nullptr : mask.data(), n_ref.data(), n_alt.data()),
           "muxgl_pileup_allele_counts");

@@ -34,12 +34,19 @@ inline int cmd_demuxlet(int argc, char** argv) {
   double doublet_prior = 0.5;  // cmd_cram_demuxlet.cpp:32
   std::string sam, tagGroup, tagUMI;
   int32_t dummy_i = 0;
+  bool ambMix = false, ambMixUnknown = false;  // (ours) the ambient profile fitted as a mixture of the donors (muxgl_demux_soup_mix)
+  int32_t ambMixIter = 500;
+  double ambMixTol = 1e-8;
   bool deviceCalls = false;  // (ours) skip the host pass that settles mirrored alpha = 0.5 pairs and near-tie calls as the reference does
   Args a;
   cf.add(a);
   tf.add(a);
   gf.add(a, cf.lo, vr);
   a.add_bool("device-calls", &deviceCalls);
+  a.add_bool("ambient-mix", &ambMix);
+  a.add_int("ambient-mix-iter", &ambMixIter);
+  a.add_double("ambient-mix-tol", &ambMixTol);
+  a.add_bool("ambient-mix-unknown", &ambMixUnknown);
   a.add_string("vcf", &vr.path);
   a.add_multi_double("alpha", &gridAlpha);
   a.add_double("doublet-prior", &doublet_prior);
@@ -57,6 +64,9 @@ inline int cmd_demuxlet(int argc, char** argv) {
   if (gridAlpha.empty()) gridAlpha = {0, 0.5};  // :85-89
   if ((int)gridAlpha.size() > MUXGL_MAX_ALPHA) fatal("at most %d --alpha values are supported", MUXGL_MAX_ALPHA);
   tf.validate();
+  if (ambMix && !tf.ambAfFile.empty()) fatal("--ambient-mix fits the ambient profile, --ambient-af reads it: give one of them");
+  if (ambMixIter < 0) fatal("--ambient-mix-iter must not be negative");
+  if (!(std::isfinite(ambMixTol) && ambMixTol >= 0.0)) fatal("--ambient-mix-tol must be a finite number >= 0");
   gf.init(vr);
   Pileup p;
   StageTimer tm;
@@ -125,7 +135,36 @@ inline int cmd_demuxlet(int argc, char** argv) {
     write_unknown_demux(OutFile(out + ".unk.gz", true), t, cells.data(), V, A, dp.alpha, ju.data(), uj.data(), uu.data());
     tm.lap("demuxlet: write .unk.gz");
   }
-  std::vector<double> ambProfile;  // of --write-ambient and --fit-ambient, made by the first of them
+  std::vector<double> ambProfile;  // of --write-ambient and --fit-ambient, made by the first of them (or by --ambient-mix)
+  if (ambMix) {
+    const size_t S = (size_t)p.S(), M = V + (ambMixUnknown ? 1 : 0);
+    const std::vector<uint8_t> mask = ambient_mask(p, tf, p.cell_uniq_reads.data());
+    std::vector<double> gp0;  // the unknown donor: Hardy-Weinberg at the population frequency
+    if (ambMixUnknown) {
+      gp0.resize(S * 3);
+      for (size_t s = 0; s < S; ++s) {
+        const double f = std::min(1.0, std::max(0.0, p.snps[s].af));
+        gp0[s * 3] = (1.0 - f) * (1.0 - f), gp0[s * 3 + 1] = 2.0 * f * (1.0 - f), gp0[s * 3 + 2] = f * f;
+      }
+    }
+    std::vector<double> pi(M), grad(M), ll((size_t)ambMixIter + 1);
+    ambProfile.resize(S);
+    int32_t nIter = 0, status = 0;
+    int64_t nReads = 0;
+    check(h, muxgl_demux_soup_mix(h, mask.empty() ? nullptr : mask.data(), 0, nullptr, nullptr, ambMixUnknown ? 1 : 0,
+                                  ambMixUnknown ? gp0.data() : nullptr, nullptr, ambMixIter, ambMixTol, pi.data(), grad.data(),
+                                  ll.data(), ambProfile.data(), &nIter, &nReads, &status, nullptr),
+          "muxgl_demux_soup_mix");
+    tm.lap("demuxlet: muxgl_demux_soup_mix");
+    double llEnd = ll[0];
+    for (double x : ll)
+      if (!std::isnan(x)) llEnd = x;
+    notice("Ambient mixture: %lld reads, %d steps, status %d, log-likelihood %.4lf at the start and %.4lf at the end",
+           (long long)nReads, (int)nIter, (int)status, ll[0], llEnd);
+    write_soup_mix(OutFile(out + ".soupmix.gz", true), OutFile(out + ".soupmix.af.gz", true), t.label, V, M, pi.data(),
+                   grad.data(), S, ambProfile.data());
+    tm.lap("demuxlet: write .soupmix.gz");
+  }
   auto profile = [&]() {
     return ambient_profile(ambProfile, h, p, tf, p.cell_uniq_reads.data(), tm, "demuxlet: muxgl_pileup_allele_counts").data();
   };

@@ -46,7 +46,21 @@
 //       information is not positive), MIX.LLK.MLE, MIX.LRT = 2 (MIX.LLK.MLE - the better of SNG1.LLK and SNG2.LLK; SNG1.LLK
 //       alone when x < 1), STATUS (0 interior, 1 lower bound, 2 upper bound, 3 step cap, 5 no scored marker); all %.4lf.
 //       .best and every other file are unchanged
-//   popscle-amd freemuxlet --plp P --nsample K --out O [...]                   mirrors cmdCramFreemux2 (cmd_cram_freemux2.cpp)
+//       --ambient-mix: the ALT fraction of the ambient RNA per marker fitted as a mixture of the donors of the VCF
+//       (muxgl_demux_soup_mix) instead of counted per marker: the soup is free RNA of the pooled donors, so its ALT fraction
+//       is a weighted mean of their genotype dosages with the same shares at every marker -- V unknowns where the count
+//       route estimates one per marker from 0-3 reads.  The reads are those of the droplets of --ambient-max-reads (0 =
+//       all), as for the count profile; --ambient-mix-iter N (default 500) caps the EM steps, --ambient-mix-tol x (default
+//       1e-8) is the largest change of a share at which it stops; --ambient-mix-unknown adds one component for a donor
+//       missing from the VCF, with the Hardy-Weinberg genotype frequencies of the AF column of .var.gz as its genotype
+//       prior (the panel mean, the library's default, is the mean of the other components: its share would not be
+//       identified).  Fatal together with --ambient-af.  Writes <O>.soupmix.gz (BGZF), one row per component: SM_ID
+//       (UNKNOWN for the extra component), SHARE, GRAD (%.6lf; GRAD is 1 at the maximum where SHARE > 0 and at most 1
+//       where it is 0), and <O>.soupmix.af.gz (BGZF): the fitted profile, one value (%.17g) per line in .var.gz order, the
+//       format --ambient-af reads, so a freemuxlet run can take it.  A notice gives the reads used, the steps, the status
+//       (0 converged, 1 step cap, 2 no read took part) and the log-likelihood at the start and at the end.  With it
+//       --write-ambient and --fit-ambient use the fitted profile; without it every output file is what it was
+//   popscle-amd freemuxlet --plp P --nsample K --out O [...]                  mirrors cmdCramFreemux2 (cmd_cram_freemux2.cpp)
 //       --write-singlets: also <O>.clust1.sing2.gz (BGZF), the singlet log-likelihood of every droplet against every
 //       cluster as the last EM iteration formed it (llks[j(j+1)/2 + j], cmd_cram_freemux2.cpp:448-455; the reference
 //       prints only the best and the next).  One row per droplet, in the order of .clust1.samples.gz, and cluster

@@ -409,6 +409,20 @@ inline void write_droplet_ldist(OutFile&& w, int64_t nvis, const int32_t* drops_
   w.close();
 }
 
+// ---- the soup mixture of demuxlet (--ambient-mix) ----
+// .soupmix.gz: one row per component of muxgl_demux_soup_mix -- the V samples of the panel in VCF column order and, where
+// M == V + 1, the donor missing from the VCF as UNKNOWN -- with its share of the soup and its gradient (1 at a maximum of
+// the likelihood where the share is above 0, at most 1 where it is 0); and .soupmix.af.gz: the fitted ALT fraction of the
+// soup, one value per line in .var.gz order, written so that --ambient-af reads back the same doubles
+inline void write_soup_mix(OutFile&& w, OutFile&& wf, const Label& donor, size_t V, size_t M, const double* pi /* [M] */,
+                           const double* grad /* [M] */, size_t S, const double* amb_af /* [S] */) {
+  w.printf("SM_ID\tSHARE\tGRAD\n");
+  for (size_t v = 0; v < M; ++v) w.printf("%s\t%.6lf\t%.6lf\n", v < V ? donor((int)v).c_str() : "UNKNOWN", pi[v], grad[v]);
+  w.close();
+  for (size_t s = 0; s < S; ++s) wf.printf("%.17g\n", amb_af[s]);
+  wf.close();
+}
+
 // ---- the cluster-level tables of freemuxlet ----
 // .clust1.anchors.gz: one row per cluster -- the donor it is held to, the greedy cluster it started from with the log Bayes
 // factor of that match, and the droplets called singlets of it.  mode: [nAnchor] MUXGL_ANCHOR_*, or NULL for no MODE column

@@ -111,6 +111,9 @@ SYMBOLS = {
     "muxgl_demux_unknown": (C.c_int, [_VP, C.POINTER(_DemuxParams), _VP, _VP, _VP, _VP, _VP]),
     "muxgl_demux_ambient": (C.c_int, [_VP, C.POINTER(_DemuxParams), _VP, C.c_int32, _VP, _VP, _VP]),
     "muxgl_pileup_allele_counts": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "muxgl_pileup_read_hist": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, _VP]),
+    "muxgl_demux_soup_mix": (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int32, _VP, _VP, C.c_int32, C.c_double,
+                                       _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "muxgl_demux_ambient_fit": (C.c_int, [_VP, C.POINTER(_DemuxParams), _VP, C.c_int32, _VP, C.c_double,
                                           _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "muxgl_demux_alpha_fit": (C.c_int, [_VP, C.POINTER(_DemuxParams), C.c_int32, _VP, C.c_double,
@@ -284,6 +287,31 @@ def ambient_profile(n_ref, n_alt, af):
     if n_ref.shape != n_alt.shape or af.shape != n_ref.shape or n_ref.ndim != 1:
         raise ValueError("n_ref, n_alt and af must be [S]")
     return (n_alt + af) / (n_ref + n_alt + 1.0)
+
+
+def soup_mix_summary(fit, names=None):
+    """What a caller reads off the dict of Engine.demux_soup_mix.  Pure numpy.  Returns a dict: order, the components by
+    share descending (ties to the lower index); shares, pi in that order; names, the components' names in that order where
+    `names` is given (the panel's sample ids; component V is "UNKNOWN"); ll_gain, the last evaluated LL minus the LL at
+    the start (>= 0 for an EM run, 0 with n_iter_max == 0); max_grad_dev, the largest |grad - 1| over the components with
+    pi > 0 (0 at a maximum of the likelihood; NaN where no record took part)."""
+    pi = np.asarray(fit["pi"], dtype=np.float64)
+    grad = np.asarray(fit["grad"], dtype=np.float64)
+    ll = np.asarray(fit["ll"], dtype=np.float64)
+    order = np.argsort(-pi, kind="stable")
+    seen = ll[~np.isnan(ll)]
+    on = pi > 0.0
+    out = {"order": order.astype(np.int32), "shares": pi[order],
+           "ll_gain": float(seen[-1] - seen[0]) if seen.size else 0.0,
+           "max_grad_dev": float(np.abs(grad[on] - 1.0).max()) if on.any() and fit.get("status", 0) != 2 else float("nan")}
+    if names is not None:
+        names = list(names)
+        if len(names) == pi.size - 1:
+            names.append("UNKNOWN")
+        if len(names) != pi.size:
+            raise ValueError("names must name every component")
+        out["names"] = [names[i] for i in order]
+    return out
 
 
 def ambient_summary(ll, rhos):
@@ -612,6 +640,72 @@ class Engine:
         n_alt = np.zeros(self.S, dtype=np.int64)
         self._check(self.lib.muxgl_pileup_allele_counts(self.h, _ptr(mask), _ptr(n_ref), _ptr(n_alt)))
         return n_ref, n_alt
+
+    def pileup_read_hist(self, mask=None):
+        """muxgl_pileup_read_hist: (keys, counts), int64 [n] each: the usable reads of the droplets whose mask entry is true
+        (None: all of them) as a histogram, keys = marker * 256 + read byte strictly ascending, counts > 0; exact integer
+        counts from the device."""
+        if mask is not None:
+            mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+            if mask.shape != (self.C,):
+                raise ValueError("mask must be [C]")
+        n = C.c_int64(0)
+        self._check(self.lib.muxgl_pileup_read_hist(self.h, _ptr(mask), None, None, 0, C.byref(n)))
+        keys = np.zeros(n.value, dtype=np.int64)
+        counts = np.zeros(n.value, dtype=np.int64)
+        self._check(self.lib.muxgl_pileup_read_hist(self.h, _ptr(mask), _ptr(keys), _ptr(counts), n.value, C.byref(n)))
+        return keys, counts
+
+    SOUP_MIX_FIELDS = ("pi", "grad", "ll", "amb_af")
+
+    def demux_soup_mix(self, mask=None, hist=None, with_unknown=False, gp0=None, pi0=None, n_iter_max=500, tol=1e-8,
+                       want=SOUP_MIX_FIELDS):
+        """muxgl_demux_soup_mix: the soup's ALT profile fitted as a mixture of the panel's donors (include/muxgl.h).  The
+        reads are those of the droplets of `mask` (None: all), or the histogram hist = (keys, counts) of pileup_read_hist
+        (mask must then be None).  with_unknown adds component V, a donor missing from the panel, with genotype prior
+        gp0 [S][3] or the panel mean (None).  pi0: the start [M], or None for uniform shares.  dict of pi, grad float64 [M],
+        ll float64 [n_iter_max + 1] (NaN behind the last evaluation), amb_af float64 [S] (want: the subset of the four to
+        fetch), n_iter, n_reads, status (0 converged, 1 iteration cap, 2 no record took part) and kernel_ms.
+        soup_mix_summary() gives the sorted shares and the fit's diagnostics."""
+        unknown = set(want) - set(self.SOUP_MIX_FIELDS)
+        if unknown:
+            raise ValueError(f"unknown fields {sorted(unknown)}")
+        M = self.V + (1 if with_unknown else 0)
+        keys = counts = None
+        n_rec = 0
+        if hist is not None:
+            if mask is not None:
+                raise ValueError("mask and hist exclude each other")
+            keys = _arr(hist[0], np.int64, "keys").reshape(-1)
+            counts = _arr(hist[1], np.int64, "counts").reshape(-1)
+            if keys.size != counts.size:
+                raise ValueError("keys and counts must have one length")
+            n_rec = keys.size
+            if n_rec == 0:  # (an empty histogram is still a histogram: a non-NULL pointer says so)
+                keys = np.zeros(1, dtype=np.int64)
+                counts = np.zeros(1, dtype=np.int64)
+        elif mask is not None:
+            mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+            if mask.shape != (self.C,):
+                raise ValueError("mask must be [C]")
+        if gp0 is not None:
+            gp0 = _arr(gp0, np.float64, "gp0")
+            if gp0.shape != (self.S, 3):
+                raise ValueError("gp0 must be [S][3]")
+        if pi0 is not None:
+            pi0 = _arr(pi0, np.float64, "pi0")
+            if pi0.shape != (M,):
+                raise ValueError("pi0 must be [M]")
+        n_iter_max = int(n_iter_max)
+        shapes = {"pi": M, "grad": M, "ll": max(n_iter_max, 0) + 1, "amb_af": self.S}
+        out = {name: np.zeros(shapes[name], dtype=np.float64) for name in self.SOUP_MIX_FIELDS if name in want}
+        n_iter, status, n_reads, ms = C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_float(0.0)
+        self._check(self.lib.muxgl_demux_soup_mix(self.h, _ptr(mask), n_rec, _ptr(keys), _ptr(counts), 1 if with_unknown else 0,
+                                                   _ptr(gp0), _ptr(pi0), n_iter_max, float(tol),
+                                                   *[_ptr(out.get(n)) for n in self.SOUP_MIX_FIELDS],
+                                                   C.byref(n_iter), C.byref(n_reads), C.byref(status), C.byref(ms)))
+        out.update(n_iter=int(n_iter.value), n_reads=int(n_reads.value), status=int(status.value), kernel_ms=float(ms.value))
+        return out
 
     def demux_results_view(self):
         """zero-copy view of the pinned [C] record buffer of the last run"""
