@@ -1,6 +1,7 @@
-// ambient_table.hpp -- the skeleton the two ambient tables share (muxgl_demux_ambient in demux_ambient.hip,
-// muxgl_fmx_ambient in fmx_ambient.hip): the sweep and emit kernels, the batch, the width and chunk dispatch and the host
-// run.  A unit brings its weight kernel -- the only place where the two models differ -- and a description of the call.
+// ambient_table.hpp -- what the two ambient tables share (muxgl_demux_ambient in demux_ambient.hip, muxgl_fmx_ambient in
+// fmx_ambient.hip): the sweep and emit kernels, the batch, the width and chunk dispatch and the host run, itself a
+// customer of table_call.hpp's table_batches like the singlet and unknown-donor tables.  A unit brings its weight kernel
+// -- the only place where the two models differ -- and a description of the call.
 //
 // What the skeleton guarantees to both callers:
 //   * wt[(e - eb0)][r][0..2], the unit's weight triple of entry e at rho r, is read and never rescaled; the table is
@@ -16,11 +17,10 @@
 //     call, for any budget, for any split of the rhos over calls, on one device, on a group and through the sharded
 //     driver.
 //   * Nothing proportional to nnz x n_rho is held for the whole pileup: cells are swept in batches of whole cells whose
-//     device bytes (table_plan::ambient_bytes) fit the unit's budget, each batch copied out before the next.  The call
-//     caches nothing on the handle and leaves its timing slots alone.
-//   * The order of the run: plan, the refusal of a cell over the budget, the launch limits, the rho grid, six
-//     allocations (af, wt, slab, out, items, cells), the event pair; per batch fill, upload, start, weights, sweep, emit,
-//     stop, copy out, add.
+//     device bytes (table_plan::ambient_bytes) fit the unit's budget.  The call caches nothing on the handle and leaves
+//     its timing slots alone.
+//   * The order of the run is table_call.hpp's protocol; here the rho grid, four buffers (af, wt, slab, out), the event
+//     pair and the profile's copy to the device, per batch weights, sweep and emit inside the bracket, then the copy-out.
 // UNR, the entries per lane between two renormalisations, is the unit's: how many factors a product can take without
 // leaving the normal range depends on the smallest factor its weights allow (Tool::unr(WH, CH), see each unit).
 #pragma once
@@ -158,10 +158,8 @@ void ambient_launch_sweep(muxgl_handle* h, const ambient_call& call, int NR, int
 
 template <class Tool, int CH>
 void ambient_sweep_width(muxgl_handle* h, const ambient_call& call, int NR, int nch, const ambient_batch& b) {
-  int WH = 64;
-  while (WH > 1 && WH / 2 >= call.W) WH /= 2;
 #define CALL_S(N) ambient_launch_sweep<Tool, N, CH>(h, call, NR, nch, b)
-  DISPATCH_WIDTH(WH, CALL_S);
+  DISPATCH_WIDTH(lane_width(call.W), CALL_S);
 #undef CALL_S
 }
 
@@ -184,67 +182,38 @@ template <class Tool, class Weights>
 int ambient_table_run(muxgl_handle* h, const ambient_call& call, const double* amb_af, int NR, const double* rho,
                       double* ll_amb, float* kernel_ms, Weights&& weights) {
   const int W = call.W;
-  const int64_t C = h->C, S = h->S;
-  std::vector<int64_t> cell_ptr((size_t)C + 1);
-  HIPCHK(h, hipMemcpyAsync(cell_ptr.data(), h->d_cell_ptr, sizeof(int64_t) * (size_t)(C + 1), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-
-  // batches of whole cells whose device bytes fit the budget (table_plan.hpp)
-  const size_t budget = dev_slab_budget(call.budget_env);
-  auto bytes_of = [&](int64_t len, int64_t np) { return table_plan::ambient_bytes(len, np, NR, W); };
-  const table_plan::batches bt = table_plan::plan(cell_ptr.data(), C, budget, bytes_of);
-  if (bt.over >= 0) {
-    const int64_t len = cell_ptr[(size_t)bt.over + 1] - cell_ptr[(size_t)bt.over];
-    MUXGL_FAIL(h, "%s: droplet %lld alone (%lld entries x %d rhos x %d %s: %.1f MB) exceeds the budget of %.1f MB (raise %s)",
-               call.who, (long long)(h->cell_base + bt.over), (long long)len, NR, W, call.noun,
-               (double)bytes_of(len, table_plan::parts(len)) / 1048576.0, (double)budget / 1048576.0, call.budget_env);
-  }
+  const int64_t S = h->S;
   const int nblk = (W + 63) / 64;
   const int nch = (NR + 3) / 4, CH = (NR + nch - 1) / nch;  // chunks of the rhos, rhos per chunk (1..4)
-  if (table_plan::exceeds_one_launch((double)bt.max_rows * nblk * nch, 4.0) ||
-      table_plan::exceeds_one_launch((double)bt.max_cells * W * NR, 256.0))
-    MUXGL_FAIL(h, "%s: a batch of %lld rows x %d %s x %d rhos exceeds one launch (lower %s)", call.who, (long long)bt.max_rows,
-               W, call.noun, NR, call.budget_env);
+  const table_call tc = {call.who, call.budget_env, call.begin, (double)nblk * nch, 0.0, (double)W * NR,
+                         table_plan::shape(W, call.noun, NR, "rhos"), table_plan::shape(NR, "rhos", W, call.noun)};
+  table_batches<ambient_cell> tb;
+  if (tb.plan(h, tc, [=](int64_t len, int64_t np) { return table_plan::ambient_bytes(len, np, NR, W); })) return 1;
   ambient_rhos rh;
   for (int i = 0; i < AMBIENT_MAX_RHO; ++i) rh.a[i] = i < NR ? rho[i] : rho[NR - 1];  // (a slot past the end is not written)
 
   dev_tmp<double> d_af, d_wt, d_slab, d_out;
-  dev_tmp<ambient_item> d_items;
-  dev_tmp<ambient_cell> d_cells;
   if (dev_alloc(h, &d_af.p, (size_t)S)) return 1;
-  if (dev_alloc(h, &d_wt.p, (size_t)bt.max_entries * NR * 3)) return 1;
-  if (dev_alloc(h, &d_slab.p, (size_t)bt.max_rows * NR * W)) return 1;
-  if (dev_alloc(h, &d_out.p, (size_t)bt.max_cells * W * NR)) return 1;
-  if (dev_alloc(h, &d_items.p, (size_t)bt.max_rows)) return 1;
-  if (dev_alloc(h, &d_cells.p, (size_t)bt.max_cells)) return 1;
+  if (dev_alloc(h, &d_wt.p, (size_t)tb.bt.max_entries * NR * 3)) return 1;
+  if (dev_alloc(h, &d_slab.p, (size_t)tb.bt.max_rows * NR * W)) return 1;
+  if (dev_alloc(h, &d_out.p, (size_t)tb.bt.max_cells * W * NR)) return 1;
   call_events ev;  // (the handle's timing slots keep their values)
   if (ev.create(h, kernel_ms, call.who)) return 1;
-
   if (S > 0) HIPCHK(h, hipMemcpyAsync(d_af.p, amb_af, sizeof(double) * (size_t)S, hipMemcpyHostToDevice, h->stream));
-  std::vector<ambient_item> items;
-  std::vector<ambient_cell> cells;
-  int64_t c0 = 0;
-  for (const int64_t c1 : bt.end) {
-    const int64_t nc = c1 - c0;
-    table_plan::fill(cell_ptr.data(), c0, c1, call.begin, items, nullptr, &cells);
-    const ambient_batch b = {cell_ptr[(size_t)c0], cell_ptr[(size_t)c1], (int64_t)items.size(), nc, d_items.p, d_cells.p,
-                             d_wt.p, d_slab.p, d_out.p, d_af.p};
-    if (table_upload(h, items, d_items.p, cells, d_cells.p)) return 1;
-    if (ev.start(h)) return 1;
-    if (b.eb1 > b.eb0 && weights(rh, b)) return 1;
-    if (ambient_sweep_dispatch<Tool>(h, call, CH, NR, nch, b)) return 1;
-    {
-      const int64_t n = nc * W * NR;
-      hipLaunchKernelGGL(ambient_emit_kernel<Tool>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, nc, d_cells.p, W,
-                         NR, d_slab.p, d_out.p);
-      HIPCHK(h, hipGetLastError());
-    }
-    if (ev.stop(h)) return 1;
-    HIPCHK(h, hipMemcpyAsync(ll_amb + (size_t)c0 * W * NR, d_out.p, sizeof(double) * (size_t)nc * W * NR, hipMemcpyDeviceToHost,
-                             h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    ev.add();
-    c0 = c1;
-  }
-  return 0;
+  return tb.run(h, ev,
+      [&](const table_batch<ambient_cell>& t) {
+        const ambient_batch b = {t.eb0, t.eb1, t.n_items, t.nc(), t.d_items, t.d_recs, d_wt.p, d_slab.p, d_out.p, d_af.p};
+        if (b.eb1 > b.eb0 && weights(rh, b)) return 1;
+        if (ambient_sweep_dispatch<Tool>(h, call, CH, NR, nch, b)) return 1;
+        const int64_t n = b.nc * W * NR;
+        hipLaunchKernelGGL(ambient_emit_kernel<Tool>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, b.nc, b.d_cells, W,
+                           NR, d_slab.p, d_out.p);
+        HIPCHK(h, hipGetLastError());
+        return 0;
+      },
+      [&](const table_batch<ambient_cell>& t) {
+        HIPCHK(h, hipMemcpyAsync(ll_amb + (size_t)t.c0 * W * NR, d_out.p, sizeof(double) * (size_t)t.nc() * W * NR,
+                                 hipMemcpyDeviceToHost, h->stream));
+        return 0;
+      });
 }

@@ -19,6 +19,7 @@
 #include "../../include/muxgl.h"
 #include "fit_args.hpp"
 #include "fmx_refusal.hpp"
+#include "lane_width.hpp"
 #include "path_choice.hpp"
 #include "stream_plan.hpp"
 
@@ -340,7 +341,7 @@ struct host_timer {
   } while (0)
 
 // CALL(W) for the lane width W of a sweep whose lanes are (entry slot, column): the columns rounded up to a power of two,
-// 64 from 33 columns on (match_plan::lane_width), in the manner of demux_entry.hpp's DISPATCH_NA.  It names the seven
+// 64 from 33 columns on (lane_width.hpp), in the manner of demux_entry.hpp's DISPATCH_NA.  It names the seven
 // widths a unit instantiates (fmx_pairs.hip has no width 1 and keeps a switch of its own).
 #define DISPATCH_WIDTH(W, CALL) \
   switch (W) {                  \
@@ -447,7 +448,7 @@ struct call_events {
     if (ms) HIPCHK(h, hipEventRecord(ev0, h->stream));
     return 0;
   }
-  int stop(muxgl_handle* h) {
+  int stop(muxgl_handle* h, bool /*last batch (table_call.hpp)*/ = false) {
     if (ms) HIPCHK(h, hipEventRecord(ev1, h->stream));
     return 0;
   }

@@ -18,10 +18,10 @@
 //     products identically and every ambient product belongs to one rho, so the chunking changes no bit.  A marker
 //     without genotypes gets ones: its row of gp is (1, 0, 0), so its factor is exactly 1 and the sweep has no branch.
 //   * the sweep (lane = sample column of a 64-column block, one dot gp_j . w_e[r] per (entry, column, rho)), the emit
-//     kernel, the batches and the host run are ambient_table.hpp's, shared with fmx_ambient.hip; what they guarantee --
-//     no bit depends on the chunking, the budget, the split of the rhos or the devices -- is written there.  This unit
-//     cuts a long cell into fixed parts of 2048 entries and sweeps inside the streamed call's budget (4 GiB or a third
-//     of the device, MUXGL_DEMUX_SLAB_MB).
+//     kernel and the host run (on table_call.hpp's batch loop) are ambient_table.hpp's, shared with fmx_ambient.hip;
+//     what they guarantee -- no bit depends on the chunking, the budget, the split of the rhos or the devices -- is
+//     written there.  This unit cuts a long cell into fixed parts of 2048 entries and sweeps inside the streamed call's
+//     budget (4 GiB or a third of the device, MUXGL_DEMUX_SLAB_MB).
 //   * amb_count_kernel, lane = entry: the usable reads of the entry by allele, added to its marker's two counters with
 //     integer atomics (exact, and the same in any order); the entry's droplet, for the mask, by bisection of cell_ptr.
 #include <algorithm>

@@ -17,11 +17,12 @@
 //     products of a sample are multiplied in a fixed butterfly at the end.
 //   * table_join_kernel (table_call.hpp): the logs of the parts of a long cell, added in entry order.
 // Which cell goes into which batch, its cut into parts (fixed parts of 2048 entries) and the order of the work items
-// are table_plan.hpp's.  The cut of a cell depends on the cell alone and every reduction tree is fixed: the table is
+// are table_plan.hpp's; the host body that drives the plan is table_call.hpp's table_batches, whose customer this unit
+// is (its cost: the slab rows of a cell; one bracket in its timing slot, open from the weight kernel on).  The cut of a cell depends on the cell alone and every reduction tree is fixed: the table is
 // bit-identical from run to run, for any slab budget, on one device, on a group and through the sharded driver.
 //
 // Memory: [nnz][3] weights and a slab of the table.  When the table exceeds the budget (the streamed call's: 4 GiB or a
-// third of the device, MUXGL_DEMUX_SLAB_MB) the cells are swept in batches and each batch is copied out before the next.
+// third of the device, MUXGL_DEMUX_SLAB_MB) the cells are swept in batches (table_call.hpp has the protocol).
 #include <algorithm>
 #include <vector>
 
@@ -136,55 +137,28 @@ void launch_sweep(muxgl_handle* h, int64_t n_items, int nblk, const sng_item* d_
 }  // namespace
 
 int demux_singlets_run(muxgl_handle* h, const muxgl_demux_params* p, double* sng) {
-  const int V = h->V, A = p->n_alpha;
-  const int64_t C = h->C;
-  std::vector<int64_t> cell_ptr((size_t)C + 1);
-  HIPCHK(h, hipMemcpyAsync(cell_ptr.data(), h->d_cell_ptr, sizeof(int64_t) * (size_t)(C + 1), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-
-  // batches of cells whose rows (one per part) fit the budget (table_plan.hpp)
-  const int64_t rows_cap = std::max<int64_t>(1, (int64_t)(dev_slab_budget("MUXGL_DEMUX_SLAB_MB") / (sizeof(double) * (size_t)V)));
-  const table_plan::batches bt = table_plan::plan(cell_ptr.data(), C, (size_t)rows_cap, [](int64_t, int64_t np) { return (size_t)np; });
-  const int nblk = (V + 63) / 64;
-  if (table_plan::exceeds_one_launch((double)bt.max_rows * (double)nblk, 4.0))
-    MUXGL_FAIL(h, "muxgl_demux_singlets: a batch of %lld rows x %d samples exceeds one launch (lower MUXGL_DEMUX_SLAB_MB)",
-               (long long)bt.max_rows, V);
-
-  int VH = 64;
-  while (VH > 1 && VH / 2 >= V) VH /= 2;
+  const int V = h->V, A = p->n_alpha, nblk = (V + 63) / 64, VH = lane_width(V);
+  const table_call call = {"muxgl_demux_singlets", "MUXGL_DEMUX_SLAB_MB", table_plan::fixed_begin, (double)nblk, 0.0, 0.0,
+                           table_plan::shape(V, "samples"), ""};
+  table_batches<table_plan::cut> tb;
+  if (tb.plan(h, call, [V](int64_t, int64_t np) { return table_plan::singlet_bytes(np, V); })) return 1;
   const demux_grid al = demux_grid_of(p);
 
   dev_tmp<double> d_wt, d_slab;
-  dev_tmp<sng_item> d_items;
-  dev_tmp<table_plan::cut> d_cuts;
-  std::vector<sng_item> items;
-  std::vector<table_plan::cut> cuts;
   if (dev_alloc(h, &d_wt.p, (size_t)h->nnz * 3)) return 1;
-  if (dev_alloc(h, &d_slab.p, (size_t)bt.max_rows * V)) return 1;
-  if (dev_alloc(h, &d_items.p, (size_t)bt.max_rows)) return 1;
-  if (dev_alloc(h, &d_cuts.p, (size_t)bt.max_cuts)) return 1;
+  if (dev_alloc(h, &d_slab.p, (size_t)tb.bt.max_rows * V)) return 1;
   tic(h, MUXGL_T_DEMUX_SINGLETS);
-  if (h->nnz > 0 && weights_dispatch(h, A, al, d_wt.p)) return 1;
-  int64_t c0 = 0;
-  for (const int64_t c1 : bt.end) {
-    const int64_t nc = c1 - c0;
-    table_plan::fill(cell_ptr.data(), c0, c1, table_plan::fixed_begin, items, &cuts, nullptr);
-    const int64_t n_items = (int64_t)items.size();
-    if (table_upload(h, items, d_items.p, cuts, d_cuts.p)) return 1;
-#define CALL_S(W) launch_sweep<W>(h, n_items, nblk, d_items.p, d_wt.p, d_slab.p)
-    DISPATCH_WIDTH(VH, CALL_S);
+  if (h->nnz > 0 && weights_dispatch(h, A, al, d_wt.p)) return 1;  // the whole pileup's, once per call
+  return tb.run(h, table_slot_timer{MUXGL_T_DEMUX_SINGLETS},
+      [&](const table_batch<table_plan::cut>& b) {
+#define CALL_S(W) launch_sweep<W>(h, b.n_items, nblk, b.d_items, d_wt.p, d_slab.p)
+        DISPATCH_WIDTH(VH, CALL_S);
 #undef CALL_S
-    HIPCHK(h, hipGetLastError());
-    if (!cuts.empty()) {
-      const int64_t n = (int64_t)cuts.size() * V;
-      hipLaunchKernelGGL(table_join_kernel<double>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
-                         (int64_t)cuts.size(), d_cuts.p, V, d_slab.p);
-      HIPCHK(h, hipGetLastError());
-    }
-    if (c1 == C) toc(h, MUXGL_T_DEMUX_SINGLETS);
-    HIPCHK(h, hipMemcpyAsync(sng + (size_t)c0 * V, d_slab.p, sizeof(double) * (size_t)nc * V, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    c0 = c1;
-  }
-  return 0;
+        HIPCHK(h, hipGetLastError());
+        return table_join(h, b, V, d_slab.p);
+      },
+      [&](const table_batch<table_plan::cut>& b) {
+        HIPCHK(h, hipMemcpyAsync(sng + (size_t)b.c0 * V, d_slab.p, sizeof(double) * (size_t)b.nc() * V, hipMemcpyDeviceToHost, h->stream));
+        return 0;
+      });
 }

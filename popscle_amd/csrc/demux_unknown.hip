@@ -24,13 +24,14 @@
 //     samples and spend a whole second block on one column at 64.
 //   * unk_emit_kernel: the logs of the parts of a cell added in entry order and written in the caller's layout.
 // Which cell goes into which batch, its cut into parts (fixed parts of 2048 entries) and the order of the work items
-// are table_plan.hpp's.  The cut of a cell depends on the cell alone and every reduction tree is fixed: the tables are
+// are table_plan.hpp's; the host body that drives the plan is table_call.hpp's table_batches, whose customer this unit
+// is.  The cut of a cell depends on the cell alone and every reduction tree is fixed: the tables are
 // bit-identical from call to call, for any budget, for any subset of outputs, on one device, on a group and through the
 // sharded driver.
 //
 // Memory: nothing proportional to nnz x n_alpha is held for the whole pileup.  Cells are swept in batches of whole cells
 // whose weights ([entries][n_alpha][6]), slab rows and output rows (table_plan::unknown_bytes) fit the streamed call's
-// budget (4 GiB or a third of the device, MUXGL_DEMUX_SLAB_MB); each batch is copied out before the next.
+// budget (4 GiB or a third of the device, MUXGL_DEMUX_SLAB_MB); table_call.hpp has the protocol of the batches.
 #include <algorithm>
 #include <vector>
 
@@ -260,10 +261,8 @@ void launch_sweep(muxgl_handle* h, int A, int nch, int j0, int ncol, const unk_b
 
 template <int CH>
 void sweep_dispatch_vh(muxgl_handle* h, int A, int nch, int j0, int ncol, const unk_batch& b) {
-  int VH = 64;
-  while (VH > 1 && VH / 2 >= ncol) VH /= 2;
 #define CALL_S(W) launch_sweep<W, CH>(h, A, nch, j0, ncol, b)
-  DISPATCH_WIDTH(VH, CALL_S);
+  DISPATCH_WIDTH(lane_width(ncol), CALL_S);
 #undef CALL_S
 }
 
@@ -282,81 +281,51 @@ int sweep_dispatch(muxgl_handle* h, int CH, int A, int nch, int j0, int ncol, co
 int demux_unknown_run(muxgl_handle* h, const muxgl_demux_params* p, const double* gp0, double* ll_ju, double* ll_uj,
                       double* ll_uu, float* kernel_ms) {
   const int V = h->V, A = p->n_alpha, VC = V + 1;
-  const int64_t C = h->C, S = h->S;
-  std::vector<int64_t> cell_ptr((size_t)C + 1);
-  HIPCHK(h, hipMemcpyAsync(cell_ptr.data(), h->d_cell_ptr, sizeof(int64_t) * (size_t)(C + 1), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-
-  // batches of whole cells whose device bytes fit the budget (table_plan.hpp)
-  const size_t budget = dev_slab_budget("MUXGL_DEMUX_SLAB_MB");
-  auto bytes_of = [&](int64_t len, int64_t np) { return table_plan::unknown_bytes(len, np, A, VC); };
-  const table_plan::batches bt = table_plan::plan(cell_ptr.data(), C, budget, bytes_of);
-  if (bt.over >= 0) {
-    const int64_t len = cell_ptr[(size_t)bt.over + 1] - cell_ptr[(size_t)bt.over];
-    MUXGL_FAIL(h, "muxgl_demux_unknown: droplet %lld alone (%lld entries x %d alphas x %d samples: %.1f MB) exceeds the "
-                  "budget of %.1f MB (raise MUXGL_DEMUX_SLAB_MB)",
-               (long long)(h->cell_base + bt.over), (long long)len, A, V,
-               (double)bytes_of(len, table_plan::parts(len)) / 1048576.0, (double)budget / 1048576.0);
-  }
+  const int64_t S = h->S;
   const int nblk = (V + 63) / 64;
   const int nch = (A + 2) / 3, CH = (A + nch - 1) / nch;  // chunks of the grid, alphas per chunk (1..3)
-  if (table_plan::exceeds_one_launch((double)bt.max_rows * nblk * nch, 4.0) ||
-      table_plan::exceeds_one_launch((double)bt.max_cells * VC * A, 256.0))
-    MUXGL_FAIL(h, "muxgl_demux_unknown: a batch of %lld rows x %d samples x %d alphas exceeds one launch (lower MUXGL_DEMUX_SLAB_MB)",
-               (long long)bt.max_rows, V, A);
+  const table_call call = {"muxgl_demux_unknown", "MUXGL_DEMUX_SLAB_MB", table_plan::fixed_begin, (double)nblk * nch, 0.0,
+                           (double)VC * A, table_plan::shape(V, "samples", A, "alphas"), table_plan::shape(A, "alphas", V, "samples")};
+  table_batches<unk_cell> tb;
+  if (tb.plan(h, call, [=](int64_t len, int64_t np) { return table_plan::unknown_bytes(len, np, A, VC); })) return 1;
   const demux_grid al = demux_grid_of(p);
 
   dev_tmp<double> d_u, d_wt, d_slab, d_ju, d_uj, d_uu;
-  dev_tmp<unk_item> d_items;
-  dev_tmp<unk_cell> d_cells;
   if (dev_alloc(h, &d_u.p, (size_t)S * 3)) return 1;
-  if (dev_alloc(h, &d_wt.p, (size_t)bt.max_entries * A * 6)) return 1;
-  if (dev_alloc(h, &d_slab.p, (size_t)bt.max_rows * A * 2 * VC)) return 1;
-  if (dev_alloc(h, &d_ju.p, (size_t)bt.max_cells * V * A)) return 1;
-  if (dev_alloc(h, &d_uj.p, (size_t)bt.max_cells * V * A)) return 1;
-  if (dev_alloc(h, &d_uu.p, (size_t)bt.max_cells * A)) return 1;
-  if (dev_alloc(h, &d_items.p, (size_t)bt.max_rows)) return 1;
-  if (dev_alloc(h, &d_cells.p, (size_t)bt.max_cells)) return 1;
+  if (dev_alloc(h, &d_wt.p, (size_t)tb.bt.max_entries * A * 6)) return 1;
+  if (dev_alloc(h, &d_slab.p, (size_t)tb.bt.max_rows * A * 2 * VC)) return 1;
+  if (dev_alloc(h, &d_ju.p, (size_t)tb.bt.max_cells * V * A)) return 1;
+  if (dev_alloc(h, &d_uj.p, (size_t)tb.bt.max_cells * V * A)) return 1;
+  if (dev_alloc(h, &d_uu.p, (size_t)tb.bt.max_cells * A)) return 1;
   call_events ev;  // (the handle's timing slots keep their values)
-  if (ev.create(h, kernel_ms, "muxgl_demux_unknown")) return 1;
-
+  if (ev.create(h, kernel_ms, call.who)) return 1;
   if (gp0 && S > 0) HIPCHK(h, hipMemcpyAsync(d_u.p, gp0, sizeof(double) * (size_t)S * 3, hipMemcpyHostToDevice, h->stream));
-  std::vector<unk_item> items;
-  std::vector<unk_cell> cells;
-  int64_t c0 = 0;
-  for (const int64_t c1 : bt.end) {
-    const int64_t nc = c1 - c0;
-    table_plan::fill(cell_ptr.data(), c0, c1, table_plan::fixed_begin, items, nullptr, &cells);
-    const unk_batch b = {cell_ptr[(size_t)c0], cell_ptr[(size_t)c1], (int64_t)items.size(), nc, d_items.p, d_cells.p, d_wt.p,
-                         d_slab.p, d_ju.p, d_uj.p, d_uu.p, d_u.p};
-    if (table_upload(h, items, d_items.p, cells, d_cells.p)) return 1;
-    if (ev.start(h)) return 1;
-    if (c0 == 0 && S > 0) {  // the unknown donor's prior, once per call
-      if (gp0)
-        hipLaunchKernelGGL(unk_neutral_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, h->stream, S, h->d_has_gp, d_u.p);
-      else
-        hipLaunchKernelGGL(unk_mean_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, h->stream, S, h->d_gp, h->d_has_gp,
-                           V, d_u.p);
-      HIPCHK(h, hipGetLastError());
-    }
-    if (b.eb1 > b.eb0 && weights_dispatch(h, A, al, b)) return 1;
-    if (sweep_dispatch(h, CH, A, nch, 0, V, b)) return 1;  // the samples
-    if (sweep_dispatch(h, CH, A, nch, V, 1, b)) return 1;  // the unknown donor's own column
-    {
-      const int64_t n = nc * VC * A;
-      hipLaunchKernelGGL(unk_emit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, nc, d_cells.p, V, A,
-                         d_slab.p, d_ju.p, d_uj.p, d_uu.p);
-      HIPCHK(h, hipGetLastError());
-    }
-    if (ev.stop(h)) return 1;
-    const size_t nva = sizeof(double) * (size_t)nc * V * A;
-    if (ll_ju) HIPCHK(h, hipMemcpyAsync(ll_ju + (size_t)c0 * V * A, d_ju.p, nva, hipMemcpyDeviceToHost, h->stream));
-    if (ll_uj) HIPCHK(h, hipMemcpyAsync(ll_uj + (size_t)c0 * V * A, d_uj.p, nva, hipMemcpyDeviceToHost, h->stream));
-    if (ll_uu)
-      HIPCHK(h, hipMemcpyAsync(ll_uu + (size_t)c0 * A, d_uu.p, sizeof(double) * (size_t)nc * A, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    ev.add();
-    c0 = c1;
-  }
-  return 0;
+  return tb.run(h, ev,
+      [&](const table_batch<unk_cell>& t) {
+        const unk_batch b = {t.eb0, t.eb1, t.n_items, t.nc(), t.d_items, t.d_recs, d_wt.p, d_slab.p, d_ju.p, d_uj.p, d_uu.p, d_u.p};
+        if (t.c0 == 0 && S > 0) {  // the unknown donor's prior, once per call
+          if (gp0)
+            hipLaunchKernelGGL(unk_neutral_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, h->stream, S, h->d_has_gp, d_u.p);
+          else
+            hipLaunchKernelGGL(unk_mean_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, h->stream, S, h->d_gp, h->d_has_gp,
+                               V, d_u.p);
+          HIPCHK(h, hipGetLastError());
+        }
+        if (b.eb1 > b.eb0 && weights_dispatch(h, A, al, b)) return 1;
+        if (sweep_dispatch(h, CH, A, nch, 0, V, b)) return 1;  // the samples
+        if (sweep_dispatch(h, CH, A, nch, V, 1, b)) return 1;  // the unknown donor's own column
+        const int64_t n = b.nc * VC * A;
+        hipLaunchKernelGGL(unk_emit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, b.nc, b.d_cells, V, A,
+                           d_slab.p, d_ju.p, d_uj.p, d_uu.p);
+        HIPCHK(h, hipGetLastError());
+        return 0;
+      },
+      [&](const table_batch<unk_cell>& t) {
+        const size_t nva = sizeof(double) * (size_t)t.nc() * V * A;
+        if (ll_ju) HIPCHK(h, hipMemcpyAsync(ll_ju + (size_t)t.c0 * V * A, d_ju.p, nva, hipMemcpyDeviceToHost, h->stream));
+        if (ll_uj) HIPCHK(h, hipMemcpyAsync(ll_uj + (size_t)t.c0 * V * A, d_uj.p, nva, hipMemcpyDeviceToHost, h->stream));
+        if (ll_uu)
+          HIPCHK(h, hipMemcpyAsync(ll_uu + (size_t)t.c0 * A, d_uu.p, sizeof(double) * (size_t)t.nc() * A, hipMemcpyDeviceToHost, h->stream));
+        return 0;
+      });
 }

@@ -23,10 +23,10 @@
 //     passes of RC (4, 8 or 16); every pass repeats the nine identically and every ambient product belongs to one rho,
 //     so the passes change no bit: 24 bytes per entry and rho.
 //   * the sweep (lane = cluster of a 64-cluster block, one dot q_j . w_e[r] per (entry, cluster, rho)), the emit kernel,
-//     the batches and the host run are ambient_table.hpp's, shared with demux_ambient.hip; what they guarantee -- no bit
-//     depends on the chunking, the budget, the split of the rhos or the devices -- is written there.  This unit cuts a
-//     long cell into the equal parts of the wave plan, as muxgl_fmx_singlets cuts a cell, and sweeps inside the streamed
-//     E-step's budget (4 GiB or a third of the device, MUXGL_FMX_SLAB_MB).
+//     and the host run (on table_call.hpp's batch loop) are ambient_table.hpp's, shared with demux_ambient.hip; what
+//     they guarantee -- no bit depends on the chunking, the budget, the split of the rhos or the devices -- is written
+//     there.  This unit cuts a long cell into the equal parts of the wave plan, as muxgl_fmx_singlets cuts a cell, and
+//     sweeps inside the streamed E-step's budget (4 GiB or a third of the device, MUXGL_FMX_SLAB_MB).
 #include <algorithm>
 #include <cmath>
 #include <vector>

@@ -19,7 +19,8 @@
 //     and the G partial products of a cluster are multiplied in a fixed butterfly at the end.
 //   * table_join_kernel (table_call.hpp): the logs of the parts of a long cell, added in entry order.
 // Which cell goes into which batch, its cut into parts (the equal parts of the wave plan, as fmx_stream.hip's
-// sweep_block cuts a cell) and the order of the work items are table_plan.hpp's.  The cut depends on the cell alone and
+// sweep_block cuts a cell) and the order of the work items are table_plan.hpp's; the host body that drives the plan is
+// table_call.hpp's table_batches, whose customer this unit is (one bracket in its timing slot).  The cut depends on the cell alone and
 // every reduction tree is fixed: the table is bit-identical from call to call, for any slab budget, on one device, on a
 // group and through the sharded driver.
 //
@@ -27,8 +28,8 @@
 // against a packed [nnz][3] copy, a path that is gone).
 //
 // Memory: a slab of the table (the streamed E-step's budget: 4 GiB or a third of the device, MUXGL_FMX_SLAB_MB) and the
-// work items.  When the table exceeds the budget the cells are swept in batches and each batch is copied out before the
-// next.  Nothing proportional to C x K^2.
+// work items.  When the table exceeds the budget the cells are swept in batches (table_call.hpp has the protocol).
+// Nothing proportional to C x K^2.
 #include <algorithm>
 #include <vector>
 
@@ -105,53 +106,27 @@ void launch_sweep(muxgl_handle* h, int64_t n_items, int nblk, const fsg_item* d_
 }
 
 int fmx_singlets_run(muxgl_handle* h, double* sng) {
-  const int K = h->K;
-  const int64_t C = h->C;
-  std::vector<int64_t> cell_ptr((size_t)C + 1);
-  HIPCHK(h, hipMemcpyAsync(cell_ptr.data(), h->d_cell_ptr, sizeof(int64_t) * (size_t)(C + 1), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-
-  // batches of cells whose rows (one per part) fit the budget (table_plan.hpp)
-  const int64_t rows_cap = std::max<int64_t>(1, (int64_t)(dev_slab_budget("MUXGL_FMX_SLAB_MB") / (sizeof(double) * (size_t)K)));
-  const table_plan::batches bt = table_plan::plan(cell_ptr.data(), C, (size_t)rows_cap, [](int64_t, int64_t np) { return (size_t)np; });
-  const int nblk = (K + 63) / 64;
-  if (table_plan::exceeds_one_launch((double)bt.max_rows * (double)nblk, 4.0))
-    MUXGL_FAIL(h, "muxgl_fmx_singlets: a batch of %lld rows x %d clusters exceeds one launch (lower MUXGL_FMX_SLAB_MB)",
-               (long long)bt.max_rows, K);
-  int KH = 64;
-  while (KH > 1 && KH / 2 >= K) KH /= 2;
+  const int K = h->K, nblk = (K + 63) / 64, KH = lane_width(K);
+  const table_call call = {"muxgl_fmx_singlets", "MUXGL_FMX_SLAB_MB", table_plan::equal_begin, (double)nblk, 0.0, 0.0,
+                           table_plan::shape(K, "clusters"), ""};
+  table_batches<table_plan::cut> tb;
+  if (tb.plan(h, call, [K](int64_t, int64_t np) { return table_plan::singlet_bytes(np, K); })) return 1;
 
   dev_tmp<double> d_slab;
-  dev_tmp<fsg_item> d_items;
-  dev_tmp<table_plan::cut> d_cuts;
-  std::vector<fsg_item> items;
-  std::vector<table_plan::cut> cuts;
-  if (dev_alloc(h, &d_slab.p, (size_t)bt.max_rows * K)) return 1;
-  if (dev_alloc(h, &d_items.p, (size_t)bt.max_rows)) return 1;
-  if (dev_alloc(h, &d_cuts.p, (size_t)bt.max_cuts)) return 1;
+  if (dev_alloc(h, &d_slab.p, (size_t)tb.bt.max_rows * K)) return 1;
   tic(h, MUXGL_T_FMX_SINGLETS);
-  int64_t c0 = 0;
-  for (const int64_t c1 : bt.end) {
-    const int64_t nc = c1 - c0;
-    table_plan::fill(cell_ptr.data(), c0, c1, table_plan::equal_begin, items, &cuts, nullptr);
-    const int64_t n_items = (int64_t)items.size();
-    if (table_upload(h, items, d_items.p, cuts, d_cuts.p)) return 1;
-#define CALL_S(W) launch_sweep<W>(h, n_items, nblk, d_items.p, d_slab.p)
-    DISPATCH_WIDTH(KH, CALL_S);
+  return tb.run(h, table_slot_timer{MUXGL_T_FMX_SINGLETS},
+      [&](const table_batch<table_plan::cut>& b) {
+#define CALL_S(W) launch_sweep<W>(h, b.n_items, nblk, b.d_items, d_slab.p)
+        DISPATCH_WIDTH(KH, CALL_S);
 #undef CALL_S
-    HIPCHK(h, hipGetLastError());
-    if (!cuts.empty()) {
-      const int64_t n = (int64_t)cuts.size() * K;
-      hipLaunchKernelGGL(table_join_kernel<double>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
-                         (int64_t)cuts.size(), d_cuts.p, K, d_slab.p);
-      HIPCHK(h, hipGetLastError());
-    }
-    if (c1 == C) toc(h, MUXGL_T_FMX_SINGLETS);
-    HIPCHK(h, hipMemcpyAsync(sng + (size_t)c0 * K, d_slab.p, sizeof(double) * (size_t)nc * K, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    c0 = c1;
-  }
-  return 0;
+        HIPCHK(h, hipGetLastError());
+        return table_join(h, b, K, d_slab.p);
+      },
+      [&](const table_batch<table_plan::cut>& b) {
+        HIPCHK(h, hipMemcpyAsync(sng + (size_t)b.c0 * K, d_slab.p, sizeof(double) * (size_t)b.nc() * K, hipMemcpyDeviceToHost, h->stream));
+        return 0;
+      });
 }
 
 }  // namespace

@@ -24,14 +24,15 @@
 //     columns of a slab row (the clusters, then u, then uu).
 //   * fun_split_kernel: the cells' rows into the three tables of the caller's layout.
 // Which cell goes into which batch, its cut into parts (the equal parts of the wave plan, as muxgl_fmx_singlets cuts a
-// cell) and the order of the work items are table_plan.hpp's.  The cut of a cell depends on the cell alone and every
+// cell) and the order of the work items are table_plan.hpp's; the host body that drives the plan is table_call.hpp's
+// table_batches, whose customer this unit is.  The cut of a cell depends on the cell alone and every
 // reduction tree is fixed: the tables are bit-identical from call to call, for any budget, for any subset of outputs,
 // on one device, on a group and through the sharded driver.
 //
 // Memory: nothing proportional to nnz is held for the whole pileup beyond what the handle already has.  Cells are swept
 // in batches of whole cells whose weights, slab rows and table rows (table_plan::fmx_unknown_bytes) fit the streamed
-// E-step's budget (4 GiB or a third of the device, MUXGL_FMX_SLAB_MB); each batch is copied out before the next.  The
-// call caches nothing on the handle.
+// E-step's budget (4 GiB or a third of the device, MUXGL_FMX_SLAB_MB); table_call.hpp has the protocol of the batches.
+// The call caches nothing on the handle.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -201,93 +202,55 @@ void launch_sweep(muxgl_handle* h, int64_t n_items, int nblk, const fun_item* d_
 }
 
 int fmx_unknown_run(muxgl_handle* h, const double* gp0, double* ll_ju, double* ll_u, double* ll_uu, float* kernel_ms) {
-  const int K = h->K, KC = K + 2;
-  const int64_t C = h->C, S = h->S;
-  std::vector<int64_t> cell_ptr((size_t)C + 1);
-  HIPCHK(h, hipMemcpyAsync(cell_ptr.data(), h->d_cell_ptr, sizeof(int64_t) * (size_t)(C + 1), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-
-  // batches of whole cells whose device bytes fit the budget (table_plan.hpp)
-  const size_t budget = dev_slab_budget("MUXGL_FMX_SLAB_MB");
-  auto bytes_of = [&](int64_t len, int64_t np) { return table_plan::fmx_unknown_bytes(len, np, K); };
-  const table_plan::batches bt = table_plan::plan(cell_ptr.data(), C, budget, bytes_of);
-  if (bt.over >= 0) {
-    const int64_t len = cell_ptr[(size_t)bt.over + 1] - cell_ptr[(size_t)bt.over];
-    MUXGL_FAIL(h, "muxgl_fmx_unknown: droplet %lld alone (%lld entries x %d clusters: %.1f MB) exceeds the budget of %.1f MB "
-                  "(raise MUXGL_FMX_SLAB_MB)",
-               (long long)(h->cell_base + bt.over), (long long)len, K, (double)bytes_of(len, table_plan::parts(len)) / 1048576.0,
-               (double)budget / 1048576.0);
-  }
-  const int nblk = (K + 63) / 64;
-  if (table_plan::exceeds_one_launch((double)bt.max_rows * (double)nblk, 4.0) ||
-      table_plan::exceeds_one_launch((double)bt.max_rows * (double)KC, 256.0))
-    MUXGL_FAIL(h, "muxgl_fmx_unknown: a batch of %lld rows x %d clusters exceeds one launch (lower MUXGL_FMX_SLAB_MB)",
-               (long long)bt.max_rows, K);
-  int KH = 64;
-  while (KH > 1 && KH / 2 >= K) KH /= 2;
+  const int K = h->K, KC = K + 2, nblk = (K + 63) / 64, KH = lane_width(K);
+  const int64_t S = h->S;
+  const table_call call = {"muxgl_fmx_unknown", "MUXGL_FMX_SLAB_MB", table_plan::equal_begin, (double)nblk, (double)KC, 0.0,
+                           table_plan::shape(K, "clusters"), table_plan::shape(K, "clusters")};
+  table_batches<table_plan::cut> tb;
+  if (tb.plan(h, call, [K](int64_t len, int64_t np) { return table_plan::fmx_unknown_bytes(len, np, K); })) return 1;
 
   dev_tmp<double> d_u, d_wt, d_slab, d_ju, d_lu, d_uu;
-  dev_tmp<fun_item> d_items;
-  dev_tmp<table_plan::cut> d_cuts;
-  std::vector<fun_item> items;
-  std::vector<table_plan::cut> cuts;
   if (dev_alloc(h, &d_u.p, (size_t)S * 3)) return 1;
-  if (dev_alloc(h, &d_wt.p, (size_t)bt.max_entries * FUN_W)) return 1;
-  if (dev_alloc(h, &d_slab.p, (size_t)bt.max_rows * KC)) return 1;
-  if (dev_alloc(h, &d_ju.p, (size_t)bt.max_cells * K)) return 1;
-  if (dev_alloc(h, &d_lu.p, (size_t)bt.max_cells)) return 1;
-  if (dev_alloc(h, &d_uu.p, (size_t)bt.max_cells)) return 1;
-  if (dev_alloc(h, &d_items.p, (size_t)bt.max_rows)) return 1;
-  if (dev_alloc(h, &d_cuts.p, (size_t)bt.max_cuts)) return 1;
+  if (dev_alloc(h, &d_wt.p, (size_t)tb.bt.max_entries * FUN_W)) return 1;
+  if (dev_alloc(h, &d_slab.p, (size_t)tb.bt.max_rows * KC)) return 1;
+  if (dev_alloc(h, &d_ju.p, (size_t)tb.bt.max_cells * K)) return 1;
+  if (dev_alloc(h, &d_lu.p, (size_t)tb.bt.max_cells)) return 1;
+  if (dev_alloc(h, &d_uu.p, (size_t)tb.bt.max_cells)) return 1;
   call_events ev;  // (the handle's timing slots keep their values)
-  if (ev.create(h, kernel_ms, "muxgl_fmx_unknown")) return 1;
-
+  if (ev.create(h, kernel_ms, call.who)) return 1;
   if (gp0 && S > 0) HIPCHK(h, hipMemcpyAsync(d_u.p, gp0, sizeof(double) * (size_t)S * 3, hipMemcpyHostToDevice, h->stream));
-  int64_t c0 = 0;
-  for (const int64_t c1 : bt.end) {
-    const int64_t nc = c1 - c0, eb0 = cell_ptr[(size_t)c0], eb1 = cell_ptr[(size_t)c1];
-    table_plan::fill(cell_ptr.data(), c0, c1, table_plan::equal_begin, items, &cuts, nullptr);
-    const int64_t n_items = (int64_t)items.size();
-    if (table_upload(h, items, d_items.p, cuts, d_cuts.p)) return 1;
-    if (ev.start(h)) return 1;
-    if (c0 == 0 && !gp0 && S > 0) {  // the unknown donor's prior, once per call
-      hipLaunchKernelGGL(fun_prior_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, h->stream, S, h->d_af, d_u.p);
-      HIPCHK(h, hipGetLastError());
-    }
-    if (eb1 > eb0) {
-      hipLaunchKernelGGL(fun_weight_kernel, dim3((unsigned)((eb1 - eb0 + 255) / 256)), dim3(256), 0, h->stream, eb0, eb1,
-                         h->d_entry_snp, h->d_egls, d_u.p, d_wt.p);
-      HIPCHK(h, hipGetLastError());
-    }
-#define CALL_S(W) launch_sweep<W>(h, n_items, nblk, d_items.p, eb0, d_wt.p, d_slab.p)
-    DISPATCH_WIDTH(KH, CALL_S);
+  return tb.run(h, ev,
+      [&](const table_batch<table_plan::cut>& b) {
+        if (b.c0 == 0 && !gp0 && S > 0) {  // the unknown donor's prior, once per call
+          hipLaunchKernelGGL(fun_prior_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, h->stream, S, h->d_af, d_u.p);
+          HIPCHK(h, hipGetLastError());
+        }
+        if (b.eb1 > b.eb0) {
+          hipLaunchKernelGGL(fun_weight_kernel, dim3((unsigned)((b.eb1 - b.eb0 + 255) / 256)), dim3(256), 0, h->stream, b.eb0,
+                             b.eb1, h->d_entry_snp, h->d_egls, d_u.p, d_wt.p);
+          HIPCHK(h, hipGetLastError());
+        }
+#define CALL_S(W) launch_sweep<W>(h, b.n_items, nblk, b.d_items, b.eb0, d_wt.p, d_slab.p)
+        DISPATCH_WIDTH(KH, CALL_S);
 #undef CALL_S
-    HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(fun_scalar_kernel, dim3((unsigned)((n_items + 3) / 4)), dim3(256), 0, h->stream, n_items, d_items.p, eb0,
-                       d_wt.p, K, d_slab.p);
-    HIPCHK(h, hipGetLastError());
-    if (!cuts.empty()) {
-      const int64_t n = (int64_t)cuts.size() * KC;
-      hipLaunchKernelGGL(table_join_kernel<double>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
-                         (int64_t)cuts.size(), d_cuts.p, KC, d_slab.p);
-      HIPCHK(h, hipGetLastError());
-    }
-    {
-      const int64_t n = nc * KC;
-      hipLaunchKernelGGL(fun_split_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, nc, K, d_slab.p, d_ju.p,
-                         d_lu.p, d_uu.p);
-      HIPCHK(h, hipGetLastError());
-    }
-    if (ev.stop(h)) return 1;
-    if (ll_ju)
-      HIPCHK(h, hipMemcpyAsync(ll_ju + (size_t)c0 * K, d_ju.p, sizeof(double) * (size_t)nc * K, hipMemcpyDeviceToHost, h->stream));
-    if (ll_u) HIPCHK(h, hipMemcpyAsync(ll_u + c0, d_lu.p, sizeof(double) * (size_t)nc, hipMemcpyDeviceToHost, h->stream));
-    if (ll_uu) HIPCHK(h, hipMemcpyAsync(ll_uu + c0, d_uu.p, sizeof(double) * (size_t)nc, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    ev.add();
-    c0 = c1;
-  }
-  return 0;
+        HIPCHK(h, hipGetLastError());
+        hipLaunchKernelGGL(fun_scalar_kernel, dim3((unsigned)((b.n_items + 3) / 4)), dim3(256), 0, h->stream, b.n_items, b.d_items,
+                           b.eb0, d_wt.p, K, d_slab.p);
+        HIPCHK(h, hipGetLastError());
+        if (table_join(h, b, KC, d_slab.p)) return 1;
+        const int64_t n = b.nc() * KC;
+        hipLaunchKernelGGL(fun_split_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, b.nc(), K, d_slab.p,
+                           d_ju.p, d_lu.p, d_uu.p);
+        HIPCHK(h, hipGetLastError());
+        return 0;
+      },
+      [&](const table_batch<table_plan::cut>& b) {
+        const size_t nc = (size_t)b.nc();
+        if (ll_ju) HIPCHK(h, hipMemcpyAsync(ll_ju + (size_t)b.c0 * K, d_ju.p, sizeof(double) * nc * K, hipMemcpyDeviceToHost, h->stream));
+        if (ll_u) HIPCHK(h, hipMemcpyAsync(ll_u + b.c0, d_lu.p, sizeof(double) * nc, hipMemcpyDeviceToHost, h->stream));
+        if (ll_uu) HIPCHK(h, hipMemcpyAsync(ll_uu + b.c0, d_uu.p, sizeof(double) * nc, hipMemcpyDeviceToHost, h->stream));
+        return 0;
+      });
 }
 
 }  // namespace

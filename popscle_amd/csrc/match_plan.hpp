@@ -6,17 +6,15 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "lane_width.hpp"
+
 namespace match_plan {
 
 // parts of `part` consecutive SNPs a cluster's S SNPs are cut into (S >= 1): one log per (cluster, part, donor)
 inline int parts(int64_t S, int64_t part) { return (int)((S + part - 1) / part); }
 
 // donor lanes of a SNP slot: V rounded up to a power of two, 64 from 33 donors on (64 / VH SNPs side by side in a wave)
-inline int lane_width(int V) {
-  int VH = 64;
-  while (VH > 1 && VH / 2 >= V) VH /= 2;
-  return VH;
-}
+using ::lane_width;
 
 // bytes of a cluster in a batch: logs of the parts (donors, where ll is asked for; HWE), counts of the parts, read
 // counts, results

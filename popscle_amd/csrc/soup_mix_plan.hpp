@@ -12,6 +12,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "lane_width.hpp"
+
 namespace soup_mix_plan {
 
 // active markers per block of the update sweep: one partial row of the transposed product per block, added in block
@@ -20,11 +22,7 @@ constexpr int UPDATE_BLOCK = 256;
 
 // component lanes of a marker slot: M rounded up to a power of two, 64 from 33 components on (64 / width markers side by
 // side in a wave; beyond 64 components a lane takes the components lane, lane + 64, ...)
-inline int lane_width(int M) {
-  int W = 64;
-  while (W > 1 && W / 2 >= M) W /= 2;
-  return W;
-}
+using ::lane_width;
 inline int markers_per_wave(int M) { return 64 / lane_width(M); }
 inline int64_t waves(int64_t n_markers, int M) {
   const int g = markers_per_wave(M);

@@ -1,7 +1,8 @@
-// table_plan.hpp -- the host side of the four per-droplet tables (demux_singlets.hip, fmx_singlets.hip,
-// demux_unknown.hip, fmx_unknown.hip): how the cells of a call are cut into work items and swept in batches.  Plain C++
-// (no HIP), in the manner of pairs_plan.hpp, so tests/test_table_plan.py compiles it on its own
-// (tests/csrc/table_plan_probe.cpp) and holds it to the loops it replaced.
+// table_plan.hpp -- the host side of the five per-droplet table calls (demux_singlets.hip, fmx_singlets.hip,
+// demux_unknown.hip, fmx_unknown.hip and, through ambient_table.hpp, the two ambient tables): how the cells of a call are
+// cut into work items and swept in batches, what a cell costs, and the words of the two refusals.  Plain C++ (no HIP), in
+// the manner of pairs_plan.hpp, so tests/test_table_plan.py compiles it on its own (tests/csrc/table_plan_probe.cpp) and
+// holds it to the loops it replaced.  The host body that drives a plan on a device is table_call.hpp's.
 //
 // A cell of more than PART entries is cut into ceil(len / PART) parts, every other cell (an empty one too) is one part.
 // A part is one work item with a slab row of its own: the first part of a cell writes the cell's row (rows [0, cells of
@@ -14,6 +15,8 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
+#include <string>
 #include <vector>
 
 namespace table_plan {
@@ -48,7 +51,7 @@ struct batches {
   int64_t over = -1;         // the first cell whose cost alone exceeds the budget (it is a batch of its own), or none
 };
 
-// cost(len, parts) of a cell, in the unit of the budget: rows for the singlet tables, bytes for the unknown-donor calls
+// cost(len, parts) of a cell, in the unit of the budget
 template <class Cost>
 batches plan(const int64_t* cell_ptr, int64_t C, size_t budget, Cost cost) {
   batches b;
@@ -73,6 +76,10 @@ batches plan(const int64_t* cell_ptr, int64_t C, size_t budget, Cost cost) {
   }
   return b;
 }
+
+// device bytes of a cell in a batch of a singlet table of W columns: its slab rows, one per part (the slab alone counts,
+// as ever: parts x 8 W <= budget is parts <= budget / (8 W), the row count the two calls once divided out themselves)
+inline size_t singlet_bytes(int64_t np, int W) { return (size_t)np * sizeof(double) * (size_t)W; }
 
 // device bytes of a cell in a batch of the unknown-donor call at A alphas and VC = V + 1 columns: its entries' weights,
 // its slab rows (one per part) with their items, and its rows of the three tables with its record
@@ -118,5 +125,27 @@ inline void fill(const int64_t* cell_ptr, int64_t c0, int64_t c1, begin_fn begin
 
 // whether `units` work units at `per_block` a workgroup need more workgroups than one launch takes
 inline bool exceeds_one_launch(double units, double per_block) { return units / per_block >= 2147483647.0; }
+
+// ---- the two refusals of a table call, in one wording.  who: the call's name; env: the variable that sets the budget;
+// shape: the call's words for the size of a row, "65 samples" or "4 alphas x 65 samples":
+inline std::string shape(int n, const char* noun) { return std::to_string(n) + " " + noun; }
+inline std::string shape(int n, const char* noun, int m, const char* of) { return shape(n, noun) + " x " + shape(m, of); }
+
+// droplet `droplet` (an index of the whole pileup) of `entries` entries costs `bytes` alone, more than the budget
+inline std::string alone_message(const char* who, int64_t droplet, int64_t entries, const std::string& shape, size_t bytes,
+                                 size_t budget, const char* env) {
+  char buf[512];
+  snprintf(buf, sizeof(buf), "%s: droplet %lld alone (%lld entries x %s: %.1f MB) exceeds the budget of %.1f MB (raise %s)", who,
+           (long long)droplet, (long long)entries, shape.c_str(), (double)bytes / 1048576.0, (double)budget / 1048576.0, env);
+  return buf;
+}
+
+// the largest batch, of `rows` slab rows, needs more workgroups than one launch takes
+inline std::string launch_message(const char* who, int64_t rows, const std::string& shape, const char* env) {
+  char buf[512];
+  snprintf(buf, sizeof(buf), "%s: a batch of %lld rows x %s exceeds one launch (lower %s)", who, (long long)rows, shape.c_str(),
+           env);
+  return buf;
+}
 
 }  // namespace table_plan

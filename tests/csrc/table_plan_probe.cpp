@@ -1,7 +1,11 @@
-// Test shim around popscle_amd/csrc/table_plan.hpp, the host side of the three per-droplet tables: the batches of cells
+// Test shim around popscle_amd/csrc/table_plan.hpp, the host side of the per-droplet tables: the batches of cells
 // for a budget, and per batch the work items with the cuts (singlet tables) or the cell records (unknown-donor call), as
-// each of the three callers asks for them.
+// each of the three callers asks for them; the words of the two refusals of all five calls; the lane width
+// (lane_width.hpp).
 // Plain C++; nothing here touches a device (see tests/test_table_plan.py).
+#include <cstring>
+
+#include "lane_width.hpp"
 #include "table_plan.hpp"
 
 namespace {
@@ -15,9 +19,44 @@ table_plan::batches plan_of(int caller, const int64_t* cell_ptr, int64_t C, uint
   return table_plan::plan(cell_ptr, C, (size_t)budget, [](int64_t, int64_t np) { return (size_t)np; });
 }
 
+// the words of the five calls for the size of a row, as each hands them to table_call (tests/test_table_plan.py finds
+// these expressions in the units): 0 muxgl_demux_singlets, 1 muxgl_fmx_singlets, 2 muxgl_demux_unknown, 3
+// muxgl_fmx_unknown, 4 an ambient table (NR rhos, W of call.noun)
+struct shapes {
+  std::string launch, alone;
+};
+struct ambient_call {
+  const char* noun;
+};
+shapes shapes_of(int which, int A, int W, const char* noun) {
+  const int V = W, K = W, NR = A;
+  const ambient_call call = {noun};
+  switch (which) {
+    case 0: return {table_plan::shape(V, "samples"), ""};
+    case 1: return {table_plan::shape(K, "clusters"), ""};
+    case 2: return {table_plan::shape(V, "samples", A, "alphas"), table_plan::shape(A, "alphas", V, "samples")};
+    case 3: return {table_plan::shape(K, "clusters"), table_plan::shape(K, "clusters")};
+    default: return {table_plan::shape(W, call.noun, NR, "rhos"), table_plan::shape(NR, "rhos", W, call.noun)};
+  }
+}
+
 }  // namespace
 
 extern "C" {
+
+int probe_lane_width(int n) { return lane_width(n); }
+
+// the two refusals as call `call` (shapes_of) words them; an empty string where the call has no such refusal
+void probe_table_alone_message(int call, const char* who, int64_t droplet, int64_t entries, int A, int W, const char* noun,
+                               uint64_t bytes, uint64_t budget, const char* env, char* out, size_t out_len) {
+  const shapes sh = shapes_of(call, A, W, noun);
+  const std::string m = sh.alone.empty() ? "" : table_plan::alone_message(who, droplet, entries, sh.alone, bytes, budget, env);
+  snprintf(out, out_len, "%s", m.c_str());
+}
+void probe_table_launch_message(int call, const char* who, int64_t rows, int A, int W, const char* noun, const char* env,
+                                char* out, size_t out_len) {
+  snprintf(out, out_len, "%s", table_plan::launch_message(who, rows, shapes_of(call, A, W, noun).launch, env).c_str());
+}
 
 int64_t probe_table_part() { return table_plan::PART; }
 int probe_table_sizes(int which) {

@@ -263,6 +263,29 @@ def test_budget_does_not_matter(tmp_path):
     _same(outs[0], outs[1], "1 MB")
 
 
+def test_a_droplet_over_the_budget_is_refused_and_the_handle_stays_usable(monkeypatch):
+    """one droplet with an entry at each of 27 000 markers beside two short ones: at K = 2 its weights alone
+    (40 bytes an entry) exceed a budget of 1 MB, whatever the batches"""
+    n = 27000
+    rng = np.random.default_rng(7650)
+    lens = np.array([5, n, 300])
+    snp = np.concatenate([np.sort(rng.choice(n, l, replace=False)) for l in lens]).astype(np.int32)
+    reads = ((rng.integers(0, 2, snp.size) << 7) | rng.integers(13, 21, snp.size)).astype(np.uint8)   # one read an entry
+    cell_ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    p = synth.Pileup(3, n, cell_ptr, snp, np.arange(snp.size + 1, dtype=np.int64), reads, rng.uniform(0.05, 0.95, n))
+    assert 40 * n > (1 << 20)
+    monkeypatch.delenv("MUXGL_FMX_SLAB_MB", raising=False)
+    with prepared(p) as e:
+        e.fmx_set_clusters(2, np.array([0, 1, 0], dtype=np.int32))
+        e.fmx_iterate(0.5, 0.1)
+        monkeypatch.setenv("MUXGL_FMX_SLAB_MB", "1")
+        with pytest.raises(muxgl.MuxglError, match="muxgl_fmx_unknown: droplet .* exceeds the budget .*MUXGL_FMX_SLAB_MB"):
+            e.fmx_unknown()
+        monkeypatch.delenv("MUXGL_FMX_SLAB_MB")
+        t = e.fmx_unknown()   # the same handle, at the default budget
+        assert all(t[name].shape[0] == 3 and np.isfinite(t[name]).all() for name in FIELDS)
+
+
 @pytest.mark.parametrize("K", [20, 300])
 def test_device_groups(K):
     p = _long_cells_pileup(7701 + K)

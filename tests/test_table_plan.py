@@ -46,6 +46,12 @@ def probe(tmp_path_factory):
     lib.probe_table_plan.restype = C.c_int64
     lib.probe_table_fill.argtypes = [C.c_int, p64, C.c_int64, C.c_int64, p64, p64, p64]
     lib.probe_table_fill.restype = C.c_int64
+    lib.probe_table_alone_message.argtypes = [C.c_int, C.c_char_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_char_p,
+                                              C.c_uint64, C.c_uint64, C.c_char_p, C.c_char_p, C.c_size_t]
+    lib.probe_table_alone_message.restype = None
+    lib.probe_table_launch_message.argtypes = [C.c_int, C.c_char_p, C.c_int64, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
+                                               C.c_char_p, C.c_size_t]
+    lib.probe_table_launch_message.restype = None
     return lib
 
 
@@ -272,3 +278,99 @@ def test_random_lengths(probe):
             canon = {}
             for budget in budgets_of(caller, lens, A, V, rng):
                 check(probe, caller, lens, budget, A, V, canon)
+
+
+# ---- the two refusals, worded once (table_plan::alone_message, launch_message) with the words of each call
+# (table_plan::shape, as the probe restates them and test_the_units_hand_in_these_words finds them in the units).  The literals are the format strings the five calls once carried, with the numbers put in:
+# droplet 7 of 6145 entries, 4 alphas / rhos, 65 samples / clusters, 5 767 168 B = 5.5 MB against a budget of 1 MB, a
+# largest batch of 123456789012 rows.
+DEMUX_ENV, FMX_ENV = b"MUXGL_DEMUX_SLAB_MB", b"MUXGL_FMX_SLAB_MB"
+CALLS = {  # name: (shapes_of number, who, noun, env)
+    "demux_singlets": (0, b"muxgl_demux_singlets", b"", DEMUX_ENV),
+    "fmx_singlets": (1, b"muxgl_fmx_singlets", b"", FMX_ENV),
+    "demux_unknown": (2, b"muxgl_demux_unknown", b"", DEMUX_ENV),
+    "fmx_unknown": (3, b"muxgl_fmx_unknown", b"", FMX_ENV),
+    "demux_ambient": (4, b"muxgl_demux_ambient", b"samples", DEMUX_ENV),
+    "fmx_ambient": (4, b"muxgl_fmx_ambient", b"clusters", FMX_ENV),
+}
+
+
+def alone_message(lib, name):
+    call, who, noun, env = CALLS[name]
+    out = C.create_string_buffer(512)
+    lib.probe_table_alone_message(call, who, 7, 6145, 4, 65, noun, 5767168, 1 << 20, env, out, 512)
+    return out.value.decode()
+
+
+def launch_message(lib, name):
+    call, who, noun, env = CALLS[name]
+    out = C.create_string_buffer(512)
+    lib.probe_table_launch_message(call, who, 123456789012, 4, 65, noun, env, out, 512)
+    return out.value.decode()
+
+
+@pytest.mark.parametrize("name,text", [
+    ("demux_unknown", "muxgl_demux_unknown: droplet 7 alone (6145 entries x 4 alphas x 65 samples: 5.5 MB) exceeds the "
+                      "budget of 1.0 MB (raise MUXGL_DEMUX_SLAB_MB)"),
+    ("fmx_unknown", "muxgl_fmx_unknown: droplet 7 alone (6145 entries x 65 clusters: 5.5 MB) exceeds the budget of 1.0 MB "
+                    "(raise MUXGL_FMX_SLAB_MB)"),
+    ("demux_ambient", "muxgl_demux_ambient: droplet 7 alone (6145 entries x 4 rhos x 65 samples: 5.5 MB) exceeds the budget "
+                      "of 1.0 MB (raise MUXGL_DEMUX_SLAB_MB)"),
+    ("fmx_ambient", "muxgl_fmx_ambient: droplet 7 alone (6145 entries x 4 rhos x 65 clusters: 5.5 MB) exceeds the budget of "
+                    "1.0 MB (raise MUXGL_FMX_SLAB_MB)"),
+])
+def test_refusal_of_a_droplet_over_the_budget_alone(probe, name, text):
+    assert alone_message(probe, name) == text
+
+
+def test_the_units_hand_in_these_words():
+    probe_src = open(os.path.join(ROOT, "tests", "csrc", "table_plan_probe.cpp")).read()
+    csrc = os.path.join(ROOT, "popscle_amd", "csrc")
+    for unit, who, env, words in [
+            ("demux_singlets.hip", "muxgl_demux_singlets", "MUXGL_DEMUX_SLAB_MB", 'table_plan::shape(V, "samples"), ""}'),
+            ("fmx_singlets.hip", "muxgl_fmx_singlets", "MUXGL_FMX_SLAB_MB", 'table_plan::shape(K, "clusters"), ""}'),
+            ("demux_unknown.hip", "muxgl_demux_unknown", "MUXGL_DEMUX_SLAB_MB",
+             'table_plan::shape(V, "samples", A, "alphas"), table_plan::shape(A, "alphas", V, "samples")}'),
+            ("fmx_unknown.hip", "muxgl_fmx_unknown", "MUXGL_FMX_SLAB_MB",
+             'table_plan::shape(K, "clusters"), table_plan::shape(K, "clusters")}'),
+            ("ambient_table.hpp", None, None,
+             'table_plan::shape(W, call.noun, NR, "rhos"), table_plan::shape(NR, "rhos", W, call.noun)}')]:
+        src = open(os.path.join(csrc, unit)).read()
+        assert words in src and words in probe_src, unit
+        if who:
+            assert f'table_call call = {{"{who}", "{env}", ' in src, unit
+    assert '{"muxgl_demux_ambient", h->V, "samples", h->d_gp, "MUXGL_DEMUX_SLAB_MB", ' in open(os.path.join(csrc, "demux_ambient.hip")).read()
+    assert '{"muxgl_fmx_ambient", h->K, "clusters", h->d_cgp, "MUXGL_FMX_SLAB_MB", ' in open(os.path.join(csrc, "fmx_ambient.hip")).read()
+    assert "table_call tc = {call.who, call.budget_env, " in open(os.path.join(csrc, "ambient_table.hpp")).read()
+
+
+def test_the_singlet_tables_refuse_no_droplet(probe):
+    assert alone_message(probe, "demux_singlets") == "" and alone_message(probe, "fmx_singlets") == ""
+
+
+@pytest.mark.parametrize("name,text", [
+    ("demux_singlets", "muxgl_demux_singlets: a batch of 123456789012 rows x 65 samples exceeds one launch "
+                       "(lower MUXGL_DEMUX_SLAB_MB)"),
+    ("fmx_singlets", "muxgl_fmx_singlets: a batch of 123456789012 rows x 65 clusters exceeds one launch "
+                     "(lower MUXGL_FMX_SLAB_MB)"),
+    ("demux_unknown", "muxgl_demux_unknown: a batch of 123456789012 rows x 65 samples x 4 alphas exceeds one launch "
+                      "(lower MUXGL_DEMUX_SLAB_MB)"),
+    ("fmx_unknown", "muxgl_fmx_unknown: a batch of 123456789012 rows x 65 clusters exceeds one launch "
+                    "(lower MUXGL_FMX_SLAB_MB)"),
+    ("demux_ambient", "muxgl_demux_ambient: a batch of 123456789012 rows x 65 samples x 4 rhos exceeds one launch "
+                      "(lower MUXGL_DEMUX_SLAB_MB)"),
+    ("fmx_ambient", "muxgl_fmx_ambient: a batch of 123456789012 rows x 65 clusters x 4 rhos exceeds one launch "
+                    "(lower MUXGL_FMX_SLAB_MB)"),
+])
+def test_refusal_of_a_batch_over_one_launch(probe, name, text):
+    assert launch_message(probe, name) == text
+
+
+def test_lane_width(probe):
+    """the power of two in 1..64 that seven loops once computed: while (W > 1 && W / 2 >= n) W /= 2, from 64"""
+    assert [probe.probe_lane_width(n) for n in (0, 1, 2, 3, 33, 64, 65, 1024)] == [1, 1, 2, 4, 64, 64, 64, 64]
+    for n in range(0, 200):
+        w = 64
+        while w > 1 and w // 2 >= n:
+            w //= 2
+        assert probe.probe_lane_width(n) == w
