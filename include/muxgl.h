@@ -159,7 +159,8 @@ enum {
                                Where the default-grid path runs its cells as two groups on two streams (below,
                                muxgl_demux_oct_split) the first group's share runs underneath the second group's sweep:
                                the slot is then what remained of the step's device time behind the end of the last
-                               sweep, i.e. the exposed part */
+                               sweep, i.e. the exposed part (to the end of the later of the two finishes, which run
+                               on a stream each and are joined by the host before muxgl_demux_run returns) */
   MUXGL_T_DEMUX_SWEEP = 1,  /* per-entry likelihoods (a4,a5) fused with the sample-pair x alpha sweep (a6); with two cell
                                groups: from the start of the step to the end of the later of the two sweeps (the later
                                of two elapsed times, taken on the host).  SWEEP and REDUCE never overlap */

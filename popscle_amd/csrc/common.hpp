@@ -118,12 +118,15 @@ struct muxgl_handle {
   int device = 0;
   hipStream_t stream = nullptr;
   bool owns_stream = true;
-  // the sweep of the oct path's second cell group (demux_oct.hip) runs on a stream of the handle's own, forked from
-  // `stream` and joined back into it before the launcher returns: every other call sees one stream.  Stream and events
-  // are made by the first two-group run (a handle that never takes that path has none) and go with the handle
+  // the oct path's second cell group (demux_oct.hip) runs on a stream of the handle's own, forked from `stream` and
+  // joined by the HOST: muxgl_demux_run waits for both streams before it returns (join_stream2 below), so every other
+  // call sees one stream.  Stream and events are made by the first two-group run (a handle that never takes that path
+  // has none) and go with the handle
   hipStream_t stream2 = nullptr;
-  hipEvent_t ev_fork = nullptr;    // the fork where no timing event is recorded (MUXGL_NO_EVENTS)
-  hipEvent_t ev_sweep2 = nullptr;  // end of the second group's sweep: a time stamp, and the join
+  bool stream2_busy = false;        // work of the current run is outstanding on stream2
+  hipEvent_t ev_fork = nullptr;     // the fork where no timing event is recorded (MUXGL_NO_EVENTS)
+  hipEvent_t ev_sweep2 = nullptr;   // end of the second group's sweep: a time stamp
+  hipEvent_t ev_finish2 = nullptr;  // end of the second group's finish: a time stamp
   bool split_timed = false;  // the brackets SWEEP / REDUCE of this run are those of a two-group run (collect_timing)
   std::string err;
   int role = MUXGL_ROLE_FULL;
@@ -482,23 +485,33 @@ static inline void clear_timing(muxgl_handle* h) {
     h->ms[i] = 0.f;
   }
 }
+// The host's join of a two-group run of the oct path (demux_oct.hip): waits for what the run left on stream2.  Called
+// behind the wait for the handle's stream by whoever reads the run's records or timing slots, and in front of whatever
+// frees what the second group writes (muxgl_set_pileup, muxgl_destroy): nothing is outstanding on stream2 outside a run.
+static inline hipError_t join_stream2(muxgl_handle* h) {
+  if (!h->stream2_busy) return hipSuccess;
+  h->stream2_busy = false;
+  return hipStreamSynchronize(h->stream2);
+}
 // Reads the brackets recorded since the last call: a slot is summed ONCE per bracket (its `used` mark is cleared here,
 // so the phased API, which collects after every phase, does not add the earlier phases' times again) and only when
 // the elapsed-time query succeeds; ms[] keeps the last value of every slot until clear_timing.  ms_calls counts the
 // collecting calls (include/muxgl.h says which entry points those are).
 static inline void collect_timing(muxgl_handle* h) {
   if (h->split_timed) {
-    // The oct sweep ran as two cell groups on two streams (demux_oct.hip).  With A = the start (start event of SWEEP),
-    // E1 / E2 = the ends of the two sweeps (stop event of SWEEP, ev_sweep2) and F = the end of the step behind the join
-    // (stop event of REDUCE): SWEEP = max(E1, E2) - A, the later of two elapsed times taken here on the host -- no wait
-    // on the device orders the first group's finish behind the second group's sweep --, REDUCE = F - A - SWEEP.
+    // The oct path ran as two cell groups on two streams (demux_oct.hip).  With A = the start (start event of SWEEP),
+    // E1 / E2 = the ends of the two sweeps (stop event of SWEEP, ev_sweep2) and F1 / F2 = the ends of the two finishes
+    // (stop event of REDUCE, ev_finish2): SWEEP = max(E1, E2) - A and REDUCE = max(F1, F2) - A - SWEEP, the later of two
+    // elapsed times each, taken here on the host -- nothing on the device orders one group behind the other.
     h->split_timed = false;
     h->ev_used[MUXGL_T_DEMUX_SWEEP] = h->ev_used[MUXGL_T_DEMUX_REDUCE] = false;
-    float t1 = 0.f, t2 = 0.f, tf = 0.f;
+    float t1 = 0.f, t2 = 0.f, tf = 0.f, tf2 = 0.f;
     hipEvent_t a = h->ev[2 * MUXGL_T_DEMUX_SWEEP];
     if (hipEventElapsedTime(&t1, a, h->ev[2 * MUXGL_T_DEMUX_SWEEP + 1]) == hipSuccess &&
         hipEventElapsedTime(&t2, a, h->ev_sweep2) == hipSuccess &&
-        hipEventElapsedTime(&tf, a, h->ev[2 * MUXGL_T_DEMUX_REDUCE + 1]) == hipSuccess) {
+        hipEventElapsedTime(&tf, a, h->ev[2 * MUXGL_T_DEMUX_REDUCE + 1]) == hipSuccess &&
+        hipEventElapsedTime(&tf2, a, h->ev_finish2) == hipSuccess) {
+      tf = tf > tf2 ? tf : tf2;
       const float ts = t1 > t2 ? t1 : t2, tr = tf > ts ? tf - ts : 0.f;
       h->ms[MUXGL_T_DEMUX_SWEEP] = ts;
       h->ms_sum[MUXGL_T_DEMUX_SWEEP] += (double)ts;

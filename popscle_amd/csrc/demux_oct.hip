@@ -1161,23 +1161,29 @@ int oct_launch_t(muxgl_handle* h, const muxgl_demux_params* p) {
                          st->d_cell_chunk_ptr, d_part, st->d_part_e, d_slots, h->V, al, p->doublet_prior, h->h_dcells);
   };
   if (cut > 0) {
-    // Two cell groups as a pipeline: the sweep of the cells from `cut` on runs on stream2 beside the handle's stream, which
-    // carries the first group's sweep and both finishes.  The two sweeps are on the device together (the first gets
-    // there first and ends first; the dispatcher fills freed slots as it does for one launch, so the sweep as a whole
-    // is no shorter); the first group's finish (its fixed chain of dependent steps, the write-back of its partials)
-    // runs underneath the longer-running second sweep; only the second group's finish is exposed.  A chunk's partials go to its cell's place (chunk_pos) and
-    // a cell's record to its own: the groups share every buffer without overlap.  stream2 is forked from the handle's
-    // stream by the step's first event and joined back into it by the wait in front of the second finish, whatever
-    // happens in between: what follows on the handle's stream is ordered behind both groups.
-    // (Measured and dropped, profiles/oct_split.md: the second group's finish on stream2 as well and the join at the end
-    // -- the step then ends with two dependent hand-overs between queues instead of none; the first group on stream2;
-    // a lower or higher priority for stream2.)
+    // Two cell groups, each on a stream of its own: the handle's stream carries the first group's sweep and finish,
+    // stream2 -- forked from it by the step's first event -- the sweep and finish of the cells from `cut` on.  The two
+    // sweeps are on the device together (the first gets there first and ends first; the dispatcher fills freed slots as
+    // it does for one launch, so the sweep as a whole is no shorter); the first group's finish (its fixed chain of
+    // dependent steps, the write-back of its partials) runs underneath the longer-running second sweep; only the second
+    // group's finish is exposed, and it follows its sweep on the same queue: a plain dependent boundary, no event, no
+    // hand-over between queues.  A chunk's partials go to its cell's place (chunk_pos) and a cell's record to its own:
+    // the groups share every buffer without overlap, the two finishes read disjoint partials and write disjoint
+    // records and may overlap in time.
+    // The join is the HOST's: nothing on the device waits for stream2.  A run that got as far as the fork leaves
+    // h->stream2_busy set, and muxgl_demux_run waits for both streams (join_stream2, common.hpp) before it reads a
+    // timing slot or a record; every way out of this function behind the fork that reports a failure waits here.  So
+    // whatever is enqueued later on the handle's stream is ordered behind both groups by that wait of the host, not by
+    // the stream.  (A join on the device at the end of the step was measured and dropped, profiles/oct_split.md: it
+    // ends the step with two dependent hand-overs between queues.  Also dropped there: the first group on stream2; a
+    // lower or higher priority for stream2.)
     hipError_t e = hipSuccess;
     if (!h->stream2) {  // the first two-group run of this handle (muxgl_destroy releases them)
       e = hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking);
       if (e != hipSuccess) h->stream2 = nullptr;
       if (e == hipSuccess && !h->ev_fork) e = hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming);
       if (e == hipSuccess && !h->ev_sweep2) e = hipEventCreate(&h->ev_sweep2);
+      if (e == hipSuccess && !h->ev_finish2) e = hipEventCreate(&h->ev_finish2);
       if (e != hipSuccess) {
         if (h->stream2) (void)hipStreamDestroy(h->stream2);
         h->stream2 = nullptr;
@@ -1192,22 +1198,21 @@ int oct_launch_t(muxgl_handle* h, const muxgl_demux_params* p) {
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamWaitEvent(h->stream2, fork, 0);
     if (e != hipSuccess) MUXGL_FAIL(h, "demux_oct_launch: %s", hipGetErrorString(e));
+    h->stream2_busy = true;  // behind the fork: the host joins
     sweep(h->stream2, st->oct_unit0[1], st->oct_unit0[2]);
     e = hipGetLastError();
-    hipError_t ej = hipEventRecord(h->ev_sweep2, h->stream2);  // the end of the second sweep: a time stamp, and the join
-    toc(h, MUXGL_T_DEMUX_SWEEP);                                // the end of the first
-    if (e == hipSuccess && ej == hipSuccess) {
-      finish(h->stream, 0, cut);
-      e = hipGetLastError();
-    }
-    if (ej == hipSuccess) ej = hipStreamWaitEvent(h->stream, h->ev_sweep2, 0);
-    if (ej != hipSuccess) (void)hipStreamSynchronize(h->stream2);  // (no join on the device: join here)
-    if (e == hipSuccess) e = ej;
+    if (e == hipSuccess && !timing_off()) e = hipEventRecord(h->ev_sweep2, h->stream2);  // the end of the second sweep
+    toc(h, MUXGL_T_DEMUX_SWEEP);                                                          // the end of the first
     if (e == hipSuccess) {
-      finish(h->stream, cut, h->C);
+      finish(h->stream, 0, cut);
+      finish(h->stream2, cut, h->C);
       e = hipGetLastError();
     }
-    if (e != hipSuccess) MUXGL_FAIL(h, "demux_oct_launch: %s", hipGetErrorString(e));
+    if (e == hipSuccess && !timing_off()) e = hipEventRecord(h->ev_finish2, h->stream2);
+    if (e != hipSuccess) {
+      (void)join_stream2(h);
+      MUXGL_FAIL(h, "demux_oct_launch: %s", hipGetErrorString(e));
+    }
     toc(h, MUXGL_T_DEMUX_REDUCE);
     h->split_timed = !timing_off();
     h->records_on_host = true;

@@ -335,6 +335,7 @@ int muxgl_set_pileup_role(muxgl_handle* h, int role, int64_t C, int64_t S, int64
     if (dev_alloc(h, &h->d_dcells, (size_t)C)) return 1;
     if (dev_alloc(h, &h->d_fcells, (size_t)C)) return 1;
     if (dev_alloc(h, &h->d_clust, (size_t)(C + MUXGL_XCHG_PAD))) return 1;
+    (void)join_stream2(h);  // (outstanding only behind a join that failed: the second group writes h_dcells)
     if (h->h_dcells) (void)hipHostFree(h->h_dcells);
     if (h->h_fcells) (void)hipHostFree(h->h_fcells);
     h->h_dcells = nullptr;
@@ -407,6 +408,7 @@ void muxgl_destroy(muxgl_handle* h) {
   }
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
+  (void)join_stream2(h);
   if (h->col) muxgl_destroy(h->col);
   h->col = nullptr;
   dev_free(&h->d_cell_ptr);
@@ -475,6 +477,7 @@ void muxgl_destroy(muxgl_handle* h) {
   if (h->ev_stat) (void)hipEventDestroy(h->ev_stat);
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
   if (h->ev_sweep2) (void)hipEventDestroy(h->ev_sweep2);
+  if (h->ev_finish2) (void)hipEventDestroy(h->ev_finish2);
   if (h->stream2) (void)hipStreamDestroy(h->stream2);
   for (int i = 0; i < 2 * MUXGL_T_COUNT; ++i)
     if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
@@ -618,7 +621,10 @@ int muxgl_demux_run(muxgl_handle* h, const muxgl_demux_params* p, muxgl_demux_ce
       toc(h, MUXGL_T_DEMUX_D2H);
     }
   }
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  const hipError_t e1 = hipStreamSynchronize(h->stream);
+  const hipError_t e2 = join_stream2(h);  // a two-group run of the oct path: its second group is joined here, by the host
+  HIPCHK(h, e1);
+  HIPCHK(h, e2);
   collect_timing(h);
   if (out && h->C) memcpy(out, h->h_dcells, sizeof(muxgl_demux_cell) * (size_t)h->C);
   if (full_ll && h->C)
